@@ -20,10 +20,15 @@
 Launch: `python bench.py` (N=1) or
         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
              bench.py --gpus N --steps K --warmup W`.
-Rank 0 prints ONE JSON line.  The CPU oracle is used here ONLY for the reported `cpu_baseline` (and the RMSE next to it); it is
-never inside the timed GPU region.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the
+film's mean); nothing else is rendered or measured.  --dump-outputs DIR writes the film of the last timed step to DIR (film.npy, or a
+fixed seeded sample of its pixels where the film is larger than 64 MB) so that two builds can be compared output for output.
 
-Beside the contract's fields the default N = 1 line carries (all measured live, outside the timed region):
+--full adds everything else, all outside the timed region: the single-frame rate (the same K steps on one stream), the kernel durations
+of an untimed pass and the roofline built on them, the CPU baseline with the RMSE of GPU against the CPU oracle and the parity gate
+(exit code 3).  The CPU oracle is used ONLY there; it is never inside the timed GPU region.
+
+Beside those, the default N = 1 cornell line of a --full run carries (all measured live, outside the timed region):
   extra_workloads     one step each of configs[2] (veach), configs[3] (batch) and configs[4] (stress) with their kernel durations
   projected_scaling   kernel-level strong-scaling efficiency for N = 2, 4, 8 from rendering every 1/N shard of the frame on this
                       one GPU (the slowest shard sets the pace), and the cost of an N = 8 shard when launches are pipelined
@@ -192,9 +197,12 @@ def parse():
                     help="integrator_enum_t of the path frames (profiling direct_lighting_t = 6 and the recursive integrators 8 / 9 / 10; the metric's configs use 11)")
     ap.add_argument("--no-pipeline", action="store_true", help="render the timed steps on one stream (no overlap of a frame's start with the previous frame's tail): `value` is then the single-frame rate")
     ap.add_argument("--pipeline", action="store_true", help="(the default since round 5, at every N: consecutive frames on two streams; kept so that old command lines still parse)")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra_workloads and projected_scaling (they run for the default N = 1 cornell line only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="beside the headline: single-frame rate, kernel durations and roofline, cpu_baseline, parity gate, "
+                    "and for the default N = 1 cornell line extra_workloads, projected_scaling and boundary")
+    ap.add_argument("--no-extra", action="store_true", help="(with --full) skip extra_workloads and projected_scaling (they run for the default N = 1 cornell line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip cpu_baseline and the RMSE figures next to it")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the film of the last timed step to DIR as .npy (float32)")
     return ap.parse_args()
 
 
@@ -426,6 +434,23 @@ def contract_frac(frames, kernel_ms_per_frame, world=1):
     return achieved, launch_bytes
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, film):
+    """--dump-outputs: the film of the last timed step (float32, height x width x 3, what a caller of the path receives) as out_dir/film.npy.  A film of
+    more than 64 MB (batch, stress) is sampled instead: 2^20 pixels drawn with a fixed seed, so the same pixels for the same film size -- their values as
+    film_sample.npy (pixels x 3) and their (row, column) as film_sample_pixels.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    if film.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "film.npy"), film)
+        return
+    h, w = film.shape[:2]
+    idx = np.sort(np.random.default_rng(20251015).choice(h * w, size=1 << 20, replace=False))
+    np.save(os.path.join(out_dir, "film_sample.npy"), film.reshape(h * w, 3)[idx])
+    np.save(os.path.join(out_dir, "film_sample_pixels.npy"), np.stack([idx // w, idx % w], 1).astype(np.float64))
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -487,10 +512,11 @@ def main():
     # per-kernel durations are those of kernels that have the chip to themselves.
     pipeline = not args.no_pipeline
 
-    def run_workload(wargs, steps, warmup, record_in_timed=False, pipeline=pipeline):
-        """-> dict(frames, name, elapsed, kernel_ms per frame, film_mean): `warmup` untimed and `steps` timed steps of the workload, then an
-        untimed pass that reads every frame's kernel duration (HIP events recorded by the library around render_kernel only).
-        record_in_timed (the 25-second stress frame): the timed steps themselves read the kernel durations, nothing is rendered twice."""
+    def run_workload(wargs, steps, warmup, record_in_timed=False, pipeline=pipeline, kernel_pass=True, keep_film=False):
+        """-> dict(frames, name, elapsed, kernel_ms per frame, film_mean, film): `warmup` untimed and `steps` timed steps of the workload, then
+        (kernel_pass) an untimed pass that reads every frame's kernel duration (HIP events recorded by the library around render_kernel only).
+        record_in_timed (the 25-second stress frame): the timed steps themselves read the kernel durations, nothing is rendered twice.
+        keep_film: `film` is a host copy of rank 0's film as the last timed step left it (None otherwise)."""
         frames, (FH, FW_), name = workload(wargs)
         film = torch.zeros((FH, FW_, 3), dtype=torch.float32, device=dev) if rank == 0 else None
 
@@ -523,32 +549,61 @@ def main():
             step(record_in_timed)
         barrier()
         elapsed = time.perf_counter() - t0
-        if not record_in_timed:
+        film_mean = float(film.mean().item()) if film is not None else None
+        film_host = film.cpu().numpy() if (keep_film and film is not None) else None
+        if kernel_pass and not record_in_timed:
             for _ in range(1 if frames[0].samples > 2e10 else max(1, min(steps, 3))):
                 step(True)
             barrier()
-        t = torch.tensor([elapsed] + [sum(k) / len(k) for k in kernel_ms], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed] + ([sum(k) / len(k) for k in kernel_ms] if (kernel_pass or record_in_timed) else []), dtype=torch.float64, device=dev)
         if world > 1:
             tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         return {"frames": frames, "name": name, "elapsed": float(t[0].item()), "kernel_ms": [float(v) for v in t[1:].tolist()], "priming": priming,
-                "film_mean": float(film.mean().item()) if film is not None else None}
+                "film_mean": film_mean, "film": film_host}
 
-    R = run_workload(args, args.steps, args.warmup)
+    R = run_workload(args, args.steps, args.warmup, kernel_pass=args.full, keep_film=bool(args.dump_outputs))
     frames, name, elapsed, frame_kernel_ms = R["frames"], R["name"], R["elapsed"], R["kernel_ms"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, R["film"])
     # the same K steps with nothing overlapped (skipped for the 20-second stress frame, where a launch's start-up and tail are 1e-5 of it)
     R1 = None
-    if pipeline and frames[0].samples <= 2e10:
+    if args.full and pipeline and frames[0].samples <= 2e10:
         R1 = run_workload(args, args.steps, 1, pipeline=False)
 
     if rank == 0:
         samples_per_step = sum(fr.samples for fr in frames)
         ms_per_step = elapsed / args.steps * 1e3
         value = samples_per_step * args.steps / elapsed / 1e6
+        iteration = args.integrator == A.INTEGRATOR_PATH_TRACING_ITERATION
+        both_mis = frames[0].params.direct_sample == A.DIRECT_BOTH_MIS and iteration
+        p0 = frames[0].params
+        line = {
+            "schema": 6,   # round of the line's layout: since 5 `value` is the pipelined rate (`single_frame.value` continues rounds 1-4's series) and `roofline.frac` the floor model's
+            "metric": "Msamples/s (paths*spp)", "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "launch_mode": "pipelined (consecutive frames on two streams)" if pipeline else "single frame (one stream, nothing overlapped)",
+            "kernels": "the library's table (kyhip_set_jit(0) for everything timed here; this process started in mode %s)" % JIT_DEFAULT_MODE,
+            "pipeline_priming_steps": R["priming"],   # untimed steps beyond `warmup` that brought the second stream's buffers into being (0 when warmup >= 2)
+            "single_frame": ({"value": samples_per_step * args.steps / R1["elapsed"] / 1e6, "unit": "Msamples/s", "ms_per_step": R1["elapsed"] / args.steps * 1e3,
+                              "steps": args.steps, "note": "the same steps with every frame on one stream: no overlap of a frame's start with the previous frame's tail"}
+                             if R1 else ({"value": value, "unit": "Msamples/s", "ms_per_step": ms_per_step, "steps": args.steps} if not pipeline else None)),
+            "ranks": ranks, "communicator": comm,
+            "config": {"workload": name, "frames": [fr.label for fr in frames], "width": p0.width, "height": p0.height, "spp": p0.samples_per_pixel,
+                       "max_path_depth": p0.max_path_depth, "direct_sample": {0: "idle", 4: "bsdf", 8: "light", 16: "bsdf_mis", 32: "light_mis", 48: "both_mis"}[p0.direct_sample],
+                       "integrator": {6: "direct_lighting", 8: "simple_path_tracing_recursion", 9: "path_tracing_recursion", 10: "path_tracing_recursion_defered", 11: "path_tracing_iteration"}[args.integrator],
+                       "seed": p0.seed, "tile": [p0.tile_w, p0.tile_h],
+                       "parallelism": "image tiles interleaved over %d GPU(s), one film-tile gather per frame; launches %s" % (world, "pipelined on two streams" if pipeline else "on one stream")},
+            "film_mean": R["film_mean"],
+        }
+        if not args.full:
+            print(json.dumps(line), flush=True)
+            if world > 1:
+                tdist.destroy_process_group()
+            return
         # roofline of the dominant kernel (render_kernel): one launch per frame; the figure is over the step's launches
         achieved, launch_bytes = contract_frac(frames, frame_kernel_ms, world)
         kernel_total_ms = sum(frame_kernel_ms)
-        iteration = args.integrator == A.INTEGRATOR_PATH_TRACING_ITERATION
-        both_mis = frames[0].params.direct_sample == A.DIRECT_BOTH_MIS and iteration
         # counters of the real bound: profiles/valu.json and profiles/hbm_traffic.json hold what a builder-run rocprofv3 session measured
         # (tools/final_profiles.sh -> tools/make_valu_json.py).  They are NOT measured by this run: `source` names the files, and `stale` says
         # whether this run's kernel time has moved more than 2 % away from the profiled launch (after scaling to the same sample count).
@@ -568,7 +623,6 @@ def main():
                 valu["lane_slot_frac"] = valu["issue_frac_2clk"] * valu["lane_occupancy"]   # useful lane-slots / (2-clock issue x 64 lanes): the kernel's own roofline fraction
             if same_workload and valu.get("hbm_bytes_per_launch") and valu.get("samples_per_launch"):
                 traffic = valu["hbm_bytes_per_launch"] * (samples_per_step / world) / valu["samples_per_launch"]
-        p0 = frames[0].params
         # the design-independent roofline: useful lane-instructions of the launch set over the measured kernel time, against the chip's lane-slots
         props = torch.cuda.get_device_properties(dev)
         peak_tlaneops = props.multi_processor_count * 128 * MAX_CLOCK_HZ / 1e12   # 256 CUs x 4 SIMDs x 32 lanes per clock x 2.4 GHz = 78.6 (half the guide's 157.3 TFLOP/s, which counts an FMA as two)
@@ -609,49 +663,30 @@ def main():
         frac = (model_achieved / peak_tlaneops) if model_achieved is not None else None
         if exceeds:
             frac, model_achieved = lane_slot_frac, lane_slot_frac * peak_tlaneops
-        line = {
-            "schema": 6,   # round of the line's layout: since 5 `value` is the pipelined rate (`single_frame.value` continues rounds 1-4's series) and `roofline.frac` the floor model's
-            "metric": "Msamples/s (paths*spp)", "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "launch_mode": "pipelined (consecutive frames on two streams)" if pipeline else "single frame (one stream, nothing overlapped)",
-            "kernels": "the library's table (kyhip_set_jit(0) for everything timed here; this process started in mode %s)" % JIT_DEFAULT_MODE,
-            "pipeline_priming_steps": R["priming"],   # untimed steps beyond `warmup` that brought the second stream's buffers into being (0 when warmup >= 2)
-            "single_frame": ({"value": samples_per_step * args.steps / R1["elapsed"] / 1e6, "unit": "Msamples/s", "ms_per_step": R1["elapsed"] / args.steps * 1e3,
-                              "steps": args.steps, "note": "the same steps with every frame on one stream: no overlap of a frame's start with the previous frame's tail"}
-                             if R1 else ({"value": value, "unit": "Msamples/s", "ms_per_step": ms_per_step, "steps": args.steps} if not pipeline else None)),
-            "ranks": ranks, "communicator": comm,
-            "config": {"workload": name, "frames": [fr.label for fr in frames], "width": p0.width, "height": p0.height, "spp": p0.samples_per_pixel,
-                       "max_path_depth": p0.max_path_depth, "direct_sample": {0: "idle", 4: "bsdf", 8: "light", 16: "bsdf_mis", 32: "light_mis", 48: "both_mis"}[p0.direct_sample],
-                       "integrator": {6: "direct_lighting", 8: "simple_path_tracing_recursion", 9: "path_tracing_recursion", 10: "path_tracing_recursion_defered", 11: "path_tracing_iteration"}[args.integrator],
-                       "seed": p0.seed, "tile": [p0.tile_w, p0.tile_h],
-                       "parallelism": "image tiles interleaved over %d GPU(s), one film-tile gather per frame; launches %s" % (world, "pipelined on two streams" if pipeline else "on one stream")},
-            # The kernel keeps all path state in registers and LDS and is bound by VALU issue, so the roofline that bounds it is lane-slots:
-            # `achieved` = USEFUL lane-instructions (the reference's event counts x the least work that decides each, `valu_model`: a floor under what any
-            # kernel must execute) over the kernel time measured live with HIP events; `peak` = CUs x 4 SIMDs x 32 lanes per clock x the maximum engine
-            # clock; `lane_slot_frac` = the active lane-instructions the kernel really executed (its counters, profiles/valu.json) over the same peak and
-            # time: frac <= lane_slot_frac <= 1, the gap between the two is instructions that do no path arithmetic.  `contract` keeps SURVEY 8(d)'s figure -- ALGORITHMIC bytes of an HBM
-            # ray-pool tracer over the same kernel time against 8 TB/s -- which stopped bounding anything at 14.7 Gsamples/s because those bytes
-            # never move here; `traffic` is what the memory side really saw (profiled build only); `valu` are the kernel's own utilisation counters.
-            "roofline": {"bound": "valu", "achieved": model_achieved, "peak": peak_tlaneops, "unit": "Tlaneop/s (useful fp32 / int32 VALU lane-instructions per second)",
-                         "frac": frac,
-                         "lane_slot_frac": lane_slot_frac, "executed_lane_instr_per_sample": executed_per_sample,
-                         "useful_lane_instr_per_sample": (model_ops / (samples_per_step / world)) if model_ops is not None else None,
-                         "valu_model_exceeds_executed": exceeds,
-                         #  why the check above is None when it is: the counter set of profiles/valu.json describes other kernel sources or another workload
-                         "valu_counters_status": ("current" if exceeds is not None else
-                                                  ("none for this workload" if not valu else (valu.get("stale_reason") or ("stale: kernel time moved" if valu.get("stale") else "no executed figure")))),
-                         "traffic": traffic, "traffic_source": (valu or {}).get("source") if traffic is not None else None,
-                         "kernel": "render_kernel", "kernel_ms": kernel_total_ms, "kernel_ms_per_frame": frame_kernel_ms,
-                         "samples_per_launch_set": samples_per_step // world,
-                         "valu_model": {"frames": model_frames, "lane_op_costs": LANE_OP, "counters_source": "tests/golden/work_counters.json (CPU oracle; SURVEY section 6 for the reference's own)",
-                                        "peak_definition": "%d CUs x 4 SIMDs x 32 lanes/clk x %.2f GHz (maximum engine clock)" % (props.multi_processor_count, MAX_CLOCK_HZ / 1e9)} if model_ops is not None else None,
-                         "contract": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                                      "algorithmic_bytes_per_sample": launch_bytes * world / samples_per_step,
-                                      "note": "SURVEY 8(d): 128 B per path iteration + 12 B of film per sample; a throughput-equivalent, these bytes never move"},
-                         "valu": valu},
-            "film_mean": R["film_mean"],
-        }
+        # The kernel keeps all path state in registers and LDS and is bound by VALU issue, so the roofline that bounds it is lane-slots:
+        # `achieved` = USEFUL lane-instructions (the reference's event counts x the least work that decides each, `valu_model`: a floor under what any
+        # kernel must execute) over the kernel time measured live with HIP events; `peak` = CUs x 4 SIMDs x 32 lanes per clock x the maximum engine
+        # clock; `lane_slot_frac` = the active lane-instructions the kernel really executed (its counters, profiles/valu.json) over the same peak and
+        # time: frac <= lane_slot_frac <= 1, the gap between the two is instructions that do no path arithmetic.  `contract` keeps SURVEY 8(d)'s figure -- ALGORITHMIC bytes of an HBM
+        # ray-pool tracer over the same kernel time against 8 TB/s -- which stopped bounding anything at 14.7 Gsamples/s because those bytes
+        # never move here; `traffic` is what the memory side really saw (profiled build only); `valu` are the kernel's own utilisation counters.
+        line["roofline"] = {"bound": "valu", "achieved": model_achieved, "peak": peak_tlaneops, "unit": "Tlaneop/s (useful fp32 / int32 VALU lane-instructions per second)",
+                            "frac": frac,
+                            "lane_slot_frac": lane_slot_frac, "executed_lane_instr_per_sample": executed_per_sample,
+                            "useful_lane_instr_per_sample": (model_ops / (samples_per_step / world)) if model_ops is not None else None,
+                            "valu_model_exceeds_executed": exceeds,
+                            #  why the check above is None when it is: the counter set of profiles/valu.json describes other kernel sources or another workload
+                            "valu_counters_status": ("current" if exceeds is not None else
+                                                     ("none for this workload" if not valu else (valu.get("stale_reason") or ("stale: kernel time moved" if valu.get("stale") else "no executed figure")))),
+                            "traffic": traffic, "traffic_source": (valu or {}).get("source") if traffic is not None else None,
+                            "kernel": "render_kernel", "kernel_ms": kernel_total_ms, "kernel_ms_per_frame": frame_kernel_ms,
+                            "samples_per_launch_set": samples_per_step // world,
+                            "valu_model": {"frames": model_frames, "lane_op_costs": LANE_OP, "counters_source": "tests/golden/work_counters.json (CPU oracle; SURVEY section 6 for the reference's own)",
+                                           "peak_definition": "%d CUs x 4 SIMDs x 32 lanes/clk x %.2f GHz (maximum engine clock)" % (props.multi_processor_count, MAX_CLOCK_HZ / 1e9)} if model_ops is not None else None,
+                            "contract": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                                         "algorithmic_bytes_per_sample": launch_bytes * world / samples_per_step,
+                                         "note": "SURVEY 8(d): 128 B per path iteration + 12 B of film per sample; a throughput-equivalent, these bytes never move"},
+                            "valu": valu}
         default_line = world == 1 and args.workload == "cornell" and both_mis and not (args.width or args.height or args.spp or args.depth)
         if default_line and not args.no_extra:
             line["extra_workloads"] = extra_workloads(args, run_workload, peak_tlaneops, lib, local_rank, kernel_total_ms, parity=not args.no_cpu_baseline)

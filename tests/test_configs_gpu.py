@@ -251,7 +251,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     (pipelined by default, --no-pipeline for the single-frame rate), both rates are in the line, and so is which device each rank used."""
     import sys
     env = dict(os.environ, KY_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
-    args = ["--steps", "2", "--warmup", "1", "--workload", "batch", "--spp", "16", "--width", "256", "--no-cpu-baseline"]
+    args = ["--steps", "2", "--warmup", "1", "--workload", "batch", "--spp", "16", "--width", "256", "--no-cpu-baseline", "--full"]
     bench = os.path.join(ROOT, "bench.py")
     torchrun = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(29700 + os.getpid() % 200), bench, "--gpus", "2"]
@@ -293,6 +293,22 @@ def test_bench_two_ranks_with_masked_devices(tmp_path):
                       "--master-port", str(29950 + os.getpid() % 40), bench, "--gpus", "2"] + args, env, tmp_path)
     assert j2["n_gpus"] == 2 and j2["film_mean"] == j1["film_mean"] > 0.01
     assert [(r["local_rank"], r["hip_ordinal"], r["visible_devices"], r["mask"]) for r in j2["ranks"]] == [(0, 0, 1, "0"), (1, 0, 1, "0")]
+
+
+def test_bench_plain_line_and_dumped_film(tmp_path):
+    """A plain bench.py run times its K steps and prints the headline, nothing else (the roofline, the single-frame rate and the CPU baseline
+    are --full's); --dump-outputs writes the film of the last timed step, the same film on every run with the same arguments."""
+    import sys
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "cornell", "--spp", "16", "--width", "256",
+            "--height", "192"]
+    j1 = _bench_line(args + ["--dump-outputs", str(tmp_path / "a")], dict(os.environ), tmp_path)
+    j2 = _bench_line(args + ["--dump-outputs", str(tmp_path / "b")], dict(os.environ), tmp_path)
+    for j in (j1, j2):
+        assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0 and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert not ({"roofline", "cpu_baseline", "extra_workloads", "parity_gate"} & set(j))
+    a, b = np.load(tmp_path / "a" / "film.npy"), np.load(tmp_path / "b" / "film.npy")
+    assert a.shape == (192, 256, 3) and a.dtype == np.float32 and np.array_equal(a, b)
+    assert abs(float(a.mean()) - j1["film_mean"]) < 1e-6 and j1["film_mean"] > 0.01
 
 
 def test_c2_headline_frame_through_the_cpp_driver(A, api, O, tmp_path):

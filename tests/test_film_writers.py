@@ -2,6 +2,7 @@
 store_bmp_impl, store_hdr_impl) against an independent numpy restatement of ky.cpp:1548, 1646-1782 (oracle/film_writers.py),
 byte for byte; the numpy BMP routine itself is pinned by the file the REFERENCE BINARY writes (smallpt_rewrite.cpp carries
 the same store_bmp_impl)."""
+import hashlib
 import os
 import subprocess
 import tempfile
@@ -62,15 +63,22 @@ def test_numpy_bmp_header_is_the_reference_binarys():
     assert mine[:54] == g["header"].tobytes() and len(mine) == int(g["file_bytes"])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_EXE), reason="oracle/_ref/smallpt_rewrite not built (needs /root/reference)")
 def test_numpy_bmp_reproduces_the_reference_binarys_file(A, O):
     """Whole file, every byte: the reference renders and writes image.bmp; the oracle renders the same film (byte-exact
-    restatement, tests/test_smallpt_rewrite.py) and the numpy writer encodes it."""
+    restatement, tests/test_smallpt_rewrite.py) and the numpy writer encodes it.  Where oracle/_ref/smallpt_rewrite is not built
+    (`make -C oracle ref` needs the reference tree), the file is the one the committed fixture records -- made by that binary
+    (tests/golden/make_smallpt_rewrite_fixture.py): its 54-byte header, its length and the SHA-256 of its pixels."""
+    film = O.sprw_render(O.sprw_scene(), A.SmallptParams(1024, 768, 4, 1234, 10, A.SP_VARIANT_REWRITE), rng_mode=1)
+    mine = FW.bmp_bytes(film)          # a float64 film: smallpt_rewrite's Float is double, GammaEncoding identical otherwise
+    if not os.path.exists(REF_EXE):
+        g = np.load(GOLD)
+        assert len(mine) == int(g["file_bytes"]) == 54 + 1024 * 768 * 3 and mine[:54] == g["header"].tobytes()
+        px = np.frombuffer(mine[54:], np.uint8).reshape(768, 1024, 3)[::-1, :, ::-1]   # bottom-up BGR -> top-down RGB, as the fixture hashes it
+        assert hashlib.sha256(np.ascontiguousarray(px).tobytes()).digest() == g["sha256"].tobytes()
+        return
     with tempfile.TemporaryDirectory() as d:
         subprocess.check_call([REF_EXE, "16"], cwd=d, stderr=subprocess.DEVNULL)
         ref = open(os.path.join(d, "image.bmp"), "rb").read()
-    film = O.sprw_render(O.sprw_scene(), A.SmallptParams(1024, 768, 4, 1234, 10, A.SP_VARIANT_REWRITE), rng_mode=1)
-    mine = FW.bmp_bytes(film)          # a float64 film: smallpt_rewrite's Float is double, GammaEncoding identical otherwise
     assert len(mine) == len(ref)
     diff = np.flatnonzero(np.frombuffer(mine, np.uint8) != np.frombuffer(ref, np.uint8))
     assert diff.size == 0, diff[:10]

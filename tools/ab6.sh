@@ -3,7 +3,7 @@
 # (single stream, 3 timed steps + 1 warm-up; the first name is usually repeated at the end to show the box's drift)
 ARGS="$1"; shift
 for v in "$@"; do
-  KYHIP_LIB=$PWD/build_variants/$v.so python3 bench.py $ARGS --steps 3 --warmup 1 --no-pipeline --no-cpu-baseline --no-extra 2>/dev/null | python3 -c "
+  KYHIP_LIB=$PWD/build_variants/$v.so python3 bench.py $ARGS --steps 3 --warmup 1 --no-pipeline --full --no-cpu-baseline --no-extra 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
