@@ -242,6 +242,14 @@ int         kyhip_device_count(void);
    (tiles * tile_w * tile_h * 3).  Pure host arithmetic. */
 int64_t kyhip_shard_tile_count(const ky_render_params* params);
 int64_t kyhip_shard_float_count(const ky_render_params* params);
+/* The film's range rule (DESIGN.md "Film").  A launch adds each pixel's radiance to a signed 32.32 fixed-point word in terms (chunk sums, samples,
+   deferred shadow rays); N is the most terms one word can receive in a launch of `params` on a scene of n_lights lights, on engine 0 (lane) or 1
+   (queue; path_tracing_iteration only, other integrators run on the lane engine), with deferred shadow rays (deferred = 1) or without; n_lights
+   0 .. KYHIP_MAX_LIGHTS.  Every term at or beyond +-T, T = min(2e9, 2^31 / N) as a float rounded down, sets the pixel's +inf / -inf flag instead of
+   being added, so the word never wraps; *limit (may be NULL) receives T.  Returns N, or KY_ERR_LIMIT when T would be below 1.  kyhip_render and its
+   device variants refuse with KY_ERR_LIMIT, before any device work, a launch whose count with deferred shadow rays (the largest of its counts) is
+   such.  Pure host arithmetic. */
+int64_t kyhip_film_term_limit(const ky_render_params* params, int n_lights, int engine, int deferred, float* limit);
 
 /*
  * kyhip_render -- drop-in for integrator_t::render(scene, sampler, film) (ky.cpp:3689-3729).

@@ -107,6 +107,7 @@ KYHIP_SYMBOLS = {
     "kyhip_device_count": (C.c_int, []),
     "kyhip_shard_tile_count": (C.c_int64, [PP]),
     "kyhip_shard_float_count": (C.c_int64, [PP]),
+    "kyhip_film_term_limit": (C.c_int64, [PP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "kyhip_render": (C.c_int, [C.c_int, SP, PP, C.c_void_p, C.c_size_t]),
     "kyhip_workspace_bytes": (C.c_size_t, [PP]),
     "kyhip_render_tiles_device": (C.c_int, [C.c_int, SP, PP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

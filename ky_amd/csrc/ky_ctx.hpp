@@ -43,7 +43,8 @@ struct DevBuf {
 struct StreamState {
     bool used = false;
     hipStream_t stream = nullptr;
-    unsigned* d_counter = nullptr;
+    unsigned* d_counter = nullptr;         // word 0: the render kernels' work counter; word 1: the launch's film term limit (film_limit, ky_device.hpp) ...
+    uint32_t counter_limit_bits = 0;       // ... as last written on this state's stream (0: not yet -- a limit is >= 1)
     void* ws = nullptr;
     size_t ws_bytes = 0;
     bool ws_clean = false;                 // `ws` and the work counter hold zeros: the last frame's resolve_kernel put them back (no fills before the next frame's launch)

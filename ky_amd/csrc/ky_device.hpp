@@ -98,7 +98,7 @@ KY_DEV bool is_black_bits(const float* c) {
 }
 
 // One channel of a film sum -> what goes into the 32.32 fixed-point accumulator and into the pixel's flag word, without a branch:
-// NaN, +inf and -inf (or beyond the accumulator's range) set flag bits 1 << ch, 8 << ch, 64 << ch and add nothing.
+// NaN, +inf and -inf (or a term at or beyond the launch's term limit, film_limit below) set flag bits 1 << ch, 8 << ch, 64 << ch and add nothing.
 // rint(a * 2^32) as a two's-complement 64-bit number for |a| <= 2e9, in single precision: the integer part and the fraction are converted apart.
 // floor(|a|) < 2^31 converts exactly; |a| - floor(|a|) is exact (a multiple of |a|'s ulp with fewer significant bits than |a|); times 2^32 it is exact
 // too, an integer already when it is 2^24 or more and rounded to the nearest even integer by v_rndne_f32 when it is less, and at most 2^32 - 2^8.
@@ -111,20 +111,27 @@ KY_DEV unsigned long long fixed_from_float(float a) {
     const unsigned long long v = ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
     return a < 0 ? 0ull - v : v;
 }
-KY_DEV unsigned long long film_fixed(float a, int ch, unsigned& flags) {
-    const bool nan = a != a, pos = a > 2.0e9f, neg = a < -2.0e9f;
+// The launch's term limit T (DESIGN.md "Film", range rule): a term the launch adds to a pixel's 32.32 word lies in (-T, T), or it sets the word's +inf / -inf
+// flag bit instead.  The host picks T = min(2e9, 2^31 / N) for the N terms one word can receive in the launch (film_term_limit, ky_pack.cpp), so the word never
+// wraps; T >= 1, so for non-negative radiance a flagged term is exact (it alone makes the pixel 1).  The host leaves T in word 1 of the work-counter block, and
+// the kernels read it where a term is classified instead of holding it across the render loop: as a kernel argument it stayed live in an SGPR through the loop
+// and cost the hot kernels 18 (Cornell) and 7 (Veach) more spilled SGPRs, 1.7 and 3.2 %.  A relaxed atomic load, which the compiler does not hoist out of the loop.
+KY_DEV float film_limit(const unsigned* counter) {
+    return __uint_as_float(__hip_atomic_load(counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+// The limit to classify the three channels c of one term by: a term whose channels are non-negative and sum to less than 1 is below every accepted launch's T
+// (T >= 1), so 1 classifies it the same way and the load is skipped.  A load per term measured 35 % of configs[2] on the deferred shadow rays' resolve.
+KY_DEV float film_limit_for(const float* c, const unsigned* counter) {
+    float limit = 1.f;
+    if (!(fminf(fminf(c[0], c[1]), c[2]) >= 0.f && c[0] + c[1] + c[2] < 1.f)) limit = film_limit(counter);
+    return limit;
+}
+// `limit` is film_limit() (or film_limit_for()): a term in (-limit, limit) is added, one at or beyond it is flagged.
+KY_DEV unsigned long long film_fixed(float a, float limit, int ch, unsigned& flags) {
+    const bool nan = a != a, pos = a >= limit, neg = a <= -limit;
     flags |= (nan ? 1u << ch : 0u) | (pos ? 8u << ch : 0u) | (neg ? 64u << ch : 0u);
     const float b = (nan | pos | neg) ? 0.f : a;
     return fixed_from_float(b);
-}
-
-// float -> 32.32 fixed point (|a| <= 2e9): exact for |a| >= 2^-8, truncated below
-KY_DEV long long to_fixed32(float a) {
-    const float aa = fabsf(a);
-    const float hi = floorf(aa);
-    const float fr = aa - hi;
-    const unsigned long long v = ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)(fr * 4294967296.0f);
-    return a < 0 ? -(long long)v : (long long)v;
 }
 
 constexpr float K_PI = 3.14159265358979323846f;
@@ -1710,6 +1717,7 @@ struct ShadowQueue {
     unsigned long long* c_def;      // LDS: [3][256] fixed-point sums of resolved contributions, per lane
     unsigned long long* accum;      // global fixed-point accumulators of the shard
     unsigned* flags;                // global NaN / inf flags of the shard
+    const unsigned* counter;        // the launch's work counter; word 1: the term limit (film_limit) -- every resolved ray is one term of its pixel's word
 };
 struct SqRay {
     f3 o, d, c;
@@ -1733,9 +1741,10 @@ KY_DEV void sq_trace(SceneRef S, const ShadowQueue& q, const SqRay& r) {
     const int pix = (int)(r.tag >> 6), owner = (int)((threadIdx.x & ~63u) | (r.tag & 63u));
     const bool local = q.c_pix[owner] == pix;   // the lane that pushed the ray is still on that pixel: its LDS sum takes it
     unsigned fl = 0;
+    const float limit = film_limit_for(c, q.counter);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const unsigned long long fx = film_fixed(c[ch], ch, fl);   // NaN / +-inf: flag bits, nothing added
+        const unsigned long long fx = film_fixed(c[ch], limit, ch, fl);   // NaN / +-inf / beyond the limit: flag bits, nothing added
         if (fx != 0) {
             if (local) atomicAdd(&q.c_def[ch * 256 + owner], fx);
             else atomicAdd(&q.accum[(size_t)pix * 3 + ch], fx);

@@ -30,6 +30,16 @@ bool valid_params(const ky_render_params* p);
 bool shard_in_range(const ky_render_params* p);
 ShardConst make_shard(const ky_render_params* p);
 RenderConst make_rc(const ky_render_params* p);
+// The film's range rule (DESIGN.md "Film"): N = the most terms one accumulator word can receive in a launch of p (n_lights lights, on the queue engine or
+// the lane engine with or without deferred shadow rays), and the term limit T = min(2e9, 2^31 / N) as a float rounded down (0 when it is below 1:
+// such a launch is refused with KY_ERR_LIMIT).  n_lights: 0 .. KYHIP_MAX_LIGHTS.
+long long film_term_count(const ky_render_params* p, int n_lights, bool queue_engine, bool deferred);
+float film_term_limit(long long n_terms);
+// Whether every kernel a launch of p on a scene of n_lights lights may run on has a term limit T >= 1: the count with deferred shadow rays (where the strategy
+// has them) bounds every other one.  film_range_check: KY_OK, or KY_ERR_LIMIT with the message -- the render entry points call it next to shard_in_range,
+// before any device work.
+bool film_in_range(const ky_render_params* p, int n_lights);
+int film_range_check(const ky_render_params* p, const ky_scene* scene);
 inline size_t workspace_bytes_for(const ShardConst& s) { return (size_t)s.n_pix * (3 * sizeof(unsigned long long) + sizeof(unsigned)); }   // per pixel: 3 x 64-bit fixed-point sums + one flag word
 
 // ---- scene packing (ky_pack.cpp) ----

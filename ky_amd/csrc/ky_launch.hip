@@ -372,6 +372,19 @@ static const Variant* pick_variant(const ky_render_params* p, const DScene* pack
 }
 
 }  // extern "C"
+// The launch's film term limit into word 1 of the stream state's counter block (film_limit, ky_device.hpp), stream-ordered before the kernel; written only when it
+// changes (a run of frames with the same parameters writes it once).  film_in_range has made sure that every count a launch can have leaves a limit >= 1.
+static int set_film_limit(StreamState* st, long long n_terms, hipStream_t stream) {
+    const float t = film_term_limit(n_terms);
+    if (t == 0.f) return fail(KY_ERR_DEVICE, "internal: %lld film terms per pixel passed film_in_range", n_terms);
+    uint32_t bits;
+    std::memcpy(&bits, &t, sizeof bits);
+    if (st->counter_limit_bits != bits) {
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(st->d_counter + 1), (int)bits, 1, stream));
+        st->counter_limit_bits = bits;
+    }
+    return KY_OK;
+}
 int kyh::render_replay_feat(const ky_scene* scene, const ky_render_params* p, const DScene* packed) {   // (ky_ctx.hpp)
     const Variant* v = pick_variant(p, packed, shadow_queue_wanted(scene), p->width * p->height);
     return v != nullptr ? (v->feat & (KY_FEAT_BOXES | KY_FEAT_SINGLE_ENV)) : 0;
@@ -383,6 +396,7 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
                               size_t workspace_bytes, void* stream_) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
     if (!shard_in_range(p)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices (%d x %d, %d spp)", p->width, p->height, p->samples_per_pixel);
+    if (film_range_check(p, scene) != KY_OK) return KY_ERR_LIMIT;
     if (!d_tiles) return fail(KY_ERR_INVALID_VALUE, "d_tiles is NULL");
     DeviceCtx* c;
     int rcode = get_ctx(device, &c);
@@ -434,6 +448,8 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
         const unsigned need_blocks = (unsigned)(((unsigned long long)sh.n_items * 64u + QE_SLOTS - 1) / QE_SLOTS);
         if (grid > need_blocks) grid = need_blocks;
         if (grid < 1) grid = 1;
+        rcode = set_film_limit(st, film_term_count(p, sc->h->n_lights, true, false), stream);
+        if (rcode != KY_OK) return rcode;
         HIP_TRY(hipEventRecord(st->ev0, stream));
         if (variant == 0) hipLaunchKernelGGL((render_kernel_q<false, KY_DIRECT_BOTH_MIS>), dim3(grid), dim3(QE_THREADS), 0, stream, sc->d, rc, sh, st->d_counter, accum, flags);
         else if (variant == 1) hipLaunchKernelGGL((render_kernel_q<false, -1>), dim3(grid), dim3(QE_THREADS), 0, stream, sc->d, rc, sh, st->d_counter, accum, flags);
@@ -527,6 +543,8 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
             HIP_TRY(hipMalloc(&st->d_shadow_queue, blocks * 4 * KY_SQ_ENTRY * KY_SQ_CAP * sizeof(float4)));
             st->sq_blocks = blocks;
         }
+        rcode = set_film_limit(st, film_term_count(p, sc->h->n_lights, false, queue), stream);
+        if (rcode != KY_OK) return rcode;
         HIP_TRY(hipEventRecord(st->ev0, stream));
         float4* queue_mem = queue ? st->d_shadow_queue : (float4*)nullptr;
         if (jk) {

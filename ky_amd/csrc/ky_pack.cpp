@@ -91,6 +91,40 @@ ShardConst make_shard(const ky_render_params* p) {
     return s;
 }
 
+// What adds to a pixel's word in one launch (every pixel belongs to one tile, and a launch renders each of its tiles once):
+//  - queue engine: one term per sample -- film_add_sample when the sample's path ends, at ky_queue.hpp:381 (a miss or the depth cap) or :492 (any other
+//    end), after either of which the slot regenerates;
+//  - lane engine: one term per chunk -- the flush in ky_render.hpp (plain form or film_fixed), which folds in the LDS sum c_def of the chunk's resolved
+//    shadow rays; with deferred shadow rays (QUEUE instantiations: iterative integrator, strategies both_mis / light_mis / light) also one term per
+//    resolved ray (sq_trace, into c_def or straight into the word).  Rays per sample: path_shade runs on vertices with bounces < max_path_depth only
+//    (path_intersect, ky_device.hpp:2130), and sample_all_light pushes per vertex and light one ray under light_mis / light
+//    (estimate_by_emitter_deferred) and two under both_mis (that and estimate_by_bsdf's sq_push_bsdf_query).
+// The sum of the magnitudes of N terms below T is below N T <= 2^31: the word's signed 32.32 value cannot wrap, whatever the order of the adds.
+long long film_term_count(const ky_render_params* p, int n_lights, bool queue_engine, bool deferred) {
+    const long long spp = p->samples_per_pixel;
+    const bool iteration = p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION;
+    if (queue_engine && iteration) return spp;
+    long long n = chunk_count(chunk_plan(p->samples_per_pixel));
+    const int per_light = p->direct_sample == KY_DIRECT_BOTH_MIS ? 2 : (p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) ? 1 : 0;
+    if (deferred && iteration) n += spp * p->max_path_depth * (n_lights > 0 ? n_lights : 0) * per_light;
+    return n;
+}
+float film_term_limit(long long n_terms) {
+    if (n_terms < 1) n_terms = 1;
+    float f = (float)std::min(2.0e9, 2147483648.0 / (double)n_terms);
+    while ((long double)f * (long double)n_terms > 2147483648.0L) f = std::nextafter(f, 0.f);   // rounded down: N T <= 2^31 exactly (N < 2^40: the product is exact)
+    return f >= 1.f ? f : 0.f;
+}
+bool film_in_range(const ky_render_params* p, int n_lights) {
+    n_lights = n_lights < 0 ? 0 : (n_lights > KYHIP_MAX_LIGHTS ? KYHIP_MAX_LIGHTS : n_lights);   // (more lights: pack_scene refuses the scene)
+    return film_term_limit(film_term_count(p, n_lights, false, true)) > 0.f;
+}
+int film_range_check(const ky_render_params* p, const ky_scene* scene) {
+    if (!scene || film_in_range(p, scene->light_count)) return KY_OK;   // (a missing scene is refused where it is read)
+    return fail(KY_ERR_LIMIT, "%d spp, depth %d, %d lights: too many terms per pixel for the film's 32.32 accumulator (DESIGN.md \"Film\")", p->samples_per_pixel,
+                p->max_path_depth, scene->light_count);
+}
+
 RenderConst make_rc(const ky_render_params* p) {
     RenderConst rc{};
     rc.integrator = p->integrator; rc.max_path_depth = p->max_path_depth; rc.strategy = p->direct_sample; rc.seed = p->seed;
@@ -950,6 +984,13 @@ int kyhip_set_shadow_queue(int mode) {
 int64_t kyhip_shard_tile_count(const ky_render_params* p) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
     return make_shard(p).n_tiles;
+}
+int64_t kyhip_film_term_limit(const ky_render_params* p, int n_lights, int engine, int deferred, float* limit) {
+    if (!valid_params(p) || n_lights < 0 || n_lights > KYHIP_MAX_LIGHTS || (engine != 0 && engine != 1)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    const long long n = film_term_count(p, n_lights, engine == 1, deferred != 0);
+    const float t = film_term_limit(n);
+    if (limit) *limit = t;
+    return t > 0.f ? n : fail(KY_ERR_LIMIT, "%lld terms per pixel: no term limit >= 1 keeps their sum inside the 32.32 accumulator", n);
 }
 int64_t kyhip_shard_float_count(const ky_render_params* p) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");

@@ -77,17 +77,16 @@ __device__ unsigned long long g_qe_stats[32];   // [q] batches, [8+q] lanes, [16
 KY_DEV unsigned lds_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 KY_DEV int lds_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-// L = L + Li * (1. / spp) (3717-3721) for one finished sample, straight into the pixel's fixed-point accumulator
-KY_DEV void film_add_sample(unsigned long long* __restrict__ accum, unsigned* __restrict__ flags, int pix, f3 L) {
+// L = L + Li * (1. / spp) (3717-3721) for one finished sample, straight into the pixel's fixed-point accumulator: one term per sample and channel,
+// rounded like every other term (fixed_from_float) and flagged at or beyond the launch's term limit like them (film_fixed, film_limit)
+KY_DEV void film_add_sample(unsigned long long* __restrict__ accum, unsigned* __restrict__ flags, int pix, f3 L, const unsigned* counter) {
     const float v[3] = {L.x, L.y, L.z};
+    const float limit = film_limit_for(v, counter);
     unsigned fl = 0;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const float a = v[ch];
-        if (a != a) fl |= 1u << ch;               // NaN
-        else if (a > 2.0e9f) fl |= 8u << ch;      // +inf (or beyond the accumulator's range)
-        else if (a < -2.0e9f) fl |= 64u << ch;    // -inf
-        else if (a != 0.f) atomicAdd(&accum[(size_t)pix * 3 + ch], (unsigned long long)to_fixed32(a));
+        const unsigned long long fx = film_fixed(v[ch], limit, ch, fl);
+        if (fx != 0) atomicAdd(&accum[(size_t)pix * 3 + ch], fx);
     }
     if (fl) atomicOr(&flags[pix], fl);
 }
@@ -380,7 +379,7 @@ __global__ __launch_bounds__(QE_THREADS, KY_QE_WAVES) void render_kernel_q(const
                     Lo = Lo + beta * (hit ? emission : env);
                 }
                 if (!hit || bounces >= rc.max_path_depth) {
-                    film_add_sample(accum, flags, W.pix[sl], Lo * rc.inv_spp);
+                    film_add_sample(accum, flags, W.pix[sl], Lo * rc.inv_spp, counter);
                     dest = QS_REGEN;
                 } else {
                     const DMat& M = Lds.mat[Lds.hit[hs].material];
@@ -491,7 +490,7 @@ __global__ __launch_bounds__(QE_THREADS, KY_QE_WAVES) void render_kernel_q(const
                     }
                 }
                 if (ended) {
-                    film_add_sample(accum, flags, W.pix[sl], mk3(W.lr[sl], W.lg[sl], W.lb[sl]) * rc.inv_spp);
+                    film_add_sample(accum, flags, W.pix[sl], mk3(W.lr[sl], W.lg[sl], W.lb[sl]) * rc.inv_spp, counter);
                     dest = QS_REGEN;
                 }
             }

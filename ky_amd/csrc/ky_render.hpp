@@ -109,7 +109,7 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
     bool exhausted = false;   // the global counter ran past n_items
     // per lane: the pixel chunk being worked on
     c_pix[tid] = -1;
-    ShadowQueue sq{nullptr, 0, c_pix, c_def, accum, flags};
+    ShadowQueue sq{nullptr, 0, c_pix, c_def, accum, flags, counter};
     if (QUEUE) {
         c_def[tid] = 0; c_def[256 + tid] = 0; c_def[512 + tid] = 0;
         sq.base = queue_mem + (size_t)(blockIdx.x * 4 + (threadIdx.x >> 6)) * (KY_SQ_ENTRY * KY_SQ_CAP);
@@ -144,7 +144,9 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                 // Nearly every chunk sum is three finite, non-negative numbers far below the accumulator's range: when that holds for every flushing lane of the wavefront
                 // (one min3, two adds, two compares; a NaN fails the sum's test) the conversion needs no classification, no sign and no flag word -- 30 instead of 75
                 // VALU instructions for every lane of the wavefront, flushing or not.  Any other wavefront takes the complete form below.
-                const bool plain = fminf(fminf(v[0], v[1]), v[2]) >= 0.f && (v[0] + v[1] + v[2]) < 2.0e9f;
+                // "Small" is below 1: every launch the host accepts has a term limit T >= 1 (film_limit), and the float sum of three non-negative numbers is at
+                // least each of them.  Only the other wavefronts read T.
+                const bool plain = fminf(fminf(v[0], v[1]), v[2]) >= 0.f && (v[0] + v[1] + v[2]) < 1.0f;
                 if (__all(plain)) {
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) {
@@ -157,9 +159,10 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                 } else
                 {
                     unsigned fl = 0;
+                    const float limit = film_limit(counter);
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) {
-                        unsigned long long fx = film_fixed(v[ch], ch, fl);   // NaN / +-inf: flag bits, nothing added
+                        unsigned long long fx = film_fixed(v[ch], limit, ch, fl);   // NaN / +-inf / beyond the limit: flag bits, nothing added
                         if (QUEUE) { fx += c_def[ch * 256 + tid]; c_def[ch * 256 + tid] = 0; }
                         if (fx != 0) atomicAdd(&accum[(size_t)pix * 3 + ch], fx);
                     }

@@ -39,6 +39,16 @@ def rmse(a, b):
     return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
 
 
+def chunk_count(spp):
+    """chunk_plan (ky_shard.hpp): 24-sample bulk chunks, then 256 samples in 16s, 128 in 8s, 64 in 4s at the end of the range."""
+    b3 = spp
+    b2 = b3 - 64 if b3 > 64 else 0
+    b1 = b2 - 128 if b2 > 128 else 0
+    b0 = b1 - 256 if b1 > 256 else 0
+    head = (b0 // 24) * 24
+    return head // 24 + (b1 - head + 15) // 16 + (b2 - b1 + 7) // 8 + (b3 - b2 + 3) // 4
+
+
 class CustomScene:
     """A ky_scene assembled directly from ctypes structs (the C-ABI view of scene_t's public constructor, ky.cpp:3151)."""
 
