@@ -316,20 +316,8 @@ KY_DEV bool full_shape_hit(const DShapeFull& S, f3 o, f3 d, float tmax, float& t
     }
 }
 
-// rectangle_t::intersect (1261-1297) for a planar parallelogram: plane hit, then dual-basis coordinates of the hit
-// point; |u - 0.5| <= 0.5 and |v - 0.5| <= 0.5 is "inside".  A zero denominator gives inf / NaN, which compare false.
-KY_DEV bool par_hit(const float4 q0, const float4 q1, const float4 q2, f3 o, f3 d, float tmax, float& t_out) {
-    const float den = q0.x * d.x + q0.y * d.y + q0.z * d.z;
-    const float num = q0.w - (q0.x * o.x + q0.y * o.y + q0.z * o.z);   // n.(p0 - o)
-    const float t = num * rcp(den);
-    const f3 h = o + t * d;
-    const float u = (h.x * q1.x + h.y * q1.y + h.z * q1.z) - q1.w;
-    const float v = (h.x * q2.x + h.y * q2.y + h.z * q2.z) - q2.w;
-    t_out = t;
-    return (fabsf(u) <= 0.5f) & (fabsf(v) <= 0.5f) & (t > K_SHAPE_EPS) & (t < tmax);
-}
-
-// the same up to the range tests: distance and the hit point's dual-basis coordinates minus one half (hit_update_nearest / hit_update_any test them)
+// rectangle_t::intersect (1261-1297) for a planar parallelogram: plane hit, then dual-basis coordinates of the hit point minus one half; |u| <= 0.5 and |v| <= 0.5
+// is "inside" (hit_update tests them in the scans, par_hit below for one shape).  A zero denominator gives inf / NaN, which compare false.
 // ... for a plank about the x axis (KY_FEAT_X_PLANKS): q0.x = q1.x = q2.y = q2.z = 0, the terms they multiply are left out.  The roundings are written out --
 // explicit fused multiply-adds, and the products that must round on their own as instructions the compiler cannot fuse (mul_sv) -- because the sums must round where the
 // general form's do: the compiler fuses a three-term sum x a + y b + z c as fma(z, c, fma(y, b, x a)), which with x = 0 is fma(z, c, round(y b)); left to itself it fuses
@@ -361,6 +349,14 @@ KY_DEV void par_coords(const float4 q0, const float4 q1, const float4 q2, f3 o, 
     v = (h.x * q2.x + h.y * q2.y + h.z * q2.z) - q2.w;
 }
 
+// one parallelogram given as a record (surf_hit; the lamp's test in estimate_by_bsdf, with tmax = K_INF): true and the distance if eps < t < tmax inside it
+KY_DEV bool par_hit(const float4 q0, const float4 q1, const float4 q2, f3 o, f3 d, float tmax, float& t_out) {
+    float t, u, v;
+    par_coords(q0, q1, q2, o, d, t, u, v);
+    t_out = t;
+    return (fabsf(u) <= 0.5f) & (fabsf(v) <= 0.5f) & (t > K_SHAPE_EPS) & (t < tmax);
+}
+
 // rectangle_t::intersect (1261-1297) for a rectangle in an axis plane (aar_scan below, and the lamp's test in estimate_by_bsdf): the plane hit is one
 // subtraction and one multiply by the ray's reciprocal direction, the inside test needs only the two in-plane coordinates (12 VALU instead of 26).
 // A zero direction component gives inf / NaN, which compare false.
@@ -386,43 +382,38 @@ KY_DEV const DSurf& scene_surf(SceneRef S, int i) { return scene_at<DSurf>(S, op
 // an instruction per 1.84 ns against 1.1 for the vector unit: ky_amd DESIGN 3, "what bounds the kernel").  `ex` is the mask on entry (wave-uniform control
 // flow inside the scan loops: the same for every surface of a scan).
 
-KY_DEV void hit_update_nearest(unsigned long long ex, float u, float ru, float v, float rv, float t, float& tmax, int& best, int i) {
+// What a scan asks of a ray, with where the answer goes.  QNearest: the nearest hit before tmax (tmax shrinks, best becomes the surface's sorted index i);
+// QAny: is there a hit before tmax (occ, a lane flag in a VGPR, is set); QEscape: the same for a ray without an end (tmax = inf: "does the ray leave the scene").
+struct QNearest { static constexpr bool nearest = true, escape = false; float& tmax; int& best; int i; };   // (i is not read for a box: its faces' indices travel in the distances)
+struct QAny { static constexpr bool nearest = false, escape = false; float tmax; unsigned& occ; };
+struct QEscape { static constexpr bool nearest = false, escape = true; unsigned& occ; };
+
+// The pieces the chains below are put together from.  QNearest ends in the two moves, the others in setting the flag; QEscape leaves `t < tmax` out: every finite
+// distance lies before the end, and a distance that is not finite has failed the chain already (its in-plane coordinates are NaN or out of range; a box's distances
+// are at most 1e30 x a coordinate difference: finite).
+#define KY_CMPX_EPS_T   "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
+#define KY_CMPX_T_TMAX  "v_cmpx_lt_f32_e64 %[tmp], %[t], %[tmax]\n\t"
+#define KY_SET_NEAREST  "v_mov_b32_e32 %[tmax], %[t]\n\t" "v_mov_b32_e32 %[best], %[i]\n\t"
+#define KY_SET_OCC      "v_mov_b32_e32 %[occ], 1\n\t"
+#define KY_RESTORE_EXEC "s_mov_b64 exec, %[ex]"
+
+#define KY_CMPX_UV      "v_cmpx_le_f32_e64 %[tmp], |%[u]|, %[ru]\n\t" "v_cmpx_le_f32_e64 %[tmp], |%[v]|, %[rv]\n\t"
+#define KY_UV_IN        [u] "v"(u), [ru] "s"(ru), [v] "v"(v), [rv] "s"(rv), [t] "v"(t)
+template <class Q>
+KY_DEV void hit_update(unsigned long long ex, float u, float ru, float v, float rv, float t, Q q) {
     unsigned long long tmp;
-    asm volatile(
-        "v_cmpx_le_f32_e64 %[tmp], |%[u]|, %[ru]\n\t"
-        "v_cmpx_le_f32_e64 %[tmp], |%[v]|, %[rv]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[t], %[tmax]\n\t"
-        "v_mov_b32_e32 %[tmax], %[t]\n\t"
-        "v_mov_b32_e32 %[best], %[i]\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [tmax] "+v"(tmax), [best] "+v"(best), [tmp] "=&s"(tmp)
-        : [u] "v"(u), [ru] "s"(ru), [v] "v"(v), [rv] "s"(rv), [t] "v"(t), [eps] "s"(K_SHAPE_EPS), [i] "s"(i), [ex] "s"(ex));
-}
-KY_DEV void hit_update_any(unsigned long long ex, float u, float ru, float v, float rv, float t, float tmax, unsigned& occ) {
-    unsigned long long tmp;
-    asm volatile(
-        "v_cmpx_le_f32_e64 %[tmp], |%[u]|, %[ru]\n\t"
-        "v_cmpx_le_f32_e64 %[tmp], |%[v]|, %[rv]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[t], %[tmax]\n\t"
-        "v_mov_b32_e32 %[occ], 1\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [occ] "+v"(occ), [tmp] "=&s"(tmp)
-        : [u] "v"(u), [ru] "s"(ru), [v] "v"(v), [rv] "s"(rv), [t] "v"(t), [tmax] "v"(tmax), [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex));
-}
-// ... for a ray without an end (tmax = inf: "does the ray leave the scene"): every finite distance lies before it, and a distance that is not finite has failed the chain
-// already (its in-plane coordinates are NaN or out of range), so the fourth compare is gone
-KY_DEV void hit_update_any_unbounded(unsigned long long ex, float u, float ru, float v, float rv, float t, unsigned& occ) {
-    unsigned long long tmp;
-    asm volatile(
-        "v_cmpx_le_f32_e64 %[tmp], |%[u]|, %[ru]\n\t"
-        "v_cmpx_le_f32_e64 %[tmp], |%[v]|, %[rv]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_mov_b32_e32 %[occ], 1\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [occ] "+v"(occ), [tmp] "=&s"(tmp)
-        : [u] "v"(u), [ru] "s"(ru), [v] "v"(v), [rv] "s"(rv), [t] "v"(t), [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex));
+    if constexpr (Q::nearest)
+        asm volatile(KY_CMPX_UV KY_CMPX_EPS_T KY_CMPX_T_TMAX KY_SET_NEAREST KY_RESTORE_EXEC
+                     : [tmax] "+v"(q.tmax), [best] "+v"(q.best), [tmp] "=&s"(tmp)
+                     : KY_UV_IN, [eps] "s"(K_SHAPE_EPS), [i] "s"(q.i), [ex] "s"(ex));
+    else if constexpr (Q::escape)
+        asm volatile(KY_CMPX_UV KY_CMPX_EPS_T KY_SET_OCC KY_RESTORE_EXEC
+                     : [occ] "+v"(q.occ), [tmp] "=&s"(tmp)
+                     : KY_UV_IN, [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex));
+    else
+        asm volatile(KY_CMPX_UV KY_CMPX_EPS_T KY_CMPX_T_TMAX KY_SET_OCC KY_RESTORE_EXEC
+                     : [occ] "+v"(q.occ), [tmp] "=&s"(tmp)
+                     : KY_UV_IN, [tmax] "v"(q.tmax), [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex));
 }
 
 // Which form the rectangle loops take (a compile-time choice per instantiation, made by measurement: docs/rounds/round5.md): on the record's byte offset alone
@@ -430,6 +421,19 @@ KY_DEV void hit_update_any_unbounded(unsigned long long ex, float u, float ru, f
 // 0.3-0.7 % SLOWER on configs[1] (its register allocation spills one more SGPR in the bookkeeping block).
 KY_DEV bool aar_by_offset(SceneRef S) { return S.sphere_lights(); }
 
+// one record of aar_scan (at byte offset `off`) against the ray: `oa`, `ia` its origin and reciprocal direction along the plane's axis, `ou_`, `du_`, `ov_`, `dv_` its
+// origin and direction along the two in-plane axes
+template <bool NEAREST>
+KY_DEV void aar_record(SceneRef S, unsigned long long ex, unsigned off, float oa, float ia, float ou_, float du_, float ov_, float dv_, float& tmax, int& best, unsigned& occ_v) {
+    const DAar& r = scene_at<DAar>(S, off);
+    const float4 q0 = r.q0;
+    const float rv = r.q1.x;
+    const float t = (q0.x - oa) * ia;                 // aar_hit
+    const float u = (ou_ + t * du_) - q0.y;
+    const float v = (ov_ + t * dv_) - q0.w;
+    if (NEAREST) hit_update(ex, u, q0.z, v, rv, t, QNearest{tmax, best, __float_as_int(r.q1.y)});   // the surface's sorted index travels in its record
+    else hit_update(ex, u, q0.z, v, rv, t, QAny{tmax, occ_v});
+}
 // the axis-aligned rectangles of one axis: records [first, first + n) of the table at byte offset `aar_off`, whose sorted surface indices are the same
 template <int AXIS, bool NEAREST>
 KY_DEV void aar_scan(SceneRef S, unsigned aar_off, int first, int n, f3 o, f3 d, f3 inv_d, float& tmax, int& best, unsigned& occ_v) {
@@ -444,14 +448,7 @@ KY_DEV void aar_scan(SceneRef S, unsigned aar_off, int first, int n, f3 o, f3 d,
         const unsigned end = off + (unsigned)n * (unsigned)sizeof(DAar);
         do {
             asm volatile("" : "+s"(off));
-            const DAar& r = scene_at<DAar>(S, off);
-            const float4 q0 = r.q0;
-            const float rv = r.q1.x;
-            const float t = (q0.x - oa) * ia;                 // aar_hit
-            const float u = (ou_ + t * du_) - q0.y;
-            const float v = (ov_ + t * dv_) - q0.w;
-            if (NEAREST) hit_update_nearest(ex, u, q0.z, v, rv, t, tmax, best, __float_as_int(r.q1.y));   // the surface's sorted index travels in its record
-            else hit_update_any(ex, u, q0.z, v, rv, t, tmax, occ_v);
+            aar_record<NEAREST>(S, ex, off, oa, ia, ou_, du_, ov_, dv_, tmax, best, occ_v);
             off += (unsigned)sizeof(DAar);
         } while (off != end);
         return;
@@ -459,27 +456,25 @@ KY_DEV void aar_scan(SceneRef S, unsigned aar_off, int first, int n, f3 o, f3 d,
     int i = first;
     for (; i < first + n; ++i) {
         asm volatile("" : "+s"(off));
-        const DAar& r = scene_at<DAar>(S, off);
-        const float4 q0 = r.q0;
-        const float rv = r.q1.x;
-        const float t = (q0.x - oa) * ia;                 // aar_hit
-        const float u = (ou_ + t * du_) - q0.y;
-        const float v = (ov_ + t * dv_) - q0.w;
-        if (NEAREST) hit_update_nearest(ex, u, q0.z, v, rv, t, tmax, best, __float_as_int(r.q1.y));   // the surface's sorted index travels in its record
-        else hit_update_any(ex, u, q0.z, v, rv, t, tmax, occ_v);
+        aar_record<NEAREST>(S, ex, off, oa, ia, ou_, du_, ov_, dv_, tmax, best, occ_v);
         off += (unsigned)sizeof(DAar);
     }
 }
 
+// a sphere record (centre, radius^2 in w) against a ray's line: neg_b = (c - o).d, and the discriminant of the quadratic
+KY_DEV void sph_discr(const float4 c, f3 o, f3 d, float& neg_b, float& discr) {
+    const f3 oc = mk3(c.x, c.y, c.z) - o;
+    neg_b = dot(oc, d);
+    discr = neg_b * neg_b - dot(oc, oc) + c.w;
+}
 // sphere_t::intersect, 1336-1393.  sqrt of a negative discriminant is NaN, which fails both range tests.
 // The second half -- root, two distances, four range tests -- runs only when some lane's LINE meets the sphere (a wave-uniform branch on the discriminants' signs):
 // for a lamp that subtends a thousandth of the sphere of directions that is one wavefront in fifty, and a Veach vertex tests five such lamps three times over.
 // `sparse` (a compile-time constant at every call): the scene's spheres are small lamps (KY_FEAT_SPHERE_LIGHTS).  With the two big spheres of a Cornell box some lane's
 // line nearly always meets the sphere and the branch only costs (configs[1] -1.3 %); with Veach's lamps it pays (configs[2] +1.9 %).
 KY_DEV bool sph_hit(const float4 c, f3 o, f3 d, float tmax, float& t_out, bool sparse = false) {
-    const f3 oc = mk3(c.x, c.y, c.z) - o;
-    const float neg_b = dot(oc, d);
-    const float discr = neg_b * neg_b - dot(oc, oc) + c.w;
+    float neg_b, discr;
+    sph_discr(c, o, d, neg_b, discr);
     bool hit = false;
     t_out = neg_b;   // (read by no caller without a hit)
     if (!sparse || __any(discr >= 0.f)) {
@@ -498,51 +493,31 @@ KY_DEV bool sph_hit(const float4 c, f3 o, f3 d, float tmax, float& t_out, bool s
 // 6 VALU + 1 SALU for the nearest-hit update where four compares, three selects and the index move were 8 + 3; 5 + 1 for the any-hit flag where the lane masks'
 // bookkeeping was 4 + 7.  (A NaN root -- the line misses the sphere -- fails both range tests as before.  The two wait states between a VALU write of VCC and
 // the select that reads it are written out: the compiler's hazard recogniser does not look inside an asm statement.)
-KY_DEV void sph_update_nearest(unsigned long long ex, float neg_b, float discr, float& tmax, int& best, int i) {
-    const float sq = fsqrt(discr);
-    const float t0 = neg_b - sq, t1 = neg_b + sq;
+// QEscape: some crossing lies beyond the epsilon iff the farther one does (a NaN root -- the line misses the sphere -- fails the compare): no select.
+#define KY_SPH_ROOT "v_cmp_lt_f32_e32 vcc, %[eps], %[t0]\n\t" "s_nop 1\n\t" "v_cndmask_b32_e32 %[t], %[t1], %[t0], vcc\n\t"
+template <class Q>
+KY_DEV void sph_update(unsigned long long ex, float neg_b, float discr, Q q) {
     unsigned long long tmp;
-    float t;
-    asm volatile(
-        "v_cmp_lt_f32_e32 vcc, %[eps], %[t0]\n\t"
-        "s_nop 1\n\t"
-        "v_cndmask_b32_e32 %[t], %[t1], %[t0], vcc\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[t], %[tmax]\n\t"
-        "v_mov_b32_e32 %[tmax], %[t]\n\t"
-        "v_mov_b32_e32 %[best], %[i]\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [tmax] "+v"(tmax), [best] "+v"(best), [tmp] "=&s"(tmp), [t] "=&v"(t)
-        : [t0] "v"(t0), [t1] "v"(t1), [eps] "s"(K_SHAPE_EPS), [i] "s"(i), [ex] "s"(ex)
-        : "vcc");
-}
-KY_DEV void sph_update_any(unsigned long long ex, float neg_b, float discr, float tmax, unsigned& occ) {
-    const float sq = fsqrt(discr);
-    const float t0 = neg_b - sq, t1 = neg_b + sq;
-    unsigned long long tmp;
-    float t;
-    asm volatile(
-        "v_cmp_lt_f32_e32 vcc, %[eps], %[t0]\n\t"
-        "s_nop 1\n\t"
-        "v_cndmask_b32_e32 %[t], %[t1], %[t0], vcc\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[t], %[tmax]\n\t"
-        "v_mov_b32_e32 %[occ], 1\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [occ] "+v"(occ), [tmp] "=&s"(tmp), [t] "=&v"(t)
-        : [t0] "v"(t0), [t1] "v"(t1), [tmax] "v"(tmax), [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex)
-        : "vcc");
-}
-// ... without an end: some crossing lies beyond the epsilon iff the farther one does (a NaN root -- the line misses the sphere -- fails the compare)
-KY_DEV void sph_update_any_unbounded(unsigned long long ex, float neg_b, float discr, unsigned& occ) {
-    const float t1 = neg_b + fsqrt(discr);
-    unsigned long long tmp;
-    asm volatile(
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t1]\n\t"
-        "v_mov_b32_e32 %[occ], 1\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [occ] "+v"(occ), [tmp] "=&s"(tmp)
-        : [t1] "v"(t1), [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex));
+    if constexpr (Q::escape) {
+        const float t = neg_b + fsqrt(discr);
+        asm volatile(KY_CMPX_EPS_T KY_SET_OCC KY_RESTORE_EXEC
+                     : [occ] "+v"(q.occ), [tmp] "=&s"(tmp)
+                     : [t] "v"(t), [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex));
+    } else {
+        const float sq = fsqrt(discr);
+        const float t0 = neg_b - sq, t1 = neg_b + sq;
+        float t;
+        if constexpr (Q::nearest)
+            asm volatile(KY_SPH_ROOT KY_CMPX_EPS_T KY_CMPX_T_TMAX KY_SET_NEAREST KY_RESTORE_EXEC
+                         : [tmax] "+v"(q.tmax), [best] "+v"(q.best), [tmp] "=&s"(tmp), [t] "=&v"(t)
+                         : [t0] "v"(t0), [t1] "v"(t1), [eps] "s"(K_SHAPE_EPS), [i] "s"(q.i), [ex] "s"(ex)
+                         : "vcc");
+        else
+            asm volatile(KY_SPH_ROOT KY_CMPX_EPS_T KY_CMPX_T_TMAX KY_SET_OCC KY_RESTORE_EXEC
+                         : [occ] "+v"(q.occ), [tmp] "=&s"(tmp), [t] "=&v"(t)
+                         : [t0] "v"(t0), [t1] "v"(t1), [tmax] "v"(q.tmax), [eps] "s"(K_SHAPE_EPS), [ex] "s"(ex)
+                         : "vcc");
+    }
 }
 
 // A box's faces in one slab test (DBox, ky_scene.hpp; host: find_boxes).  A ray meets the boundary of a convex box at the two ends of the segment it has inside
@@ -559,77 +534,56 @@ KY_DEV float vmax(float a, float b) { float r; asm("v_max_f32_e32 %0, %1, %2" : 
 KY_DEV float vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 KY_DEV float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 KY_DEV float face_tag(float t, float surface_bits) { return __uint_as_float((__float_as_uint(t) & ~15u) | __float_as_uint(surface_bits)); }   // v_and_or_b32 (the surface from its SGPR)
-// one candidate (the entry or the exit point) as a v_cmpx chain like hit_update_nearest's: the box is met, eps < t < tmax, the face is a surface
-KY_DEV void box_candidate(unsigned long long ex, float t_enter, float t_leave, float t, float& tmax, int& best) {
-    unsigned long long tmp;
-    const unsigned surface = __float_as_uint(t) & 15u;
-    asm volatile(
-        "v_cmpx_le_f32_e64 %[tmp], %[te], %[tl]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[t], %[tmax]\n\t"
-        "v_cmpx_ne_u32_e64 %[tmp], %[none], %[s]\n\t"
-        "v_mov_b32_e32 %[tmax], %[t]\n\t"
-        "v_mov_b32_e32 %[best], %[s]\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [tmax] "+v"(tmax), [best] "+v"(best), [tmp] "=&s"(tmp)
-        : [te] "v"(t_enter), [tl] "v"(t_leave), [t] "v"(t), [s] "v"(surface), [eps] "s"(K_SHAPE_EPS), [none] "n"(KY_BOX_NO_FACE), [ex] "s"(ex));
-}
-KY_DEV void box_update_nearest(unsigned long long ex, const float4 q0, const float4 q1, const float4 q2, f3 o, f3 inv_c, float& tmax, int& best) {
+// the slab test's arithmetic: the six tagged plane distances, and where the ray enters and leaves the box
+KY_DEV void box_slab(const float4 q0, const float4 q1, const float4 q2, f3 o, f3 inv_c, float& t_enter, float& t_leave) {
     const float xl = face_tag((q0.x - o.x) * inv_c.x, q0.w), xh = face_tag((q1.x - o.x) * inv_c.x, q1.w);
     const float yl = face_tag((q0.y - o.y) * inv_c.y, q2.x), yh = face_tag((q1.y - o.y) * inv_c.y, q2.y);
     const float zl = face_tag((q0.z - o.z) * inv_c.z, q2.z), zh = face_tag((q1.z - o.z) * inv_c.z, q2.w);
-    const float t_enter = vmax3(vmin(xl, xh), vmin(yl, yh), vmin(zl, zh));
-    const float t_leave = vmin3(vmax(xl, xh), vmax(yl, yh), vmax(zl, zh));
-    box_candidate(ex, t_enter, t_leave, t_enter, tmax, best);
-    box_candidate(ex, t_enter, t_leave, t_leave, tmax, best);   // (after a hit at the entry point tmax <= t_leave: the chain's third compare keeps the entry)
+    t_enter = vmax3(vmin(xl, xh), vmin(yl, yh), vmin(zl, zh));
+    t_leave = vmin3(vmax(xl, xh), vmax(yl, yh), vmax(zl, zh));
 }
-
-// The same for an any-hit query (scene_t::occluded's scan, 3193-3195; an environment light's "does the ray leave the scene"): some face that is a surface is met inside
-// (eps, tmax) iff the entry point or the exit point is such a face's -- two chains that set a flag instead of noting distance and surface.
-KY_DEV void box_candidate_any(unsigned long long ex, float t_enter, float t_leave, float t, float tmax, unsigned& occ) {
+// one candidate (the entry or the exit point) as a v_cmpx chain like hit_update's: the box is met, eps < t < tmax, the face is a surface
+#define KY_CMPX_BOX_MET "v_cmpx_le_f32_e64 %[tmp], %[te], %[tl]\n\t"
+#define KY_CMPX_FACE    "v_cmpx_ne_u32_e64 %[tmp], %[none], %[i]\n\t"
+#define KY_BOX_IN       [te] "v"(t_enter), [tl] "v"(t_leave), [t] "v"(t)
+template <class Q>
+KY_DEV void box_candidate(unsigned long long ex, float t_enter, float t_leave, float t, Q q) {
     unsigned long long tmp;
     const unsigned surface = __float_as_uint(t) & 15u;
-    asm volatile(
-        "v_cmpx_le_f32_e64 %[tmp], %[te], %[tl]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[t], %[tmax]\n\t"
-        "v_cmpx_ne_u32_e64 %[tmp], %[none], %[s]\n\t"
-        "v_mov_b32_e32 %[occ], 1\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [occ] "+v"(occ), [tmp] "=&s"(tmp)
-        : [te] "v"(t_enter), [tl] "v"(t_leave), [t] "v"(t), [tmax] "v"(tmax), [s] "v"(surface), [eps] "s"(K_SHAPE_EPS), [none] "n"(KY_BOX_NO_FACE), [ex] "s"(ex));
+    if constexpr (Q::nearest)
+        asm volatile(KY_CMPX_BOX_MET KY_CMPX_EPS_T KY_CMPX_T_TMAX KY_CMPX_FACE KY_SET_NEAREST KY_RESTORE_EXEC
+                     : [tmax] "+v"(q.tmax), [best] "+v"(q.best), [tmp] "=&s"(tmp)
+                     : KY_BOX_IN, [i] "v"(surface), [eps] "s"(K_SHAPE_EPS), [none] "n"(KY_BOX_NO_FACE), [ex] "s"(ex));
+    else if constexpr (Q::escape)
+        asm volatile(KY_CMPX_BOX_MET KY_CMPX_EPS_T KY_CMPX_FACE KY_SET_OCC KY_RESTORE_EXEC
+                     : [occ] "+v"(q.occ), [tmp] "=&s"(tmp)
+                     : KY_BOX_IN, [i] "v"(surface), [eps] "s"(K_SHAPE_EPS), [none] "n"(KY_BOX_NO_FACE), [ex] "s"(ex));
+    else
+        asm volatile(KY_CMPX_BOX_MET KY_CMPX_EPS_T KY_CMPX_T_TMAX KY_CMPX_FACE KY_SET_OCC KY_RESTORE_EXEC
+                     : [occ] "+v"(q.occ), [tmp] "=&s"(tmp)
+                     : KY_BOX_IN, [tmax] "v"(q.tmax), [i] "v"(surface), [eps] "s"(K_SHAPE_EPS), [none] "n"(KY_BOX_NO_FACE), [ex] "s"(ex));
 }
-KY_DEV void box_update_any(unsigned long long ex, const float4 q0, const float4 q1, const float4 q2, f3 o, f3 inv_c, float tmax, unsigned& occ) {
-    const float xl = face_tag((q0.x - o.x) * inv_c.x, q0.w), xh = face_tag((q1.x - o.x) * inv_c.x, q1.w);
-    const float yl = face_tag((q0.y - o.y) * inv_c.y, q2.x), yh = face_tag((q1.y - o.y) * inv_c.y, q2.y);
-    const float zl = face_tag((q0.z - o.z) * inv_c.z, q2.z), zh = face_tag((q1.z - o.z) * inv_c.z, q2.w);
-    const float t_enter = vmax3(vmin(xl, xh), vmin(yl, yh), vmin(zl, zh));
-    const float t_leave = vmin3(vmax(xl, xh), vmax(yl, yh), vmax(zl, zh));
-    box_candidate_any(ex, t_enter, t_leave, t_enter, tmax, occ);
-    box_candidate_any(ex, t_enter, t_leave, t_leave, tmax, occ);
+// QNearest: after a hit at the entry point tmax <= t_leave, so the chain's third compare keeps the entry.  QAny / QEscape (scene_t::occluded's scan, 3193-3195; an
+// environment light's "does the ray leave the scene"): some face that is a surface is met inside (eps, tmax) iff the entry point or the exit point is such a face's.
+template <class Q>
+KY_DEV void box_update(unsigned long long ex, const float4 q0, const float4 q1, const float4 q2, f3 o, f3 inv_c, Q q) {
+    float t_enter, t_leave;
+    box_slab(q0, q1, q2, o, inv_c, t_enter, t_leave);
+    box_candidate(ex, t_enter, t_leave, t_enter, q);
+    box_candidate(ex, t_enter, t_leave, t_leave, q);
 }
-KY_DEV void box_candidate_any_unbounded(unsigned long long ex, float t_enter, float t_leave, float t, unsigned& occ) {
-    unsigned long long tmp;
-    const unsigned surface = __float_as_uint(t) & 15u;
-    asm volatile(
-        "v_cmpx_le_f32_e64 %[tmp], %[te], %[tl]\n\t"
-        "v_cmpx_lt_f32_e64 %[tmp], %[eps], %[t]\n\t"
-        "v_cmpx_ne_u32_e64 %[tmp], %[none], %[s]\n\t"
-        "v_mov_b32_e32 %[occ], 1\n\t"
-        "s_mov_b64 exec, %[ex]"
-        : [occ] "+v"(occ), [tmp] "=&s"(tmp)
-        : [te] "v"(t_enter), [tl] "v"(t_leave), [t] "v"(t), [s] "v"(surface), [eps] "s"(K_SHAPE_EPS), [none] "n"(KY_BOX_NO_FACE), [ex] "s"(ex));
-}
-// (the distances are at most 1e30 x a coordinate difference: finite, so "before the end" always holds)
-KY_DEV void box_update_any_unbounded(unsigned long long ex, const float4 q0, const float4 q1, const float4 q2, f3 o, f3 inv_c, unsigned& occ) {
-    const float xl = face_tag((q0.x - o.x) * inv_c.x, q0.w), xh = face_tag((q1.x - o.x) * inv_c.x, q1.w);
-    const float yl = face_tag((q0.y - o.y) * inv_c.y, q2.x), yh = face_tag((q1.y - o.y) * inv_c.y, q2.y);
-    const float zl = face_tag((q0.z - o.z) * inv_c.z, q2.z), zh = face_tag((q1.z - o.z) * inv_c.z, q2.w);
-    const float t_enter = vmax3(vmin(xl, xh), vmin(yl, yh), vmin(zl, zh));
-    const float t_leave = vmin3(vmax(xl, xh), vmax(yl, yh), vmax(zl, zh));
-    box_candidate_any_unbounded(ex, t_enter, t_leave, t_enter, occ);
-    box_candidate_any_unbounded(ex, t_enter, t_leave, t_leave, occ);
-}
+// (the chains' pieces stay local to the chains)
+#undef KY_CMPX_EPS_T
+#undef KY_CMPX_T_TMAX
+#undef KY_SET_NEAREST
+#undef KY_SET_OCC
+#undef KY_RESTORE_EXEC
+#undef KY_CMPX_UV
+#undef KY_UV_IN
+#undef KY_SPH_ROOT
+#undef KY_CMPX_BOX_MET
+#undef KY_CMPX_FACE
+#undef KY_BOX_IN
 
 // one shape given as a generic record (KAT entry point, light shapes re-intersected by pdf_direction)
 // `general` false: the caller knows the record is a parallelogram or a sphere (SceneRef::general)
@@ -657,7 +611,7 @@ KY_DEV int trace_nearest(SceneRef S, f3 o, f3 d, float& tmax) {
         for (int k = 0; k < bhead.x; ++k) {
             asm volatile("" : "+s"(off));
             const DBox& B = scene_at<DBox>(S, off);
-            box_update_nearest(ex, B.q0, B.q1, B.q2, o, inv_c, tmax, best);
+            box_update(ex, B.q0, B.q1, B.q2, o, inv_c, QNearest{tmax, best, 0});
             off += (unsigned)sizeof(DBox);
         }
         if (bhead.y > 0) {
@@ -688,7 +642,7 @@ KY_DEV int trace_nearest(SceneRef S, f3 o, f3 d, float& tmax) {
             // (the planks' short form, KY_FEAT_X_PLANKS, is taken by the any-hit scans only: here it is worth another 0.5 % of configs[2], but the sphere-lights kernel's
             // allocation then spills three registers around its five-light loop -- 60 -> 106 GB of memory-side traffic per 9.4e8 samples, docs/rounds/round6.md section 3)
             par_coords(r.q0, r.q1, r.q2, o, d, t, u, v);
-            hit_update_nearest(ex, u, 0.5f, v, 0.5f, t, tmax, best, n_aar + i);
+            hit_update(ex, u, 0.5f, v, 0.5f, t, QNearest{tmax, best, n_aar + i});
             off += (unsigned)sizeof(DPar);
         }
     }
@@ -698,10 +652,9 @@ KY_DEV int trace_nearest(SceneRef S, f3 o, f3 d, float& tmax) {
         for (int i = 0; i < n_sph; ++i) {
             asm volatile("" : "+s"(off));
             const float4 c = scene_at<DSph>(S, off).c;
-            const f3 oc = mk3(c.x, c.y, c.z) - o;
-            const float neg_b = dot(oc, d);
-            const float discr = neg_b * neg_b - dot(oc, oc) + c.w;
-            if (!S.sphere_lights() || __any(discr >= 0.f)) sph_update_nearest(ex, neg_b, discr, tmax, best, n_aar + n_par + i);   // (sph_hit's `sparse` rule)
+            float neg_b, discr;
+            sph_discr(c, o, d, neg_b, discr);
+            if (!S.sphere_lights() || __any(discr >= 0.f)) sph_update(ex, neg_b, discr, QNearest{tmax, best, n_aar + n_par + i});   // (sph_hit's `sparse` rule)
             off += (unsigned)sizeof(DSph);
         }
     }
@@ -718,7 +671,7 @@ KY_DEV int trace_nearest(SceneRef S, f3 o, f3 d, float& tmax) {
 // scene_t::occluded's traversal (3193-3195): any hit inside (eps, tmax) occludes.  `T` (wave-uniform): the table of planar surfaces
 // to test -- S->trav (all), or the occluder table when the ray qualifies for it (DScene::occ).
 KY_DEV bool trace_any_planar(SceneRef S, const DTrav& T, f3 o, f3 d, float tmax) {
-    unsigned occ = 0;   // a lane flag in a VGPR: the scans OR into it (hit_update_any)
+    unsigned occ = 0;   // a lane flag in a VGPR: the scans OR into it (hit_update)
     const unsigned t_off = opaque_off(scene_off(S, &T));
     const int4 head = scene_at<int4>(S, t_off), axis = scene_at<int4>(S, t_off + 16u);   // n_aar, n_par; n_aar_axis[3]
     const int n_aar = head.x, n_par = S.no_par() ? 0 : head.y;
@@ -739,7 +692,7 @@ KY_DEV bool trace_any_planar(SceneRef S, const DTrav& T, f3 o, f3 d, float tmax)
             const DPar& r = scene_at<DPar>(S, off);
             float t, u, v;
             par_coords(r.q0, r.q1, r.q2, o, d, t, u, v, S.x_planks());
-            hit_update_any(ex, u, 0.5f, v, 0.5f, t, tmax, occ);
+            hit_update(ex, u, 0.5f, v, 0.5f, t, QAny{tmax, occ});
             off += (unsigned)sizeof(DPar);
         }
     }
@@ -756,14 +709,13 @@ KY_DEV bool trace_any_round(SceneRef S, bool occ, f3 o, f3 d, float tmax) {
         for (int i = 0; i < n_sph; ++i) {
             asm volatile("" : "+s"(off));
             const float4 c = scene_at<DSph>(S, off).c;
-            const f3 oc = mk3(c.x, c.y, c.z) - o;
-            const float neg_b = dot(oc, d);
-            const float discr = neg_b * neg_b - dot(oc, oc) + c.w;
+            float neg_b, discr;
+            sph_discr(c, o, d, neg_b, discr);
             // sphere-light scenes: a shadow ray is AIMED at a lamp, so its line always meets that lamp -- 2e-3 beyond tmax (3187-3201) -- and with five lamps every sphere is
             // some lane's target.  The root is needed only if some lane's nearer crossing can lie before tmax: neg_b - sqrt(discr) < tmax <=> e < 0 or e^2 < discr, e = neg_b - tmax
             // (no square root; conservative: the far crossing and eps are left to the full test).
             const float e = neg_b - tmax;
-            if (!S.sphere_lights() || __any((discr >= 0.f) & ((e < 0.f) | (e * e < discr)))) sph_update_any(ex, neg_b, discr, tmax, occ_v);
+            if (!S.sphere_lights() || __any((discr >= 0.f) & ((e < 0.f) | (e * e < discr)))) sph_update(ex, neg_b, discr, QAny{tmax, occ_v});
             off += (unsigned)sizeof(DSph);
         }
         occ = occ | (occ_v != 0);
@@ -800,8 +752,8 @@ KY_DEV void aar_scan_any_pair(SceneRef S, unsigned long long ex, unsigned aar_of
         const float tA = (q0.x - oaA) * iaA, tB = (q0.x - oaB) * iaB;
         const float uA = (ouA + tA * duA) - q0.y, uB = (ouB + tB * duB) - q0.y;
         const float vA = (ovA + tA * dvA) - q0.w, vB = (ovB + tB * dvB) - q0.w;
-        hit_update_any_unbounded(ex, uA, q0.z, vA, rv, tA, occA);
-        hit_update_any(ex, uB, q0.z, vB, rv, tB, B.tmax, occB);
+        hit_update(ex, uA, q0.z, vA, rv, tA, QEscape{occA});
+        hit_update(ex, uB, q0.z, vB, rv, tB, QAny{B.tmax, occB});
         off += (unsigned)sizeof(DAar);
     }
 }
@@ -820,8 +772,8 @@ KY_DEV void trace_any_pair(SceneRef S, const AnyRay& A, const AnyRay& B, bool& o
             asm volatile("" : "+s"(off));
             const DBox& Bx = scene_at<DBox>(S, off);
             const float4 q0 = Bx.q0, q1 = Bx.q1, q2 = Bx.q2;
-            box_update_any_unbounded(ex, q0, q1, q2, A.o, iA, occA);
-            box_update_any(ex, q0, q1, q2, B.o, iB, B.tmax, occB);
+            box_update(ex, q0, q1, q2, A.o, iA, QEscape{occA});
+            box_update(ex, q0, q1, q2, B.o, iB, QAny{B.tmax, occB});
             off += (unsigned)sizeof(DBox);
         }
         if (bhead.y > 0) {
@@ -847,9 +799,9 @@ KY_DEV void trace_any_pair(SceneRef S, const AnyRay& A, const AnyRay& B, bool& o
             const DPar& r = scene_at<DPar>(S, off);
             float t, u, v;
             par_coords(r.q0, r.q1, r.q2, A.o, A.d, t, u, v, S.x_planks());
-            hit_update_any_unbounded(ex, u, 0.5f, v, 0.5f, t, occA);
+            hit_update(ex, u, 0.5f, v, 0.5f, t, QEscape{occA});
             par_coords(r.q0, r.q1, r.q2, B.o, B.d, t, u, v, S.x_planks());
-            hit_update_any(ex, u, 0.5f, v, 0.5f, t, B.tmax, occB);
+            hit_update(ex, u, 0.5f, v, 0.5f, t, QAny{B.tmax, occB});
             off += (unsigned)sizeof(DPar);
         }
     }
@@ -861,8 +813,8 @@ KY_DEV void trace_any_pair(SceneRef S, const AnyRay& A, const AnyRay& B, bool& o
             const float4 c = scene_at<DSph>(S, off).c;
             const f3 ocA = mk3(c.x, c.y, c.z) - A.o, ocB = mk3(c.x, c.y, c.z) - B.o;
             const float nbA = dot(ocA, A.d), nbB = dot(ocB, B.d);
-            sph_update_any_unbounded(ex, nbA, nbA * nbA - dot(ocA, ocA) + c.w, occA);
-            sph_update_any(ex, nbB, nbB * nbB - dot(ocB, ocB) + c.w, B.tmax, occB);
+            sph_update(ex, nbA, nbA * nbA - dot(ocA, ocA) + c.w, QEscape{occA});
+            sph_update(ex, nbB, nbB * nbB - dot(ocB, ocB) + c.w, QAny{B.tmax, occB});
             off += (unsigned)sizeof(DSph);
         }
     }

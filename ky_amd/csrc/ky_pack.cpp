@@ -313,7 +313,7 @@ static void shape_extent(const ky_shape& sh, const double* n, double& lo, double
 }
 // find_boxes: groups of axis-aligned rectangles that are WHOLE faces of one axis-aligned box (exact float equality of every coordinate: the corners a scene
 // builder copies from one table, 3299-3314 / 3336-3351).  A ray crosses the boundary of a convex box where it enters and where it leaves, so the nearest hit
-// among a box's faces needs no test per face (box_update_nearest, ky_device.hpp).  A box is taken when
+// among a box's faces needs no test per face (box_update, ky_device.hpp).  A box is taken when
 //   * at least KY_BOX_MIN_FACES of its six faces are surfaces (fewer: testing them one by one is cheaper), no face twice;
 //   * no OTHER axis-aligned rectangle of the scene lies in the plane of one of those faces: a hit at exactly the same distance on two surfaces goes to the
 //     earlier one in the reference's list (3177-3180), which the per-rectangle scan reproduces and a box cannot -- so a box never takes part in such a tie
@@ -517,7 +517,7 @@ bool specialisation_enabled() {
 }
 
 // The boxes (find_boxes, KY_FEAT_BOXES) can be switched off on their own: KYHIP_BOXES=0 or kyhip_set_boxes(0).  A box's slab test computes a hit distance that
-// differs from the per-rectangle test's by up to 15 units in the last place (box_update_nearest), so this switch -- unlike the one above -- moves an image beyond
+// differs from the per-rectangle test's by up to 15 units in the last place (box_update), so this switch -- unlike the one above -- moves an image beyond
 // its last bit (tests/test_boxes.py measures by how much); it exists for that test, for the tests that compare two kernels bit for bit, and for A/B measurements.
 static int g_boxes = -1;
 bool boxes_enabled() {

@@ -191,9 +191,6 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                     it.y0 = trow * sh.tile_h + by * 8;
                     it.pix0 = (k * sh.tile_h + by * 8) * sh.tile_w + bx * 8;
                     chunk_range(chunk_plan(rc.spp), c, it.s_begin, it.s_end);
-#ifdef KY_EXP_TRANSPOSE   // experiment (1024 spp, 64 chunks of 16): item c of a block = its pixel c, the item's 64 units = that pixel's 64 chunks
-                    it.x0 += c & 7; it.y0 += c >> 3; it.pix0 += (c >> 3) * sh.tile_w + (c & 7);
-#endif
                     my_ring[fetched % KY_RING] = it;
                 }
                 ++fetched;
@@ -204,23 +201,14 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                 const int mine = cursor + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(need_mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need_mask, 0u));
                 if (mine < fetched * 64) {
                     const ItemSlot it = my_ring[(mine >> 6) % KY_RING];
-#ifdef KY_EXP_TRANSPOSE
-                    const int px = 0, py = 0;
-#else
                     const int px = mine & 7, py = (mine >> 3) & 7;
-#endif
                     const int x = it.x0 + px, y = it.y0 + py;
                     const bool in_range = x < rc.width && y < rc.height;
                     c_xy[tid] = x | (y << 16);
                     c_pix[tid] = it.pix0 + py * sh.tile_w + px;
                     if (!QUEUE) c_key[tid] = sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x));
-#ifdef KY_EXP_TRANSPOSE
-                    c_se[tid] = ((unsigned)((mine & 63) * 16) << 7) | 16u;
-                    open = in_range;
-#else
                     c_se[tid] = ((unsigned)it.s_begin << 7) | (unsigned)(it.s_end - it.s_begin);
                     open = in_range && it.s_begin < it.s_end;
-#endif
                     has_item = in_range;
                 } else {
                     done = true;  // only reachable once the queue is exhausted

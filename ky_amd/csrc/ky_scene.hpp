@@ -126,7 +126,7 @@ struct DAar {
 // An axis-aligned BOX some of whose six faces are surfaces of the scene, each exactly a whole face (host: find_boxes -- the room of a Cornell box, its lamp
 // housing): 48 B.  q0 = (lo, s[0]), q1 = (hi, s[1]), q2 = (s[2], s[3], s[4], s[5]) with s[f] = the sorted surface index of face f = 2 axis + (0: the lo plane,
 // 1: the hi plane) as an integer's bits, KY_BOX_NO_FACE = 15 for an open side -- so a box's faces have sorted indices below 15.  A ray meets the boundary of a
-// convex box where it enters and where it leaves it, so the nearest hit among up to six rectangles is one slab test (box_update_nearest, ky_device.hpp:
+// convex box where it enters and where it leaves it, so the nearest hit among up to six rectangles is one slab test (box_update, ky_device.hpp:
 // 40 VALU instructions against 12 per rectangle).
 struct DBox {
     float4 q0, q1, q2;

@@ -156,7 +156,7 @@ def test_slab_test_finds_what_the_rectangle_scan_finds(A, api, O):
             lib.kyhip_set_boxes(prev)
         same = (with_boxes[:, 0] == scan[:, 0]) & (with_boxes[:, 8] == scan[:, 8])
         hit = same & (scan[:, 0] > 0)
-        # the slab test's distance carries the surface in its last four mantissa bits: 15 units in the last place, 1.8e-6 (box_update_nearest)
+        # the slab test's distance carries the surface in its last four mantissa bits: 15 units in the last place, 1.8e-6 (box_update)
         assert np.abs(with_boxes[hit, 1] - scan[hit, 1]).max() <= 4e-6 * np.maximum(1.0, scan[hit, 1]).max(), name
         assert np.abs(with_boxes[hit, 2:5] - scan[hit, 2:5]).max() <= 2e-5, name
         assert np.abs(with_boxes[hit, 5:8] - scan[hit, 5:8]).max() <= 1e-6, name
@@ -306,7 +306,7 @@ def test_boxy_rooms_nobody_tuned_for(A, api, O, seed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", range(int(os.environ.get("KY_BOXY_ROOMS", "8"))))
 def test_boxy_rooms_any_pair(A, api, O, seed):
-    """The any-hit form of the slab test (box_update_any, round 6: the environment estimate's pair scan) on the rooms nobody tuned for -- two or three boxes with four to
+    """The any-hit form of the slab test (box_update with QAny / QEscape, round 6: the environment estimate's pair scan) on the rooms nobody tuned for -- two or three boxes with four to
     six faces each, rays from inside, outside and from a hair off the faces themselves, with and without an end: "meets a surface" against the oracle's
     scene_t::intersect, every disagreement a proven tie."""
     W, H = 48, 40
