@@ -139,11 +139,14 @@ typedef enum ky_integrator_kind {
 /* direct_sample_enum_t (ky.cpp:3608-3623).  Matched by exact value (3840-3862). */
 typedef enum ky_direct_sample {
     KY_DIRECT_IDLE      = 0,
+    KY_DIRECT_SINGLE_LIGHT = 1,      /* flag (sample_single_light, 3612): ONE light per vertex, picked uniformly, its estimate divided by the pick
+                                        probability (3813-3832).  Accepted only as KY_DIRECT_SINGLE_BOTH_MIS: the reference's function is fixed to both_mis */
     KY_DIRECT_BSDF      = 4,
     KY_DIRECT_LIGHT     = 8,
     KY_DIRECT_BSDF_MIS  = 16,
     KY_DIRECT_LIGHT_MIS = 32,
-    KY_DIRECT_BOTH_MIS  = 48
+    KY_DIRECT_BOTH_MIS  = 48,
+    KY_DIRECT_SINGLE_BOTH_MIS = 49   /* KY_DIRECT_SINGLE_LIGHT | KY_DIRECT_BOTH_MIS */
 } ky_direct_sample;
 
 /* sampler_t subclasses that can be instantiated (ky.cpp:922, 949). */
@@ -399,6 +402,10 @@ int kyhip_kat_li(int device, const ky_scene* scene, const ky_render_params* para
    direct_sample 4 / 8: the plain estimators (by_bsdf uses random_bsdf as the float2 it draws itself, 3900); 16 / 32: the MIS halves;
    48: both MIS halves (not yet weighted by the 0.5 of 4083).  Vertices on delta surfaces return zeros (4571). */
 int kyhip_kat_nee(int device, const ky_scene* scene, int direct_sample, int light, const float* in15, int n, float* out6);
+/* integrator_t::sample_single_light (3813-3832) at given vertices with given numbers.  in16: a kyhip_kat_nee row, then pick_u; the light is
+ * min((int)(pick_u * light_count), light_count - 1) in fp32.  out6: the picked light's two both_mis halves (BSDF half, light half), each already
+ * divided by the pick probability 1 / light_count, and -- like kyhip_kat_nee's -- not weighted by the 0.5 of 4083.  A scene without lights is refused. */
+int kyhip_kat_single_light(int device, const ky_scene* scene, const float* in16, int n, float* out6);
 
 /* The same sample of path_tracing_iteration_t vertex by vertex (the reference's LOG_VAST at ky.cpp:4578 prints the same facts):
    one row of 26 floats per vertex that reaches the continuation sample (4586):

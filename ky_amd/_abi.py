@@ -18,6 +18,7 @@ INTEGRATOR_POSITION, INTEGRATOR_NORMAL, INTEGRATOR_BASECOLOR = 0, 1, 2
 INTEGRATOR_DIRECT_LIGHTING, INTEGRATOR_PATH_TRACING_ITERATION = 6, 11
 INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION, INTEGRATOR_PATH_TRACING_RECURSION, INTEGRATOR_PATH_TRACING_RECURSION_DEFERED = 8, 9, 10
 DIRECT_IDLE, DIRECT_BSDF, DIRECT_LIGHT, DIRECT_BSDF_MIS, DIRECT_LIGHT_MIS, DIRECT_BOTH_MIS = 0, 4, 8, 16, 32, 48
+DIRECT_SINGLE_LIGHT, DIRECT_SINGLE_BOTH_MIS = 1, 49   # sample_single_light: accepted as 1 | 48 only
 SAMPLER_DEBUG, SAMPLER_RANDOM = 0, 1
 SP_VARIANT_SMALLPT, SP_VARIANT_REWRITE = 0, 1
 KY_OK, KY_ERR_INVALID_VALUE, KY_ERR_LIMIT, KY_ERR_DEVICE, KY_ERR_NO_DEVICE = 0, -1, -2, -3, -4
@@ -117,6 +118,7 @@ KYHIP_SYMBOLS = {
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "kyhip_kat_single_light": (C.c_int, [C.c_int, SP, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_li_trace": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_smallpt_scene": (C.c_int, [SSP]),
     "kyhip_smallpt_scene_rewrite": (C.c_int, [SSP]),

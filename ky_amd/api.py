@@ -267,6 +267,15 @@ def kat_nee(scene, direct_sample, light, in15, device=0):
     return out
 
 
+def kat_single_light(scene, in16, device=0):
+    """kyhip_kat_single_light: rows of a kat_nee row + pick_u -> the picked light's two both_mis halves times the light count."""
+    lib = A.load_kyhip()
+    in16 = np.ascontiguousarray(in16, np.float32)
+    out = np.zeros((in16.shape[0], 6), np.float32)
+    _check(lib.kyhip_kat_single_light(device, _scene_ptr(scene), _fptr(in16), in16.shape[0], _fptr(out)))
+    return out
+
+
 def kat_li_trace(scene, params, x, y, s, max_rows=64, device=0):
     """kyhip_kat_li_trace: (rows [n, 26], li [3]) of one camera sample of path_tracing_iteration_t."""
     lib = A.load_kyhip()

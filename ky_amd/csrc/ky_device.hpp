@@ -178,6 +178,7 @@ struct LdsScene {
     const DHit* hit;
     const DMat* mat;
     const float (*light_color)[4];
+    const DLight* light;   // the lights' records for per-lane reads (stage_lights: kernels that may run sample_single_light), null elsewhere
 };
 template <int NS, int NM>
 struct LdsSceneStaticT {
@@ -219,6 +220,21 @@ KY_DEV LdsScene stage_scene(SceneRef S) {
     }
     __syncthreads();
     return LdsScene{reinterpret_cast<const DHit*>(dst_h), reinterpret_cast<const DMat*>(dst_m), reinterpret_cast<const float (*)[4]>(dst_l)};
+}
+
+// sample_single_light's table: every lane estimates the light IT drew, so what an estimate reads of a DLight -- its parameters, the sampled shape with its frame,
+// the record pdf_direction re-intersects, the carrier list -- is read per lane, from a copy of the scene's light records in LDS (240 B each, beside the tables of
+// stage_scene).  Cooperative copy by the whole workgroup when `want` (workgroup-uniform) holds; ends with a barrier then.
+KY_DEV LdsScene stage_lights(SceneRef S, LdsScene L, bool want) {
+    __shared__ __attribute__((aligned(16))) uint32_t lights[KYHIP_MAX_LIGHTS * sizeof(DLight) / 4];
+    if (want) {
+        const int nl = S->n_lights < KYHIP_MAX_LIGHTS ? S->n_lights : KYHIP_MAX_LIGHTS;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(S->light);
+        for (int i = threadIdx.x; i < nl * (int)(sizeof(DLight) / 4); i += blockDim.x) lights[i] = src[i];
+        __syncthreads();
+        L.light = reinterpret_cast<const DLight*>(lights);
+    }
+    return L;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -374,6 +390,17 @@ KY_DEV const T& scene_at(SceneRef S, unsigned off) { return *(const T*)((const c
 KY_DEV unsigned opaque_off(unsigned off) { asm volatile("" : "+s"(off)); return off; }
 KY_DEV const DLight& scene_light(SceneRef S, int li) { return scene_at<DLight>(S, opaque_off((unsigned)__builtin_offsetof(DScene, light) + (unsigned)li * (unsigned)sizeof(DLight))); }
 KY_DEV const DSurf& scene_surf(SceneRef S, int i) { return scene_at<DSurf>(S, opaque_off((unsigned)__builtin_offsetof(DScene, all) + (unsigned)i * (unsigned)sizeof(DSurf))); }
+// PER_LANE (sample_single_light's estimators): the lane's own light record `Lp` (LDS) and records indexed by it, read per lane; otherwise the wave-uniform forms above
+template <bool PER_LANE>
+KY_DEV const DLight& light_record(SceneRef S, int li, const DLight* Lp) {
+    if constexpr (PER_LANE) return *Lp;
+    else return scene_light(S, li);
+}
+template <bool PER_LANE>
+KY_DEV const DSurf& surf_record(SceneRef S, int i) {
+    if constexpr (PER_LANE) return S->all[i];
+    else return scene_surf(S, i);
+}
 
 // The four range tests of a hit and the update they guard, as a chain of v_cmpx: each compare NARROWS the exec mask to the lanes that passed, the
 // update is two plain moves under what is left (the surface index straight from its SGPR), one s_mov restores the mask.  As C++ (`ok = a & b & c & d;
@@ -1444,10 +1471,13 @@ KY_DEV void sq_push_bsdf_query(SceneRef S, ShadowQueue& q, bool push, f3 o, f3 d
 // The estimate is ADDED, times `w`, to `acc` by the lanes that have one, under their own predicate (in place: no default value travels through the
 // nesting levels, no select afterwards): the render kernels pass the path's radiance sum and throughput x strategy weight, the KAT entry a zeroed
 // value and w = 1.
-template <bool MIS>
+template <bool MIS, bool PER_LANE = false>
 KY_DEV void estimate_by_bsdf(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, int li, float u0, float u1, bool active, f3& acc, f3 w,
-                             ShadowQueue* sq = nullptr, f3 beta = f3{0, 0, 0}, float weight = 0.f, unsigned tag = 0, RideAlong* ra = nullptr) {
-    const DLight& L = scene_light(S, li);
+                             ShadowQueue* sq = nullptr, f3 beta = f3{0, 0, 0}, float weight = 0.f, unsigned tag = 0, RideAlong* ra = nullptr, const DLight* Lp = nullptr) {
+    // PER_LANE with `Lp` (sample_single_light; false and null everywhere else): this LANE's light record, in LDS, and `li` its own index -- the scans below stay
+    // wave-uniform over the surfaces, what is compared against the light is the lane's.  A lane whose light is a delta light sits the call out.
+    const DLight& L = light_record<PER_LANE>(S, li, Lp);
+    if (PER_LANE) { if (S.is_delta(L.kind)) active = false; } else
     if (S.is_delta(L.kind)) return;  // light.is_delta(), 3894 / 3977 (wave-uniform)
     BsdfSample bs;
     // what `live` guards: read at the end only for lanes whose sample counts (and, in the query loop, through __shfl from such lanes)
@@ -1457,7 +1487,9 @@ KY_DEV void estimate_by_bsdf(SceneRef S, const LdsScene& Lds, const Vertex& v, f
     bs.pdf = any_f();
     bool live = false, lit = false;   // live: the sample's value and pdf count; lit: it sees light (Li is set and not black)
     float t_l = any_f();              // fast path: distance of the nearest carrier hit
-    const bool fast = S.is_area(L.kind) && ((S.feat & KY_FEAT_CARRIERS) || (L.n_carriers >= 0 && S->n_gen == 0));  // wave-uniform
+    // (per-lane lights: the carrier test where the instantiation's facts say that EVERY light takes it; a decision per light would not be wave-uniform)
+    const bool fast = PER_LANE ? ((S.feat & KY_FEAT_CARRIERS) != 0 && (S.feat & (KY_FEAT_SINGLE_AREA | KY_FEAT_SPHERE_LIGHTS)) != 0)
+                         : (S.is_area(L.kind) && ((S.feat & KY_FEAT_CARRIERS) || (L.n_carriers >= 0 && S->n_gen == 0)));  // wave-uniform
     if (fast) {
         // Only the DIRECTION is sampled up front; the BSDF value and pdf (a pow for the Phong lobe) are evaluated for the few
         // lanes whose ray reaches a carrier that emits towards it -- for all other lanes Li = 0 decides the estimate (3996-4003).
@@ -1514,7 +1546,7 @@ KY_DEV void estimate_by_bsdf(SceneRef S, const LdsScene& Lds, const Vertex& v, f
             if (S.sphere_lights() && k == 0)   // the first carrier's sphere from the light's own record (DLight::aar): one load, not index -> table
                 hit = sph_hit(make_float4(L.aar[0], L.aar[1], L.aar[2], L.aar[3]), o, bs.wi, t_l, t, true);
             else
-                hit = surf_hit(scene_surf(S, L.carrier[k]), S->full, o, bs.wi, t_l, t, S.general, S.sphere_lights());
+                hit = surf_hit(surf_record<PER_LANE>(S, L.carrier[k]), S->full, o, bs.wi, t_l, t, S.general, S.sphere_lights());   // (per-lane light: its own carriers, a per-lane record)
             const bool ok = act & hit;
             t_l = ok ? t : t_l;
             c = ok ? L.carrier[k] : c;
@@ -1743,10 +1775,10 @@ KY_DEV void sq_drain(SceneRef S, ShadowQueue& q) {
 // weight -> [sampled shape's own hit] -> push; the reference's order (occlusion before the BSDF value) gives the same sum
 // because every factor is computed from the same inputs and a zero factor zeroes the term either way.
 // Wave-uniform call.  beta x weight = throughput x strategy weight x 1 / spp: what multiplies this estimate in the pixel's sum.
-template <bool MIS>
+template <bool MIS, bool PER_LANE = false>
 KY_DEV void estimate_by_emitter_deferred(SceneRef S, const Vertex& v, f3 wo, int li, float u0, float u1, bool active, f3 beta, float weight,
-                                         unsigned tag, ShadowQueue& q) {
-    const DLight& L = scene_light(S, li);
+                                         unsigned tag, ShadowQueue& q, const DLight* Lp = nullptr) {
+    const DLight& L = light_record<PER_LANE>(S, li, Lp);   // PER_LANE: the lane's own light (estimate_by_bsdf)
     bool push = false;
     SqRay r{any3(), any3(), any3(), any_f(), tag};   // read by sq_push only for lanes that push
     if (active) {
@@ -1773,7 +1805,7 @@ KY_DEV void estimate_by_emitter_deferred(SceneRef S, const Vertex& v, f3 wo, int
         bsdf_eval_parts(v, wo, S.is_area(L.kind) ? r.d : ls.wi, col, scale, bsdf_pdf, abs_cos_i);
         const bool delta_light = S.is_delta(L.kind);
         // f |cos| Li / pdf (3956) or 2 f |cos| Li / (p_l + p_b) (4057 / 4070), times throughput and strategy weight: the scalar factors first, the three channels once;
-        // an area light's Li is its colour where the sample is lit (a wave-uniform value: scalar operands) and the predicate below says whether it is
+        // an area light's Li is its colour where the sample is lit (a wave-uniform value: scalar operands; PER_LANE: the lane's own, from LDS, in VGPRs) and the predicate below says whether it is
         const float fc = scale * abs_cos_i;   // f |cos| = col x fc
         const float k = fc * (ip ? ((!MIS || delta_light) ? ls.pdf : (2.f * ls.pdf) * rcp(1.f + bsdf_pdf * ls.pdf))
                                  : ((!MIS || delta_light) ? rcp(ls.pdf) : 2.f * rcp(ls.pdf + bsdf_pdf))) * weight;
@@ -1785,7 +1817,7 @@ KY_DEV void estimate_by_emitter_deferred(SceneRef S, const Vertex& v, f3 wo, int
         // (with reciprocal densities every light is an area light, whose `lit` already says that the density is not zero)
         push = (area ? ls.lit : !is_black(ls.Li)) && (ip || !(MIS ? ls.pdf <= 0 : ls.pdf == 0)) && !(fc <= 0.f) && !is_black(col);
         // the sampled shape itself is the likeliest occluder (quirk 1): one test here saves the ray a full traversal
-        if (S.is_area(L.kind) && L.sampled_is_surface) {   // wave-uniform
+        if (S.is_area(L.kind) && L.sampled_is_surface) {   // wave-uniform (PER_LANE: per lane, a divergent branch)
             float t;
             if (surf_hit(L.isect, S->full, r.o, r.d, r.tmax, t, S.general, S.sphere_lights(), false)) push = false;   // (every one of these rays is aimed at the sphere: not sparse)
         }
@@ -1811,13 +1843,13 @@ KY_DEV bool light_sample_occluded(SceneRef S, int li, f3 o, f3 dir, float tmax) 
     return occ;
 }
 
-template <bool MIS>
-KY_DEV void estimate_by_emitter(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, int li, float u0, float u1, f3& acc, f3 w) {
-    const DLight& L = scene_light(S, li);
+template <bool MIS, bool PER_LANE = false>
+KY_DEV void estimate_by_emitter(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, int li, float u0, float u1, f3& acc, f3 w, const DLight* Lp = nullptr) {
+    const DLight& L = light_record<PER_LANE>(S, li, Lp);   // PER_LANE: the lane's own light (estimate_by_bsdf)
     KY_PROBE(3);
     const bool ip = S.ipdf();   // (compile-time) ls.pdf is the density's reciprocal: shape_sample_direction
     const LightSample ls = light_sample_Li(L, v.position, v.normal, u0, u1, S.feat, ip);
-    const bool area = S.is_area(L.kind);   // (wave-uniform)
+    const bool area = S.is_area(L.kind);   // (wave-uniform; PER_LANE: the lane's own light's kind, the branches on it diverge)
     const bool dead = (area ? !ls.lit : is_black(ls.Li)) || (!(ip || area) && (MIS ? (ls.pdf <= 0) : (ls.pdf == 0)));   // (an area light's `lit` says that the density is not zero -- and it is never negative)
     KY_CLK(5);
     if (!dead) {
@@ -1836,7 +1868,11 @@ KY_DEV void estimate_by_emitter(SceneRef S, const LdsScene& Lds, const Vertex& v
         }
         const f3 o = offset_ray_origin(v.position, v.normal, dir);
         KY_PROBE(4);
-        const bool occ = light_sample_occluded(S, li, o, dir, dist - 2e-3f);
+        // (per-lane lights: DLight::shadow_table is per light, and a scan's table is wave-uniform -- the lanes share the table the deferred rays of all lights
+        // share: DScene::occ where every light allows it, every surface otherwise)
+        bool occ;
+        if constexpr (PER_LANE) occ = trace_any(S, S->occ_deferred_ok ? S->occ : S->trav, o, dir, dist - 2e-3f);
+        else occ = light_sample_occluded(S, li, o, dir, dist - 2e-3f);
         KY_CLK(6);
         if (!occ) {
             KY_PROBE(5);
@@ -1847,7 +1883,7 @@ KY_DEV void estimate_by_emitter(SceneRef S, const LdsScene& Lds, const Vertex& v
             const float fc = scale * abs_cos_i;   // f |cos| = col x fc
             if (!(fc <= 0.f) && !is_black(col)) {    // !is_black(f |cos|), 3952 / 4052: some channel positive (colours are not negative; a NaN factor counts)
                 const bool delta_light = S.is_delta(L.kind);
-                // 3956 / 4057 / 4070, the scalar factors first; an area light's Li is its colour where the sample is lit (wave-uniform: scalar operands)
+                // 3956 / 4057 / 4070, the scalar factors first; an area light's Li is its colour where the sample is lit (wave-uniform: scalar operands; PER_LANE: per lane, vector operands)
                 const float k = fc * (ip ? ((!MIS || delta_light) ? ls.pdf : (2.f * ls.pdf) * rcp(1.f + bsdf_pdf * ls.pdf))
                                          : ((!MIS || delta_light) ? rcp(ls.pdf) : 2.f * rcp(ls.pdf + bsdf_pdf)));
                 acc = acc + ((col * (area ? ld3(L.color) : ls.Li)) * w) * k;
@@ -1860,11 +1896,12 @@ KY_DEV void estimate_by_emitter(SceneRef S, const LdsScene& Lds, const Vertex& v
 // the same estimator as a WAVE-UNIFORM call whose shadow traversal also serves the lanes of `ra` (RideAlong) that still wait: when there are any,
 // shadow rays and look-up rays go through one nearest-hit scan of the whole scene (a shadow ray is occluded iff that scan finds a hit
 // inside its interval: the occluder tables are subsets that decide the same, tests/test_occluders.py).
-template <bool MIS>
-KY_DEV void estimate_by_emitter_ride(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, int li, float u0, float u1, bool active, RideAlong& ra, f3& acc, f3 w) {
-    const DLight& L = scene_light(S, li);
+template <bool MIS, bool PER_LANE = false>
+KY_DEV void estimate_by_emitter_ride(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, int li, float u0, float u1, bool active, RideAlong& ra, f3& acc, f3 w,
+                                     const DLight* Lp = nullptr) {
+    const DLight& L = light_record<PER_LANE>(S, li, Lp);   // PER_LANE: the lane's own light (estimate_by_bsdf)
     LightSample ls{any3(), any3(), any3(), any_f(), false, any3(), any_f()};
-    const bool area = S.is_area(L.kind);   // (wave-uniform)
+    const bool area = S.is_area(L.kind);   // (wave-uniform; PER_LANE: the lane's own light's kind, the branches on it diverge)
     bool dead = true;
     if (active) {
         ls = light_sample_Li(L, v.position, v.normal, u0, u1, S.feat);
@@ -1894,7 +1931,8 @@ KY_DEV void estimate_by_emitter_ride(SceneRef S, const LdsScene& Lds, const Vert
         occ = hs >= 0;
         if (ride) { ra.hs = hs; ra.t = tmax; ra.want = false; }
     } else if (!dead) {
-        occ = light_sample_occluded(S, li, o, dir, tmax);
+        if constexpr (PER_LANE) occ = trace_any(S, S->occ_deferred_ok ? S->occ : S->trav, o, dir, tmax);   // (estimate_by_emitter)
+        else occ = light_sample_occluded(S, li, o, dir, tmax);
     }
     if (!dead && !occ) {
         f3 col;
@@ -2010,6 +2048,62 @@ KY_DEV void sample_all_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f
             if (active) Lo = Lo + w * (Lb + Ll);
             if (li < 16) *decisions |= (is_black(Lb) ? 0u : 1u << li) | (is_black(Ll) ? 0u : 1u << (16 + li));
         }
+    }
+}
+
+// sample_single_light, 3813-3832: ONE light per vertex, picked uniformly from the sample's own stream, its both_mis estimate (4076-4088) divided by the pick
+// probability 1 / n.  Wave-uniform call; the `active` lanes draw five numbers in the order of the reference's sequenced statements -- the pick, random_light,
+// random_bsdf (unlike sample_all_light's argument order) -- and ADD beta x 0.5 n x (the two halves) to Lo.  A scene without lights draws nothing.
+// Every lane holds its OWN light: which lane renders which sample must not show in the image, so the index cannot be made wave-uniform, and a loop over
+// the lights present in the wavefront would run as many estimates as sample_all_light with a fraction of the lanes each.  The estimators are the ones
+// above with the light's record read per lane from LDS (LdsScene::light, stage_lights): one BSDF half, one light sample, one shadow ray per vertex, whatever
+// the lights' kinds -- the kinds are branches inside light_sample_Li, there is no loop over lights or kinds.
+//  - BSDF half: where the facts say that every light takes the carrier test (KY_FEAT_CARRIERS with sphere lights), a lane tests its own light's carriers and
+//    asks the wave-uniform "is anything in front" query; otherwise one nearest-hit scan of the scene and "does the hit carry MY light" per lane (3994).
+//  - shadow ray: DLight::shadow_table is per light, so the lanes scan the table the deferred rays of all lights share -- DScene::occ when every light
+//    allows it (occ_deferred_ok), every surface otherwise -- inline or through the wave's stack (`sq`).
+// A kernel whose facts name ONE light (KY_FEAT_SINGLE_LIGHT) picks index 0 with probability 1 -- it still draws the pick -- and runs that light's
+// wave-uniform estimators as they are.
+// `decisions`: bit li = the BSDF half of the PICKED light was non-black, bit 16 + li its light half; no other light's bits are set.
+template <bool DEBUG_SAMPLER>
+KY_DEV void sample_single_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, Sampler& smp, bool active, f3& Lo, f3 beta,
+                                unsigned* decisions = nullptr, ShadowQueue* sq = nullptr, float weight = 0.f, unsigned tag = 0, RideAlong* ra = nullptr) {
+    const int nl = S.single_light() ? 1 : S->n_lights;
+    if (nl == 0) return;   // 3816-3818
+    int li = 0;
+    float ub0 = any_f(), ub1 = any_f(), ul0 = any_f(), ul1 = any_f();   // drawn, and read, by the active lanes only
+    if (active) {
+        const float u = sampler_next<DEBUG_SAMPLER>(smp);
+        li = min((int)(u * (float)nl), nl - 1);   // 3821
+        ul0 = sampler_next<DEBUG_SAMPLER>(smp); ul1 = sampler_next<DEBUG_SAMPLER>(smp);   // random_light, 3824
+        ub0 = sampler_next<DEBUG_SAMPLER>(smp); ub1 = sampler_next<DEBUG_SAMPLER>(smp);   // random_bsdf, 3825
+    }
+    const float fn = (float)nl;   // 1 / pick probability, 3830
+    const f3 w = beta * (0.5f * fn);
+    const float wq = weight * (0.5f * fn);
+    f3 Lb = mk3(0, 0, 0), Ll = mk3(0, 0, 0);      // tracing only: the two halves on their own
+    f3& ab = decisions ? Lb : Lo;
+    f3& al = decisions ? Ll : Lo;
+    const f3 wt = decisions ? mk3(1, 1, 1) : w;
+    if (S.single_light()) {   // (compile-time) the one light's estimators, as sample_all_light runs them
+        if ((S.feat & KY_FEAT_SINGLE_ENV) && !sq && !ra) {
+            if (active) estimate_env_both(S, v, wo, ub0, ub1, ul0, ul1, ab, al, wt);
+        } else {
+            estimate_by_bsdf<true>(S, Lds, v, wo, 0, ub0, ub1, active, ab, wt, sq, beta, wq, tag, ra);
+            if (sq) estimate_by_emitter_deferred<true>(S, v, wo, 0, ul0, ul1, active, beta, wq, tag, *sq);
+            else if (ra) estimate_by_emitter_ride<true>(S, Lds, v, wo, 0, ul0, ul1, active, *ra, al, wt);
+            else if (active) estimate_by_emitter<true>(S, Lds, v, wo, 0, ul0, ul1, al, wt);
+        }
+    } else {
+        const DLight* Lp = Lds.light + li;   // this lane's light (an idle lane: light 0, read by nobody)
+        estimate_by_bsdf<true, true>(S, Lds, v, wo, li, ub0, ub1, active, ab, wt, sq, beta, wq, tag, ra, Lp);
+        if (sq) estimate_by_emitter_deferred<true, true>(S, v, wo, li, ul0, ul1, active, beta, wq, tag, *sq, Lp);
+        else if (ra) estimate_by_emitter_ride<true, true>(S, Lds, v, wo, li, ul0, ul1, active, *ra, al, wt, Lp);
+        else if (active) estimate_by_emitter<true, true>(S, Lds, v, wo, li, ul0, ul1, al, wt, Lp);
+    }
+    if (decisions) {
+        if (active) Lo = Lo + w * (Lb + Ll);
+        if (li < 16) *decisions |= (is_black(Lb) ? 0u : 1u << li) | (is_black(Ll) ? 0u : 1u << (16 + li));
     }
 }
 
@@ -2167,6 +2261,9 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
         es_f = es.f;
         es_k = fabsf(dot(es.wi, v.normal)) / es.pdf;
     }
+    if (!simple && rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS) {   // sample_single_light: one light per vertex
+        sample_single_light<DEBUG_SAMPLER>(S, Lds, v, wo, ps.smp, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag, riding ? &ra : nullptr);
+    } else
     if (!simple) {  // simple_path_tracing_recursion_t samples the BSDF only
         sample_all_light<DEBUG_SAMPLER>(S, Lds, v, wo, ps.smp, rc.strategy, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag,
                                         riding ? &ra : nullptr);  // 4575 / 4337 / 4458

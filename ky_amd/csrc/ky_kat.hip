@@ -120,7 +120,7 @@ __global__ void kat_any_pair_kernel(const DScene* __restrict__ S_, const float* 
 template <bool DEBUG_SAMPLER, bool BOXES>
 __global__ void kat_li_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env) {
     const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_scene<true>(S);   // KAT kernels: always the scene-sized dynamic block
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);   // KAT kernels: always the scene-sized dynamic block
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     PathState ps;
     bool alive = i < n;
@@ -166,11 +166,41 @@ __global__ void kat_nee_kernel(const DScene* __restrict__ S, int strategy, int l
     }
 }
 
+// sample_single_light's pick and the picked light's two both_mis halves times the light count (3813-3832), the lights read per lane as the render kernels read them
+__global__ void kat_single_light_kernel(const DScene* __restrict__ S, const float* __restrict__ in16, int n, float* __restrict__ out6) {
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), true);   // KAT kernels: always the scene-sized dynamic block
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = i < n;
+    const float* r = in16 + 16 * (size_t)(active ? i : 0);
+    Vertex v;
+    v.position = ld3(r); v.normal = ld3(r + 3);
+    v.t = 0.f;
+    v.surface = 0;
+    for (int j = 0; j < S->n_surfaces; ++j)
+        if (S->orig[j] == (int)r[9]) v.surface = j;          // the caller's surface index -> the device's sorted index
+    v.bsdf = make_bsdf(Lds.mat[Lds.hit[v.surface].material], r[10]);
+    const f3 wo = ld3(r + 6);
+    vertex_prepare(v, wo);
+    const int nl = S->n_lights;
+    const int li = active ? min((int)(r[15] * (float)nl), nl - 1) : 0;   // 3821
+    const DLight* Lp = Lds.light + li;
+    f3 Lb = mk3(0, 0, 0), Ll = mk3(0, 0, 0);
+    const bool nee = active && !bsdf_is_delta(v.bsdf);
+    const float fn = (float)nl;
+    const f3 w = mk3(fn, fn, fn);   // 1 / pick probability, 3830
+    estimate_by_bsdf<true, true>(S, Lds, v, wo, li, r[11], r[12], nee, Lb, w, nullptr, f3{0, 0, 0}, 0.f, 0, nullptr, Lp);   // (wave-uniform call)
+    if (nee) estimate_by_emitter<true, true>(S, Lds, v, wo, li, r[13], r[14], Ll, w, Lp);
+    if (active) {
+        float* o = out6 + 6 * (size_t)i;
+        o[0] = Lb.x; o[1] = Lb.y; o[2] = Lb.z; o[3] = Ll.x; o[4] = Ll.y; o[5] = Ll.z;
+    }
+}
+
 // one camera sample, traced vertex by vertex (lane 0 walks the path; the other lanes only keep the wave-uniform calls company)
 template <bool DEBUG_SAMPLER, bool BOXES>
 __global__ void kat_li_trace_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s, int max_rows, float* __restrict__ out, int single_env) {
     const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_scene<true>(S);   // KAT kernels: always the scene-sized dynamic block
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);   // KAT kernels: always the scene-sized dynamic block
     PathState ps;
     bool alive = threadIdx.x == 0;
     VertexTrace tr{out + 4, max_rows, 0};
@@ -332,6 +362,22 @@ int kyhip_kat_nee(int device, const ky_scene* scene, int direct_sample, int ligh
         SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
         if (r != KY_OK) return r;
         hipLaunchKernelGGL(kat_nee_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, direct_sample, light, d_in, n, d_out);
+        return (int)KY_OK;
+    });
+}
+
+int kyhip_kat_single_light(int device, const ky_scene* scene, const float* in16, int n, float* out6) {
+    if (!scene || !in16 || !out6 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (scene->light_count <= 0) return fail(KY_ERR_INVALID_VALUE, "sample_single_light picks among the scene's lights: the scene has none");
+    for (int i = 0; i < n; ++i) {
+        const float sf = in16[16 * (size_t)i + 9], u = in16[16 * (size_t)i + 15];
+        if (!(sf >= 0 && sf < scene->surface_count)) return fail(KY_ERR_INVALID_VALUE, "row %d: surface out of range", i);
+        if (!(u >= 0.f && u < 1.f)) return fail(KY_ERR_INVALID_VALUE, "row %d: pick_u outside [0, 1)", i);
+    }
+    return kat_run(device, in16, (size_t)n * 16 * 4, out6, (size_t)n * 6 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
+        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
+        if (r != KY_OK) return r;
+        hipLaunchKernelGGL(kat_single_light_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, d_in, n, d_out);
         return (int)KY_OK;
     });
 }

@@ -322,6 +322,12 @@ static const Variant g_variants[] = {
     KY_VARIANT(false, KY_DIRECT_LIGHT, false, false, 0, IT),
     KY_VARIANT(false, KY_DIRECT_BSDF_MIS, false, false, 0, IT),
     KY_VARIANT(false, KY_DIRECT_LIGHT_MIS, false, false, 0, IT),
+    // the iterative integrator, sample_single_light (strategy 49): one light per vertex, read per lane (ky_device.hpp, sample_single_light).  Scenes with one
+    // light, the other integrators, the debug sampler and general shapes take the run-time-dispatched kernels below, or their own instantiation
+    KY_VARIANT(false, KY_DIRECT_SINGLE_BOTH_MIS, true, false, KY_FEAT_VEACH, IT),              // several sphere lights: a lane tests its own lamp's carriers; deferred shadow rays
+    KY_VARIANT(false, KY_DIRECT_SINGLE_BOTH_MIS, false, false, KY_FEAT_VEACH, IT),             // ... inline shadow rays
+    KY_VARIANT(false, KY_DIRECT_SINGLE_BOTH_MIS, true, false, 0, IT),                          // any lights: one nearest-hit scan and "does the hit carry my light"
+    KY_VARIANT(false, KY_DIRECT_SINGLE_BOTH_MIS, false, false, 0, IT),
     // direct_lighting_t and the three recursive integrators with both_mis (render_multiple_integrator 4740-4777)
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_CORNELL, KY_INTEGRATOR_PATH_TRACING_RECURSION),
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV, KY_INTEGRATOR_PATH_TRACING_RECURSION),
@@ -441,7 +447,9 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
     st->ws_clean = false;   // until this frame's resolve_kernel is enqueued
 
     // the queue engine implements path_tracing_iteration_t; every other integrator runs on the lane engine
-    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene) {
+    // (... and the queue engine has no sample_single_light: a strategy-49 launch runs on the lane engine, and kyhip_last_kernel says so)
+    const bool single = p->direct_sample == KY_DIRECT_SINGLE_BOTH_MIS;
+    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single) {
         const int variant = p->sampler == KY_SAMPLER_DEBUG ? 2 : (p->direct_sample == KY_DIRECT_BOTH_MIS ? 0 : 1);
         const int per_cu = c->q_blocks_per_cu[variant] > 0 ? c->q_blocks_per_cu[variant] : 1;
         unsigned grid = (unsigned)(c->cus * per_cu);
@@ -475,9 +483,9 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
             // the box traversal pays where it was measured to (one lamp, one point / directional light: +3-4 %; one environment light under both_mis, whose estimate's two
             // rays share one any-hit scan: estimate_env_both); in instantiations that inline the nearest-hit traversal more than once (an environment light's BSDF-sampled
             // rays under the other strategies, several lights) it measured 7-10 % SLOWER: those keep the rectangle scan
-            const bool env_pair = (feat & KY_FEAT_SINGLE_ENV) && p->direct_sample == KY_DIRECT_BOTH_MIS && p->integrator != KY_INTEGRATOR_PATH_TRACING_RECURSION;
+            const bool env_pair = (feat & KY_FEAT_SINGLE_ENV) && (p->direct_sample == KY_DIRECT_BOTH_MIS || single) && p->integrator != KY_INTEGRATOR_PATH_TRACING_RECURSION;
             if (!((feat & (KY_FEAT_SINGLE_AREA | KY_FEAT_SINGLE_DELTA)) || env_pair)) feat &= ~KY_FEAT_BOXES;
-            const bool want_queue = (p->direct_sample == KY_DIRECT_BOTH_MIS || p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) &&
+            const bool want_queue = (p->direct_sample == KY_DIRECT_BOTH_MIS || single || p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) &&
                                     p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && sh.n_pix < (1 << 26) && !general && shadow_queue_wanted(scene);
             const bool same = v->dbg == dbg && v->strategy == p->direct_sample && v->queue == want_queue && v->general == general && v->feat == feat &&
                               v->integrator == p->integrator && v->large == large_scene;
@@ -545,6 +553,14 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
         }
         rcode = set_film_limit(st, film_term_count(p, sc->h->n_lights, false, queue), stream);
         if (rcode != KY_OK) return rcode;
+        if (single) {   // which form of sample_single_light this launch's kernel runs
+            const int kfeat = jk ? ((p->sampler == KY_SAMPLER_DEBUG || sc->h->general != 0) ? 0 : sc->h->feat) : v->feat;   // the facts the kernel was compiled with
+            const bool one = (kfeat & KY_FEAT_SINGLE_LIGHT) != 0;
+            c->last_note += one ? " [sample_single_light: one light, its wave-uniform estimators]"
+                                : ((kfeat & KY_FEAT_SPHERE_LIGHTS) && !jk ? " [sample_single_light: per-lane lights, each lane tests its own lamp's carriers]"
+                                                                          : " [sample_single_light: per-lane lights]");
+            if (current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no sample_single_light]";
+        }
         HIP_TRY(hipEventRecord(st->ev0, stream));
         float4* queue_mem = queue ? st->d_shadow_queue : (float4*)nullptr;
         if (jk) {

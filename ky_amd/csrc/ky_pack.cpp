@@ -56,6 +56,7 @@ bool valid_params(const ky_render_params* p) {
     switch (p->direct_sample) {
     case KY_DIRECT_IDLE: case KY_DIRECT_BSDF: case KY_DIRECT_LIGHT: case KY_DIRECT_BSDF_MIS:
     case KY_DIRECT_LIGHT_MIS: case KY_DIRECT_BOTH_MIS: break;
+    case KY_DIRECT_SINGLE_BOTH_MIS: break;   // sample_single_light (3813-3832), which is fixed to both_mis: flag 1 alone or on another strategy stays refused
     default: return false;   // empty std::function -> bad_function_call (ky.cpp:3860)
     }
     if (p->sampler != KY_SAMPLER_DEBUG && p->sampler != KY_SAMPLER_RANDOM) return false;
@@ -103,9 +104,12 @@ ShardConst make_shard(const ky_render_params* p) {
 long long film_term_count(const ky_render_params* p, int n_lights, bool queue_engine, bool deferred) {
     const long long spp = p->samples_per_pixel;
     const bool iteration = p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION;
-    if (queue_engine && iteration) return spp;
+    if (queue_engine && iteration && p->direct_sample != KY_DIRECT_SINGLE_BOTH_MIS) return spp;   // (strategy 49 runs on the lane engine whichever engine is chosen)
     long long n = chunk_count(chunk_plan(p->samples_per_pixel));
-    const int per_light = p->direct_sample == KY_DIRECT_BOTH_MIS ? 2 : (p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) ? 1 : 0;
+    // (sample_single_light pushes for ONE light per vertex -- its estimate times the light count, ky.cpp:3830 -- so both_mis's count over all lights bounds it; terms
+    // beyond the limit that count leaves saturate like any other)
+    const bool both = p->direct_sample == KY_DIRECT_BOTH_MIS || p->direct_sample == KY_DIRECT_SINGLE_BOTH_MIS;
+    const int per_light = both ? 2 : (p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) ? 1 : 0;
     if (deferred && iteration) n += spp * p->max_path_depth * (n_lights > 0 ? n_lights : 0) * per_light;
     return n;
 }

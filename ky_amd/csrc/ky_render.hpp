@@ -45,6 +45,9 @@ using namespace kyd;
 #ifndef KY_WAVES_PER_EU_NO_FACTS_GENERAL
 #define KY_WAVES_PER_EU_NO_FACTS_GENERAL 6   // ... with general shapes (triangle / disk tests inline): -4 ... +2 % at seven, left at six; and path_tracing_recursion_t, whose
 #endif                                       // recursion keeps a frame per level: 10.8 -> 15.0 ms at seven on the Cornell box with lamp and point light (the other integrators +1.5 ... +3 %)
+#ifndef KY_WAVES_PER_EU_SINGLE
+#define KY_WAVES_PER_EU_SINGLE 5    // sample_single_light (strategy 49), every instantiation.  The Veach row (deferred rays, 24.3 KB of LDS) at five: 95 VGPRs, nothing spilled, no scratch, five workgroups per CU dispatched; at six: 80 VGPRs, 15 spilled (52 B scratch); at seven the compiler is back at 95 VGPRs and five (seven blocks of 24.3 KB exceed a CU's 160 KB).  Measured, 1280 x 720 x 1024 spp: 47.3 / 47.1 / 47.4 ms at five / six / seven, inside the runs' 1 % (at 4096 spp six is 1.3 % ahead: 181.9 against 184.3 ms): left at five, which spills nowhere but the fact-free deferred row (96 VGPRs, 12 B; its 28.9 KB block admits five)
+#endif
 #ifndef KY_WAVES_PER_EU_GENERIC
 #define KY_WAVES_PER_EU_GENERIC 5   // strategy / integrator read at run time: more code alive at once, 96 VGPRs measured best
 #endif
@@ -71,7 +74,8 @@ struct ItemSlot {  // one fetched work item, decoded once (wave-uniform) and rea
 // resident wavefronts per SIMD an instantiation is compiled for (its register budget): measured per family, see the KY_WAVES_PER_EU_* notes above
 template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE>
 constexpr int ky_waves_per_eu() {
-    return STRATEGY >= 0 ? (QUEUE ? (FEAT ? KY_WAVES_PER_EU_QUEUE_FEAT : KY_WAVES_PER_EU_QUEUE)
+    return STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS ? KY_WAVES_PER_EU_SINGLE :
+           STRATEGY >= 0 ? (QUEUE ? (FEAT ? KY_WAVES_PER_EU_QUEUE_FEAT : KY_WAVES_PER_EU_QUEUE)
                                   : ((FEAT == 0 && STRATEGY == KY_DIRECT_BOTH_MIS) ? ((GENERAL || INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_RECURSION) ? KY_WAVES_PER_EU_NO_FACTS_GENERAL : KY_WAVES_PER_EU_NO_FACTS)
                                      : ((FEAT != 0 && STRATEGY == KY_DIRECT_BOTH_MIS && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION) ? ((FEAT & KY_FEAT_SINGLE_ENV) ? KY_WAVES_PER_EU_ENV : KY_WAVES_PER_EU_HOT) : KY_WAVES_PER_EU)))
                          : KY_WAVES_PER_EU_GENERIC;
@@ -82,7 +86,7 @@ constexpr int ky_waves_per_eu() {
 template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false>
 KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
                                unsigned* __restrict__ flags, float4* __restrict__ queue_mem) {
-    static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
+    static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
                   "the deferred shadow rays belong to the iterative integrator's strategies with a light-sampling half");
     static_assert(FEAT == 0 || (STRATEGY >= 0 && !GENERAL && !DEBUG_SAMPLER), "scene facts are instantiated for kernels with a fixed strategy only");
     static_assert(STRATEGY >= 0 || INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION, "the run-time-dispatched kernel reads the integrator from rc");
@@ -94,10 +98,16 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
     __shared__ uint32_t c_key[QUEUE ? 1 : 256];   // the pixel's sampler key; the deferred-rays kernels recompute it per sample instead (1 KB of their LDS block)
     __shared__ unsigned long long c_def[QUEUE ? 3 * 256 : 1];   // QUEUE: fixed-point sums of the lane's resolved shadow rays
     const int tid = threadIdx.x;
-    const LdsScene Lds = stage_scene<LARGE, (FEAT & KY_FEAT_SMALL_TABLES) != 0>(S);
+    LdsScene lds_tables = stage_scene<LARGE, (FEAT & KY_FEAT_SMALL_TABLES) != 0>(S);
     if (STRATEGY >= 0) { rc.strategy = STRATEGY; rc.integrator = INTEGRATOR; }  // compile-time constants from here on
-    const int nee_weight = (rc.strategy == KY_DIRECT_IDLE || rc.integrator < KY_INTEGRATOR_DIRECT_LIGHTING ||
+    // sample_single_light reads its lights per lane: the kernels that may run it for several lights stage the light records too (3.75 KB of LDS)
+    if constexpr ((STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY < 0) && (FEAT & KY_FEAT_SINGLE_LIGHT) == 0)
+        lds_tables = stage_lights(S, lds_tables, rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    const LdsScene Lds = lds_tables;
+    int nee_weight = (rc.strategy == KY_DIRECT_IDLE || rc.integrator < KY_INTEGRATOR_DIRECT_LIGHTING ||
                             rc.integrator == KY_INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION) ? 0 : S->n_lights;
+    if constexpr (STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY < 0)   // one light's estimate per vertex, however many lights the scene has
+        if (rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS) nee_weight = min(nee_weight, 1);
 
     const int lane = threadIdx.x & 63;
     ItemSlot* my_ring = ring[threadIdx.x >> 6];

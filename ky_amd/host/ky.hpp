@@ -669,6 +669,8 @@ enum class direct_sample_enum_t {
     idle, sample_single_light = 1, sample_all_light = 2, bsdf = 4, light = 8, bsdf_mis = 16, light_mis = 32,
     both_mis = bsdf_mis | light_mis, default_stragtgy = sample_all_light | both_mis
 };
+// sample_single_light | both_mis (= KY_DIRECT_SINGLE_BOTH_MIS) is the one combination with sample_single_light the library renders (ky.cpp:3813-3832)
+constexpr direct_sample_enum_t operator|(direct_sample_enum_t a, direct_sample_enum_t b) { return (direct_sample_enum_t)((int)a | (int)b); }
 enum class integrator_enum_t {
     position, normal, basecolor, delta_bsdf, delta_light, direct_lighting_point, direct_lighting, stochastic_raytracing,
     simple_path_tracing_recursion, path_tracing_recursion, path_tracing_recursion_defered, path_tracing_iteration

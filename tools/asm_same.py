@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/asm_same.py <base.s> <new.s> : per kernel of two device listings: A (same text), B (same instructions and descriptor, registers renamed) or DIFFERENT; exit status 1 if any kernel is neither A nor B"""
+"""tools/asm_same.py <base.s> <new.s> : per kernel of two device listings: A (same text), B (same instructions and descriptor, registers renamed, local labels renumbered) or DIFFERENT; a kernel only one listing has is NEW / GONE; exit status 1 if any kernel both listings have is neither A nor B, or one is GONE"""
 import re, sys
 REG = re.compile(r"\b([sva])\[(\d+):(\d+)\]|\b(?:([sva])\d+|(vcc_lo|vcc_hi)|(vcc))\b")   # s12, v7, a3, s[4:5], vcc, vcc_lo, vcc_hi as operands
 def blank(m):
@@ -23,17 +23,18 @@ def kernels(path):
 def blanked(body):
     """instructions, labels and directives with every register operand blanked; comments dropped"""
     code = (l.split(";")[0].rstrip() for l in body if ".amdhsa_" not in l)
-    return [REG.sub(blank, l) for l in code if l]
+    # (a function's local labels carry its ordinal in the listing, .LBB<ordinal>_<block>: a kernel added before it renumbers them)
+    return [re.sub(r"\.(LBB|LJTI|LCPI)\d+_", r".\1_", REG.sub(blank, l)) for l in code if l]
 
 base, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-count = {"A": 0, "B": 0, "DIFFERENT": 0}
+count = {"A": 0, "B": 0, "DIFFERENT": 0, "NEW": 0, "GONE": 0}
 for sym in sorted(set(base) | set(new)):
     a, b = base.get(sym), new.get(sym)
-    if a is None or b is None: cls = "DIFFERENT"   # a kernel only one listing has
+    if a is None or b is None: cls = "NEW" if a is None else "GONE"   # a kernel only one listing has
     elif a == b: cls = "A"
     elif blanked(a) == blanked(b) and [l for l in a if ".amdhsa_" in l] == [l for l in b if ".amdhsa_" in l]: cls = "B"
     else: cls = "DIFFERENT"
     count[cls] += 1
     print("%-9s %s" % (cls, sym))
-print("%d kernels: A %d  B %d  different %d" % (len(set(base) | set(new)), count["A"], count["B"], count["DIFFERENT"]))
-sys.exit(1 if count["DIFFERENT"] else 0)
+print("%d kernels: A %d  B %d  different %d  new %d  gone %d" % (len(set(base) | set(new)), count["A"], count["B"], count["DIFFERENT"], count["NEW"], count["GONE"]))
+sys.exit(1 if count["DIFFERENT"] or count["GONE"] else 0)   # (a kernel that vanished is a change to the existing instantiations; a NEW one is not)

@@ -10,7 +10,8 @@ lib.kyhip_set_jit(0)   # the rates of the TABLE's kernels (run-time instantiatio
 spp = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 lights = (("point", A.CB_LIGHT_POINT), ("direction", A.CB_LIGHT_DIRECTION), ("area", A.CB_LIGHT_AREA), ("environment", A.CB_LIGHT_ENVIRONMENT))
 integrators = (("direct_lighting", 6), ("simple_recursion", 8), ("recursion", 9), ("recursion_defered", 10), ("iteration", 11))
-strategies = (("idle", 0), ("bsdf", 4), ("light", 8), ("bsdf_mis", 16), ("light_mis", 32), ("both_mis", 48))
+strategies = (("idle", 0), ("bsdf", 4), ("light", 8), ("bsdf_mis", 16), ("light_mis", 32), ("both_mis", 48),
+              ("single_both_mis", 49))   # sample_single_light: one light per vertex
 W, H = 1024, 768
 
 
