@@ -12,6 +12,8 @@
  *   ky_drivers lighting_enum [spp] [w] [h]  BASELINE.json configs[1]: the scene of the reference's (commented-out) render_lighting_enum
  *                                (4907-4935: Cornell, both small spheres, area light) at 1024 x 768, 1024 spp, path_tracing_iteration d5
  *                                both_mis; writes lighting_enum.bmp
+ *   ky_drivers lighting_cells [spp] [cell]  render_lighting_enum (4907-4935) made to work: the scene above as emitted, direct, indirect and all light,
+ *                                path_tracing_recursion_defered_t(10, both_mis, e) into a film_grid_t(1, 4, cell, cell) (256); writes lighting_cells.bmp
  *   ky_drivers batch [spp] [res] BASELINE.json configs[3]: render_multiple_scene scaled up -- the four Cornell light variants
  *                                (both_mis), Veach (both_mis) and a first-hit AOV pass, each res x res (1024) at spp (2048),
  *                                into a film_grid_t(2, 3, res, res); writes batch.bmp
@@ -192,6 +194,23 @@ static void render_lighting_enum(int spp, int width, int height) {
     film.store_image("lighting_enum");
 }
 
+// render_lighting_enum as the reference wrote it (4907-4935) -- it is commented out there: lighting_enum_t is never read (4423) and film_grid_t has no next_cell().
+// One Cornell box four times: what it emits, its direct light, its indirect light, all of it.
+static void render_lighting_cells(int spp, int cell) {
+    film_grid_t film(1, 4, cell, cell);
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, film.get_resolution());
+    std::unique_ptr<sampler_t> sampler = std::make_unique<random_sampler_t>(spp);
+    double kernel_ms = 0;
+    for (auto e : {lighting_enum_t::emit, lighting_enum_t::direct, lighting_enum_t::indirect, lighting_enum_t::all}) {
+        std::unique_ptr<integrator_t> integrator = std::make_unique<path_tracing_recursion_defered_t>(10, direct_sample_enum_t::both_mis, e);
+        use_devices(*integrator); integrator->render(&scene, sampler.get(), &film);
+        kernel_ms += integrator->last_kernel_ms();
+        film.next_subfilm();
+    }
+    std::printf("lighting_cells: 4 cells %dx%d, %d spp: kernels %.3f ms\n", cell, cell, spp, kernel_ms);
+    film.store_image("lighting_cells");
+}
+
 // BASELINE.json configs[4]: the stress frame
 static void render_stress(int spp, int res) {
     film_t film(res, res);
@@ -212,6 +231,8 @@ int main(int argc, char* argv[]) {
             render_single_scene(argc > 2 ? std::atoi(argv[2]) : 0);
         } else if (!std::strcmp(which, "lighting_enum")) {
             render_lighting_enum(argc > 2 ? std::atoi(argv[2]) : 1024, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 768);
+        } else if (!std::strcmp(which, "lighting_cells")) {
+            render_lighting_cells(argc > 2 ? std::atoi(argv[2]) : 10, argc > 3 ? std::atoi(argv[3]) : 256);
         } else if (!std::strcmp(which, "batch")) {
             render_batch(argc > 2 ? std::atoi(argv[2]) : 2048, argc > 3 ? std::atoi(argv[3]) : 1024);
         } else if (!std::strcmp(which, "stress")) {

@@ -268,6 +268,43 @@ int kyhip_render(int device, const ky_scene* scene, const ky_render_params* para
                  float* film_rgb, size_t film_row_stride_px);
 
 /*
+ * Light classes -- lighting_enum_t (ky.cpp:3591-3603), the argument of path_tracing_recursion_defered_t (4415) behind render_lighting_enum (4907-4935).
+ * A contribution to a sample's radiance belongs to the class given by k, the number of scattering vertices between the camera and the emitter (the
+ * expansion at 3582-3589): emit k = 0, direct k = 1, indirect k >= 2.  For path_tracing_iteration_t (11) and path_tracing_recursion_defered_t (10):
+ * emission or environment radiance added at a vertex with bounces == b has k = b (b >= 1 only after a delta bounce), the light estimate at that vertex
+ * k = b + 1 -- so a lamp seen in one mirror is direct light, in two indirect.  direct_lighting_t (6): emission k = 0, its estimate k = 1, nothing else.
+ * A masked render adds to the film only the contributions whose class bit is set; the sample is otherwise the unmasked one -- its random numbers,
+ * their order, every path decision, the roulette -- and clamp01 applies to the masked mean.  So per camera sample the three classes add up to
+ * the unmasked radiance, and lighting 1 / 3 are what the unmasked render gives at max_path_depth 0 / 1.
+ * The scattering bits diffuse = 8 and specular = 16 have no meaning in the reference: accepted both set or both clear (31 = lighting_enum_t::all = 7).
+ *
+ * kyhip_render_lighting: kyhip_render in every respect (it adds, the shard named by params, pinned films) for the classes of `lighting`.  With 7 / 31
+ *   it IS kyhip_render: the same kernel, the same film.  A mask that selects nothing the launch can produce (indirect alone at depth <= 1 or on
+ *   integrator 6) adds nothing and returns KY_OK.  KY_ERR_INVALID_VALUE, before any device work and with the film untouched: lighting 0, a bit above
+ *   31, exactly one of 8 / 16; any mask but all on integrators 0, 1, 2, 8, 9, whose terms are not one class each.
+ *   kyhip_last_kernel names the form of a masked launch behind the kernel: ", lighting 3: depth 1", ", lighting 4: emission at the first vertex and
+ *   its direct light dropped".  The queue engine has no masked form: such a launch runs on the lane engine, and the name says so.
+ * kyhip_lighting_plan: how that launch is run (host arithmetic, no device).  *effective_depth: the max_path_depth it renders at -- min(depth, 1)
+ *   without the indirect class, 0 with emit alone: paths end where what they could still add is masked out --, -1: nothing is launched.  *dropped:
+ *   what is left for the kernel, bit 1 no emission at the first vertex (bounces == 0), bit 2 no k = 1 term (the first vertex's light estimate,
+ *   whose random numbers are still drawn, and emission at bounces == 1).  Either pointer may be NULL.
+ * kyhip_kat_li_lighting: kyhip_kat_li for the samples of that launch.
+ */
+typedef enum ky_lighting {
+    KY_LIGHTING_EMIT     = 1,
+    KY_LIGHTING_DIRECT   = 2,
+    KY_LIGHTING_INDIRECT = 4,
+    KY_LIGHTING_ALL      = 7
+} ky_lighting;
+int kyhip_render_lighting(int device, const ky_scene* scene, const ky_render_params* params, int lighting,
+                          float* film_rgb, size_t film_row_stride_px);
+int kyhip_lighting_plan(const ky_render_params* params, int lighting, int* effective_depth, int* dropped);
+/* The refusals alone, without render params (host arithmetic): KY_OK when `integrator` (ky_integrator_kind) renders the classes of `lighting`. */
+int kyhip_lighting_check(int integrator, int lighting);
+int kyhip_kat_li_lighting(int device, const ky_scene* scene, const ky_render_params* params, int lighting,
+                          int x, int y, int s0, int n, float* out3);
+
+/*
  * Device-resident variants used by the multi-GPU path and by bench.py (inputs and outputs stay in
  * HBM; nothing crosses PCIe inside the timed region).
  *

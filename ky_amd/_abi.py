@@ -20,6 +20,7 @@ INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION, INTEGRATOR_PATH_TRACING_RECURSION, INT
 DIRECT_IDLE, DIRECT_BSDF, DIRECT_LIGHT, DIRECT_BSDF_MIS, DIRECT_LIGHT_MIS, DIRECT_BOTH_MIS = 0, 4, 8, 16, 32, 48
 DIRECT_SINGLE_LIGHT, DIRECT_SINGLE_BOTH_MIS = 1, 49   # sample_single_light: accepted as 1 | 48 only
 SAMPLER_DEBUG, SAMPLER_RANDOM = 0, 1
+LIGHTING_EMIT, LIGHTING_DIRECT, LIGHTING_INDIRECT, LIGHTING_ALL = 1, 2, 4, 7   # ky_lighting (lighting_enum_t, ky.cpp:3591-3603)
 SP_VARIANT_SMALLPT, SP_VARIANT_REWRITE = 0, 1
 KY_OK, KY_ERR_INVALID_VALUE, KY_ERR_LIMIT, KY_ERR_DEVICE, KY_ERR_NO_DEVICE = 0, -1, -2, -3, -4
 # hard limits of the device path (include/kyhip.h)
@@ -110,6 +111,10 @@ KYHIP_SYMBOLS = {
     "kyhip_shard_float_count": (C.c_int64, [PP]),
     "kyhip_film_term_limit": (C.c_int64, [PP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "kyhip_render": (C.c_int, [C.c_int, SP, PP, C.c_void_p, C.c_size_t]),
+    "kyhip_render_lighting": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_void_p, C.c_size_t]),
+    "kyhip_lighting_plan": (C.c_int, [PP, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kyhip_lighting_check": (C.c_int, [C.c_int, C.c_int]),
+    "kyhip_kat_li_lighting": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhip_workspace_bytes": (C.c_size_t, [PP]),
     "kyhip_render_tiles_device": (C.c_int, [C.c_int, SP, PP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kyhip_film_add_tiles_device": (C.c_int, [C.c_int, PP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -146,6 +151,8 @@ KYHOST_SYMBOLS = {
     "kyhost_scene_flatten": (SP, [C.c_void_p]),
     "kyhost_render": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "kyhost_render_lighting": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "kyhost_debug_area": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int,
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhost_store_image": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -76,15 +76,27 @@ def _scene_ptr(scene):
     return scene.flat if hasattr(scene, "flat") else scene
 
 
-def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0)):
-    """kyhip_render: integrator_t::render(scene, sampler, film) on the GPU; returns the (accumulated) host film."""
+def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0), lighting=None):
+    """kyhip_render: integrator_t::render(scene, sampler, film) on the GPU; returns the (accumulated) host film.
+    lighting: a mask of LIGHTING_EMIT / _DIRECT / _INDIRECT -- kyhip_render_lighting, only those light classes are added."""
     lib = A.load_kyhip()
     if film is None:
         film = np.zeros((params.height, params.width, 3), np.float32)
     stride = film.shape[1] if row_stride_px is None else row_stride_px
     base = film.ctypes.data + (origin_px[1] * stride + origin_px[0]) * 12
-    _check(lib.kyhip_render(device, _scene_ptr(scene), C.byref(params), C.c_void_p(base), stride))
+    if lighting is None:
+        _check(lib.kyhip_render(device, _scene_ptr(scene), C.byref(params), C.c_void_p(base), stride))
+    else:
+        _check(lib.kyhip_render_lighting(device, _scene_ptr(scene), C.byref(params), int(lighting), C.c_void_p(base), stride))
     return film
+
+
+def lighting_plan(params, lighting):
+    """kyhip_lighting_plan (host only): (effective_depth, dropped) of render(..., lighting=lighting); effective_depth -1: nothing is launched."""
+    lib = A.load_kyhip()
+    depth, dropped = C.c_int(0), C.c_int(0)
+    _check(lib.kyhip_lighting_plan(C.byref(params), int(lighting), C.byref(depth), C.byref(dropped)), lib)
+    return depth.value, dropped.value
 
 
 class PinnedFilm:
@@ -120,15 +132,20 @@ def render_multi(scene, params, devices, film=None, row_stride_px=None, origin_p
 
 
 def render_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, seed=1234,
-                    grid=None, cell=0, film=None, device=0):
-    """Drive the C++ host classes exactly like a reference driver: create_integrator(...)->render(&scene, sampler, &film)."""
+                    grid=None, cell=0, film=None, device=0, lighting=None):
+    """Drive the C++ host classes exactly like a reference driver: create_integrator(...)->render(&scene, sampler, &film).
+    lighting: integrator->set_lighting(lighting) first (lighting_enum_t: the light classes render() adds)."""
     host = A.load_kyhost()
     rows, cols = grid if grid else (0, 0)
     fw, fh = (cols * width, rows * height) if grid else (width, height)
     if film is None:
         film = np.zeros((fh, fw, 3), np.float32)
-    rc = host.kyhost_render(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, rows, cols,
-                            cell, _fptr(film), device)
+    if lighting is None:
+        rc = host.kyhost_render(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, rows, cols,
+                                cell, _fptr(film), device)
+    else:
+        rc = host.kyhost_render_lighting(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, rows, cols,
+                                         cell, _fptr(film), device, int(lighting))
     if rc == -2:
         return None  # create_integrator returned nullptr (ky.cpp:4638)
     if rc != 0:
@@ -256,6 +273,14 @@ def kat_li(scene, params, x, y, s0, n, device=0):
     lib = A.load_kyhip()
     out = np.zeros((n, 3), np.float32)
     _check(lib.kyhip_kat_li(device, _scene_ptr(scene), C.byref(params), x, y, s0, n, _fptr(out)))
+    return out
+
+
+def kat_li_lighting(scene, params, lighting, x, y, s0, n, device=0):
+    """kyhip_kat_li_lighting: kat_li for the samples of render(..., lighting=lighting)."""
+    lib = A.load_kyhip()
+    out = np.zeros((n, 3), np.float32)
+    _check(lib.kyhip_kat_li_lighting(device, _scene_ptr(scene), C.byref(params), int(lighting), x, y, s0, n, _fptr(out)))
     return out
 
 

@@ -45,6 +45,7 @@ struct StreamState {
     hipStream_t stream = nullptr;
     unsigned* d_counter = nullptr;         // word 0: the render kernels' work counter; word 1: the launch's film term limit (film_limit, ky_device.hpp) ...
     uint32_t counter_limit_bits = 0;       // ... as last written on this state's stream (0: not yet -- a limit is >= 1)
+    int counter_drop = 0;                  // word 2: a masked launch's drop bits for the run-time-dispatched masked kernels, as last written (0: not yet -- such a launch drops something)
     void* ws = nullptr;
     size_t ws_bytes = 0;
     bool ws_clean = false;                 // `ws` and the work counter hold zeros: the last frame's resolve_kernel put them back (no fills before the next frame's launch)
@@ -67,7 +68,7 @@ struct SceneSlot {
     hipStream_t upload_stream = nullptr;
     unsigned long long last_use = 0;
 };
-constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8;
+constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8, KY_MAX_VARIANTS = 96;
 // what kyhip_render / kyhip_render_multi keep between calls (the host-film seam); `m` serialises such calls per device, it is never
 // taken while a context's enqueue mutex is held
 // (measured on configs[1]'s 9.4 MB film, tools/seam_trace.py: what a call costs beyond its kernel -- the film's pinned download alone is 0.18 ms -- is
@@ -95,8 +96,8 @@ struct DeviceCtx {
     unsigned long long clock = 0;
     StreamState* last_launch = nullptr;    // kyhip_kernel_ms reads its event pair
     hipStream_t stream = nullptr;   // the library's own stream on this device (kyhip_render_multi)
-    int variant_blocks[64] = {};           // resident workgroups per CU of g_variants[i] (0: not asked yet) ...
-    size_t variant_lds[64] = {};           // ... for a scene block of this many bytes
+    int variant_blocks[KY_MAX_VARIANTS] = {};           // resident workgroups per CU of g_variants[i] (0: not asked yet) ...
+    size_t variant_lds[KY_MAX_VARIANTS] = {};           // ... for a scene block of this many bytes
     int last_variant = -1;
     int q_blocks_per_cu[3] = {0, 0, 0};
     struct JitKernel { hipModule_t module = nullptr; hipFunction_t fn = nullptr; int per_cu = 0; size_t lds = ~(size_t)0; bool failed = false; };
@@ -112,6 +113,10 @@ int upload_scene(DeviceCtx* c, const ky_scene* scene, hipStream_t stream, SceneS
 // The facts of the table kernel kyhip_render_tiles_device runs these parameters on that decide WHICH tests a ray goes through (KY_FEAT_BOXES: the box traversal;
 // KY_FEAT_SINGLE_ENV: the environment estimate's any-hit pair scan): the per-sample replay entries (ky_kat.hip) take the same ones, so that a replayed sample takes
 // every decision the rendered one took
-int render_replay_feat(const ky_scene* scene, const ky_render_params* p, const kyd::DScene* packed);
+// (drop: the drop bits of a masked launch, kyhip_render_lighting: it takes the masked rows)
+int render_replay_feat(const ky_scene* scene, const ky_render_params* p, const kyd::DScene* packed, int drop = 0);
+// kyhip_render_tiles_device with a lighting plan's drop bits (lighting_plan, ky_host.hpp) and what kyhip_last_kernel says of the launch's form
+int render_tiles_device(int device, const ky_scene* scene, const ky_render_params* p, float* d_tiles, void* d_workspace, size_t workspace_bytes, void* stream,
+                        int drop, const char* lighting_note);
 bool render_uses_boxes(const ky_scene* scene, const ky_render_params* p, const kyd::DScene* packed);
 }  // namespace kyh

@@ -2107,6 +2107,20 @@ KY_DEV void sample_single_light(SceneRef S, const LdsScene& Lds, const Vertex& v
     }
 }
 
+// What a vertex's light estimate draws from the sample's stream, drawn and thrown away: the vertex whose estimate a masked render drops (light classes,
+// DESIGN.md section 3) traces none of its rays and pushes none, and every later draw of the sample stays where it was.  sample_all_light: four numbers per light,
+// two more under the plain bsdf strategy for a light that is not a delta light (3894-3900); sample_single_light: the pick and four, nothing without lights.
+template <bool DEBUG_SAMPLER>
+KY_DEV void light_estimate_draws(SceneRef S, Sampler& smp, int strategy, bool active) {
+    if (!active) return;
+    const int nl = S.single_light() ? 1 : S->n_lights;
+    int n = 4 * nl;
+    if (strategy == KY_DIRECT_SINGLE_BOTH_MIS) n = nl > 0 ? 5 : 0;
+    else if (strategy == KY_DIRECT_BSDF)
+        for (int li = 0; li < nl; ++li) n += S.is_delta(S->light[li].kind) ? 0 : 2;
+    for (int i = 0; i < n; ++i) (void)sampler_next<DEBUG_SAMPLER>(smp);
+}
+
 // ---------------------------------------------------------------------------------------------
 // one path = one camera sample.  path_tracing_iteration_t::Li (4529-4617), direct_lighting_t::Li
 // (4136-4154) and debug_integrator_t::Li (4105-4122) share this state machine: step() advances
@@ -2143,8 +2157,12 @@ KY_DEV void path_begin(PathState& ps, SceneRef S, uint32_t pixel_key, int x, int
 
 // First half of a path vertex: trace the current ray and account for what the hit (or miss) itself contributes.
 // Returns false when the path has ended (radiance complete in ps.Lo); true when `v` holds a vertex to shade.
-template <bool DEBUG_SAMPLER>
-KY_DEV bool path_intersect(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc) {
+// DROP (light classes, lighting_enum_t 3591-3603): bit 0 -- nothing the camera ray's own hit or miss emits is added (class k = 0); bit 1 -- no
+// class k = 1 term: here the emission a path finds at bounces == 1, which it reads after a delta bounce only (the look-up goes with the add), in path_shade the
+// first vertex's light estimate.  0: nothing dropped, and the code of every instantiation that does not name DROP is what it was.  -1: the bits are `drop_rt`.
+template <bool DEBUG_SAMPLER, int DROP = 0>
+KY_DEV bool path_intersect(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc, int drop_rt = 0) {
+    const int drop = DROP >= 0 ? DROP : drop_rt;
     float t = K_INF;
     KY_PROBE(0);
     const int hs = trace_nearest(S, ps.o, ps.d, t);  // scene->intersect, 4542
@@ -2168,6 +2186,7 @@ KY_DEV bool path_intersect(PathState& ps, Vertex& v, SceneRef S, const LdsScene&
         see = ps.bounces == 0;                                 // 4328-4331
     else
         see = rc.integrator == KY_INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION;   // every way out of 4201-4237 returns it; the debug integrators: never
+    if (drop != 0 && ps.bounces < 2 && ((drop >> ps.bounces) & 1)) see = false;   // the class of what this vertex emits is its bounce count
     if (see) {
         if (hit) {
             if (!S.no_carried_light()) {   // (a scene lit by one delta or environment light: no surface carries a light)
@@ -2204,9 +2223,12 @@ struct VertexTrace {
 };
 
 // `tr` is a null constant everywhere but in the trace KAT kernel, which removes the tracing code.
-template <bool DEBUG_SAMPLER>
+// DROP / drop_rt: path_intersect's; bit 1 drops the light estimate of the vertex at bounces == 0, whose draws are still made (light_estimate_draws).
+template <bool DEBUG_SAMPLER, int DROP = 0>
 KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc, bool active,
-                       int lobe = -1, VertexTrace* tr = nullptr, ShadowQueue* sq = nullptr, unsigned tag = 0, bool ride_along = false, bool free_state = false) {
+                       int lobe = -1, VertexTrace* tr = nullptr, ShadowQueue* sq = nullptr, unsigned tag = 0, bool ride_along = false, bool free_state = false,
+                       int drop_rt = 0) {
+    const int drop = DROP >= 0 ? DROP : drop_rt;
     if (active) {
         // material->scattering(isect) for the nearest hit (3083); only plastic draws a lobe number (2663).
         // lobe >= 0: the caller has already made that draw (path_pick_lobe).
@@ -2242,7 +2264,9 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
     const bool defered = rc.integrator == KY_INTEGRATOR_PATH_TRACING_RECURSION_DEFERED;
     const bool simple = rc.integrator == KY_INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION;
     const bool delta = bsdf_is_delta(v.bsdf);
-    const bool nee = active && !delta;  // 4571
+    const bool lit = active && !delta;  // 4571
+    const bool unlit = (drop & 2) != 0 && lit && ps.bounces == 0;   // this vertex's estimate is the class that is dropped: the lane sits the estimators out
+    const bool nee = lit && !unlit;
     KY_PROBE(6);
     unsigned decisions = 0;
     // path_tracing_recursion_t, specular vertex (4341-4349): look the emitter up along a sampled direction, from the un-offset hit point
@@ -2268,6 +2292,7 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
         sample_all_light<DEBUG_SAMPLER>(S, Lds, v, wo, ps.smp, rc.strategy, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag,
                                         riding ? &ra : nullptr);  // 4575 / 4337 / 4458
     }
+    if ((drop & 2) != 0 && !simple) light_estimate_draws<DEBUG_SAMPLER>(S, ps.smp, rc.strategy, unlit);
     KY_CLK(8);
     if (rc.integrator == KY_INTEGRATOR_DIRECT_LIGHTING) return false;  // 4153
     if (!active) {

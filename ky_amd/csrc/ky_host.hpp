@@ -40,6 +40,17 @@ float film_term_limit(long long n_terms);
 // before any device work.
 bool film_in_range(const ky_render_params* p, int n_lights);
 int film_range_check(const ky_render_params* p, const ky_scene* scene);
+// Light classes (lighting_enum_t, ky.cpp:3591-3603): how a render of p that keeps only the classes of `lighting` (bit 1 emit, 2 direct, 4
+// indirect; 8 and 16 both or neither) is run.  Most of a mask is a shorter path: without the indirect class the launch's depth is min(depth, 1), with emit alone 0,
+// and what is left for the kernels are two drop bits (path_intersect, ky_device.hpp): 1 no emission at the first vertex, 2 no k = 1 term.  `nothing`: the mask
+// selects no class this launch can produce -- no launch at all.  `plain`: the launch is the unmasked one (every class it can produce is selected).
+struct LightingPlan {
+    int mask = 7, effective_depth = 0, dropped = 0;
+    bool nothing = false, plain = true;
+};
+int lighting_check(int integrator, int lighting);   // KY_OK, or KY_ERR_INVALID_VALUE with the message: the mask's own validity and whether the integrator renders it
+int lighting_plan(const ky_render_params* p, int lighting, LightingPlan* out);   // KY_OK, or KY_ERR_INVALID_VALUE with the message
+std::string lighting_note(const ky_render_params* p, int lighting, const LightingPlan& plan);   // what kyhip_last_kernel says of the launch's form ("" for a plain one)
 inline size_t workspace_bytes_for(const ShardConst& s) { return (size_t)s.n_pix * (3 * sizeof(unsigned long long) + sizeof(unsigned)); }   // per pixel: 3 x 64-bit fixed-point sums + one flag word
 
 // ---- scene packing (ky_pack.cpp) ----

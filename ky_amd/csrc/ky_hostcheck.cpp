@@ -167,6 +167,9 @@ int kyhip_kat_occluded(int, const ky_scene*, const float*, int, float*) { return
 int kyhip_kat_any_pair(int, const ky_scene*, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_occluded_between(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li(int, const ky_scene*, const ky_render_params*, int, int, int, int, float*) { return no_gpu(); }
+// (the masked entries refuse an invalid mask before they look for a device, like the real ones: lighting_plan is host code)
+int kyhip_render_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, float*, size_t) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
+int kyhip_kat_li_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, int, int, int, int, float*) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }
 int kyhip_smallpt_render(int, const ky_smallpt_sphere* spheres, int n, const ky_smallpt_params* p, double* image) {

@@ -135,6 +135,25 @@ __global__ void kat_li_kernel(const DScene* __restrict__ S_, RenderConst rc, int
     if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
 }
 
+// kat_li_kernel for a masked launch (kyhip_render_lighting): the same walk with the launch's drop bits (path_intersect, ky_device.hpp)
+template <bool DEBUG_SAMPLER, bool BOXES>
+__global__ void kat_li_lighting_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env, int drop) {
+    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    PathState ps;
+    bool alive = i < n;
+    if (alive) path_begin<DEBUG_SAMPLER>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i);
+    while (__any(alive)) {  // path_shade is a wave-uniform call
+        Vertex v;
+        bool have_vertex = false;
+        if (alive) have_vertex = path_intersect<DEBUG_SAMPLER, -1>(ps, v, S, Lds, rc, drop);
+        const bool cont = path_shade<DEBUG_SAMPLER, -1>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, nullptr, 0, false, false, drop);
+        alive = have_vertex && cont;
+    }
+    if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
+}
+
 // one light's direct-lighting estimate at given vertices with given random numbers (estimate_direct_lighting_*, 3889-4088)
 __global__ void kat_nee_kernel(const DScene* __restrict__ S, int strategy, int li, const float* __restrict__ in15, int n, float* __restrict__ out6) {
     const LdsScene Lds = stage_scene<true>(S);   // KAT kernels: always the scene-sized dynamic block
@@ -345,6 +364,36 @@ int kyhip_kat_li(int device, const ky_scene* scene, const ky_render_params* p, i
         else if (dbg) hipLaunchKernelGGL((kat_li_kernel<true, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
         else if (boxes) hipLaunchKernelGGL((kat_li_kernel<false, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
         else hipLaunchKernelGGL((kat_li_kernel<false, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
+        return (int)KY_OK;
+    });
+}
+
+// kyhip_kat_li for the samples of a masked render: what kyhip_render_lighting(lighting) adds per camera sample, before the mean and its clamp
+int kyhip_kat_li_lighting(int device, const ky_scene* scene, const ky_render_params* p, int lighting, int x, int y, int s0, int n, float* out3) {
+    LightingPlan plan;
+    int rcode = lighting_plan(p, lighting, &plan);
+    if (rcode != KY_OK) return rcode;
+    if (plan.plain) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);
+    if (!scene || !out3 || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (plan.nothing) { std::memset(out3, 0, (size_t)n * 3 * sizeof(float)); return KY_OK; }
+    ky_render_params q = *p;
+    q.max_path_depth = plan.effective_depth;
+    const RenderConst rc = make_rc(&q);
+    const bool dbg = p->sampler == KY_SAMPLER_DEBUG;
+    const int drop = plan.dropped;
+    float dummy = 0.f;
+    return kat_run(device, &dummy, 4, out3, (size_t)n * 3 * 4, [&](DeviceCtx* c, const float*, float* d_out) {
+        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
+        if (r != KY_OK) return r;
+        const size_t lds = lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
+        const dim3 grid((n + 255) / 256), block(256);
+        const int rf = render_replay_feat(scene, &q, sc->h, drop);
+        const bool boxes = (rf & KY_FEAT_BOXES) != 0;
+        const int env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
+        if (dbg && boxes) hipLaunchKernelGGL((kat_li_lighting_kernel<true, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
+        else if (dbg) hipLaunchKernelGGL((kat_li_lighting_kernel<true, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
+        else if (boxes) hipLaunchKernelGGL((kat_li_lighting_kernel<false, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
+        else hipLaunchKernelGGL((kat_li_lighting_kernel<false, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
         return (int)KY_OK;
     });
 }

@@ -269,9 +269,14 @@ struct Variant {
     int feat, integrator;
     bool large;
     RenderFn fn;
+    int drop;   // light classes (kyhip_render_lighting): 0 the unmasked kernel, 1 / 2 / 3 these drop bits at compile time, -1 the launch's bits read at run time
 };
-#define KY_VARIANT(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel<D, S, Q, G, F, I>}
-#define KY_VARIANT_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel<D, S, Q, G, F, I, true>}
+#define KY_VARIANT(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel<D, S, Q, G, F, I>, 0}
+#define KY_VARIANT_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel<D, S, Q, G, F, I, true>, 0}
+#define KY_VARIANT_MASKED(DROP, D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel_masked<DROP, D, S, Q, G, F, I>, DROP}
+#define KY_VARIANT_MASKED_LARGE(DROP, D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel_masked<DROP, D, S, Q, G, F, I, true>, DROP}
+// a row's three masked twins: emission at the first vertex dropped (lighting 2, 6), the k = 1 terms (5), both (4)
+#define KY_VARIANT_MASKED3(D, S, Q, G, F, I) KY_VARIANT_MASKED(1, D, S, Q, G, F, I), KY_VARIANT_MASKED(2, D, S, Q, G, F, I), KY_VARIANT_MASKED(3, D, S, Q, G, F, I)
 constexpr int IT = KY_INTEGRATOR_PATH_TRACING_ITERATION;
 static const Variant g_variants[] = {
 #ifdef KY_FEW_VARIANTS   // measurement builds (tools/mkvariant.sh -DKY_FEW_VARIANTS): the headline kernels and one catch-all, compiled in a sixth of the time
@@ -285,6 +290,7 @@ static const Variant g_variants[] = {
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV | KY_FEAT_SMALL_TABLES | KY_FEAT_BOXES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT),
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV | KY_FEAT_SMALL_TABLES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT),
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV, IT),
+    KY_VARIANT_MASKED(-1, false, -1, false, false, 0, IT),   // the one catch-all of masked launches (kyhip_render_lighting)
     KY_VARIANT(false, -1, false, false, 0, IT),
 #else
     // the iterative integrator, both_mis: by scene facts
@@ -345,6 +351,20 @@ static const Variant g_variants[] = {
     // scenes with triangles, disks or non-planar quads under the default strategy: the strategy as a compile-time constant is worth 17-23 % over the
     // run-time-dispatched kernel below (round 4: tools/room_rates.py, the random rooms with general shapes)
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, true, 0, IT),
+    // masked launches (light classes, kyhip_render_lighting; a launch with nothing dropped never takes one of these rows, nor a masked launch a row above): the both_mis
+    // rows the lighting driver's scenes land on -- the Cornell lamp, one environment light, the sphere lights with deferred rays -- and the two fact-free ones
+    KY_VARIANT_MASKED3(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_CORNELL | KY_FEAT_SMALL_TABLES | KY_FEAT_BOXES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT),
+    KY_VARIANT_MASKED3(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV | KY_FEAT_SMALL_TABLES | KY_FEAT_BOXES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT),
+    KY_VARIANT_MASKED3(false, KY_DIRECT_BOTH_MIS, true, false, KY_FEAT_VEACH | KY_FEAT_FLAT_PHONG | KY_FEAT_X_PLANKS, IT),
+    KY_VARIANT_MASKED3(false, KY_DIRECT_BOTH_MIS, true, false, 0, IT),
+    KY_VARIANT_MASKED3(false, KY_DIRECT_BOTH_MIS, false, false, 0, IT),
+    // ... every other masked launch: the run-time-dispatched kernels with the drop bits read per launch (the unmasked ones below carry no branch for them)
+    KY_VARIANT_MASKED(-1, false, -1, false, false, 0, IT),
+    KY_VARIANT_MASKED(-1, true, -1, false, false, 0, IT),
+    KY_VARIANT_MASKED(-1, false, -1, false, true, 0, IT),
+    KY_VARIANT_MASKED(-1, true, -1, false, true, 0, IT),
+    KY_VARIANT_MASKED_LARGE(-1, false, -1, false, true, 0, IT),
+    KY_VARIANT_MASKED_LARGE(-1, true, -1, false, true, 0, IT),
     // everything else: strategy and integrator at run time; the debug sampler; scenes with general shapes
     KY_VARIANT(false, -1, false, false, 0, IT),
     KY_VARIANT(true, -1, false, false, 0, IT),
@@ -356,14 +376,15 @@ static const Variant g_variants[] = {
 #endif
 };
 constexpr int KY_N_VARIANTS = (int)(sizeof g_variants / sizeof g_variants[0]);
-static_assert(KY_N_VARIANTS <= 64, "DeviceCtx::variant_blocks");
+static_assert(KY_N_VARIANTS <= KY_MAX_VARIANTS, "DeviceCtx::variant_blocks");
 
-static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix) {
+static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0) {
     const bool dbg = p->sampler == KY_SAMPLER_DEBUG;
     const bool general = packed->general != 0;
     const bool large = packed->n_surfaces > KY_LDS_SURFACES || packed->n_materials > KY_LDS_MATERIALS;
     for (const Variant& v : g_variants) {
         if (v.dbg != dbg || v.large != large) continue;
+        if (v.drop != drop && !(v.drop < 0 && drop != 0)) continue;
         if (general && !v.general) continue;
         if (v.strategy >= 0) {
             if (!specialisation_enabled() && !(v.strategy == KY_DIRECT_BOTH_MIS && v.feat == 0 && v.integrator == IT)) continue;   // KYHIP_SPECIALISE=0 keeps both_mis (and its queue form)
@@ -374,7 +395,8 @@ static const Variant* pick_variant(const ky_render_params* p, const DScene* pack
         if (v.queue && !(n_pix < (1 << 26) && deferred_rays)) continue;
         return &v;
     }
-    return nullptr;   // not reached: the last entries accept everything
+    return nullptr;   // not reached in the full table: its last entries accept everything, masked or not (a KY_FEW_VARIANTS build has no debug-sampler, general-shapes or
+                      // large-scene kernel, masked or not: such a launch is refused with "no render kernel")
 }
 
 }  // extern "C"
@@ -391,15 +413,15 @@ static int set_film_limit(StreamState* st, long long n_terms, hipStream_t stream
     }
     return KY_OK;
 }
-int kyh::render_replay_feat(const ky_scene* scene, const ky_render_params* p, const DScene* packed) {   // (ky_ctx.hpp)
-    const Variant* v = pick_variant(p, packed, shadow_queue_wanted(scene), p->width * p->height);
+int kyh::render_replay_feat(const ky_scene* scene, const ky_render_params* p, const DScene* packed, int drop) {   // (ky_ctx.hpp)
+    const Variant* v = pick_variant(p, packed, shadow_queue_wanted(scene), p->width * p->height, drop);
     return v != nullptr ? (v->feat & (KY_FEAT_BOXES | KY_FEAT_SINGLE_ENV)) : 0;
 }
 bool kyh::render_uses_boxes(const ky_scene* scene, const ky_render_params* p, const DScene* packed) { return (render_replay_feat(scene, p, packed) & KY_FEAT_BOXES) != 0; }
-extern "C" {
-
-int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render_params* p, float* d_tiles, void* d_workspace,
-                              size_t workspace_bytes, void* stream_) {
+// kyhip_render_tiles_device, and a masked launch of it (kyhip_render_lighting): `drop` are the plan's drop bits (lighting_plan, ky_pack.cpp), `lighting_note` what
+// kyhip_last_kernel says about the launch's form.  p is the plan's launch: its depth is the effective one.
+int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_params* p, float* d_tiles, void* d_workspace,
+                             size_t workspace_bytes, void* stream_, int drop, const char* lighting_note) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
     if (!shard_in_range(p)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices (%d x %d, %d spp)", p->width, p->height, p->samples_per_pixel);
     if (film_range_check(p, scene) != KY_OK) return KY_ERR_LIMIT;
@@ -449,7 +471,8 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
     // the queue engine implements path_tracing_iteration_t; every other integrator runs on the lane engine
     // (... and the queue engine has no sample_single_light: a strategy-49 launch runs on the lane engine, and kyhip_last_kernel says so)
     const bool single = p->direct_sample == KY_DIRECT_SINGLE_BOTH_MIS;
-    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single) {
+    // (... nor a masked form: a lighting launch runs on the lane engine too)
+    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single && drop == 0) {
         const int variant = p->sampler == KY_SAMPLER_DEBUG ? 2 : (p->direct_sample == KY_DIRECT_BOTH_MIS ? 0 : 1);
         const int per_cu = c->q_blocks_per_cu[variant] > 0 ? c->q_blocks_per_cu[variant] : 1;
         unsigned grid = (unsigned)(c->cus * per_cu);
@@ -464,7 +487,7 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
         else hipLaunchKernelGGL((render_kernel_q<true, -1>), dim3(grid), dim3(QE_THREADS), 0, stream, sc->d, rc, sh, st->d_counter, accum, flags);
         c->last_variant = -2;
     } else {
-        const Variant* v = pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix);
+        const Variant* v = pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop);
         if (!v) return fail(KY_ERR_DEVICE, "internal: no render kernel for these parameters");
         const int vi = (int)(v - g_variants);
         // run-time instantiation (kyhip_set_jit(1)): this launch's own kernel -- its sampler, strategy and integrator as compile-time constants and ALL
@@ -488,11 +511,12 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
             const bool want_queue = (p->direct_sample == KY_DIRECT_BOTH_MIS || single || p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) &&
                                     p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && sh.n_pix < (1 << 26) && !general && shadow_queue_wanted(scene);
             const bool same = v->dbg == dbg && v->strategy == p->direct_sample && v->queue == want_queue && v->general == general && v->feat == feat &&
-                              v->integrator == p->integrator && v->large == large_scene;
+                              v->integrator == p->integrator && v->large == large_scene && v->drop == drop;
             if (!same) {
-                char expr[192];
-                snprintf(expr, sizeof expr, "%s, %d, %s, %s, %d, %d, %s", dbg ? "true" : "false", p->direct_sample, want_queue ? "true" : "false",
-                         general ? "true" : "false", feat, p->integrator, large_scene ? "true" : "false");
+                char expr[192];   // (an unmasked launch's key is what it was: the drop bits are named only where there are some)
+                int en = snprintf(expr, sizeof expr, "%s, %d, %s, %s, %d, %d, %s", dbg ? "true" : "false", p->direct_sample, want_queue ? "true" : "false",
+                                  general ? "true" : "false", feat, p->integrator, large_scene ? "true" : "false");
+                if (drop != 0) snprintf(expr + en, sizeof expr - en, ", %d", drop);
                 DeviceCtx::JitKernel& k = c->jit[expr];
                 if (!k.fn && !k.failed) {
                     // mode 1: blocks for the compile the first time (a few seconds), then memory / disk.  mode 2: a missing object is compiled by a background
@@ -561,6 +585,11 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
                                                                           : " [sample_single_light: per-lane lights]");
             if (current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no sample_single_light]";
         }
+        if (drop != 0 && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no masked form]";
+        if (!jk && v->drop < 0 && st->counter_drop != drop) {   // the drop bits of a run-time-dispatched masked kernel: word 2 of the counter block, written when they change
+            HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(st->d_counter + 2), drop, 1, stream));
+            st->counter_drop = drop;
+        }
         HIP_TRY(hipEventRecord(st->ev0, stream));
         float4* queue_mem = queue ? st->d_shadow_queue : (float4*)nullptr;
         if (jk) {
@@ -576,6 +605,10 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
             c->last_variant = vi;
         }
     }
+    if (lighting_note) {
+        if (c->last_variant == -2) c->last_note.clear();   // (the queue engine's branch writes no note of its own)
+        c->last_note += lighting_note;
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(st->ev1, stream));
     st->timing_valid = true;
@@ -586,6 +619,13 @@ int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render
     HIP_TRY(hipEventRecord(st->done, stream));
     sc->readers |= 1u << (unsigned)(st - c->ss);
     return KY_OK;
+}
+
+extern "C" {
+
+int kyhip_render_tiles_device(int device, const ky_scene* scene, const ky_render_params* p, float* d_tiles, void* d_workspace,
+                              size_t workspace_bytes, void* stream_) {
+    return kyh::render_tiles_device(device, scene, p, d_tiles, d_workspace, workspace_bytes, stream_, 0, nullptr);
 }
 
 // resolves the event pair of the last launch on `device`; its stream must have been synchronised
@@ -613,6 +653,8 @@ const char* kyhip_last_kernel(int device) {
         snprintf(buf, sizeof buf, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d>", v.dbg ? "debug sampler, " : "", v.strategy, v.queue ? ", deferred shadow rays" : "",
                  v.general ? ", general shapes" : "", v.large ? ", scene-sized LDS block" : "", v.feat, v.integrator);
         name = buf;
+        if (v.drop > 0) name.insert(name.size() - 1, ", drop " + std::to_string(v.drop));
+        else if (v.drop < 0) name.insert(name.size() - 1, ", drop bits per launch");
     }
     name += c->last_note;
     return name.c_str();

@@ -129,6 +129,52 @@ int film_range_check(const ky_render_params* p, const ky_scene* scene) {
                 p->max_path_depth, scene->light_count);
 }
 
+// whether `integrator` renders the light classes of `lighting` at all: the mask alone, then the mask against the integrator
+int lighting_check(int integrator, int lighting) {
+    if (lighting <= 0 || lighting > 31) return fail(KY_ERR_INVALID_VALUE, "lighting %d: a mask of emit = 1, direct = 2, indirect = 4 (and diffuse = 8 with specular = 16) selects at least one class", lighting);
+    if (((lighting >> 3) & 1) != ((lighting >> 4) & 1))
+        return fail(KY_ERR_INVALID_VALUE, "lighting %d: the scattering bits diffuse = 8 and specular = 16 have no meaning of their own; both or neither", lighting);
+    if ((lighting & 24) && (lighting & 7) == 0) return fail(KY_ERR_INVALID_VALUE, "lighting %d selects no light class (emit = 1, direct = 2, indirect = 4)", lighting);
+    const bool classes = integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION || integrator == KY_INTEGRATOR_PATH_TRACING_RECURSION_DEFERED || integrator == KY_INTEGRATOR_DIRECT_LIGHTING;
+    if (!classes && (lighting & 7) != 7)
+        return fail(KY_ERR_INVALID_VALUE, "lighting %d on integrator %d: its terms are not one light class each; only all (7) renders there", lighting, integrator);
+    return KY_OK;
+}
+int lighting_plan(const ky_render_params* p, int lighting, LightingPlan* out) {
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
+    const int ok = lighting_check(p->integrator, lighting);
+    if (ok != KY_OK) return ok;
+    LightingPlan pl;
+    const int D = p->max_path_depth;
+    int m = lighting & 7;
+    pl.mask = m;
+    pl.effective_depth = D;
+    const bool path = p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION || p->integrator == KY_INTEGRATOR_PATH_TRACING_RECURSION_DEFERED;
+    if (!path && p->integrator != KY_INTEGRATOR_DIRECT_LIGHTING) { *out = pl; return KY_OK; }   // (lighting_check: all)
+    // the classes the launch can produce: direct_lighting_t stops after its light estimate whatever the depth; a path reaches class k at depth >= k
+    const int can = path ? (1 | (D >= 1 ? 2 : 0) | (D >= 2 ? 4 : 0)) : 3;
+    m &= can;
+    if (m == 0) { pl.nothing = true; pl.plain = false; pl.effective_depth = -1; *out = pl; return KY_OK; }
+    if (path && !(m & 4)) pl.effective_depth = (m & 2) ? (D < 1 ? D : 1) : 0;   // paths end where what they could still add is masked out
+    // (direct_lighting_t with emit alone keeps its one vertex: the kernel sits the estimate out lane by lane and still draws its numbers -- a launch that costs what
+    // the unmasked one costs, to add the emission only; a depth-0 path launch would add the same and is not substituted here)
+    const bool k1 = path ? pl.effective_depth >= 1 : true;   // the launch computes a k = 1 term at all
+    pl.dropped = ((m & 1) ? 0 : 1) | ((!(m & 2) && k1) ? 2 : 0);
+    pl.plain = pl.dropped == 0 && pl.effective_depth == D;
+    *out = pl;
+    return KY_OK;
+}
+std::string lighting_note(const ky_render_params* p, int lighting, const LightingPlan& pl) {
+    if (pl.plain || pl.nothing) return "";
+    std::string s = ", lighting " + std::to_string(lighting & 7) + ":";
+    const char* sep = " ";
+    if (pl.effective_depth != p->max_path_depth) { s += sep + ("depth " + std::to_string(pl.effective_depth)); sep = ", "; }
+    if (pl.dropped == 1) s += std::string(sep) + "emission at the first vertex dropped";
+    if (pl.dropped == 2) s += std::string(sep) + "the first vertex's direct light dropped";
+    if (pl.dropped == 3) s += std::string(sep) + "emission at the first vertex and its direct light dropped";
+    return s;
+}
+
 RenderConst make_rc(const ky_render_params* p) {
     RenderConst rc{};
     rc.integrator = p->integrator; rc.max_path_depth = p->max_path_depth; rc.strategy = p->direct_sample; rc.seed = p->seed;
@@ -983,6 +1029,16 @@ int kyhip_set_shadow_queue(int mode) {
     const int prev = shadow_queue_mode();
     if (mode >= -1 && mode <= 1) kyh::set_shadow_queue_raw(mode);
     return prev;
+}
+
+int kyhip_lighting_check(int integrator, int lighting) { return lighting_check(integrator, lighting); }
+int kyhip_lighting_plan(const ky_render_params* p, int lighting, int* effective_depth, int* dropped) {
+    LightingPlan pl;
+    const int rc = lighting_plan(p, lighting, &pl);
+    if (rc != KY_OK) return rc;
+    if (effective_depth) *effective_depth = pl.effective_depth;
+    if (dropped) *dropped = pl.dropped;
+    return KY_OK;
 }
 
 int64_t kyhip_shard_tile_count(const ky_render_params* p) {

@@ -71,8 +71,11 @@ struct ItemSlot {  // one fetched work item, decoded once (wave-uniform) and rea
 // The host's table of instantiations is g_variants below; kyhip_render_tiles_device launches the first one whose assumptions hold.
 // LARGE: the scene's per-lane tables live in dynamic shared memory sized by the scene (more than KY_LDS_SURFACES surfaces or
 // KY_LDS_MATERIALS materials; ky_device.hpp, LdsScene).
+// DROP: the light classes a masked render leaves out (path_intersect, ky_device.hpp): 0 nothing -- every instantiation that does not name it --, 1 / 2 / 3 the bits at
+// compile time (the table's masked rows, every run-time instantiation), -1 the bits are read from word 2 of the launch's work-counter block.
 // resident wavefronts per SIMD an instantiation is compiled for (its register budget): measured per family, see the KY_WAVES_PER_EU_* notes above
-template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE>
+// (a masked instantiation starts from its twin's: it is the twin with a term less)
+template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE, int DROP = 0>
 constexpr int ky_waves_per_eu() {
     return STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS ? KY_WAVES_PER_EU_SINGLE :
            STRATEGY >= 0 ? (QUEUE ? (FEAT ? KY_WAVES_PER_EU_QUEUE_FEAT : KY_WAVES_PER_EU_QUEUE)
@@ -83,14 +86,17 @@ constexpr int ky_waves_per_eu() {
 
 // The kernel's body is a device function so that two kinds of __global__ entry can wrap it: the template render_kernel below (the library's table
 // of instantiations) and the extern "C" kernel of a run-time instantiation (ky_jit.cpp).
-template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false>
+template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0>
 KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
                                unsigned* __restrict__ flags, float4* __restrict__ queue_mem) {
     static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
                   "the deferred shadow rays belong to the iterative integrator's strategies with a light-sampling half");
     static_assert(FEAT == 0 || (STRATEGY >= 0 && !GENERAL && !DEBUG_SAMPLER), "scene facts are instantiated for kernels with a fixed strategy only");
     static_assert(STRATEGY >= 0 || INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION, "the run-time-dispatched kernel reads the integrator from rc");
+    static_assert(DROP >= -1 && DROP <= 3, "two drop bits, or -1: read per launch");
     const SceneRef S{S_, GENERAL, FEAT, LARGE};
+    // (DROP < 0) the launch's drop bits: the host leaves them in word 2 of the work-counter block, next to the film's term limit
+    const int drop_rt = DROP < 0 ? (int)__builtin_amdgcn_readfirstlane(__hip_atomic_load(counter + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
     __shared__ ItemSlot ring[4][KY_RING];
     // the lane's pixel chunk (touched when a path starts or ends, not while a vertex is shaded) lives in LDS, not in registers
     __shared__ int c_xy[256], c_pix[256];
@@ -247,7 +253,7 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
             const bool tracing = alive && !have_vertex;
             if (!__any(tracing)) break;
             if (tracing) {
-                const bool ended = !path_intersect<DEBUG_SAMPLER>(ps, v, S, Lds, rc);
+                const bool ended = !path_intersect<DEBUG_SAMPLER, DROP>(ps, v, S, Lds, rc, drop_rt);
                 if (!ended) have_vertex = true;
                 if (ended) {
                     alive = false;
@@ -271,8 +277,8 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
         if (QUEUE) tag = ((unsigned)c_pix[tid] << 6) | (unsigned)lane;
         // ---- (3) shade the vertex: direct lighting, continuation ----
         {
-            const bool cont = path_shade<DEBUG_SAMPLER>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, QUEUE ? &sq : nullptr, tag,
-                                                        STRATEGY >= 0 && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_RECURSION, true);  // wave-uniform call
+            const bool cont = path_shade<DEBUG_SAMPLER, DROP>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, QUEUE ? &sq : nullptr, tag,
+                                                              STRATEGY >= 0 && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_RECURSION, true, drop_rt);  // wave-uniform call
             if (have_vertex && !cont) {
                 alive = false;
             }
@@ -289,4 +295,13 @@ __global__ __launch_bounds__(256, (ky_waves_per_eu<DEBUG_SAMPLER, STRATEGY, QUEU
     const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
     float4* __restrict__ queue_mem) {
     render_kernel_body<DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE>(S_, rc, sh, counter, accum, flags, queue_mem);
+}
+
+// The masked instantiations (light classes): a kernel template of their own, so that every instantiation of render_kernel keeps its name and its code.
+template <int DROP, bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false>
+__global__ __launch_bounds__(256, (ky_waves_per_eu<DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, DROP>())) void render_kernel_masked(
+    const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
+    float4* __restrict__ queue_mem) {
+    static_assert(DROP != 0, "nothing dropped: render_kernel");
+    render_kernel_body<DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, DROP>(S_, rc, sh, counter, accum, flags, queue_mem);
 }

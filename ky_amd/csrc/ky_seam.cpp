@@ -31,9 +31,9 @@ static int seam_reserve(void** p, size_t* have, size_t need, bool pinned) {
     return KY_OK;
 }
 
-extern "C" {
-
-int kyhip_render_multi(const int* devices, int n_devices, const ky_scene* scene, const ky_render_params* p, float* film_rgb, size_t stride_px) {
+// kyhip_render_multi; `drop` / `lighting_note`: a masked frame's drop bits and form (kyhip_render_lighting; p is then the plan's launch), 0 / null otherwise
+static int render_multi(const int* devices, int n_devices, const ky_scene* scene, const ky_render_params* p, float* film_rgb, size_t stride_px, int drop,
+                        const char* lighting_note) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
     if (!shard_in_range(p)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices (%d x %d, %d spp)", p->width, p->height, p->samples_per_pixel);
     if (film_range_check(p, scene) != KY_OK) return KY_ERR_LIMIT;
@@ -134,7 +134,7 @@ int kyhip_render_multi(const int* devices, int n_devices, const ky_scene* scene,
                 }
             }
         }
-        rcode = kyhip_render_tiles_device(devices[i], scene, &shard[i], dst, nullptr, 0, ctx[i]->stream);
+        rcode = render_tiles_device(devices[i], scene, &shard[i], dst, nullptr, 0, ctx[i]->stream, drop, lighting_note);
         if (rcode != KY_OK) break;
         if (devices[i] != root) {
             HIP_CHECK_BREAK(hipSetDevice(devices[i]));
@@ -209,6 +209,27 @@ int kyhip_render_multi(const int* devices, int n_devices, const ky_scene* scene,
     if (rcode != KY_OK) return rcode;
     if (sync_err != hipSuccess) return fail(KY_ERR_DEVICE, "render failed: %s (the caller's film may hold a part of the frame)", hipGetErrorString(sync_err));
     return KY_OK;
+}
+
+extern "C" {
+
+int kyhip_render_multi(const int* devices, int n_devices, const ky_scene* scene, const ky_render_params* p, float* film_rgb, size_t stride_px) {
+    return render_multi(devices, n_devices, scene, p, film_rgb, stride_px, 0, nullptr);
+}
+
+// integrator_t::render keeping the light classes of `lighting` only (lighting_enum_t, ky.cpp:3591-3603).  The plan is host arithmetic (lighting_plan): an
+// invalid mask is refused before any device work, a mask that selects all the launch can produce IS kyhip_render, one that selects nothing of it adds nothing.
+int kyhip_render_lighting(int device, const ky_scene* scene, const ky_render_params* p, int lighting, float* film_rgb, size_t stride_px) {
+    LightingPlan plan;
+    const int rc = lighting_plan(p, lighting, &plan);
+    if (rc != KY_OK) return rc;
+    if (plan.plain) return kyhip_render(device, scene, p, film_rgb, stride_px);
+    if (!scene || !film_rgb || stride_px < (size_t)p->width) return fail(KY_ERR_INVALID_VALUE, "bad film arguments");
+    if (plan.nothing) return KY_OK;
+    ky_render_params q = *p;
+    q.max_path_depth = plan.effective_depth;
+    const std::string note = lighting_note(p, lighting, plan);
+    return render_multi(&device, 1, scene, &q, film_rgb, stride_px, plan.dropped, note.c_str());
 }
 
 const char* kyhip_multi_status(int root_device) {

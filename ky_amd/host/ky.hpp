@@ -684,6 +684,12 @@ public:
     // current target.  Errors of the C ABI surface as exceptions, like the reference's LOG_ERROR (75-82).
     void render(scene_t* scene, sampler_t* original_sampler, film_t* film) {
         const ky_render_params p = params_for(original_sampler, film);
+        if (masked()) {   // light classes (set_lighting): kyhip_render_lighting, which renders on ONE device: devices_[0]; the rest of a list given to set_devices is not used
+                          // (a masked kyhip_render_multi is out of scope; the image does not depend on the list)
+            const int rc = kyhip_render_lighting(devices_[0], &scene->flatten(), &p, lighting_, film->target_origin(), film->row_stride_px());
+            if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_lighting: ") + kyhip_last_error());
+            return;
+        }
         // the reference spreads this loop over all cores (3696-3699); here the frame's tiles are spread over devices_
         const int rc = kyhip_render_multi(devices_.data(), (int)devices_.size(), &scene->flatten(), &p, film->target_origin(), film->row_stride_px());
         if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_multi: ") + kyhip_last_error());
@@ -709,7 +715,8 @@ public:
             for (int x = bx; x < ex; ++x) {
                 if (x < 0 || y < 0 || x >= w || y >= h) continue;
                 film->clear_color(x, y);
-                const int rc = kyhip_kat_li(devices_[0], &scene->flatten(), &p, x, y, 0, spp, li.data());
+                const int rc = masked() ? kyhip_kat_li_lighting(devices_[0], &scene->flatten(), &p, lighting_, x, y, 0, spp, li.data())
+                                        : kyhip_kat_li(devices_[0], &scene->flatten(), &p, x, y, 0, spp, li.data());
                 if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_kat_li: ") + kyhip_last_error());
                 color_t L{};
                 for (int s = 0; s < spp; ++s) L = L + color_t(li[3 * (size_t)s], li[3 * (size_t)s + 1], li[3 * (size_t)s + 2]) * inv_spp;
@@ -758,6 +765,14 @@ protected:
         return p;
     }
     static float clamp01_keep_nan(float x) { return x < 0 ? 0 : (x > 1 ? 1 : x); }   // std::clamp keeps a NaN (1545)
+    // The light classes render() adds (lighting_enum_t, 3591-3603; include/kyhip.h "Light classes"): a mask this integrator cannot render throws here, like every
+    // other invalid value of the mirror -- lighting 0, one scattering bit without the other, any mask but all on an integrator whose terms are not one class each.
+    void store_lighting(int lighting) {
+        if (kyhip_lighting_check((int)kind_, lighting) != KY_OK) throw std::runtime_error(std::string("lighting_enum_t: ") + kyhip_last_error());
+        lighting_ = lighting;
+    }
+    bool masked() const { return (lighting_ & 7) != 7; }
+    int lighting_ = 31;   // lighting_enum_t::all
     integrator_enum_t kind_;
     int max_path_depth_;
     direct_sample_enum_t direct_sample_enum_;
@@ -773,16 +788,23 @@ public:
     }
 };
 // direct_lighting_t, ky.cpp:4125-4155
+enum class lighting_enum_t { emit = 1, direct = 2, indirect = 4, all_lighting = 7, diffuse = 8, specular = 16, all_scattering = 24, all = 31 };  // 3591-3603
+constexpr lighting_enum_t operator|(lighting_enum_t a, lighting_enum_t b) { return (lighting_enum_t)((int)a | (int)b); }
 class direct_lighting_t : public integrator_t {
 public:
     explicit direct_lighting_t(direct_sample_enum_t direct_sample_enum, int device = 0)
         : integrator_t(integrator_enum_t::direct_lighting, 0, direct_sample_enum, device) {}
+    void set_lighting(lighting_enum_t lighting_enum) { store_lighting((int)lighting_enum); }   // emission k = 0, its light estimate k = 1, nothing indirect
 };
 // path_integrator_t, ky.cpp:4172-4184
 class path_integrator_t : public integrator_t {
 protected:
     path_integrator_t(integrator_enum_t kind, int max_path_depth, direct_sample_enum_t direct_sample_enum, int device)
         : integrator_t(kind, max_path_depth, direct_sample_enum, device) {}
+public:
+    // the light classes render() adds: what path_tracing_recursion_defered_t takes in its constructor (4415), for the path integrators that keep their terms apart
+    // (path_tracing_iteration_t too; the two other recursions throw for any mask but all)
+    void set_lighting(lighting_enum_t lighting_enum) { store_lighting((int)lighting_enum); }
 };
 // path_tracing_iteration_t, ky.cpp:4523-4618 -- the hot path
 class path_tracing_iteration_t : public path_integrator_t {
@@ -802,12 +824,14 @@ public:
     path_tracing_recursion_t(int max_path_depth, direct_sample_enum_t direct_sample_enum, int device = 0)
         : path_integrator_t(integrator_enum_t::path_tracing_recursion, max_path_depth, direct_sample_enum, device) {}
 };
-enum class lighting_enum_t { emit = 1, direct = 2, indirect = 4, all_lighting = 7, diffuse = 8, specular = 16, all_scattering = 24, all = 31 };  // 3591-3603
 class path_tracing_recursion_defered_t : public path_integrator_t {
 public:
-    // lighting_enum is stored and never read by the reference either (4412)
-    path_tracing_recursion_defered_t(int max_path_depth, direct_sample_enum_t direct_sample_enum, lighting_enum_t = lighting_enum_t::all, int device = 0)
-        : path_integrator_t(integrator_enum_t::path_tracing_recursion_defered, max_path_depth, direct_sample_enum, device) {}
+    // The reference stores lighting_enum and never reads it (4412, 4423), though its Li labels the three terms (Le 4545, Ld 4567, Li 4583).  Here it
+    // selects them: render() adds the classes of lighting_enum only (kyhip_render_lighting); all -- the default, and what create_integrator passes -- is the reference's image.
+    path_tracing_recursion_defered_t(int max_path_depth, direct_sample_enum_t direct_sample_enum, lighting_enum_t lighting_enum = lighting_enum_t::all, int device = 0)
+        : path_integrator_t(integrator_enum_t::path_tracing_recursion_defered, max_path_depth, direct_sample_enum, device) {
+        store_lighting((int)lighting_enum);
+    }
 };
 
 // create_integrator, ky.cpp:4621-4639.  nullptr for enums the reference's switch does not handle (4638).

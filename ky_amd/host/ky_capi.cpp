@@ -59,8 +59,8 @@ const ky_scene* kyhost_scene_flatten(void* scene) {
 // reference driver (ky.cpp:4697, 4732, 4770, 4810, 4851, 4899).  film points at the WHOLE film
 // (grid_cols*width x grid_rows*height when a grid is used) and is accumulated into.
 // Returns 0, -1 on error, -2 when create_integrator returns nullptr.
-int kyhost_render(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed,
-                  int width, int height, int grid_rows, int grid_cols, int cell, float* film, int device) {
+static int render_impl(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed,
+                       int width, int height, int grid_rows, int grid_cols, int cell, float* film, int device, int lighting) {
     int status = 0;
     int rc = guarded([&] {
         std::unique_ptr<ky::integrator_t> integrator;
@@ -70,6 +70,11 @@ int kyhost_render(void* scene, int integrator_enum, int depth, int direct_sample
         else
             integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device < 0 ? 0 : device);  // 4621
         if (!integrator) { status = -2; return; }
+        if (lighting >= 0) {   // kyhost_render_lighting: set_lighting of the integrators that have one; every other integrator renders all or throws
+            if (auto* pi = dynamic_cast<ky::path_integrator_t*>(integrator.get())) pi->set_lighting((ky::lighting_enum_t)lighting);
+            else if (auto* dl = dynamic_cast<ky::direct_lighting_t*>(integrator.get())) dl->set_lighting((ky::lighting_enum_t)lighting);
+            else if ((lighting & 7) != 7 || lighting > 31 || ((lighting >> 3) & 1) != ((lighting >> 4) & 1)) throw std::runtime_error("lighting_enum_t: the debug integrators render all only");
+        }
         // device < 0 selects a device LIST: -1 = every visible GPU; -n (n >= 2) = device 0 listed n times, which drives the
         // multi-device path (shards, gather, one add) on a single GPU
         if (device == -1) integrator->set_devices(ky::integrator_t::all_devices());
@@ -92,6 +97,17 @@ int kyhost_render(void* scene, int integrator_enum, int depth, int direct_sample
         std::memcpy(film, f->data(), n * sizeof(float));
     });
     return rc != 0 ? rc : status;
+}
+
+int kyhost_render(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed,
+                  int width, int height, int grid_rows, int grid_cols, int cell, float* film, int device) {
+    return render_impl(scene, integrator_enum, depth, direct_sample_enum, sampler_kind, spp, seed, width, height, grid_rows, grid_cols, cell, film, device, -1);
+}
+// kyhost_render after integrator->set_lighting(lighting) (lighting_enum_t, ky.cpp:3591-3603): the light classes of the mask only
+int kyhost_render_lighting(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed,
+                           int width, int height, int grid_rows, int grid_cols, int cell, float* film, int device, int lighting) {
+    if (lighting < 0) { g_host_error = "lighting_enum_t: negative mask"; return -1; }
+    return render_impl(scene, integrator_enum, depth, direct_sample_enum, sampler_kind, spp, seed, width, height, grid_rows, grid_cols, cell, film, device, lighting);
 }
 
 // create_integrator(...)->debug_area(&scene, sampler, &film, {bx, by}, {ex, ey}) on a film_t of width x height (ky.cpp:3733-3777);
