@@ -18,6 +18,8 @@
  *                                (both_mis), Veach (both_mis) and a first-hit AOV pass, each res x res (1024) at spp (2048),
  *                                into a film_grid_t(2, 3, res, res); writes batch.bmp
  *   ky_drivers stress [spp] [res] BASELINE.json configs[4]: Cornell res x res (4096), spp (16384), max depth 16; writes stress.bmp
+ *   ky_drivers progressive [spp] [w] [h]  the frame of lighting_enum (512 spp, 1024 x 768) rendered in passes of at least 64 samples (kyhip_frame_*): prints the
+ *                                reference's progress line (3703) per pass, writes progressive_preview.bmp after the first pass and progressive.bmp at the end
  * An optional last argument multiplies every spp (the reference's values are tiny because its CPU path is slow).
  * KY_DEVICES=all (or a count n: devices 0 .. n-1) makes every integrator spread its tiles over that many GPUs of the node
  * (integrator_t::set_devices); the images do not depend on it.
@@ -211,6 +213,37 @@ static void render_lighting_cells(int spp, int cell) {
     film.store_image("lighting_cells");
 }
 
+// The headline frame in passes: a picture after the first 64 samples, the reference's progress line (3703) after every pass, and a final image that is
+// render()'s bit for bit (include/kyhip.h, kyhip_frame_*).
+static void render_progressive(int spp, int width, int height) {
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, {(float)width, (float)height});
+    ky_render_params p{};
+    p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS;
+    p.samples_per_pixel = spp; p.sampler = KY_SAMPLER_RANDOM; p.seed = random_sampler_t(spp).seed();
+    p.width = width; p.height = height; p.tile_w = 16; p.tile_h = 16; p.tile_first = 0; p.tile_step = 1;
+    kyhip_frame* frame = nullptr;
+    if (kyhip_frame_begin(0, &scene.flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+    struct frame_end_t { kyhip_frame* f; ~frame_end_t() { kyhip_frame_end(f); } } frame_end{frame};
+    int done = 0, passes = 0;
+    double kernel_ms = 0;
+    const double seconds = timing_seconds([&] {
+        while (done < spp) {
+            if (kyhip_frame_render(frame, 64, &done) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_render: ") + kyhip_last_error());
+            kernel_ms += kyhip_kernel_ms(0);
+            std::printf("rendering... %d spp, %.2f%%\n", spp, 100. * done / spp);
+            if (passes++ == 0) {   // the picture so far: the mean of the samples done
+                film_t preview(width, height);
+                if (kyhip_frame_resolve(frame, 1, preview.target_origin(), preview.row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+                preview.store_image("progressive_preview");
+            }
+        }
+    });
+    film_t film(width, height);
+    if (kyhip_frame_resolve(frame, 0, film.target_origin(), film.row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+    std::printf("progressive: %dx%d, %d spp in %d passes: %.3f seconds (kernels %.3f ms)\n", width, height, spp, passes, seconds, kernel_ms);
+    film.store_image("progressive");
+}
+
 // BASELINE.json configs[4]: the stress frame
 static void render_stress(int spp, int res) {
     film_t film(res, res);
@@ -231,6 +264,8 @@ int main(int argc, char* argv[]) {
             render_single_scene(argc > 2 ? std::atoi(argv[2]) : 0);
         } else if (!std::strcmp(which, "lighting_enum")) {
             render_lighting_enum(argc > 2 ? std::atoi(argv[2]) : 1024, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 768);
+        } else if (!std::strcmp(which, "progressive")) {
+            render_progressive(argc > 2 ? std::atoi(argv[2]) : 512, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 768);
         } else if (!std::strcmp(which, "lighting_cells")) {
             render_lighting_cells(argc > 2 ? std::atoi(argv[2]) : 10, argc > 3 ? std::atoi(argv[3]) : 256);
         } else if (!std::strcmp(which, "batch")) {

@@ -366,6 +366,47 @@ int kyhip_render_multi(const int* devices, int n_devices, const ky_scene* scene,
                        float* film_rgb, size_t film_row_stride_px);
 
 /*
+ * A frame rendered in passes -- integrator_t::render (ky.cpp:3689-3729) with the picture available, and the right to stop, after every pass; the
+ * reference only reports how far it is, "rendering... N spp, x%" per row (3703).
+ * A pixel's samples are cut into chunks by a schedule that depends on samples_per_pixel only, work items are queued chunk by chunk, samples are keyed by
+ * their absolute index and a chunk's sum enters an integer accumulator: so the frame's chunks may be rendered by any number of launches, in order, and a
+ * complete frame IS kyhip_render's film, bit for bit, however its passes were cut (DESIGN.md "Passes").  A frame owns its accumulators (on `device`);
+ * kyhip_render* calls and other frames between its passes neither disturb it nor are disturbed.  All passes of a frame run the kernel its first pass
+ * took.  The queue engine renders no passes: a frame runs on the lane engine, and kyhip_last_kernel says so.  Calls on one frame must not overlap.
+ *
+ * kyhip_pass_boundaries: the sample counts at which a pass of an `spp`-sample frame can end -- the ends of the chunks of its schedule, ascending, the
+ *   last is spp.  Writes min(n, count) values to `bounds` (may be NULL with n = 0); returns count, or KY_ERR_INVALID_VALUE for spp < 1 (or above 2^24,
+ *   which no render accepts).  Pure host arithmetic.
+ * kyhip_frame_begin: validates exactly as kyhip_render does (the same statuses, before any device work); params->samples_per_pixel is the frame's
+ *   TOTAL, the shard named by params is the frame's.  The scene is copied: the caller's arrays need not outlive the call.  *out: the frame, with
+ *   nothing rendered.
+ * kyhip_frame_render: renders whole chunks until at least min_samples more samples per pixel are done or the frame is complete.  Blocking.
+ *   *samples_done (may be NULL) receives the total done so far, always a value of kyhip_pass_boundaries (or 0).  On a complete frame: KY_OK, nothing
+ *   is launched.  min_samples < 1: KY_ERR_INVALID_VALUE.  kyhip_last_kernel names the pass behind the kernel: ", pass: chunks 2..18 of 51, samples
+ *   48..308 of 500".
+ * kyhip_frame_samples: samples per pixel done so far and the frame's total (either pointer may be NULL).
+ * kyhip_frame_resolve: ADDS clamp01(value) per pixel to a host film exactly like kyhip_render (a sub-film's first pixel and its row stride; a pinned
+ *   film is added to in place by the GPU, any other film by the host).  normalise 0: value = sum / total -- for a complete frame this IS kyhip_render's
+ *   film; normalise 1: value = sum / done, the picture so far (nothing is added while done == 0).  Pixels whose sums met NaN or +-inf or saturated
+ *   resolve as they do in kyhip_render.  Does not change the frame: it may be resolved any number of times and rendered further.
+ * kyhip_frame_state_bytes / _save / _load: a checkpoint -- a header (a magic number, kyhip_kernel_source_hash, the params, a hash of the packed scene,
+ *   the samples done, the shard's pixel count), then the accumulators and the flag words.  kyhip_frame_load refuses with KY_ERR_INVALID_VALUE, the frame
+ *   untouched, a buffer shorter than the state and a state whose header differs in any field but the samples done from what `f` was begun with (another
+ *   seed, sample count, scene, film size, shard, or a library built from other kernel sources); otherwise `f` continues from the saved pass.
+ * kyhip_frame_end: releases the frame (NULL is fine).
+ */
+typedef struct kyhip_frame kyhip_frame;   /* opaque */
+int     kyhip_pass_boundaries(int spp, int* bounds, int n);
+int     kyhip_frame_begin(int device, const ky_scene* scene, const ky_render_params* params, kyhip_frame** out);
+int     kyhip_frame_render(kyhip_frame* f, int min_samples, int* samples_done);
+int     kyhip_frame_samples(const kyhip_frame* f, int* done, int* total);
+int     kyhip_frame_resolve(kyhip_frame* f, int normalise, float* film_rgb, size_t film_row_stride_px);
+int64_t kyhip_frame_state_bytes(const kyhip_frame* f);
+int     kyhip_frame_save(kyhip_frame* f, void* buf, size_t bytes);
+int     kyhip_frame_load(kyhip_frame* f, const void* buf, size_t bytes);
+void    kyhip_frame_end(kyhip_frame* f);
+
+/*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent
  * kyhip_render* call on `device`, from hipEvents recorded on the launch stream around that one
  * kernel.  The stream must have been synchronised.  Negative if no timing is available.

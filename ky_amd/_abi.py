@@ -120,6 +120,15 @@ KYHIP_SYMBOLS = {
     "kyhip_film_add_tiles_device": (C.c_int, [C.c_int, PP, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kyhip_film_add_gathered_device": (C.c_int, [C.c_int, PP, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kyhip_render_multi": (C.c_int, [C.POINTER(C.c_int), C.c_int, SP, PP, C.c_void_p, C.c_size_t]),
+    "kyhip_pass_boundaries": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "kyhip_frame_begin": (C.c_int, [C.c_int, SP, PP, C.POINTER(C.c_void_p)]),
+    "kyhip_frame_render": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "kyhip_frame_samples": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kyhip_frame_resolve": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_state_bytes": (C.c_int64, [C.c_void_p]),
+    "kyhip_frame_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_end": (None, [C.c_void_p]),
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -155,6 +164,8 @@ KYHOST_SYMBOLS = {
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "kyhost_debug_area": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int,
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kyhost_render_passes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
     "kyhost_store_image": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhost_gamma_encoding": (C.c_int, [C.c_float]),
 }
@@ -171,6 +182,7 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
     "kyhostcheck_pack": (C.c_int, [SP, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "kyhostcheck_chunks": (C.c_int, [C.c_int]),
     "kyhostcheck_shard": (C.c_longlong, [PP]),
+    "kyhostcheck_frame": (C.c_int, [PP, C.c_int]),
     "kyhostcheck_add_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_seam_stress": (C.c_int, [C.c_int]),
     "kyhostcheck_jit_stress": (C.c_int, [C.c_int, C.c_int]),

@@ -99,6 +99,84 @@ def lighting_plan(params, lighting):
     return depth.value, dropped.value
 
 
+def pass_boundaries(spp):
+    """kyhip_pass_boundaries (host only): the sample counts at which a pass of an spp-sample frame can end, ascending; the last is spp."""
+    lib = A.load_kyhip()
+    n = lib.kyhip_pass_boundaries(int(spp), None, 0)
+    if n < 0:
+        _check(n, lib)
+    out = (C.c_int * n)()
+    lib.kyhip_pass_boundaries(int(spp), out, n)
+    return list(out)
+
+
+class Frame:
+    """A frame rendered in passes (kyhip_frame_*): `with Frame(scene, params) as f: f.render(64); preview = f.resolve(normalise=True); ...`.
+    params.samples_per_pixel is the frame's total; a complete frame's resolve() is render(scene, params), bit for bit."""
+
+    def __init__(self, scene, params, device=0):
+        self._lib = A.load_kyhip()
+        self._f = C.c_void_p()
+        self.height, self.width = params.height, params.width
+        _check(self._lib.kyhip_frame_begin(device, _scene_ptr(scene), C.byref(params), C.byref(self._f)), self._lib)
+
+    def close(self):
+        if getattr(self, "_f", None):
+            self._lib.kyhip_frame_end(self._f)
+            self._f = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _samples(self):
+        done, total = C.c_int(0), C.c_int(0)
+        _check(self._lib.kyhip_frame_samples(self._f, C.byref(done), C.byref(total)), self._lib)
+        return done.value, total.value
+
+    @property
+    def done(self):
+        return self._samples()[0]
+
+    @property
+    def total(self):
+        return self._samples()[1]
+
+    def render(self, min_samples):
+        """One pass: whole chunks until at least min_samples more samples per pixel are done, or the frame is complete; returns the samples done so far."""
+        done = C.c_int(0)
+        _check(self._lib.kyhip_frame_render(self._f, int(min_samples), C.byref(done)), self._lib)
+        return done.value
+
+    def resolve(self, normalise=False, film=None, row_stride_px=None, origin_px=(0, 0)):
+        """ADDS the picture to `film` (a new zero film by default) and returns it: sum / total, or with normalise the mean of the samples done so far."""
+        if film is None:
+            film = np.zeros((self.height, self.width, 3), np.float32)
+        stride = film.shape[1] if row_stride_px is None else row_stride_px
+        base = film.ctypes.data + (origin_px[1] * stride + origin_px[0]) * 12
+        _check(self._lib.kyhip_frame_resolve(self._f, 1 if normalise else 0, C.c_void_p(base), stride), self._lib)
+        return film
+
+    def save(self):
+        """The frame's checkpoint as bytes (kyhip_frame_save)."""
+        n = self._lib.kyhip_frame_state_bytes(self._f)
+        if n < 0:
+            _check(n, self._lib)
+        buf = C.create_string_buffer(n)
+        _check(self._lib.kyhip_frame_save(self._f, buf, n), self._lib)
+        return buf.raw
+
+    def load(self, state):
+        """Continue from a checkpoint of a frame begun with the same scene and params (kyhip_frame_load); any other state raises KyError."""
+        state = bytes(state)
+        _check(self._lib.kyhip_frame_load(self._f, state, len(state)), self._lib)
+
+
 class PinnedFilm:
     """A [height, width, 3] float32 numpy view of pinned host memory from kyhip_film_alloc (include/kyhip.h): a film the GPU adds to in place.
     `array` stays valid while this object lives."""
@@ -150,6 +228,24 @@ def render_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, 
         return None  # create_integrator returned nullptr (ky.cpp:4638)
     if rc != 0:
         raise KyError("kyhost_render failed: " + host.kyhost_last_error().decode())
+    return film
+
+
+def render_passes_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, min_samples_per_pass, on_pass=None, seed=1234,
+                           film=None, device=0):
+    """create_integrator(...)->render_passes(&scene, sampler, &film, min_samples_per_pass, on_pass) through the C++ host classes: on_pass(done, total)
+    is called after every pass and stops the frame by returning False (the film then gets the mean of the samples done)."""
+    host = A.load_kyhost()
+    if film is None:
+        film = np.zeros((height, width, 3), np.float32)
+    cb_type = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, C.c_void_p)
+    cb = cb_type(lambda done, total, _user: 1 if on_pass(done, total) else 0) if on_pass else C.cast(None, cb_type)
+    rc = host.kyhost_render_passes(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device,
+                                   int(min_samples_per_pass), C.cast(cb, C.c_void_p), None)
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise KyError("kyhost_render_passes failed: " + host.kyhost_last_error().decode())
     return film
 
 

@@ -116,7 +116,25 @@ int upload_scene(DeviceCtx* c, const ky_scene* scene, hipStream_t stream, SceneS
 // (drop: the drop bits of a masked launch, kyhip_render_lighting: it takes the masked rows)
 int render_replay_feat(const ky_scene* scene, const ky_render_params* p, const kyd::DScene* packed, int drop = 0);
 // kyhip_render_tiles_device with a lighting plan's drop bits (lighting_plan, ky_host.hpp) and what kyhip_last_kernel says of the launch's form
+// (pass: the launch is a pass of a frame, kyhip_frame_render -- see FramePass; d_tiles and d_workspace are then unused)
+struct FramePass;
 int render_tiles_device(int device, const ky_scene* scene, const ky_render_params* p, float* d_tiles, void* d_workspace, size_t workspace_bytes, void* stream,
-                        int drop, const char* lighting_note);
+                        int drop, const char* lighting_note, FramePass* pass = nullptr);
+// A pass of a frame (ky_frame.cpp): chunks [chunk_first, chunk_first + chunk_count) of the frame p describes, added to the FRAME's accumulator block `ws`
+// (workspace_bytes_for(make_shard(p)) bytes, zero when the frame began) on the lane engine.  Nothing is resolved or cleared; the stream's own block is not
+// touched and its work counter is zero again behind the kernel.  All passes of a frame run one kernel: `kernel` is -1 before the first pass, which sets it
+// to the table row it took or to -3 for a run-time instantiation (then jit_expr / jit_desc / queue name it); later passes launch that kernel whatever
+// the table or the code cache would pick by then.
+struct FramePass {
+    int chunk_first = 0, chunk_count = 0;
+    void* ws = nullptr;
+    int kernel = -1;
+    bool queue = false;
+    std::string jit_expr, jit_desc;
+};
+// resolve_frame_kernel (ky_launch.hip) on `stream`: the frame's accumulators and flags, read and left as they are -> clamp01(value * scale) in the compact tile buffer
+int resolve_frame_device(const void* ws, float* d_tiles, int n_pix, double scale, hipStream_t stream);
+// The device alias of a host film that lies in ONE pinned mapping (kyhip_film_alloc, hipHostRegister), nullptr for any other film (ky_seam.cpp)
+float* film_in_place_alias(float* film_rgb, size_t span_bytes);
 bool render_uses_boxes(const ky_scene* scene, const ky_render_params* p, const kyd::DScene* packed);
 }  // namespace kyh

@@ -53,6 +53,24 @@ int lighting_plan(const ky_render_params* p, int lighting, LightingPlan* out);  
 std::string lighting_note(const ky_render_params* p, int lighting, const LightingPlan& plan);   // what kyhip_last_kernel says of the launch's form ("" for a plain one)
 inline size_t workspace_bytes_for(const ShardConst& s) { return (size_t)s.n_pix * (3 * sizeof(unsigned long long) + sizeof(unsigned)); }   // per pixel: 3 x 64-bit fixed-point sums + one flag word
 
+// ---- passes of a frame (kyhip_frame_*; the chunk arithmetic is ky_shard.hpp's) ----
+int pass_boundaries(int spp, int* bounds, int n);   // kyhip_pass_boundaries
+// A frame's checkpoint (kyhip_frame_save / _load) begins with this header; the accumulators (3 x 64 bits per pixel) and the flag words follow.  Everything in it
+// but samples_done names what the frame IS: a state is loaded only into a frame whose own header agrees in all of that.
+struct FrameHeader {
+    uint64_t magic;            // KY_FRAME_MAGIC
+    uint64_t source_hash;      // kyhip_kernel_source_hash(): another kernel source's chunk sums differ in the last bit
+    ky_render_params params;
+    uint64_t scene_hash;       // scene_hash of the packed scene
+    int32_t samples_done, n_pix;
+};
+constexpr uint64_t KY_FRAME_MAGIC = 0x31454d4152464b59ull;   // "YKFRAME1"
+FrameHeader frame_header(const ky_render_params* p, uint64_t scene_hash, int samples_done);
+// KY_OK and the chunk count the state's samples_done stands for, or KY_ERR_INVALID_VALUE with the message: a short buffer, another frame's state, a
+// samples_done at which no chunk of the frame ends
+int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, int* chunks_done);
+inline size_t frame_state_bytes(const ky_render_params* p) { return sizeof(FrameHeader) + workspace_bytes_for(make_shard(p)); }
+
 // ---- scene packing (ky_pack.cpp) ----
 void cp3(float* d, const float* s);
 void pack_shape(const ky_shape& sh, int full_index, DSurf* surf, DShapeFull* full);

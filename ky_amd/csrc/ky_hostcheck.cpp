@@ -58,6 +58,43 @@ int kyhostcheck_chunks(int spp) {
     return next == spp ? n : -1;
 }
 
+// A frame's host bookkeeping (kyhip_frame_*) on the caller's parameters, without a device: passes of at least min_samples from the first chunk to the last
+// cover every chunk once, in order, each ending at a value of pass_boundaries; a checkpoint written at every such point is accepted and gives the chunk count
+// back, and one cut short, of another seed, or with a sample count no chunk ends at is refused.  Returns the number of passes, or a negative number.
+int kyhostcheck_frame(const ky_render_params* p, int min_samples) {
+    if (!valid_params(p) || min_samples < 1) return KY_ERR_INVALID_VALUE;
+    const ChunkPlan plan = chunk_plan(p->samples_per_pixel);
+    std::vector<int> bounds((size_t)chunk_count(plan));
+    if (pass_boundaries(p->samples_per_pixel, bounds.data(), (int)bounds.size()) != (int)bounds.size()) return -10;
+    const FrameHeader own = frame_header(p, 0x1234, 0);
+    std::vector<unsigned char> state(frame_state_bytes(p), 0);
+    ky_render_params q = *p;
+    q.seed ^= 1u;
+    int passes = 0, done = 0;
+    while (done < (int)bounds.size()) {
+        const int next = pass_chunk_end(plan, done, min_samples);
+        if (next <= done || next > (int)bounds.size()) return -11;
+        if (next < (int)bounds.size() && bounds[(size_t)next - 1] - chunk_end(plan, done - 1) < min_samples) return -12;
+        done = next;
+        ++passes;
+        int back = -1;
+        FrameHeader h = own;
+        h.samples_done = bounds[(size_t)done - 1];
+        std::memcpy(state.data(), &h, sizeof h);
+        if (frame_state_check(own, state.data(), state.size(), &back) != KY_OK || back != done) return -13;
+        if (frame_state_check(own, state.data(), state.size() - 1, &back) == KY_OK || frame_state_check(own, state.data(), sizeof h - 1, &back) == KY_OK) return -14;
+        if (frame_state_check(frame_header(&q, 0x1234, 0), state.data(), state.size(), &back) == KY_OK) return -15;
+        if (frame_state_check(frame_header(p, 0x1235, 0), state.data(), state.size(), &back) == KY_OK) return -16;
+    }
+    if (chunks_at_sample(plan, 0) != 0 || chunks_at_sample(plan, p->samples_per_pixel + 1) != -1) return -17;
+    for (int s = 1, c = 0; s <= p->samples_per_pixel; ++s) {   // every sample count: a chunk count exactly at the boundaries
+        const bool is_bound = bounds[(size_t)c] == s;
+        if (chunks_at_sample(plan, s) != (is_bound ? c + 1 : -1)) return -18;
+        if (is_bound) ++c;
+    }
+    return passes;
+}
+
 // make_shard / shard_in_range / valid_params on the caller's parameters: n_items, or a negative status
 long long kyhostcheck_shard(const ky_render_params* p) {
     if (!valid_params(p)) return KY_ERR_INVALID_VALUE;
@@ -170,6 +207,22 @@ int kyhip_kat_li(int, const ky_scene*, const ky_render_params*, int, int, int, i
 // (the masked entries refuse an invalid mask before they look for a device, like the real ones: lighting_plan is host code)
 int kyhip_render_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, float*, size_t) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
 int kyhip_kat_li_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, int, int, int, int, float*) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
+// (a frame refuses what kyhip_render refuses, in its order, before it looks for a device; no frame ever exists here, so the other entries see NULL only)
+int kyhip_frame_begin(int, const ky_scene* scene, const ky_render_params* p, kyhip_frame** out) {
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
+    if (!shard_in_range(p)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices");
+    if (film_range_check(p, scene) != KY_OK) return KY_ERR_LIMIT;
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    *out = nullptr;
+    return no_gpu();
+}
+int kyhip_frame_render(kyhip_frame*, int, int*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_samples(const kyhip_frame*, int*, int*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_resolve(kyhip_frame*, int, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int64_t kyhip_frame_state_bytes(const kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_save(kyhip_frame*, void*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_load(kyhip_frame*, const void*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+void kyhip_frame_end(kyhip_frame*) {}
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }
 int kyhip_smallpt_render(int, const ky_smallpt_sphere* spheres, int n, const ky_smallpt_params* p, double* image) {

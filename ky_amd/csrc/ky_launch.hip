@@ -63,6 +63,25 @@ __global__ void resolve_kernel(unsigned long long* __restrict__ accum, unsigned*
     }
 }
 
+// A frame's accumulators (kyhip_frame_resolve) -> clamp01(value * scale) -> fp32 tile buffer, one thread per pixel: resolve_kernel's conversion and flag rules
+// word for word, but the accumulators, the flag words and every counter stay as they are -- the frame goes on adding to them.  scale is total / done for the
+// picture so far (the chunk sums were scaled by 1 / total, ky_render.hpp), applied in double before the one rounding to float; with scale == 1.0 (an exact
+// product) the output is resolve_kernel's bit for bit.
+__global__ void resolve_frame_kernel(const unsigned long long* __restrict__ accum, const unsigned* __restrict__ flags, float* __restrict__ tiles, int n_pix, double scale) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix) return;
+    const unsigned fl = flags[i];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float v = (float)((double)(long long)accum[3 * (size_t)i + ch] * (1.0 / KY_FIX_SCALE) * scale);
+        const bool nan = (fl >> ch) & 1u, pinf = (fl >> (3 + ch)) & 1u, ninf = (fl >> (6 + ch)) & 1u;
+        if (pinf) v = 1.f;
+        if (ninf) v = 0.f;
+        if (nan || (pinf && ninf)) v = 0.f;
+        tiles[3 * (size_t)i + ch] = fminf(fmaxf(v, 0.f), 1.f);
+    }
+}
+
 __global__ void film_add_kernel(const float* __restrict__ tiles, float* __restrict__ film, size_t stride_px, ShardConst sh, int width, int height) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sh.n_pix) return;
@@ -421,11 +440,11 @@ bool kyh::render_uses_boxes(const ky_scene* scene, const ky_render_params* p, co
 // kyhip_render_tiles_device, and a masked launch of it (kyhip_render_lighting): `drop` are the plan's drop bits (lighting_plan, ky_pack.cpp), `lighting_note` what
 // kyhip_last_kernel says about the launch's form.  p is the plan's launch: its depth is the effective one.
 int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_params* p, float* d_tiles, void* d_workspace,
-                             size_t workspace_bytes, void* stream_, int drop, const char* lighting_note) {
+                             size_t workspace_bytes, void* stream_, int drop, const char* lighting_note, FramePass* pass) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
     if (!shard_in_range(p)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices (%d x %d, %d spp)", p->width, p->height, p->samples_per_pixel);
     if (film_range_check(p, scene) != KY_OK) return KY_ERR_LIMIT;
-    if (!d_tiles) return fail(KY_ERR_INVALID_VALUE, "d_tiles is NULL");
+    if (!d_tiles && !pass) return fail(KY_ERR_INVALID_VALUE, "d_tiles is NULL");
     DeviceCtx* c;
     int rcode = get_ctx(device, &c);
     if (rcode != KY_OK) return rcode;
@@ -435,16 +454,21 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     rcode = upload_scene(c, scene, stream, &sc);
     if (rcode != KY_OK) return rcode;
 
-    const ShardConst sh = make_shard(p);
+    ShardConst sh = make_shard(p);
     if (sh.n_tiles == 0) return KY_OK;
+    if (pass) {   // the pass's chunks of every block; the chunk schedule, inv_spp and the film term limit below stay the whole frame's
+        if (pass->chunk_first < 0 || pass->chunk_count < 1 || pass->chunk_first + pass->chunk_count > sh.n_chunks || !pass->ws) return fail(KY_ERR_DEVICE, "internal: bad pass");
+        sh.chunk_first = pass->chunk_first;
+        sh.n_items = (unsigned)sh.n_blocks * (unsigned)pass->chunk_count;
+    }
     const RenderConst rc = make_rc(p);
     StreamState* st;
     rcode = get_stream_state(c, stream, &st);
     if (rcode != KY_OK) return rcode;
 
     const size_t need = workspace_bytes_for(sh);
-    void* ws = d_workspace;
-    if (!(d_workspace && workspace_bytes >= need)) {
+    void* ws = pass ? pass->ws : d_workspace;
+    if (!pass && !(d_workspace && workspace_bytes >= need)) {
         if (st->ws_bytes < need) {
             HIP_TRY(hipStreamSynchronize(stream));   // the previous call's kernels on this stream still use the old block
             if (st->ws) HIP_TRY(hipFree(st->ws));
@@ -461,18 +485,24 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     const size_t lds_bytes = large_scene ? (size_t)lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count) : 0;   // LARGE kernels' LdsScene
     // accumulators, flags and the work counter start at zero: resolve_kernel leaves the library's own block that way (a caller's workspace, a new block and the frame
     // after a failed launch are filled here)
-    const bool own_ws = ws == st->ws;
-    if (!(own_ws && st->ws_clean)) {
+    const bool own_ws = !pass && ws == st->ws;
+    const bool ws_was_clean = st->ws_clean;
+    if (pass) {
+        // a pass adds to what the frame's block holds; the stream's own block is left alone, and so is what ws_clean says of it: the work counter starts at zero (it
+        // may hold a failed launch's count unless ws_clean vouches for it) and is put back to zero behind the kernel
+        if (!st->ws_clean) HIP_TRY(hipMemsetAsync(st->d_counter, 0, sizeof(unsigned), stream));
+    } else if (!(own_ws && st->ws_clean)) {
         HIP_TRY(hipMemsetAsync(ws, 0, own_ws ? st->ws_bytes : need, stream));
         HIP_TRY(hipMemsetAsync(st->d_counter, 0, sizeof(unsigned), stream));
     }
-    st->ws_clean = false;   // until this frame's resolve_kernel is enqueued
+    st->ws_clean = false;   // until this frame's resolve_kernel is enqueued (a pass: until its counter reset is)
 
     // the queue engine implements path_tracing_iteration_t; every other integrator runs on the lane engine
     // (... and the queue engine has no sample_single_light: a strategy-49 launch runs on the lane engine, and kyhip_last_kernel says so)
     const bool single = p->direct_sample == KY_DIRECT_SINGLE_BOTH_MIS;
     // (... nor a masked form: a lighting launch runs on the lane engine too)
-    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single && drop == 0) {
+    // (... nor passes: a frame's pass runs on the lane engine)
+    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single && drop == 0 && !pass) {
         const int variant = p->sampler == KY_SAMPLER_DEBUG ? 2 : (p->direct_sample == KY_DIRECT_BOTH_MIS ? 0 : 1);
         const int per_cu = c->q_blocks_per_cu[variant] > 0 ? c->q_blocks_per_cu[variant] : 1;
         unsigned grid = (unsigned)(c->cus * per_cu);
@@ -487,7 +517,9 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         else hipLaunchKernelGGL((render_kernel_q<true, -1>), dim3(grid), dim3(QE_THREADS), 0, stream, sc->d, rc, sh, st->d_counter, accum, flags);
         c->last_variant = -2;
     } else {
-        const Variant* v = pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop);
+        // (a frame keeps the kernel of its first pass: the table and run-time instantiations differ in the last bit)
+        const bool pinned = pass && pass->kernel != -1;
+        const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop);
         if (!v) return fail(KY_ERR_DEVICE, "internal: no render kernel for these parameters");
         const int vi = (int)(v - g_variants);
         // run-time instantiation (kyhip_set_jit(1)): this launch's own kernel -- its sampler, strategy and integrator as compile-time constants and ALL
@@ -500,7 +532,20 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         // (a mode nobody chose -- the default of round 6 -- instantiates only where the table's pick knows nothing of the scene: a launch served by a row of facts stays on it,
         // a scene outside the table of facts gets its own kernel; kyhip_set_jit(1 / 2) / KYHIP_JIT instantiate for every launch that is not exactly a row)
         const bool jit_wanted = jit_mode != 0 && (!kyjit::mode_by_default() || v->feat == 0 || v->strategy < 0);
-        if (jit_wanted && specialisation_enabled() && p->integrator >= KY_INTEGRATOR_DIRECT_LIGHTING) {   // (kyhip_set_specialisation(0) asks for the fact-free kernels: nothing to instantiate)
+        if (pinned && pass->kernel == -3) {   // the frame's own instantiation: loaded on this device by the first pass, and modules stay loaded
+            DeviceCtx::JitKernel& k = c->jit[pass->jit_expr];
+            if (!k.fn) return fail(KY_ERR_DEVICE, "internal: the frame's kernel render_kernel<%s> is not loaded", pass->jit_expr.c_str());
+            if (k.lds != lds_bytes) {
+                int per_cu = 0;
+                HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, 256, lds_bytes));
+                k.per_cu = per_cu > 0 ? per_cu : 1;
+                k.lds = lds_bytes;
+            }
+            jk = &k;
+            queue = pass->queue;
+            c->last_jit = pass->jit_desc;
+            c->last_note.clear();
+        } else if (!pinned && jit_wanted && specialisation_enabled() && p->integrator >= KY_INTEGRATOR_DIRECT_LIGHTING) {   // (kyhip_set_specialisation(0) asks for the fact-free kernels: nothing to instantiate)
             const bool dbg = p->sampler == KY_SAMPLER_DEBUG, general = sc->h->general != 0;
             int feat = (dbg || general) ? 0 : sc->h->feat;
             // the box traversal pays where it was measured to (one lamp, one point / directional light: +3-4 %; one environment light under both_mis, whose estimate's two
@@ -548,6 +593,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
                     snprintf(desc, sizeof desc, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d> = render_kernel<", dbg ? "debug sampler, " : "", p->direct_sample,
                              want_queue ? ", deferred shadow rays" : "", general ? ", general shapes" : "", large_scene ? ", scene-sized LDS block" : "", feat, p->integrator);
                     c->last_jit = std::string(desc) + expr + ">";
+                    if (pass) { pass->jit_expr = expr; pass->jit_desc = c->last_jit; }
                 }
             }
         }
@@ -586,6 +632,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
             if (current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no sample_single_light]";
         }
         if (drop != 0 && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no masked form]";
+        if (pass && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine renders no passes]";
+        if (pass) { pass->kernel = jk ? -3 : vi; pass->queue = queue; }
         if (!jk && v->drop < 0 && st->counter_drop != drop) {   // the drop bits of a run-time-dispatched masked kernel: word 2 of the counter block, written when they change
             HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(st->d_counter + 2), drop, 1, stream));
             st->counter_drop = drop;
@@ -613,11 +661,32 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     HIP_TRY(hipEventRecord(st->ev1, stream));
     st->timing_valid = true;
     c->last_launch = st;
+    if (pass) {
+        HIP_TRY(hipMemsetAsync(st->d_counter, 0, sizeof(unsigned), stream));
+        st->ws_clean = ws_was_clean;   // the stream's own block was not touched, and the counter is zero again
+        char note[160];
+        int s0, s1, unused;
+        chunk_range(chunk_plan(rc.spp), pass->chunk_first, s0, unused);
+        chunk_range(chunk_plan(rc.spp), pass->chunk_first + pass->chunk_count - 1, unused, s1);
+        snprintf(note, sizeof note, ", pass: chunks %d..%d of %d, samples %d..%d of %d", pass->chunk_first, pass->chunk_first + pass->chunk_count - 1, sh.n_chunks, s0, s1, rc.spp);
+        c->last_note += note;
+        HIP_TRY(hipEventRecord(st->done, stream));
+        sc->readers |= 1u << (unsigned)(st - c->ss);
+        return KY_OK;
+    }
     hipLaunchKernelGGL(resolve_kernel, dim3((sh.n_pix + 255) / 256), dim3(256), 0, stream, accum, flags, d_tiles, sh.n_pix, st->d_counter);
     HIP_TRY(hipGetLastError());
     st->ws_clean = own_ws;
     HIP_TRY(hipEventRecord(st->done, stream));
     sc->readers |= 1u << (unsigned)(st - c->ss);
+    return KY_OK;
+}
+
+int kyh::resolve_frame_device(const void* ws, float* d_tiles, int n_pix, double scale, hipStream_t stream) {
+    const unsigned long long* accum = (const unsigned long long*)ws;
+    const unsigned* flags = (const unsigned*)(accum + (size_t)n_pix * 3);
+    hipLaunchKernelGGL(resolve_frame_kernel, dim3((n_pix + 255) / 256), dim3(256), 0, stream, accum, flags, d_tiles, n_pix, scale);
+    HIP_TRY(hipGetLastError());
     return KY_OK;
 }
 

@@ -175,6 +175,43 @@ std::string lighting_note(const ky_render_params* p, int lighting, const Lightin
     return s;
 }
 
+// The sample counts at which a pass of an spp-sample frame can end: the ends of the chunks of chunk_plan(spp)
+int pass_boundaries(int spp, int* bounds, int n) {
+    if (spp < 1 || spp > (1 << 24)) return fail(KY_ERR_INVALID_VALUE, "pass boundaries of %d samples per pixel (1 .. 2^24)", spp);
+    if (n > 0 && !bounds) return fail(KY_ERR_INVALID_VALUE, "bounds is NULL");
+    const ChunkPlan plan = chunk_plan(spp);
+    const int count = chunk_count(plan);
+    for (int c = 0; c < count && c < n; ++c) bounds[c] = chunk_end(plan, c);
+    return count;
+}
+FrameHeader frame_header(const ky_render_params* p, uint64_t hash, int samples_done) {
+    FrameHeader h;
+    std::memset(&h, 0, sizeof h);   // (padding too: headers are compared and saved as bytes)
+    h.magic = KY_FRAME_MAGIC;
+    h.source_hash = kyjit::source_hash();
+    h.params = *p;
+    h.scene_hash = hash;
+    h.samples_done = samples_done;
+    h.n_pix = make_shard(p).n_pix;
+    return h;
+}
+int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, int* chunks_done) {
+    if (!buf || bytes < sizeof(FrameHeader)) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no header", bytes);
+    FrameHeader theirs;
+    std::memcpy(&theirs, buf, sizeof theirs);
+    if (theirs.magic != KY_FRAME_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: not a kyhip_frame_save buffer");
+    if (theirs.source_hash != own.source_hash) return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a library with other kernel sources (%016llx, this one %016llx)",
+                                                          (unsigned long long)theirs.source_hash, (unsigned long long)own.source_hash);
+    FrameHeader same = theirs;
+    same.samples_done = own.samples_done;
+    if (std::memcmp(&same, &own, sizeof own) != 0) return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its render params, scene or film size differ from this frame's)");
+    if (bytes < frame_state_bytes(&own.params)) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes, the frame's state has %zu", bytes, frame_state_bytes(&own.params));
+    const int c = theirs.samples_done < 0 ? -1 : chunks_at_sample(chunk_plan(own.params.samples_per_pixel), theirs.samples_done);
+    if (c < 0) return fail(KY_ERR_INVALID_VALUE, "frame state: no pass of a %d-sample frame ends at %d samples", own.params.samples_per_pixel, theirs.samples_done);
+    *chunks_done = c;
+    return KY_OK;
+}
+
 RenderConst make_rc(const ky_render_params* p) {
     RenderConst rc{};
     rc.integrator = p->integrator; rc.max_path_depth = p->max_path_depth; rc.strategy = p->direct_sample; rc.seed = p->seed;
@@ -1040,6 +1077,8 @@ int kyhip_lighting_plan(const ky_render_params* p, int lighting, int* effective_
     if (dropped) *dropped = pl.dropped;
     return KY_OK;
 }
+
+int kyhip_pass_boundaries(int spp, int* bounds, int n) { return pass_boundaries(spp, bounds, n); }
 
 int64_t kyhip_shard_tile_count(const ky_render_params* p) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");

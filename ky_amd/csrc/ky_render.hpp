@@ -196,7 +196,7 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                 if (fetched > 0 && lane == 0) id = atomicAdd(counter, 1u) + gridDim.x * 4u;
                 id = __builtin_amdgcn_readfirstlane(id);
                 if (id >= sh.n_items) { exhausted = true; break; }
-                const int c = (int)(id / (unsigned)sh.n_blocks), b = (int)(id % (unsigned)sh.n_blocks);   // chunk-major
+                const int c = (int)(id / (unsigned)sh.n_blocks) + sh.chunk_first, b = (int)(id % (unsigned)sh.n_blocks);   // chunk-major; a pass of a frame starts at chunk_first
                 const int k = b / sh.blocks_per_tile, inner = b % sh.blocks_per_tile;
                 const int bx = inner % sh.blocks_w, by = inner / sh.blocks_w;
                 const int tile = sh.tile_first + k * sh.tile_step;

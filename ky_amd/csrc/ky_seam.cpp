@@ -31,6 +31,27 @@ static int seam_reserve(void** p, size_t* have, size_t need, bool pinned) {
     return KY_OK;
 }
 
+// The device alias of a host film whose whole span lies in ONE pinned mapping, nullptr for any other film
+float* kyh::film_in_place_alias(float* film_rgb, size_t span_bytes) {
+    float* alias = nullptr;
+    hipPointerAttribute_t first{}, last{};
+    void *dptr = nullptr, *dlast = nullptr;
+    //  both ends pinned is not enough: two adjacent registrations, or one whose device mapping is not one piece, would pass.  The film's
+    // whole span must lie in ONE mapping: the device alias of its last byte is span - 1 bytes beyond the alias of its first, and where the runtime knows
+    // the allocation behind the alias (hipMemGetAddressRange) the span lies inside it.
+    if (hipPointerGetAttributes(&first, film_rgb) == hipSuccess && first.type == hipMemoryTypeHost &&
+        hipPointerGetAttributes(&last, (const char*)film_rgb + span_bytes - 1) == hipSuccess && last.type == hipMemoryTypeHost &&
+        hipHostGetDevicePointer(&dptr, film_rgb, 0) == hipSuccess && dptr &&
+        hipHostGetDevicePointer(&dlast, (char*)film_rgb + span_bytes - 1, 0) == hipSuccess && dlast == (char*)dptr + span_bytes - 1) {
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        const bool known = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dptr) == hipSuccess && base && size;
+        if (!known || ((char*)dptr >= (char*)base && (char*)dptr + span_bytes <= (char*)base + size)) alias = (float*)dptr;
+    }
+    (void)hipGetLastError();   // "not a registered pointer" is the ordinary answer for a pageable film
+    return alias;
+}
+
 // kyhip_render_multi; `drop` / `lighting_note`: a masked frame's drop bits and form (kyhip_render_lighting; p is then the plan's launch), 0 / null otherwise
 static int render_multi(const int* devices, int n_devices, const ky_scene* scene, const ky_render_params* p, float* film_rgb, size_t stride_px, int drop,
                         const char* lighting_note) {
@@ -64,25 +85,8 @@ static int render_multi(const int* devices, int n_devices, const ky_scene* scene
     // A film in PINNED host memory (kyhip_film_alloc: what ky.hpp's film_t allocates; or memory the caller registered with the runtime) is added to IN PLACE by the
     // root GPU: the add kernel reads and writes the host film over PCIe (12 B in, 12 B out per pixel, both directions at once), and the staging film, its download and
     // the host threads' pass drop out -- the seam then costs the same whatever CPUs the process is granted (round 5; a pageable film takes the banded path below).
-    float* film_in_place = nullptr;
-    {
-        const size_t span = ((size_t)(p->height - 1) * stride_px + (size_t)p->width) * 3 * sizeof(float);
-        hipPointerAttribute_t first{}, last{};
-        void *dptr = nullptr, *dlast = nullptr;
-        //  both ends pinned is not enough: two adjacent registrations, or one whose device mapping is not one piece, would pass.  The film's
-        // whole span must lie in ONE mapping: the device alias of its last byte is span - 1 bytes beyond the alias of its first, and where the runtime knows
-        // the allocation behind the alias (hipMemGetAddressRange) the span lies inside it.
-        if (hipPointerGetAttributes(&first, film_rgb) == hipSuccess && first.type == hipMemoryTypeHost &&
-            hipPointerGetAttributes(&last, (const char*)film_rgb + span - 1) == hipSuccess && last.type == hipMemoryTypeHost &&
-            hipHostGetDevicePointer(&dptr, film_rgb, 0) == hipSuccess && dptr &&
-            hipHostGetDevicePointer(&dlast, (char*)film_rgb + span - 1, 0) == hipSuccess && dlast == (char*)dptr + span - 1) {
-            hipDeviceptr_t base = nullptr;
-            size_t size = 0;
-            const bool known = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)dptr) == hipSuccess && base && size;
-            if (!known || ((char*)dptr >= (char*)base && (char*)dptr + span <= (char*)base + size)) film_in_place = (float*)dptr;
-        }
-        (void)hipGetLastError();   // "not a registered pointer" is the ordinary answer for a pageable film
-    }
+    const size_t span = ((size_t)(p->height - 1) * stride_px + (size_t)p->width) * 3 * sizeof(float);
+    float* const film_in_place = film_in_place_alias(film_rgb, span);
     int rcode = seam_reserve(&sb.d_gather, &sb.gather_bytes, rank_stride * n_devices * sizeof(float), false);
     if (rcode == KY_OK && !film_in_place) rcode = seam_reserve(&sb.d_film, &sb.film_bytes, film_floats * sizeof(float), false);
     if (rcode == KY_OK && !film_in_place) rcode = seam_reserve((void**)&sb.h_stage, &sb.stage_bytes, film_floats * sizeof(float), true);

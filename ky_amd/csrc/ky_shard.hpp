@@ -81,7 +81,38 @@ struct ShardConst {
     int tiles_x, tiles_y, n_tiles;     // tiles of the whole film / tiles owned by this shard
     int blocks_w, blocks_per_tile;     // 8x8 pixel blocks inside a tile
     int n_blocks;                      // n_tiles * blocks_per_tile
-    int n_chunks;                      // chunk_count(chunk_plan(spp))
-    unsigned n_items;                  // n_blocks * n_chunks
+    int chunk_first;                   // the launch renders chunks chunk_first .. chunk_first + n_items / n_blocks - 1 of the n_chunks: 0 and all of them, but in a
+                                       // pass of a frame (kyhip_frame_render) n_items counts the pass's chunks; n_chunks and the chunk schedule stay the frame's.
+                                       // (Between the two words the work decoder reads anyway: the kernels' argument loads are what they were.)
+    unsigned n_items;                  // n_blocks * (chunks of the launch)
     int n_pix;                         // n_tiles * tile_w * tile_h
+    int n_chunks;                      // chunk_count(chunk_plan(spp)) (host only)
 };
+
+// Passes (kyhip_frame_*, DESIGN.md "Passes").  Items are queued chunk-major, so items [c0 * n_blocks, c1 * n_blocks) are chunks c0 .. c1 - 1 of every pixel block:
+// the contiguous samples [chunk_begin(c0), chunk_end(c1 - 1)) of every pixel.  A frame may therefore be rendered in any number of launches that end on chunk
+// boundaries; which chunks a launch renders is host arithmetic on the schedule of the FRAME's spp.
+KY_HD inline int chunk_end(const ChunkPlan& p, int c) {   // the sample count at which chunk c ends; 0 for c < 0
+    if (c < 0) return 0;
+    int b, e;
+    chunk_range(p, c, b, e);
+    return e;
+}
+// With `chunks_done` chunks rendered, the chunk count after a pass of at least min_samples more samples (whole chunks; at most all of them).
+inline int pass_chunk_end(const ChunkPlan& p, int chunks_done, int min_samples) {
+    const int n = chunk_count(p);
+    const long long want = (long long)chunk_end(p, chunks_done - 1) + min_samples;
+    int c = chunks_done;
+    while (c < n && chunk_end(p, c - 1) < want) ++c;
+    return c;
+}
+// The number of chunks whose last one ends at `samples` (0 for 0), or -1 when no chunk of the schedule ends there.
+inline int chunks_at_sample(const ChunkPlan& p, int samples) {
+    if (samples == 0) return 0;
+    int lo = 0, hi = chunk_count(p) - 1;   // chunk ends ascend strictly
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (chunk_end(p, mid) < samples) lo = mid + 1; else hi = mid;
+    }
+    return hi >= 0 && chunk_end(p, lo) == samples ? lo + 1 : -1;
+}

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <fstream>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <stdexcept>
@@ -693,6 +694,30 @@ public:
         // the reference spreads this loop over all cores (3696-3699); here the frame's tiles are spread over devices_
         const int rc = kyhip_render_multi(devices_.data(), (int)devices_.size(), &scene->flatten(), &p, film->target_origin(), film->row_stride_px());
         if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_multi: ") + kyhip_last_error());
+    }
+    // render() in passes (kyhip_frame_*, include/kyhip.h): the frame's samples are rendered min_samples_per_pass (or a few more: whole chunks) at a time on
+    // devices_[0], and after each pass on_pass(done, total) is called -- where the reference prints "rendering... N spp, x%" (3703).  When it returns false,
+    // or the frame is complete, the picture is added to the film like render() adds it: the mean of the samples done if the frame was stopped early, and for
+    // a complete frame exactly what render() adds.  An empty on_pass renders to the end.  Light classes (set_lighting) and device lists are render()'s only.
+    void render_passes(scene_t* scene, sampler_t* original_sampler, film_t* film, int min_samples_per_pass, const std::function<bool(int done, int total)>& on_pass) {
+        if (masked()) throw std::runtime_error("integrator_t::render_passes: light classes are rendered by render() only");
+        const ky_render_params p = params_for(original_sampler, film);
+        kyhip_frame* frame = nullptr;
+        if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        try {
+            int done = 0;
+            bool go_on = true;
+            while (go_on && done < p.samples_per_pixel) {
+                if (kyhip_frame_render(frame, min_samples_per_pass, &done) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_render: ") + kyhip_last_error());
+                if (on_pass) go_on = on_pass(done, p.samples_per_pixel);
+            }
+            const int rc = kyhip_frame_resolve(frame, done < p.samples_per_pixel ? 1 : 0, film->target_origin(), film->row_stride_px());
+            if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+        } catch (...) {   // (on_pass may throw as well)
+            kyhip_frame_end(frame);
+            throw;
+        }
+        kyhip_frame_end(frame);
     }
     // integrator_t::debug_area / debug_pixel (ky.cpp:3733-3787), the reference's single-pixel replay: a red frame is ADDED around
     // [begin, end) (color_t{1.f} = (1, 0, 0) on the pixels of [begin - 1, end], 3739-3746), then every pixel of the area is cleared and
