@@ -20,10 +20,13 @@
  *   ky_drivers stress [spp] [res] BASELINE.json configs[4]: Cornell res x res (4096), spp (16384), max depth 16; writes stress.bmp
  *   ky_drivers progressive [spp] [w] [h]  the frame of lighting_enum (512 spp, 1024 x 768) rendered in passes of at least 64 samples (kyhip_frame_*): prints the
  *                                reference's progress line (3703) per pass, writes progressive_preview.bmp after the first pass and progressive.bmp at the end
+ *   ky_drivers converge [threshold] [spp_cap] [w] [h]  the same frame until it is clean (0.01, at most 4096 spp, 1024 x 768): per pass the progress line and the noise
+ *                                statistics (kyhip_frame_noise_stats); writes converge.bmp and converge_noise.bmp, the map scaled by 1 / threshold and clamped
  * An optional last argument multiplies every spp (the reference's values are tiny because its CPU path is slow).
  * KY_DEVICES=all (or a count n: devices 0 .. n-1) makes every integrator spread its tiles over that many GPUs of the node
  * (integrator_t::set_devices); the images do not depend on it.
  */
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -244,6 +247,49 @@ static void render_progressive(int spp, int width, int height) {
     film.store_image("progressive");
 }
 
+// The same frame until it is clean: passes of at least 64 samples until at most 2 % of the pixels have a noise estimate (kyhip_frame_noise: the standard error
+// of the pixel's mean luminance, in units of the film's white) above `threshold`, or the cap is reached.  Writes the mean of the samples done and the noise
+// map scaled by 1 / threshold (white: at or above the threshold).
+static void render_converge(float threshold, int spp_cap, int width, int height) {
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, {(float)width, (float)height});
+    ky_render_params p{};
+    p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS;
+    p.samples_per_pixel = spp_cap; p.sampler = KY_SAMPLER_RANDOM; p.seed = random_sampler_t(spp_cap).seed();
+    p.width = width; p.height = height; p.tile_w = 16; p.tile_h = 16; p.tile_first = 0; p.tile_step = 1;
+    kyhip_frame* frame = nullptr;
+    if (kyhip_frame_begin(0, &scene.flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+    struct frame_end_t { kyhip_frame* f; ~frame_end_t() { kyhip_frame_end(f); } } frame_end{frame};
+    if (kyhip_frame_track_noise(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_noise: ") + kyhip_last_error());
+    const float fraction = 0.02f;
+    int done = 0, passes = 0;
+    ky_noise_stats st{};
+    bool clean = false;
+    const double seconds = timing_seconds([&] {
+        while (done < spp_cap && !clean) {
+            if (kyhip_frame_render(frame, 64, &done) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_render: ") + kyhip_last_error());
+            if (kyhip_frame_noise_stats(frame, threshold, &st) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_noise_stats: ") + kyhip_last_error());
+            ++passes;
+            std::printf("rendering... %d spp, %.2f%%\n", spp_cap, 100. * done / spp_cap);
+            std::printf("  noise after %d batches: %lld of %lld pixels above %g (%lld flagged), max %g, mean %g\n", st.batches, (long long)st.above,
+                        (long long)st.pixels, (double)threshold, (long long)st.flagged, (double)st.max, st.mean);
+            clean = st.batches >= 2 && (double)st.above <= (double)fraction * (double)(st.pixels - st.flagged);
+        }
+    });
+    std::printf("converge: %dx%d, %s at %d of %d spp in %d passes: %.3f seconds\n", width, height, clean ? "clean" : "NOT clean", done, spp_cap, passes, seconds);
+    film_t film(width, height);
+    if (kyhip_frame_resolve(frame, 1, film.target_origin(), film.row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+    film.store_image("converge");
+    std::vector<float> map((size_t)width * height, 0.f);
+    if (kyhip_frame_noise(frame, map.data(), (size_t)width) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_noise: ") + kyhip_last_error());
+    film_t noise(width, height);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const float v = std::min(map[(size_t)y * width + x] / threshold, 1.f);
+            noise.add_color(x, y, color_t{v, v, v});
+        }
+    noise.store_image("converge_noise");
+}
+
 // BASELINE.json configs[4]: the stress frame
 static void render_stress(int spp, int res) {
     film_t film(res, res);
@@ -266,6 +312,10 @@ int main(int argc, char* argv[]) {
             render_lighting_enum(argc > 2 ? std::atoi(argv[2]) : 1024, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 768);
         } else if (!std::strcmp(which, "progressive")) {
             render_progressive(argc > 2 ? std::atoi(argv[2]) : 512, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 768);
+        } else if (!std::strcmp(which, "converge")) {
+            const float threshold = argc > 2 ? (float)std::atof(argv[2]) : 0.01f;
+            if (!(threshold > 0.f)) { std::fprintf(stderr, "converge: a threshold above 0\n"); return 2; }
+            render_converge(threshold, argc > 3 ? std::atoi(argv[3]) : 4096, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768);
         } else if (!std::strcmp(which, "lighting_cells")) {
             render_lighting_cells(argc > 2 ? std::atoi(argv[2]) : 10, argc > 3 ? std::atoi(argv[3]) : 256);
         } else if (!std::strcmp(which, "batch")) {

@@ -407,6 +407,38 @@ int     kyhip_frame_load(kyhip_frame* f, const void* buf, size_t bytes);
 void    kyhip_frame_end(kyhip_frame* f);
 
 /*
+ * A frame's noise estimate: when to stop (DESIGN.md "Noise").  A frame's accumulators change by whole chunks only, so the difference between them after two passes
+ * is an exact batch sum of the pixel's samples; a frame that tracks noise keeps per pixel the luminance sum (color_t::luminance's weights, ky.cpp:249-255) at
+ * its last pass and West's weighted sum of squares of the passes' batch means, 16 bytes, advanced by one film-sized kernel behind every pass.  The render
+ * kernels know nothing of it and a tracking frame's film is the film of any other frame, bit for bit.  The estimate is weak where batch means are: the batches
+ * are few and unequal (2 to 24 samples each), and a heavy-tailed pixel is under-estimated until a firefly lands in it.
+ *
+ * kyhip_frame_track_noise: only while nothing is rendered or loaded, else KY_ERR_INVALID_VALUE.  Tracking twice is fine.
+ * kyhip_frame_noise: WRITES (does not add) width x height floats, y down, row_stride_px floats apart: per pixel of the frame's shard the standard error of its
+ *   mean luminance so far in units of the film's white, sqrt(m2 / (batches - 1) / samples) / max(1, mean luminance) -- over-range pixels are scaled down because
+ *   clamp01 hides their error.  +inf while the frame has fewer than two batches (passes); 0 for a pixel that met NaN or +-inf or saturated, whose resolved
+ *   value the flag rules pin.  Pixels of other shards are left untouched.
+ * kyhip_frame_noise_stats: over the shard's pixels inside the film -- their count, how many are flagged, how many of the others lie above `threshold`, the
+ *   others' largest value and mean.  Deterministic: two calls return identical bytes.  threshold < 0 or NaN: KY_ERR_INVALID_VALUE.
+ * kyhip_frame_render_until: passes of at least min_samples_per_pass until batches >= min_batches (a value >= 2, else KY_ERR_INVALID_VALUE) and
+ *   above <= max_fraction_above * (pixels - flagged), or until the frame is complete; KY_OK either way, *out (the statistics behind the last pass) says which.
+ *   At least one pass is rendered unless the frame is complete.  *samples_done may be NULL.
+ * kyhip_frame_noise_ms: hipEvent durations of the last pass's update kernel and of the last map (+ statistics) kernels, negative where there was none.
+ * Every argument is checked before any device work; the four calls on a frame that does not track return KY_ERR_INVALID_VALUE.
+ * A tracking frame's checkpoint (kyhip_frame_state_bytes / _save / _load) carries a trailer behind the state described above: a magic number, the batch count
+ *   and the samples done at the last update, then the per-pixel pairs.  kyhip_frame_load into a tracking frame refuses, the frame untouched, a state without
+ *   a valid trailer or whose trailer stands at another sample count than its header; a frame that does not track saves today's bytes, accepts a longer buffer
+ *   and ignores the trailer.
+ */
+typedef struct ky_noise_stats { int32_t batches, samples_done; int64_t pixels, flagged, above; float threshold, max; double mean; } ky_noise_stats;
+int     kyhip_frame_track_noise(kyhip_frame* f);
+int     kyhip_frame_noise(kyhip_frame* f, float* map, size_t row_stride_px);
+int     kyhip_frame_noise_stats(kyhip_frame* f, float threshold, ky_noise_stats* out);
+int     kyhip_frame_render_until(kyhip_frame* f, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass,
+                                 int* samples_done, ky_noise_stats* out);
+int     kyhip_frame_noise_ms(const kyhip_frame* f, float* update_ms, float* stats_ms);
+
+/*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent
  * kyhip_render* call on `device`, from hipEvents recorded on the launch stream around that one
  * kernel.  The stream must have been synchronised.  Negative if no timing is available.

@@ -72,6 +72,11 @@ class RenderParams(C.Structure):
                 ("tile_first", C.c_int32), ("tile_step", C.c_int32)]
 
 
+class NoiseStats(C.Structure):   # ky_noise_stats
+    _fields_ = [("batches", C.c_int32), ("samples_done", C.c_int32), ("pixels", C.c_int64), ("flagged", C.c_int64), ("above", C.c_int64),
+                ("threshold", C.c_float), ("max", C.c_float), ("mean", C.c_double)]
+
+
 FP = C.POINTER(C.c_float)
 SP = C.POINTER(Scene)
 PP = C.POINTER(RenderParams)
@@ -129,6 +134,11 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "kyhip_frame_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "kyhip_frame_end": (None, [C.c_void_p]),
+    "kyhip_frame_track_noise": (C.c_int, [C.c_void_p]),
+    "kyhip_frame_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_noise_stats": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(NoiseStats)]),
+    "kyhip_frame_render_until": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(NoiseStats)]),
+    "kyhip_frame_noise_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -166,6 +176,8 @@ KYHOST_SYMBOLS = {
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhost_render_passes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
+    "kyhost_render_until": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_float, C.c_float, C.c_int, C.c_int]),
     "kyhost_store_image": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhost_gamma_encoding": (C.c_int, [C.c_float]),
 }
@@ -183,6 +195,8 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
     "kyhostcheck_chunks": (C.c_int, [C.c_int]),
     "kyhostcheck_shard": (C.c_longlong, [PP]),
     "kyhostcheck_frame": (C.c_int, [PP, C.c_int]),
+    "kyhostcheck_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int]),
     "kyhostcheck_add_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_seam_stress": (C.c_int, [C.c_int]),
     "kyhostcheck_jit_stress": (C.c_int, [C.c_int, C.c_int]),

@@ -112,13 +112,19 @@ def pass_boundaries(spp):
 
 class Frame:
     """A frame rendered in passes (kyhip_frame_*): `with Frame(scene, params) as f: f.render(64); preview = f.resolve(normalise=True); ...`.
-    params.samples_per_pixel is the frame's total; a complete frame's resolve() is render(scene, params), bit for bit."""
+    params.samples_per_pixel is the frame's total; a complete frame's resolve() is render(scene, params), bit for bit.
+    noise=True: the frame keeps a per-pixel noise estimate over its passes (kyhip_frame_track_noise): noise(), noise_stats(threshold), render_until(...)."""
 
-    def __init__(self, scene, params, device=0):
+    def __init__(self, scene, params, device=0, noise=False):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
         _check(self._lib.kyhip_frame_begin(device, _scene_ptr(scene), C.byref(params), C.byref(self._f)), self._lib)
+        if noise:
+            rc = self._lib.kyhip_frame_track_noise(self._f)
+            if rc != A.KY_OK:
+                self.close()
+                _check(rc, self._lib)
 
     def close(self):
         if getattr(self, "_f", None):
@@ -170,6 +176,29 @@ class Frame:
         buf = C.create_string_buffer(n)
         _check(self._lib.kyhip_frame_save(self._f, buf, n), self._lib)
         return buf.raw
+
+    def noise(self, out=None):
+        """The (H, W) float32 noise map (kyhip_frame_noise): per pixel of the frame's shard the standard error of its mean luminance so far, in units of the
+        film's white; +inf before the second pass, 0 for flagged pixels.  Pixels of other shards keep `out`'s values (a new map: 0)."""
+        if out is None:
+            out = np.zeros((self.height, self.width), np.float32)
+        assert out.dtype == np.float32 and out.shape == (self.height, self.width) and out.strides[1] == 4 and out.strides[0] % 4 == 0
+        _check(self._lib.kyhip_frame_noise(self._f, C.c_void_p(out.ctypes.data), out.strides[0] // 4), self._lib)
+        return out
+
+    def noise_stats(self, threshold):
+        """kyhip_frame_noise_stats as a ky_noise_stats (_abi.NoiseStats): batches, samples_done, pixels, flagged, above, threshold, max, mean."""
+        st = A.NoiseStats()
+        _check(self._lib.kyhip_frame_noise_stats(self._f, float(threshold), C.byref(st)), self._lib)
+        return st
+
+    def render_until(self, threshold, max_fraction_above=0.0, min_batches=2, min_samples_per_pass=1):
+        """Passes until at most max_fraction_above of the pixels are noisier than threshold (after min_batches passes or more) or the frame is complete:
+        (samples done, the statistics behind the last pass)."""
+        done, st = C.c_int(0), A.NoiseStats()
+        _check(self._lib.kyhip_frame_render_until(self._f, float(threshold), float(max_fraction_above), int(min_batches), int(min_samples_per_pass),
+                                                  C.byref(done), C.byref(st)), self._lib)
+        return done.value, st
 
     def load(self, state):
         """Continue from a checkpoint of a frame begun with the same scene and params (kyhip_frame_load); any other state raises KyError."""
@@ -247,6 +276,22 @@ def render_passes_host_api(scene, integrator_enum, depth, direct_sample, sampler
     if rc != 0:
         raise KyError("kyhost_render_passes failed: " + host.kyhost_last_error().decode())
     return film
+
+
+def render_until_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, threshold, max_fraction_above=0.0, min_batches=2,
+                          min_samples_per_pass=1, seed=1234, film=None, device=0):
+    """create_integrator(...)->render_until(&scene, sampler, &film, threshold, max_fraction_above, min_batches, min_samples_per_pass) through the C++ host
+    classes: (the film with the mean of the samples done added, the samples done per pixel)."""
+    host = A.load_kyhost()
+    if film is None:
+        film = np.zeros((height, width, 3), np.float32)
+    rc = host.kyhost_render_until(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device,
+                                  float(threshold), float(max_fraction_above), int(min_batches), int(min_samples_per_pass))
+    if rc == -2:
+        return None
+    if rc < 0:
+        raise KyError("kyhost_render_until failed: " + host.kyhost_last_error().decode())
+    return film, rc
 
 
 def debug_area_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, begin, end, film=None, seed=1234, device=0):

@@ -3,15 +3,18 @@
  * its progress per row (3703) and has the picture only at the end; here a frame keeps its own accumulator block on the device, each pass adds whole chunks
  * of every pixel's samples to it (render_tiles_device with a FramePass, ky_launch.hip), and the picture so far can be resolved, saved and loaded between
  * passes.  Which chunks a pass renders and what a checkpoint must agree in is host arithmetic (ky_shard.hpp, ky_pack.cpp); HIP runtime calls only: no
- * kernel is defined here.
+ * kernel is defined here.  A frame that tracks noise (kyhip_frame_track_noise; DESIGN.md "Noise") also owns a per-pixel estimate that every pass advances behind its
+ * render kernel: the arithmetic is ky_noise.hpp's, the kernels ky_noise.hip's.
  */
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "ky_ctx.hpp"
+#include "ky_noise.hpp"
 
 using namespace kyh;
+using namespace kyn;
 
 struct kyhip_frame {
     int device = 0;
@@ -29,6 +32,15 @@ struct kyhip_frame {
     FramePass pass;               // the frame's accumulator block and the kernel its first pass took
     DevBuf ws, tiles, film;       // accumulators + flag words; resolve's compact tile buffer; resolve's device film (pageable host films)
     std::vector<float> stage;     // ... and its host copy
+    // the noise estimate of a frame that tracks it
+    bool track = false, loaded = false;
+    int batches = 0, n_prev = 0;  // updates so far and the samples done at the last one (the per-pixel state stands at n_prev)
+    DevBuf noise, nmap, ncls, nsums;   // n_pix NoisePixel; the map (compact tile order) and the pixels' classes; the statistics' partials and their result
+    std::vector<float> hmap;      // host copies of the map and the classes
+    std::vector<unsigned char> hcls;
+    hipEvent_t ev[4] = {};        // around the last update kernel / the last map + statistics (kyhip_frame_noise_ms)
+    bool timed[2] = {false, false};
+    ~kyhip_frame() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 static int samples_done(const kyhip_frame* f) { return chunk_end(f->plan, f->chunks_done - 1); }
@@ -89,9 +101,19 @@ int kyhip_frame_render(kyhip_frame* f, int min_samples, int* done) {
         f->pass.chunk_first = f->chunks_done;
         f->pass.chunk_count = c1 - f->chunks_done;
         rcode = render_tiles_device(f->device, &f->scene, &f->params, nullptr, nullptr, 0, c->stream, 0, nullptr, &f->pass);
+        const int n_now = chunk_end(f->plan, c1 - 1);
+        if (rcode == KY_OK && f->track) {   // the batch this pass adds, behind its render kernel
+            (void)hipEventRecord(f->ev[0], c->stream);
+            rcode = noise_update_device(f->ws.p, f->noise.p, f->sh.n_pix, f->params.samples_per_pixel, f->n_prev, n_now, c->stream);
+            (void)hipEventRecord(f->ev[1], c->stream);
+        }
         const hipError_t e = hipStreamSynchronize(c->stream);   // blocking, and also after a failed enqueue
         if (rcode != KY_OK) return rcode;
         if (e != hipSuccess) return fail(KY_ERR_DEVICE, "pass failed: %s (the frame's accumulators may hold a part of it)", hipGetErrorString(e));
+        if (f->track) { f->batches += 1; f->n_prev = n_now; f->timed[0] = true; }
+    } else if (c1 > f->chunks_done && f->track) {   // a shard without pixels: the bookkeeping alone
+        f->batches += 1;
+        f->n_prev = chunk_end(f->plan, c1 - 1);
     }
     f->chunks_done = c1;
     if (done) *done = samples_done(f);
@@ -135,12 +157,12 @@ int kyhip_frame_resolve(kyhip_frame* f, int normalise, float* film_rgb, size_t s
 
 int64_t kyhip_frame_state_bytes(const kyhip_frame* f) {
     if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
-    return (int64_t)frame_state_bytes(&f->params);
+    return (int64_t)(frame_state_bytes(&f->params) + (f->track ? noise_trailer_bytes(f->sh.n_pix) : 0));
 }
 
 int kyhip_frame_save(kyhip_frame* f, void* buf, size_t bytes) {
     if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
-    const size_t need = frame_state_bytes(&f->params);
+    const size_t base = frame_state_bytes(&f->params), need = base + (f->track ? noise_trailer_bytes(f->sh.n_pix) : 0);
     if (!buf || bytes < need) return fail(KY_ERR_INVALID_VALUE, "frame state: a buffer of %zu bytes, the state has %zu", bytes, need);
     FrameHeader h = f->header;
     h.samples_done = samples_done(f);
@@ -149,7 +171,12 @@ int kyhip_frame_save(kyhip_frame* f, void* buf, size_t bytes) {
         DeviceCtx* c;
         const int rcode = get_ctx(f->device, &c);
         if (rcode != KY_OK) return rcode;
-        HIP_TRY(hipMemcpy((char*)buf + sizeof h, f->ws.p, need - sizeof h, hipMemcpyDeviceToHost));   // (passes are blocking: nothing of the frame is in flight)
+        HIP_TRY(hipMemcpy((char*)buf + sizeof h, f->ws.p, base - sizeof h, hipMemcpyDeviceToHost));   // (passes are blocking: nothing of the frame is in flight)
+        if (f->track) HIP_TRY(hipMemcpy((char*)buf + base + sizeof(NoiseTrailer), f->noise.p, (size_t)f->sh.n_pix * sizeof(NoisePixel), hipMemcpyDeviceToHost));
+    }
+    if (f->track) {
+        const NoiseTrailer t = {KY_NOISE_MAGIC, f->batches, f->n_prev};
+        std::memcpy((char*)buf + base, &t, sizeof t);
     }
     return KY_OK;
 }
@@ -159,13 +186,135 @@ int kyhip_frame_load(kyhip_frame* f, const void* buf, size_t bytes) {
     int chunks = 0;
     int rcode = frame_state_check(f->header, buf, bytes, &chunks);
     if (rcode != KY_OK) return rcode;
+    const size_t base = frame_state_bytes(&f->params);
+    NoiseTrailer t = {};
+    if (f->track) {   // (a frame that does not track accepts a longer buffer and ignores the trailer)
+        rcode = noise_trailer_check(buf, bytes, base, f->sh.n_pix, chunk_end(f->plan, chunks - 1), &t);
+        if (rcode != KY_OK) return rcode;
+    }
     if (f->sh.n_pix > 0) {
         DeviceCtx* c;
         rcode = get_ctx(f->device, &c);
         if (rcode != KY_OK) return rcode;
-        HIP_TRY(hipMemcpy(f->ws.p, (const char*)buf + sizeof(FrameHeader), frame_state_bytes(&f->params) - sizeof(FrameHeader), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(f->ws.p, (const char*)buf + sizeof(FrameHeader), base - sizeof(FrameHeader), hipMemcpyHostToDevice));
+        if (f->track) HIP_TRY(hipMemcpy(f->noise.p, (const char*)buf + base + sizeof(NoiseTrailer), (size_t)f->sh.n_pix * sizeof(NoisePixel), hipMemcpyHostToDevice));
     }
+    // (the frame is left untouched by every REFUSAL above; a copy that fails half way is a device error, KY_ERR_DEVICE, behind which the frame's accumulators and
+    // pairs may disagree with its counts, which are advanced only here, behind both copies: such a frame is to be ended or loaded again)
+    if (f->track) { f->batches = t.batches; f->n_prev = t.n_prev; }
     f->chunks_done = chunks;
+    f->loaded = true;
+    return KY_OK;
+}
+
+// ---- the noise estimate (DESIGN.md "Noise") ----
+int kyhip_frame_track_noise(kyhip_frame* f) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (f->track) return KY_OK;
+    if (f->chunks_done != 0 || f->loaded) return fail(KY_ERR_INVALID_VALUE, "noise is tracked from a frame's first pass: this one has rendered or loaded something");
+    if (f->sh.n_pix > 0) {
+        DeviceCtx* c;
+        const int rcode = get_ctx(f->device, &c);
+        if (rcode != KY_OK) return rcode;
+        const size_t n = (size_t)f->sh.n_pix;
+        HIP_TRY(f->noise.alloc(n * sizeof(NoisePixel)));
+        HIP_TRY(f->nmap.alloc(n * sizeof(float)));
+        HIP_TRY(f->ncls.alloc(n));
+        HIP_TRY(f->nsums.alloc(((size_t)noise_blocks(f->sh.n_pix) + 1) * sizeof(NoiseSums)));
+        for (hipEvent_t& e : f->ev) if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipMemsetAsync(f->noise.p, 0, n * sizeof(NoisePixel), c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    f->track = true;
+    return KY_OK;
+}
+
+static bool good_threshold(float t) { return t >= 0.f; }   // (false for a NaN)
+
+// the map and the classes (device), and with `sums` the statistics against `threshold`: enqueued and waited for
+static int noise_map_and_stats(kyhip_frame* f, float threshold, NoiseSums* sums) {
+    DeviceCtx* c;
+    int rcode = get_ctx(f->device, &c);
+    if (rcode != KY_OK) return rcode;
+    (void)hipEventRecord(f->ev[2], c->stream);
+    rcode = noise_map_device(f->ws.p, f->noise.p, f->nmap.as<float>(), f->ncls.as<unsigned char>(), f->sh, f->params.width, f->params.height, f->batches, f->n_prev, c->stream);
+    if (rcode == KY_OK && sums) rcode = noise_stats_device(f->nmap.as<float>(), f->ncls.as<unsigned char>(), f->sh.n_pix, threshold, f->nsums.p, c->stream);
+    (void)hipEventRecord(f->ev[3], c->stream);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rcode != KY_OK) return rcode;
+    if (e != hipSuccess) return fail(KY_ERR_DEVICE, "noise map failed: %s", hipGetErrorString(e));
+    f->timed[1] = true;
+    if (sums) HIP_TRY(hipMemcpy(sums, f->nsums.as<NoiseSums>() + noise_blocks(f->sh.n_pix), sizeof *sums, hipMemcpyDeviceToHost));
+    return KY_OK;
+}
+
+int kyhip_frame_noise(kyhip_frame* f, float* map, size_t stride_px) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!f->track) return fail(KY_ERR_INVALID_VALUE, "the frame does not track noise (kyhip_frame_track_noise)");
+    if (!map || stride_px < (size_t)f->params.width) return fail(KY_ERR_INVALID_VALUE, "bad map arguments");
+    if (f->sh.n_pix == 0) return KY_OK;
+    const int rcode = noise_map_and_stats(f, 0.f, nullptr);
+    if (rcode != KY_OK) return rcode;
+    const size_t n = (size_t)f->sh.n_pix;
+    f->hmap.resize(n);
+    f->hcls.resize(n);
+    HIP_TRY(hipMemcpy(f->hmap.data(), f->nmap.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(f->hcls.data(), f->ncls.p, n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < f->sh.n_pix; ++i) {
+        if (f->hcls[(size_t)i] == KY_NOISE_PADDING) continue;
+        int x, y;
+        noise_pixel_xy(f->sh, i, x, y);
+        map[(size_t)y * stride_px + (size_t)x] = f->hmap[(size_t)i];
+    }
+    return KY_OK;
+}
+
+int kyhip_frame_noise_stats(kyhip_frame* f, float threshold, ky_noise_stats* out) {
+    if (!good_threshold(threshold)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!f->track) return fail(KY_ERR_INVALID_VALUE, "the frame does not track noise (kyhip_frame_track_noise)");
+    NoiseSums s = {};
+    if (f->sh.n_pix > 0) {
+        const int rcode = noise_map_and_stats(f, threshold, &s);
+        if (rcode != KY_OK) return rcode;
+    }
+    std::memset(out, 0, sizeof *out);
+    out->batches = f->batches;
+    out->samples_done = samples_done(f);
+    out->pixels = s.pixels; out->flagged = s.flagged; out->above = s.above;
+    out->threshold = threshold;
+    out->max = s.max;
+    out->mean = s.pixels - s.flagged > 0 ? s.sum / (double)(s.pixels - s.flagged) : 0.0;
+    return KY_OK;
+}
+
+int kyhip_frame_render_until(kyhip_frame* f, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass, int* done, ky_noise_stats* out) {
+    if (!good_threshold(threshold)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
+    if (!(max_fraction_above >= 0.f && max_fraction_above <= 1.f)) return fail(KY_ERR_INVALID_VALUE, "max_fraction_above %g: a fraction of the pixels, 0 .. 1", (double)max_fraction_above);
+    if (min_batches < 2) return fail(KY_ERR_INVALID_VALUE, "min_batches %d: the estimate needs two batches", min_batches);
+    if (min_samples_per_pass < 1) return fail(KY_ERR_INVALID_VALUE, "min_samples_per_pass %d: a pass renders at least one sample per pixel", min_samples_per_pass);
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!f->track) return fail(KY_ERR_INVALID_VALUE, "the frame does not track noise (kyhip_frame_track_noise)");
+    for (;;) {
+        int rcode = kyhip_frame_render(f, min_samples_per_pass, done);
+        if (rcode != KY_OK) return rcode;
+        rcode = kyhip_frame_noise_stats(f, threshold, out);
+        if (rcode != KY_OK) return rcode;
+        const bool clean = out->batches >= min_batches && (double)out->above <= (double)max_fraction_above * (double)(out->pixels - out->flagged);
+        if (clean || samples_done(f) >= f->params.samples_per_pixel) return KY_OK;
+    }
+}
+
+int kyhip_frame_noise_ms(const kyhip_frame* f, float* update_ms, float* stats_ms) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!f->track) return fail(KY_ERR_INVALID_VALUE, "the frame does not track noise (kyhip_frame_track_noise)");
+    float ms[2] = {-1.f, -1.f};
+    for (int k = 0; k < 2; ++k)
+        if (f->timed[k] && hipEventElapsedTime(&ms[k], f->ev[2 * k], f->ev[2 * k + 1]) != hipSuccess) ms[k] = -1.f;
+    if (update_ms) *update_ms = ms[0];
+    if (stats_ms) *stats_ms = ms[1];
     return KY_OK;
 }
 

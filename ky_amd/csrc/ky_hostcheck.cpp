@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include "ky_host.hpp"
+#include "ky_noise.hpp"
 
 using namespace kyh;
 
@@ -179,6 +180,32 @@ int kyhostcheck_jit_stress(int n_threads, int rounds) {
     return got.load();
 }
 
+// The noise estimate's arithmetic (ky_noise.hpp: what noise_update_kernel and noise_map_kernel do per pixel) on the caller's accumulators -- accum:
+// n_pass x n_pix x 3 words as they stand after each pass, done: the samples done after each pass, flags: n_pix flag words (NULL: none set) -- writing after
+// every pass the pixels' {y_prev, m2} (out_state: n_pass x n_pix x 2) and their map values (out_map: n_pass x n_pix); then, when `state` is given, the
+// trailer check of a checkpoint of state_bytes bytes whose accumulators end at base_bytes, for a frame of trailer_n_pix pixels at samples_done.
+// Returns the trailer check's status (KY_OK without one), or KY_ERR_INVALID_VALUE for arguments that are none.
+int kyhostcheck_noise(const long long* accum, const int* done, int n_pass, int n_pix, int total_spp, const unsigned* flags, double* out_state, float* out_map,
+                      const void* state, size_t state_bytes, size_t base_bytes, int trailer_n_pix, int samples_done) {
+    using namespace kyn;
+    if (n_pass < 0 || n_pix < 0 || (n_pass > 0 && n_pix > 0 && (!accum || !done || !out_state || !out_map))) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    std::vector<NoisePixel> px((size_t)n_pix, NoisePixel{0.0, 0.0});
+    int n_prev = 0;
+    for (int k = 0; k < n_pass; ++k) {
+        if (done[k] <= n_prev) return fail(KY_ERR_INVALID_VALUE, "pass %d ends at %d samples, the one before at %d", k, done[k], n_prev);
+        for (int i = 0; i < n_pix; ++i) {
+            const long long* a = accum + ((size_t)k * n_pix + (size_t)i) * 3;
+            noise_update(px[(size_t)i], noise_luminance(a[0], a[1], a[2], total_spp), n_prev, done[k]);
+            out_state[((size_t)k * n_pix + (size_t)i) * 2] = px[(size_t)i].y_prev;
+            out_state[((size_t)k * n_pix + (size_t)i) * 2 + 1] = px[(size_t)i].m2;
+            out_map[(size_t)k * n_pix + (size_t)i] = noise_value(px[(size_t)i], k + 1, done[k], flags ? flags[i] : 0u);
+        }
+        n_prev = done[k];
+    }
+    if (!state) return KY_OK;
+    NoiseTrailer t;
+    return noise_trailer_check(state, state_bytes, base_bytes, trailer_n_pix, samples_done, &t);
+}
 
 // ---- the entry points that need a GPU: absent from this build.  They exist as symbols because the host mirror (ky.hpp) and ctypes resolve every
 // symbol when a library is loaded; each validates what the product validates before it touches a device where a CPU test looks at that, and then
@@ -223,6 +250,21 @@ int64_t kyhip_frame_state_bytes(const kyhip_frame*) { return fail(KY_ERR_INVALID
 int kyhip_frame_save(kyhip_frame*, void*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_load(kyhip_frame*, const void*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 void kyhip_frame_end(kyhip_frame*) {}
+// (the noise entries check their other arguments first, like the real ones)
+int kyhip_frame_track_noise(kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_noise(kyhip_frame*, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_noise_stats(kyhip_frame*, float threshold, ky_noise_stats* out) {
+    if (!(threshold >= 0.f)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
+    return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+}
+int kyhip_frame_render_until(kyhip_frame*, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass, int*, ky_noise_stats* out) {
+    if (!(threshold >= 0.f)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
+    if (!(max_fraction_above >= 0.f && max_fraction_above <= 1.f)) return fail(KY_ERR_INVALID_VALUE, "max_fraction_above %g: a fraction of the pixels, 0 .. 1", (double)max_fraction_above);
+    if (min_batches < 2) return fail(KY_ERR_INVALID_VALUE, "min_batches %d: the estimate needs two batches", min_batches);
+    if (min_samples_per_pass < 1) return fail(KY_ERR_INVALID_VALUE, "min_samples_per_pass %d: a pass renders at least one sample per pixel", min_samples_per_pass);
+    return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+}
+int kyhip_frame_noise_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }
 int kyhip_smallpt_render(int, const ky_smallpt_sphere* spheres, int n, const ky_smallpt_params* p, double* image) {

@@ -17,6 +17,7 @@
 #include <unistd.h>
 
 #include "ky_host.hpp"
+#include "ky_noise.hpp"
 
 namespace kyh {
 
@@ -211,6 +212,21 @@ int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, int
     *chunks_done = c;
     return KY_OK;
 }
+}  // namespace kyh
+// A tracking frame's state continues behind the accumulators and flag words (state_bytes) with a NoiseTrailer and n_pix NoisePixel (ky_noise.hpp)
+int kyn::noise_trailer_check(const void* buf, size_t bytes, size_t state_bytes, int n_pix, int samples_done, NoiseTrailer* out) {
+    using kyh::fail;
+    if (!buf || bytes < state_bytes || bytes - state_bytes < noise_trailer_bytes(n_pix))
+        return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no noise trailer (the state of a frame that tracks noise has %zu)", bytes, state_bytes + noise_trailer_bytes(n_pix));
+    NoiseTrailer t;
+    std::memcpy(&t, (const char*)buf + state_bytes, sizeof t);
+    if (t.magic != KY_NOISE_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: no noise trailer behind the accumulators (saved by a frame that does not track noise?)");
+    if (t.batches < 0 || t.n_prev != samples_done)
+        return fail(KY_ERR_INVALID_VALUE, "frame state: the noise estimate stands at %d samples in %d batches, the accumulators at %d", t.n_prev, t.batches, samples_done);
+    if (out) *out = t;
+    return KY_OK;
+}
+namespace kyh {
 
 RenderConst make_rc(const ky_render_params* p) {
     RenderConst rc{};

@@ -719,6 +719,30 @@ public:
         }
         kyhip_frame_end(frame);
     }
+    // render_passes that stops by itself: passes of at least min_samples_per_pass until, after min_batches passes or more, at most max_fraction_above of the
+    // pixels have a noise estimate (kyhip_frame_noise: the standard error of the pixel's mean luminance, in units of the film's white) above `threshold`, or the
+    // frame is complete.  ADDS the mean of the samples done to the film (normalise 1) and returns the samples done per pixel.
+    int render_until(scene_t* scene, sampler_t* original_sampler, film_t* film, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass,
+                     ky_noise_stats* stats = nullptr) {
+        if (masked()) throw std::runtime_error("integrator_t::render_until: light classes are rendered by render() only");
+        const ky_render_params p = params_for(original_sampler, film);
+        kyhip_frame* frame = nullptr;
+        if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        int done = 0;
+        try {
+            ky_noise_stats st;
+            if (kyhip_frame_track_noise(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_noise: ") + kyhip_last_error());
+            if (kyhip_frame_render_until(frame, threshold, max_fraction_above, min_batches, min_samples_per_pass, &done, &st) != KY_OK)
+                throw std::runtime_error(std::string("kyhip_frame_render_until: ") + kyhip_last_error());
+            if (stats) *stats = st;
+            if (kyhip_frame_resolve(frame, 1, film->target_origin(), film->row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+        } catch (...) {
+            kyhip_frame_end(frame);
+            throw;
+        }
+        kyhip_frame_end(frame);
+        return done;
+    }
     // integrator_t::debug_area / debug_pixel (ky.cpp:3733-3787), the reference's single-pixel replay: a red frame is ADDED around
     // [begin, end) (color_t{1.f} = (1, 0, 0) on the pixels of [begin - 1, end], 3739-3746), then every pixel of the area is cleared and
     // rendered again on its own (3756-3776): the caller's sampler, the samples summed one after the other in float, one clamp, add_color.

@@ -40,3 +40,8 @@ for depth in (5,16):
         pixels = [(48, 27), (5, 5), (30, 40), (70, 30), (48, 50), (20, 20), (80, 45), (60, 8)]
         bad, tot, sg, sc = T.li_agreement(api, O, scene, params, pixels)
         print("li veach", depth, strat, bad, tot, "%.2e" % (abs(sg-sc)/max(sc,1)))
+# the noise estimate against the across-seed spread of the picture (tests/test_noise_gpu.py::test_it_measures_noise): three seed sets per sample count
+import test_noise_gpu as N
+conv = N._converging(A, api)
+for samples in (500, 112):
+    print("noise ratio", samples, " ".join("%.4f" % N._ratio(A, api, conv["map%d" % samples], samples, seeds) for seeds in N.SEED_SETS))
