@@ -22,6 +22,9 @@
  *                                reference's progress line (3703) per pass, writes progressive_preview.bmp after the first pass and progressive.bmp at the end
  *   ky_drivers converge [threshold] [spp_cap] [w] [h]  the same frame until it is clean (0.01, at most 4096 spp, 1024 x 768): per pass the progress line and the noise
  *                                statistics (kyhip_frame_noise_stats); writes converge.bmp and converge_noise.bmp, the map scaled by 1 / threshold and clamped
+ *   ky_drivers adaptive [threshold] [spp] [w] [h]  the same frame rendered adaptively (0.008, 1024 spp, 1024 x 768): passes of 64, and after each the 8 x 8 pixel
+ *                                blocks at most a tenth of whose pixels are noisier than the threshold retire (integrator_t::render_adaptive); writes adaptive.bmp:
+ *                                the picture and, next to it, the sample-count map (white: the frame's total)
  * An optional last argument multiplies every spp (the reference's values are tiny because its CPU path is slow).
  * KY_DEVICES=all (or a count n: devices 0 .. n-1) makes every integrator spread its tiles over that many GPUs of the node
  * (integrator_t::set_devices); the images do not depend on it.
@@ -290,6 +293,28 @@ static void render_converge(float threshold, int spp_cap, int width, int height)
     noise.store_image("converge_noise");
 }
 
+// The headline frame rendered adaptively (integrator_t::render_adaptive; include/kyhip.h, kyhip_frame_track_blocks ...): the picture and the samples each pixel's
+// block received, side by side.
+static void render_adaptive(float threshold, int spp, int width, int height) {
+    film_grid_t film(1, 2, width, height);
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, film.get_resolution());
+    std::unique_ptr<sampler_t> sampler = std::make_unique<random_sampler_t>(spp);
+    std::unique_ptr<integrator_t> integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
+    std::vector<int32_t> counts;
+    ky_block_stats st{};
+    const double seconds = timing_seconds([&] { st = integrator->render_adaptive(&scene, sampler.get(), &film, threshold, 0.10f, 3, 64, &counts); });
+    std::printf("adaptive: %dx%d, threshold %g: %d passes, the front at %d of %d spp, %d of %d blocks still live; %.1f samples per pixel (%d .. %d): %.3f seconds\n", width,
+                height, (double)threshold, st.passes, st.samples_done, spp, st.live, st.blocks, (double)st.pixel_samples / (double)st.pixels, st.min_samples, st.max_samples,
+                seconds);
+    film.next_subfilm();
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const float v = (float)counts[(size_t)y * width + x] / (float)spp;
+            film.add_color(x, y, color_t{v, v, v});
+        }
+    film.store_image("adaptive");
+}
+
 // BASELINE.json configs[4]: the stress frame
 static void render_stress(int spp, int res) {
     film_t film(res, res);
@@ -316,6 +341,10 @@ int main(int argc, char* argv[]) {
             const float threshold = argc > 2 ? (float)std::atof(argv[2]) : 0.01f;
             if (!(threshold > 0.f)) { std::fprintf(stderr, "converge: a threshold above 0\n"); return 2; }
             render_converge(threshold, argc > 3 ? std::atoi(argv[3]) : 4096, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768);
+        } else if (!std::strcmp(which, "adaptive")) {
+            const float threshold = argc > 2 ? (float)std::atof(argv[2]) : 0.008f;
+            if (!(threshold > 0.f)) { std::fprintf(stderr, "adaptive: a threshold above 0\n"); return 2; }
+            render_adaptive(threshold, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768);
         } else if (!std::strcmp(which, "lighting_cells")) {
             render_lighting_cells(argc > 2 ? std::atoi(argv[2]) : 10, argc > 3 ? std::atoi(argv[3]) : 256);
         } else if (!std::strcmp(which, "batch")) {

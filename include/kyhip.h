@@ -439,6 +439,50 @@ int     kyhip_frame_render_until(kyhip_frame* f, float threshold, float max_frac
 int     kyhip_frame_noise_ms(const kyhip_frame* f, float* update_ms, float* stats_ms);
 
 /*
+ * Adaptive sampling: a frame that retires clean pixel blocks between its passes (DESIGN.md "Adaptive").  The unit is the render kernels' work item, a block of
+ * 8 x 8 pixels.  A block is live, or retired at the samples it had when it retired; a retired block is never rendered again, all live blocks stand at the same
+ * sample count (the frame's front, what kyhip_frame_samples reports as done), and retirement happens only between passes and is final.  Blocks of a ragged edge
+ * tile that have no pixel inside the film are retired at 0 samples from the start.  Every pass of such a frame runs a render kernel that reads its blocks from
+ * the frame's list of live ones (kyhip_last_kernel: "... listed blocks ..., blocks: 9 of 24 live"); with nothing retired the film is kyhip_render's.
+ * Caveat: a block that stops on the estimate of its own samples is biased towards the value it had when it looked clean.
+ *
+ * kyhip_frame_track_blocks: only while nothing is rendered or loaded, else KY_ERR_INVALID_VALUE; independent of kyhip_frame_track_noise (either order).  Twice is fine.
+ * kyhip_frame_keep: `mask` is width x height bytes, y down, row_stride bytes apart; every live block none of whose pixels inside the film has a non-zero byte is
+ *   retired (the reference's debug_area: go on rendering a part of the film only).  Needs no noise tracking.  NULL mask, row_stride < width: KY_ERR_INVALID_VALUE.
+ * kyhip_frame_retire_noisy: one application of the retire rule to the live blocks as the frame stands: a block retires when batches >= min_batches and
+ *   above <= max_fraction_above * counted, over its pixels inside the film that are not flagged (kyhip_frame_render_until's comparison, per block).  Needs noise
+ *   tracking; threshold, max_fraction_above and min_batches are checked as kyhip_frame_render_until checks them.  *out: the statistics behind it.
+ * kyhip_frame_render_adaptive: kyhip_frame_render(min_samples_per_pass) then kyhip_frame_retire_noisy, until no block is live or the front has reached the
+ *   total; KY_OK either way, *out says which.  *samples_done (may be NULL): the front.
+ * kyhip_frame_sample_map: WRITES width x height int32, y down, row_stride_px apart: per pixel of the frame's shard the samples its block has received.  Pixels
+ *   of other shards are left untouched.
+ * kyhip_frame_block_stats: blocks (padding included) and how many are live, passes rendered (saved and loaded with the frame's state), the front, the smallest and largest per-pixel sample count, the
+ *   shard's pixels inside the film and the pixel-samples rendered so far (the sum of the sample map).
+ * kyhip_frame_blocks_ms: hipEvent durations of the last retire (or keep) kernel and of the last compaction of the live list, negative where there was none.
+ * On a block-tracking frame kyhip_frame_render renders the live blocks only (none live: KY_OK, nothing is launched, the front stays -- a caller's loop
+ *   `while (done < total)` must also end on kyhip_frame_block_stats' live == 0; a shard without tiles has no blocks and advances its front like any other
+ *   frame's empty shard); kyhip_frame_render_until applies its whole-frame rule as on any frame and also returns, KY_OK, as soon as no block is live: the front
+ *   and the map would not change any more. kyhip_frame_resolve with
+ *   normalise 1 scales each pixel by total / (its block's samples) in double before the one rounding (blocks at 0 samples add nothing), and with normalise 0
+ *   returns KY_ERR_INVALID_VALUE, the film untouched, while a block inside the film is retired short of the total (it would be darkened silently).
+ * Checkpoints: a block-tracking frame's header has a magic number of its own -- frames that do not track blocks refuse its states and it refuses theirs -- and
+ *   its state ends with a block trailer (behind the noise trailer when both are tracked): a magic number, the block count, then per block the retirement count
+ *   (-1: live) and its batch count; the trailer also holds the passes rendered.  kyhip_frame_load refuses, the frame untouched, a missing or short trailer, another
+ *   block count, a retirement count that is no value of kyhip_pass_boundaries (or 0) or lies beyond the header's samples done, and a block's batch count that is
+ *   not 0 on a live block or one retired at 0 samples or exceeds the noise trailer's (0 on a frame that tracks no noise).
+ * The calls on a frame that does not track blocks return KY_ERR_INVALID_VALUE; arguments are checked before any device work.
+ */
+typedef struct ky_block_stats { int32_t blocks, live, passes, samples_done, min_samples, max_samples; int64_t pixels, pixel_samples; } ky_block_stats;
+int     kyhip_frame_track_blocks(kyhip_frame* f);
+int     kyhip_frame_keep(kyhip_frame* f, const unsigned char* mask, size_t row_stride);
+int     kyhip_frame_retire_noisy(kyhip_frame* f, float threshold, float max_fraction_above, int min_batches, ky_block_stats* out);
+int     kyhip_frame_render_adaptive(kyhip_frame* f, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass,
+                                    int* samples_done, ky_block_stats* out);
+int     kyhip_frame_sample_map(kyhip_frame* f, int32_t* map, size_t row_stride_px);
+int     kyhip_frame_block_stats(kyhip_frame* f, ky_block_stats* out);
+int     kyhip_frame_blocks_ms(const kyhip_frame* f, float* retire_ms, float* list_ms);
+
+/*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent
  * kyhip_render* call on `device`, from hipEvents recorded on the launch stream around that one
  * kernel.  The stream must have been synchronised.  Negative if no timing is available.

@@ -77,6 +77,11 @@ class NoiseStats(C.Structure):   # ky_noise_stats
                 ("threshold", C.c_float), ("max", C.c_float), ("mean", C.c_double)]
 
 
+class BlockStats(C.Structure):   # ky_block_stats
+    _fields_ = [("blocks", C.c_int32), ("live", C.c_int32), ("passes", C.c_int32), ("samples_done", C.c_int32), ("min_samples", C.c_int32),
+                ("max_samples", C.c_int32), ("pixels", C.c_int64), ("pixel_samples", C.c_int64)]
+
+
 FP = C.POINTER(C.c_float)
 SP = C.POINTER(Scene)
 PP = C.POINTER(RenderParams)
@@ -139,6 +144,13 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_noise_stats": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(NoiseStats)]),
     "kyhip_frame_render_until": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(NoiseStats)]),
     "kyhip_frame_noise_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "kyhip_frame_track_blocks": (C.c_int, [C.c_void_p]),
+    "kyhip_frame_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_retire_noisy": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.POINTER(BlockStats)]),
+    "kyhip_frame_render_adaptive": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(BlockStats)]),
+    "kyhip_frame_sample_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_block_stats": (C.c_int, [C.c_void_p, C.POINTER(BlockStats)]),
+    "kyhip_frame_blocks_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -178,6 +190,8 @@ KYHOST_SYMBOLS = {
                                        C.c_void_p, C.c_void_p]),
     "kyhost_render_until": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                       C.c_float, C.c_float, C.c_int, C.c_int]),
+    "kyhost_render_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(BlockStats)]),
     "kyhost_store_image": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhost_gamma_encoding": (C.c_int, [C.c_float]),
 }
@@ -197,6 +211,8 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
     "kyhostcheck_frame": (C.c_int, [PP, C.c_int]),
     "kyhostcheck_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int]),
+    "kyhostcheck_blocks": (C.c_int, [PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int]),
     "kyhostcheck_add_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_seam_stress": (C.c_int, [C.c_int]),
     "kyhostcheck_jit_stress": (C.c_int, [C.c_int, C.c_int]),

@@ -113,15 +113,22 @@ def pass_boundaries(spp):
 class Frame:
     """A frame rendered in passes (kyhip_frame_*): `with Frame(scene, params) as f: f.render(64); preview = f.resolve(normalise=True); ...`.
     params.samples_per_pixel is the frame's total; a complete frame's resolve() is render(scene, params), bit for bit.
-    noise=True: the frame keeps a per-pixel noise estimate over its passes (kyhip_frame_track_noise): noise(), noise_stats(threshold), render_until(...)."""
+    noise=True: the frame keeps a per-pixel noise estimate over its passes (kyhip_frame_track_noise): noise(), noise_stats(threshold), render_until(...).
+    blocks=True: the frame retires 8 x 8 pixel blocks between its passes and renders the live ones only (kyhip_frame_track_blocks): keep(mask),
+    retire_noisy(...) and render_adaptive(...) (these two with noise=True), sample_map(), block_stats(); resolve(normalise=True) is then per block."""
 
-    def __init__(self, scene, params, device=0, noise=False):
+    def __init__(self, scene, params, device=0, noise=False, blocks=False):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
         _check(self._lib.kyhip_frame_begin(device, _scene_ptr(scene), C.byref(params), C.byref(self._f)), self._lib)
         if noise:
             rc = self._lib.kyhip_frame_track_noise(self._f)
+            if rc != A.KY_OK:
+                self.close()
+                _check(rc, self._lib)
+        if blocks:
+            rc = self._lib.kyhip_frame_track_blocks(self._f)
             if rc != A.KY_OK:
                 self.close()
                 _check(rc, self._lib)
@@ -199,6 +206,45 @@ class Frame:
         _check(self._lib.kyhip_frame_render_until(self._f, float(threshold), float(max_fraction_above), int(min_batches), int(min_samples_per_pass),
                                                   C.byref(done), C.byref(st)), self._lib)
         return done.value, st
+
+    def keep(self, mask):
+        """kyhip_frame_keep: retires every live block none of whose in-film pixels is set in the (H, W) mask (bool or uint8)."""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        assert m.shape == (self.height, self.width)
+        _check(self._lib.kyhip_frame_keep(self._f, C.c_void_p(m.ctypes.data), m.strides[0]), self._lib)
+
+    def retire_noisy(self, threshold, max_fraction_above=0.0, min_batches=2):
+        """kyhip_frame_retire_noisy: the retire rule applied once to the live blocks; returns the ky_block_stats (_abi.BlockStats) behind it."""
+        st = A.BlockStats()
+        _check(self._lib.kyhip_frame_retire_noisy(self._f, float(threshold), float(max_fraction_above), int(min_batches), C.byref(st)), self._lib)
+        return st
+
+    def render_adaptive(self, threshold, max_fraction_above=0.0, min_batches=2, min_samples_per_pass=1):
+        """Passes, each followed by the retire rule, until no block is live or the frame's front reaches the total: (the front, the block statistics)."""
+        done, st = C.c_int(0), A.BlockStats()
+        _check(self._lib.kyhip_frame_render_adaptive(self._f, float(threshold), float(max_fraction_above), int(min_batches), int(min_samples_per_pass),
+                                                     C.byref(done), C.byref(st)), self._lib)
+        return done.value, st
+
+    def sample_map(self, out=None):
+        """The (H, W) int32 map of the samples each pixel's block has received (kyhip_frame_sample_map); other shards' pixels keep `out`'s values (new: 0)."""
+        if out is None:
+            out = np.zeros((self.height, self.width), np.int32)
+        assert out.dtype == np.int32 and out.shape == (self.height, self.width) and out.strides[1] == 4 and out.strides[0] % 4 == 0
+        _check(self._lib.kyhip_frame_sample_map(self._f, C.c_void_p(out.ctypes.data), out.strides[0] // 4), self._lib)
+        return out
+
+    def blocks_ms(self):
+        """kyhip_frame_blocks_ms: (the last retire / keep kernel, the last compaction of the live list) in ms, negative where there was none."""
+        a, b = C.c_float(-1), C.c_float(-1)
+        _check(self._lib.kyhip_frame_blocks_ms(self._f, C.byref(a), C.byref(b)), self._lib)
+        return a.value, b.value
+
+    def block_stats(self):
+        """kyhip_frame_block_stats as a ky_block_stats (_abi.BlockStats)."""
+        st = A.BlockStats()
+        _check(self._lib.kyhip_frame_block_stats(self._f, C.byref(st)), self._lib)
+        return st
 
     def load(self, state):
         """Continue from a checkpoint of a frame begun with the same scene and params (kyhip_frame_load); any other state raises KyError."""
@@ -292,6 +338,25 @@ def render_until_host_api(scene, integrator_enum, depth, direct_sample, sampler,
     if rc < 0:
         raise KyError("kyhost_render_until failed: " + host.kyhost_last_error().decode())
     return film, rc
+
+
+def render_adaptive_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, threshold, max_fraction_above=0.0, min_batches=2,
+                             min_samples_per_pass=1, seed=1234, film=None, device=0):
+    """create_integrator(...)->render_adaptive(&scene, sampler, &film, threshold, max_fraction_above, min_batches, min_samples_per_pass, &counts) through the
+    C++ host classes: (the film with each block's mean added, the (H, W) int32 sample counts, the ky_block_stats)."""
+    host = A.load_kyhost()
+    if film is None:
+        film = np.zeros((height, width, 3), np.float32)
+    counts = np.zeros((height, width), np.int32)
+    st = A.BlockStats()
+    rc = host.kyhost_render_adaptive(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device,
+                                     float(threshold), float(max_fraction_above), int(min_batches), int(min_samples_per_pass), C.c_void_p(counts.ctypes.data),
+                                     C.byref(st))
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise KyError("kyhost_render_adaptive failed: " + host.kyhost_last_error().decode())
+    return film, counts, st
 
 
 def debug_area_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, begin, end, film=None, seed=1234, device=0):

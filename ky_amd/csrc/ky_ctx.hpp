@@ -130,6 +130,8 @@ struct FramePass {
     void* ws = nullptr;
     int kernel = -1;
     bool queue = false;
+    int n_live = -1;   // >= 0: a listed pass (a block-tracking frame, ky_blocks.hpp) over this many live blocks, whose ascending indices lie in `ws` behind the flag words
+                       // (blocks_list_offset); every pass of such a frame is listed, and the kernel its first pass took is a listed one
     std::string jit_expr, jit_desc;
 };
 // resolve_frame_kernel (ky_launch.hip) on `stream`: the frame's accumulators and flags, read and left as they are -> clamp01(value * scale) in the compact tile buffer

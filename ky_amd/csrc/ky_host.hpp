@@ -65,6 +65,8 @@ struct FrameHeader {
     int32_t samples_done, n_pix;
 };
 constexpr uint64_t KY_FRAME_MAGIC = 0x31454d4152464b59ull;   // "YKFRAME1"
+constexpr uint64_t KY_FRAME_BLOCKS_MAGIC = 0x314b4c4252464b59ull;   // "YKFRBLK1": a frame that retires pixel blocks (ky_blocks.hpp): its accumulators stand at per-block
+                                                                    // sample counts, which a frame that does not track blocks would resolve wrongly
 FrameHeader frame_header(const ky_render_params* p, uint64_t scene_hash, int samples_done);
 // KY_OK and the chunk count the state's samples_done stands for, or KY_ERR_INVALID_VALUE with the message: a short buffer, another frame's state, a
 // samples_done at which no chunk of the frame ends

@@ -12,6 +12,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include "ky_blocks.hpp"
 #include "ky_host.hpp"
 #include "ky_noise.hpp"
 
@@ -207,6 +208,47 @@ int kyhostcheck_noise(const long long* accum, const int* done, int n_pass, int n
     return noise_trailer_check(state, state_bytes, base_bytes, trailer_n_pix, samples_done, &t);
 }
 
+// The block arithmetic of a frame that retires pixel blocks (ky_blocks.hpp: what ky_blocks.hip's kernels do per block) for the shard of p.  Each part runs when its
+// pointers are given:
+//   out_block (n_pix), out_pixel (n_blocks x 64), out_inside (n_blocks): the pixel -> block map, its inverse, and each block's pixels inside the film;
+//   state (n_blocks x {retired_at, batches}, in and out) with map and cls (n_pix, compact tile order; cls NULL: derived from the film's edges, nothing flagged):
+//     blocks_init_kernel's rule when init != 0, then one application of the retire rule at `front` / `batches`;
+//   trailer: block_trailer_check of a checkpoint of trailer_bytes bytes whose block trailer begins at trailer_offset, for a frame at samples_done whose noise estimate has noise_batches batches (0: it tracks none).
+// Returns the trailer check's status (KY_OK without one), or KY_ERR_INVALID_VALUE for arguments that are none.
+int kyhostcheck_blocks(const ky_render_params* p, int* out_block, int* out_pixel, int* out_inside, int32_t* state, int init, const float* map, const unsigned char* cls,
+                       float threshold, float max_fraction_above, int min_batches, int front, int batches, const void* trailer, size_t trailer_bytes,
+                       size_t trailer_offset, int samples_done, int noise_batches) {
+    using namespace kyb;
+    if (!valid_params(p) || !shard_in_range(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    const ShardConst sh = make_shard(p);
+    for (int i = 0; i < sh.n_pix && out_block; ++i) out_block[i] = block_of_pixel(sh, i);
+    for (int b = 0; b < sh.n_blocks; ++b) {
+        int inside = 0;
+        for (int lane = 0; lane < KY_BLOCK_PIXELS; ++lane) {
+            const int i = pixel_of_block(sh, b, lane);
+            if (out_pixel) out_pixel[(size_t)b * KY_BLOCK_PIXELS + lane] = i;
+            inside += pixel_inside(sh, i, p->width, p->height);
+        }
+        if (out_inside) out_inside[b] = inside;
+        if (!state) continue;
+        BlockState s = {state[2 * b], state[2 * b + 1]};
+        if (init) s = inside > 0 ? BlockState{-1, 0} : BlockState{0, 0};
+        if (map && s.retired_at < 0) {
+            int counted = 0, above = 0;
+            for (int lane = 0; lane < KY_BLOCK_PIXELS; ++lane) {
+                const int i = pixel_of_block(sh, b, lane);
+                const int c = cls ? cls[i] : (pixel_inside(sh, i, p->width, p->height) ? kyn::KY_NOISE_INSIDE : kyn::KY_NOISE_PADDING);
+                counted += c == kyn::KY_NOISE_INSIDE;
+                above += c == kyn::KY_NOISE_INSIDE && map[i] > threshold;
+            }
+            if (block_retires(batches, min_batches, above, counted, max_fraction_above)) s = BlockState{front, batches};
+        }
+        state[2 * b] = s.retired_at; state[2 * b + 1] = s.batches;
+    }
+    if (!trailer) return KY_OK;
+    return block_trailer_check(trailer, trailer_bytes, trailer_offset, sh.n_blocks, p->samples_per_pixel, samples_done, noise_batches);
+}
+
 // ---- the entry points that need a GPU: absent from this build.  They exist as symbols because the host mirror (ky.hpp) and ctypes resolve every
 // symbol when a library is loaded; each validates what the product validates before it touches a device where a CPU test looks at that, and then
 // reports that there is no device -- exactly what libkyhip.so reports on a machine without a gfx950 GPU.
@@ -265,6 +307,28 @@ int kyhip_frame_render_until(kyhip_frame*, float threshold, float max_fraction_a
     return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
 }
 int kyhip_frame_noise_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+// (the block entries too)
+static int adaptive_args(float threshold, float max_fraction_above, int min_batches) {
+    if (!(threshold >= 0.f)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
+    if (!(max_fraction_above >= 0.f && max_fraction_above <= 1.f)) return fail(KY_ERR_INVALID_VALUE, "max_fraction_above %g: a fraction of the pixels, 0 .. 1", (double)max_fraction_above);
+    if (min_batches < 2) return fail(KY_ERR_INVALID_VALUE, "min_batches %d: the estimate needs two batches", min_batches);
+    return KY_OK;
+}
+int kyhip_frame_track_blocks(kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_keep(kyhip_frame*, const unsigned char* mask, size_t) { return fail(KY_ERR_INVALID_VALUE, mask ? "frame is NULL" : "mask is NULL"); }
+int kyhip_frame_retire_noisy(kyhip_frame*, float threshold, float max_fraction_above, int min_batches, ky_block_stats* out) {
+    const int rc = adaptive_args(threshold, max_fraction_above, min_batches);
+    return rc != KY_OK ? rc : fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+}
+int kyhip_frame_render_adaptive(kyhip_frame*, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass, int*, ky_block_stats* out) {
+    const int rc = adaptive_args(threshold, max_fraction_above, min_batches);
+    if (rc != KY_OK) return rc;
+    if (min_samples_per_pass < 1) return fail(KY_ERR_INVALID_VALUE, "min_samples_per_pass %d: a pass renders at least one sample per pixel", min_samples_per_pass);
+    return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+}
+int kyhip_frame_sample_map(kyhip_frame*, int32_t*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_block_stats(kyhip_frame*, ky_block_stats* out) { return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL"); }
+int kyhip_frame_blocks_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }
 int kyhip_smallpt_render(int, const ky_smallpt_sphere* spheres, int n, const ky_smallpt_params* p, double* image) {

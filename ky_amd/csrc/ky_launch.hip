@@ -289,11 +289,14 @@ struct Variant {
     bool large;
     RenderFn fn;
     int drop;   // light classes (kyhip_render_lighting): 0 the unmasked kernel, 1 / 2 / 3 these drop bits at compile time, -1 the launch's bits read at run time
+    bool listed;   // passes of a block-tracking frame (kyhip_frame_track_blocks): the work decoder reads the block from the frame's live list (ky_render.hpp, LISTED)
 };
 #define KY_VARIANT(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel<D, S, Q, G, F, I>, 0}
 #define KY_VARIANT_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel<D, S, Q, G, F, I, true>, 0}
 #define KY_VARIANT_MASKED(DROP, D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel_masked<DROP, D, S, Q, G, F, I>, DROP}
 #define KY_VARIANT_MASKED_LARGE(DROP, D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel_masked<DROP, D, S, Q, G, F, I, true>, DROP}
+#define KY_VARIANT_LISTED(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel_listed<D, S, Q, G, F, I>, 0, true}
+#define KY_VARIANT_LISTED_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel_listed<D, S, Q, G, F, I, true>, 0, true}
 // a row's three masked twins: emission at the first vertex dropped (lighting 2, 6), the k = 1 terms (5), both (4)
 #define KY_VARIANT_MASKED3(D, S, Q, G, F, I) KY_VARIANT_MASKED(1, D, S, Q, G, F, I), KY_VARIANT_MASKED(2, D, S, Q, G, F, I), KY_VARIANT_MASKED(3, D, S, Q, G, F, I)
 constexpr int IT = KY_INTEGRATOR_PATH_TRACING_ITERATION;
@@ -310,6 +313,7 @@ static const Variant g_variants[] = {
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV | KY_FEAT_SMALL_TABLES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT),
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV, IT),
     KY_VARIANT_MASKED(-1, false, -1, false, false, 0, IT),   // the one catch-all of masked launches (kyhip_render_lighting)
+    KY_VARIANT_LISTED(false, -1, false, false, 0, IT),       // ... and of listed passes (kyhip_frame_track_blocks)
     KY_VARIANT(false, -1, false, false, 0, IT),
 #else
     // the iterative integrator, both_mis: by scene facts
@@ -384,6 +388,19 @@ static const Variant g_variants[] = {
     KY_VARIANT_MASKED(-1, true, -1, false, true, 0, IT),
     KY_VARIANT_MASKED_LARGE(-1, false, -1, false, true, 0, IT),
     KY_VARIANT_MASKED_LARGE(-1, true, -1, false, true, 0, IT),
+    // listed passes (a block-tracking frame, kyhip_frame_track_blocks: EVERY pass of such a frame takes one of these rows, and no other launch does): the twins of
+    // the both_mis rows that have masked twins, then the run-time-dispatched kernels' twins for every other frame
+    KY_VARIANT_LISTED(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_CORNELL | KY_FEAT_SMALL_TABLES | KY_FEAT_BOXES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT),
+    KY_VARIANT_LISTED(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV | KY_FEAT_SMALL_TABLES | KY_FEAT_BOXES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT),
+    KY_VARIANT_LISTED(false, KY_DIRECT_BOTH_MIS, true, false, KY_FEAT_VEACH | KY_FEAT_FLAT_PHONG | KY_FEAT_X_PLANKS, IT),
+    KY_VARIANT_LISTED(false, KY_DIRECT_BOTH_MIS, true, false, 0, IT),
+    KY_VARIANT_LISTED(false, KY_DIRECT_BOTH_MIS, false, false, 0, IT),
+    KY_VARIANT_LISTED(false, -1, false, false, 0, IT),
+    KY_VARIANT_LISTED(true, -1, false, false, 0, IT),
+    KY_VARIANT_LISTED(false, -1, false, true, 0, IT),
+    KY_VARIANT_LISTED(true, -1, false, true, 0, IT),
+    KY_VARIANT_LISTED_LARGE(false, -1, false, true, 0, IT),
+    KY_VARIANT_LISTED_LARGE(true, -1, false, true, 0, IT),
     // everything else: strategy and integrator at run time; the debug sampler; scenes with general shapes
     KY_VARIANT(false, -1, false, false, 0, IT),
     KY_VARIANT(true, -1, false, false, 0, IT),
@@ -397,12 +414,12 @@ static const Variant g_variants[] = {
 constexpr int KY_N_VARIANTS = (int)(sizeof g_variants / sizeof g_variants[0]);
 static_assert(KY_N_VARIANTS <= KY_MAX_VARIANTS, "DeviceCtx::variant_blocks");
 
-static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0) {
+static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0, bool listed = false) {
     const bool dbg = p->sampler == KY_SAMPLER_DEBUG;
     const bool general = packed->general != 0;
     const bool large = packed->n_surfaces > KY_LDS_SURFACES || packed->n_materials > KY_LDS_MATERIALS;
     for (const Variant& v : g_variants) {
-        if (v.dbg != dbg || v.large != large) continue;
+        if (v.dbg != dbg || v.large != large || v.listed != listed) continue;
         if (v.drop != drop && !(v.drop < 0 && drop != 0)) continue;
         if (general && !v.general) continue;
         if (v.strategy >= 0) {
@@ -456,9 +473,16 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
 
     ShardConst sh = make_shard(p);
     if (sh.n_tiles == 0) return KY_OK;
+    int n_blocks_all = 0;                                   // (a listed pass) the frame's blocks, live or retired
+    const bool listed = pass && pass->n_live >= 0;
     if (pass) {   // the pass's chunks of every block; the chunk schedule, inv_spp and the film term limit below stay the whole frame's
         if (pass->chunk_first < 0 || pass->chunk_count < 1 || pass->chunk_first + pass->chunk_count > sh.n_chunks || !pass->ws) return fail(KY_ERR_DEVICE, "internal: bad pass");
         sh.chunk_first = pass->chunk_first;
+        if (pass->n_live >= 0) {   // a listed pass: the frame's live blocks, whose list lies behind the flag words of pass->ws (ky_render.hpp, LISTED)
+            if (pass->n_live < 1 || pass->n_live > sh.n_blocks || drop != 0) return fail(KY_ERR_DEVICE, "internal: bad listed pass");
+            n_blocks_all = sh.n_blocks;
+            sh.n_blocks = pass->n_live;
+        }
         sh.n_items = (unsigned)sh.n_blocks * (unsigned)pass->chunk_count;
     }
     const RenderConst rc = make_rc(p);
@@ -519,8 +543,9 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     } else {
         // (a frame keeps the kernel of its first pass: the table and run-time instantiations differ in the last bit)
         const bool pinned = pass && pass->kernel != -1;
-        const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop);
+        const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop, listed);
         if (!v) return fail(KY_ERR_DEVICE, "internal: no render kernel for these parameters");
+        if (pinned && pass->kernel >= 0 && v->listed != listed) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the block list");
         const int vi = (int)(v - g_variants);
         // run-time instantiation (kyhip_set_jit(1)): this launch's own kernel -- its sampler, strategy and integrator as compile-time constants and ALL
         // of the scene's facts -- unless the table's pick is exactly that already
@@ -556,12 +581,13 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
             const bool want_queue = (p->direct_sample == KY_DIRECT_BOTH_MIS || single || p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) &&
                                     p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && sh.n_pix < (1 << 26) && !general && shadow_queue_wanted(scene);
             const bool same = v->dbg == dbg && v->strategy == p->direct_sample && v->queue == want_queue && v->general == general && v->feat == feat &&
-                              v->integrator == p->integrator && v->large == large_scene && v->drop == drop;
+                              v->integrator == p->integrator && v->large == large_scene && v->drop == drop && v->listed == listed;
             if (!same) {
                 char expr[192];   // (an unmasked launch's key is what it was: the drop bits are named only where there are some)
                 int en = snprintf(expr, sizeof expr, "%s, %d, %s, %s, %d, %d, %s", dbg ? "true" : "false", p->direct_sample, want_queue ? "true" : "false",
                                   general ? "true" : "false", feat, p->integrator, large_scene ? "true" : "false");
                 if (drop != 0) snprintf(expr + en, sizeof expr - en, ", %d", drop);
+                else if (listed) snprintf(expr + en, sizeof expr - en, ", 0, true");   // (the form is part of the key: a listed pass never runs an unlisted kernel)
                 DeviceCtx::JitKernel& k = c->jit[expr];
                 if (!k.fn && !k.failed) {
                     // mode 1: blocks for the compile the first time (a few seconds), then memory / disk.  mode 2: a missing object is compiled by a background
@@ -670,6 +696,10 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         chunk_range(chunk_plan(rc.spp), pass->chunk_first + pass->chunk_count - 1, unused, s1);
         snprintf(note, sizeof note, ", pass: chunks %d..%d of %d, samples %d..%d of %d", pass->chunk_first, pass->chunk_first + pass->chunk_count - 1, sh.n_chunks, s0, s1, rc.spp);
         c->last_note += note;
+        if (listed) {
+            snprintf(note, sizeof note, ", blocks: %d of %d live", sh.n_blocks, n_blocks_all);
+            c->last_note += note;
+        }
         HIP_TRY(hipEventRecord(st->done, stream));
         sc->readers |= 1u << (unsigned)(st - c->ss);
         return KY_OK;
@@ -715,13 +745,14 @@ const char* kyhip_last_kernel(int device) {
     if (!c) return name.c_str();
     std::lock_guard<std::mutex> lock(c->m);
     if (c->last_variant == -2) name = "render_kernel_q (queue engine)";
-    else if (c->last_variant == -3) name = c->last_jit + " (run-time instantiation; template arguments: DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE)";
+    else if (c->last_variant == -3) name = c->last_jit + " (run-time instantiation; template arguments: DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE[, DROP[, LISTED]])";
     else if (c->last_variant >= 0) {
         const Variant& v = g_variants[c->last_variant];
         char buf[160];
         snprintf(buf, sizeof buf, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d>", v.dbg ? "debug sampler, " : "", v.strategy, v.queue ? ", deferred shadow rays" : "",
                  v.general ? ", general shapes" : "", v.large ? ", scene-sized LDS block" : "", v.feat, v.integrator);
         name = buf;
+        if (v.listed) name.insert(name.size() - 1, ", listed blocks");
         if (v.drop > 0) name.insert(name.size() - 1, ", drop " + std::to_string(v.drop));
         else if (v.drop < 0) name.insert(name.size() - 1, ", drop bits per launch");
     }

@@ -1,5 +1,6 @@
 /*
  * ky_noise.hip -- the kernels of a frame's per-pixel noise estimate (ky_noise.hpp; DESIGN.md "Noise"), film-sized and apart from the render kernels:
+ * (A frame that also retires pixel blocks, ky_blocks.hpp, hands the first two its per-block state: retired blocks keep the estimate they retired with.)
  *   noise_update_kernel   once per pass that rendered something, behind the pass's render kernel: one thread per pixel reads the three accumulators and
  *                         advances the pixel's {y_prev, m2} by the batch the pass added;
  *   noise_map_kernel      {y_prev, m2} and the flag word -> one float per pixel of the compact tile buffer and the pixel's class (inside the film, flagged,
@@ -11,16 +12,21 @@
  */
 #include <hip/hip_runtime.h>
 
+#include "ky_blocks.hpp"
 #include "ky_ctx.hpp"
 #include "ky_noise.hpp"
 
 using namespace kyn;
+using kyb::BlockState;
 
 static_assert(sizeof(NoisePixel) == 16 && sizeof(NoiseTrailer) == 16 && sizeof(NoiseSums) == 40, "the checkpoint trailer and the partials' layout");
 
-__global__ void noise_update_kernel(const unsigned long long* __restrict__ accum, NoisePixel* __restrict__ state, int n_pix, int total_spp, int n_prev, int n_now) {
+// (blocks: the per-block state of a frame that retires blocks, ky_blocks.hpp, or NULL.  A retired block's pixels are not rendered any more: their pair is frozen.)
+__global__ void noise_update_kernel(const unsigned long long* __restrict__ accum, NoisePixel* __restrict__ state, int n_pix, int total_spp, int n_prev, int n_now,
+                                    const BlockState* __restrict__ blocks, ShardConst sh) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pix) return;
+    if (blocks && blocks[kyb::block_of_pixel(sh, i)].retired_at >= 0) return;
     const double y = noise_luminance((long long)accum[3 * (size_t)i], (long long)accum[3 * (size_t)i + 1], (long long)accum[3 * (size_t)i + 2], total_spp);
     NoisePixel px = state[i];
     noise_update(px, y, n_prev, n_now);
@@ -28,9 +34,13 @@ __global__ void noise_update_kernel(const unsigned long long* __restrict__ accum
 }
 
 __global__ void noise_map_kernel(const unsigned* __restrict__ flags, const NoisePixel* __restrict__ state, float* __restrict__ map, unsigned char* __restrict__ cls,
-                                 ShardConst sh, int width, int height, int batches, int n_done) {
+                                 ShardConst sh, int width, int height, int batches, int n_done, const BlockState* __restrict__ blocks) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sh.n_pix) return;
+    if (blocks) {   // a retired block's pixels keep the value they had when it retired: its own batch and sample counts
+        const BlockState b = blocks[kyb::block_of_pixel(sh, i)];
+        if (b.retired_at >= 0) { batches = b.batches; n_done = b.retired_at; }
+    }
     int x, y;
     noise_pixel_xy(sh, i, x, y);
     const unsigned fl = flags[i];
@@ -82,19 +92,21 @@ __global__ __launch_bounds__(KY_NOISE_BLOCK) void noise_final_kernel(NoiseSums* 
 }
 
 namespace kyn {
-int noise_update_device(const void* ws, void* state, int n_pix, int total_spp, int n_prev, int n_now, void* stream) {
+int noise_update_device(const void* ws, void* state, const ShardConst& sh, int total_spp, int n_prev, int n_now, const void* blocks, void* stream) {
+    const int n_pix = sh.n_pix;
     if (n_pix <= 0) return KY_OK;
     hipLaunchKernelGGL(noise_update_kernel, dim3(noise_blocks(n_pix)), dim3(KY_NOISE_BLOCK), 0, (hipStream_t)stream, (const unsigned long long*)ws, (NoisePixel*)state, n_pix,
-                       total_spp, n_prev, n_now);
+                       total_spp, n_prev, n_now, (const BlockState*)blocks, sh);
     HIP_TRY(hipGetLastError());
     return KY_OK;
 }
 
-int noise_map_device(const void* ws, const void* state, float* map, unsigned char* cls, const ShardConst& sh, int width, int height, int batches, int n_done, void* stream) {
+int noise_map_device(const void* ws, const void* state, float* map, unsigned char* cls, const ShardConst& sh, int width, int height, int batches, int n_done,
+                     const void* blocks, void* stream) {
     if (sh.n_pix <= 0) return KY_OK;
     const unsigned* flags = (const unsigned*)((const unsigned long long*)ws + (size_t)sh.n_pix * 3);
     hipLaunchKernelGGL(noise_map_kernel, dim3(noise_blocks(sh.n_pix)), dim3(KY_NOISE_BLOCK), 0, (hipStream_t)stream, flags, (const NoisePixel*)state, map, cls, sh, width,
-                       height, batches, n_done);
+                       height, batches, n_done, (const BlockState*)blocks);
     HIP_TRY(hipGetLastError());
     return KY_OK;
 }

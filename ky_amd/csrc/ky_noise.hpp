@@ -106,8 +106,11 @@ inline size_t noise_trailer_bytes(int n_pix) { return sizeof(NoiseTrailer) + (si
 int noise_trailer_check(const void* buf, size_t bytes, size_t state_bytes, int n_pix, int samples_done, NoiseTrailer* out);
 
 // ---- the kernels (ky_noise.hip); every pointer is device memory, `stream` a hipStream_t ----
-int noise_update_device(const void* ws, void* state, int n_pix, int total_spp, int n_prev, int n_now, void* stream);
-int noise_map_device(const void* ws, const void* state, float* map, unsigned char* cls, const ShardConst& sh, int width, int height, int batches, int n_done, void* stream);
+// (blocks: NULL, or the kyb::BlockState of every block of a frame that retires blocks, ky_blocks.hpp: a retired block's pairs are frozen, and its pixels' map values
+// are taken at the block's own batch and sample counts)
+int noise_update_device(const void* ws, void* state, const ShardConst& sh, int total_spp, int n_prev, int n_now, const void* blocks, void* stream);
+int noise_map_device(const void* ws, const void* state, float* map, unsigned char* cls, const ShardConst& sh, int width, int height, int batches, int n_done,
+                     const void* blocks, void* stream);
 constexpr int KY_NOISE_BLOCK = 256;
 inline int noise_blocks(int n_pix) { return (n_pix + KY_NOISE_BLOCK - 1) / KY_NOISE_BLOCK; }
 // partials: noise_blocks(n_pix) + 1 NoiseSums; the result is the last one

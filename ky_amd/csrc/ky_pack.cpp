@@ -16,6 +16,7 @@
 #include <sched.h>
 #include <unistd.h>
 
+#include "ky_blocks.hpp"
 #include "ky_host.hpp"
 #include "ky_noise.hpp"
 
@@ -200,7 +201,10 @@ int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, int
     if (!buf || bytes < sizeof(FrameHeader)) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no header", bytes);
     FrameHeader theirs;
     std::memcpy(&theirs, buf, sizeof theirs);
-    if (theirs.magic != KY_FRAME_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: not a kyhip_frame_save buffer");
+    if (theirs.magic != KY_FRAME_MAGIC && theirs.magic != KY_FRAME_BLOCKS_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: not a kyhip_frame_save buffer");
+    if (theirs.magic != own.magic)
+        return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame that %s pixel blocks, this one %s (kyhip_frame_track_blocks)",
+                    theirs.magic == KY_FRAME_BLOCKS_MAGIC ? "retires" : "does not retire", own.magic == KY_FRAME_BLOCKS_MAGIC ? "does" : "does not");
     if (theirs.source_hash != own.source_hash) return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a library with other kernel sources (%016llx, this one %016llx)",
                                                           (unsigned long long)theirs.source_hash, (unsigned long long)own.source_hash);
     FrameHeader same = theirs;
@@ -223,6 +227,31 @@ int kyn::noise_trailer_check(const void* buf, size_t bytes, size_t state_bytes, 
     if (t.magic != KY_NOISE_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: no noise trailer behind the accumulators (saved by a frame that does not track noise?)");
     if (t.batches < 0 || t.n_prev != samples_done)
         return fail(KY_ERR_INVALID_VALUE, "frame state: the noise estimate stands at %d samples in %d batches, the accumulators at %d", t.n_prev, t.batches, samples_done);
+    if (out) *out = t;
+    return KY_OK;
+}
+// A block-tracking frame's state ends with a BlockTrailer and n_blocks BlockState (ky_blocks.hpp), at `offset`
+int kyb::block_trailer_check(const void* buf, size_t bytes, size_t offset, int n_blocks, int total_spp, int samples_done, int noise_batches, BlockTrailer* out) {
+    using kyh::fail;
+    if (!buf || bytes < offset || bytes - offset < block_trailer_bytes(n_blocks))
+        return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no block trailer (the state of this frame has %zu)", bytes, offset + block_trailer_bytes(n_blocks));
+    BlockTrailer t;
+    std::memcpy(&t, (const char*)buf + offset, sizeof t);
+    if (t.magic != KY_BLOCKS_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: no block trailer where this frame's state has one");
+    if (t.n_blocks != n_blocks) return fail(KY_ERR_INVALID_VALUE, "frame state: the block trailer counts %d blocks, the frame has %d", t.n_blocks, n_blocks);
+    if (t.passes < 0) return fail(KY_ERR_INVALID_VALUE, "frame state: the block trailer counts %d passes", t.passes);
+    const ChunkPlan plan = chunk_plan(total_spp);
+    for (int b = 0; b < n_blocks; ++b) {
+        BlockState s;
+        std::memcpy(&s, (const char*)buf + offset + sizeof t + (size_t)b * sizeof s, sizeof s);
+        // (a block's batch count is the frame's when it retired: at most the noise trailer's, and 0 where nothing was rendered yet and for a live block)
+        if (s.batches < 0 || s.batches > noise_batches || (s.retired_at <= 0 && s.batches != 0))
+            return fail(KY_ERR_INVALID_VALUE, "frame state: block %d (retired at %d) has %d batches, the noise estimate %d", b, s.retired_at, s.batches, noise_batches);
+        if (s.retired_at == -1) continue;
+        if (s.retired_at < 0 || s.retired_at > samples_done || chunks_at_sample(plan, s.retired_at) < 0)
+            return fail(KY_ERR_INVALID_VALUE, "frame state: block %d retired at %d samples: no pass of a %d-sample frame that stands at %d ends there", b, s.retired_at,
+                        total_spp, samples_done);
+    }
     if (out) *out = t;
     return KY_OK;
 }

@@ -73,9 +73,12 @@ struct ItemSlot {  // one fetched work item, decoded once (wave-uniform) and rea
 // KY_LDS_MATERIALS materials; ky_device.hpp, LdsScene).
 // DROP: the light classes a masked render leaves out (path_intersect, ky_device.hpp): 0 nothing -- every instantiation that does not name it --, 1 / 2 / 3 the bits at
 // compile time (the table's masked rows, every run-time instantiation), -1 the bits are read from word 2 of the launch's work-counter block.
+// LISTED: a pass of a frame that retires pixel blocks (kyhip_frame_track_blocks; DESIGN.md "Adaptive"): sh.n_blocks counts the frame's LIVE blocks and item id is
+// chunk id / n_live + chunk_first of block list[id % n_live], `list` the ascending live block indices behind the flag words of the frame's accumulator block
+// (flags + sh.n_pix).  One wave-uniform (scalar) load per fetched item; false -- every instantiation that does not name it -- decodes the block from the id alone.
 // resident wavefronts per SIMD an instantiation is compiled for (its register budget): measured per family, see the KY_WAVES_PER_EU_* notes above
-// (a masked instantiation starts from its twin's: it is the twin with a term less)
-template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE, int DROP = 0>
+// (a masked instantiation starts from its twin's: it is the twin with a term less; a listed one is compiled for its twin's: it is the twin with one load more per item)
+template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE, int DROP = 0, bool LISTED = false>
 constexpr int ky_waves_per_eu() {
     return STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS ? KY_WAVES_PER_EU_SINGLE :
            STRATEGY >= 0 ? (QUEUE ? (FEAT ? KY_WAVES_PER_EU_QUEUE_FEAT : KY_WAVES_PER_EU_QUEUE)
@@ -86,7 +89,7 @@ constexpr int ky_waves_per_eu() {
 
 // The kernel's body is a device function so that two kinds of __global__ entry can wrap it: the template render_kernel below (the library's table
 // of instantiations) and the extern "C" kernel of a run-time instantiation (ky_jit.cpp).
-template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0>
+template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false>
 KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
                                unsigned* __restrict__ flags, float4* __restrict__ queue_mem) {
     static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
@@ -196,7 +199,13 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                 if (fetched > 0 && lane == 0) id = atomicAdd(counter, 1u) + gridDim.x * 4u;
                 id = __builtin_amdgcn_readfirstlane(id);
                 if (id >= sh.n_items) { exhausted = true; break; }
-                const int c = (int)(id / (unsigned)sh.n_blocks) + sh.chunk_first, b = (int)(id % (unsigned)sh.n_blocks);   // chunk-major; a pass of a frame starts at chunk_first
+                const int c = (int)(id / (unsigned)sh.n_blocks) + sh.chunk_first;   // chunk-major; a pass of a frame starts at chunk_first
+                int b = (int)(id % (unsigned)sh.n_blocks);
+                if constexpr (LISTED) {   // the b-th live block of the frame.  The list is constant for the launch and b is wave-uniform: read through the constant address
+                    // space it is a scalar load, which waits for no vector memory operation (a vector load would sit out the atomic adds of the flush just before it)
+                    typedef const int __attribute__((address_space(4))) * LiveList;
+                    b = __builtin_amdgcn_readfirstlane(((LiveList)(const int*)(flags + sh.n_pix))[b]);
+                }
                 const int k = b / sh.blocks_per_tile, inner = b % sh.blocks_per_tile;
                 const int bx = inner % sh.blocks_w, by = inner / sh.blocks_w;
                 const int tile = sh.tile_first + k * sh.tile_step;
@@ -304,4 +313,12 @@ __global__ __launch_bounds__(256, (ky_waves_per_eu<DEBUG_SAMPLER, STRATEGY, QUEU
     float4* __restrict__ queue_mem) {
     static_assert(DROP != 0, "nothing dropped: render_kernel");
     render_kernel_body<DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, DROP>(S_, rc, sh, counter, accum, flags, queue_mem);
+}
+
+// The listed instantiations (passes of a block-tracking frame): a kernel template of their own too.
+template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false>
+__global__ __launch_bounds__(256, (ky_waves_per_eu<DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, 0, true>())) void render_kernel_listed(
+    const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
+    float4* __restrict__ queue_mem) {
+    render_kernel_body<DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, 0, true>(S_, rc, sh, counter, accum, flags, queue_mem);
 }

@@ -743,6 +743,36 @@ public:
         kyhip_frame_end(frame);
         return done;
     }
+    // render_until per 8 x 8 pixel block (kyhip_frame_track_blocks ..., include/kyhip.h): after every pass the blocks at most max_fraction_above of whose pixels lie
+    // above `threshold` (after min_batches passes or more) retire and are rendered no further; the passes go on over the others until none is left or the frame
+    // is complete.  ADDS per pixel the mean of the samples its block received (normalise 1) and returns the block statistics; sample_counts, when given,
+    // receives width x height counts, y down: the samples each pixel's block received.  A block that stops on its own samples' estimate is biased towards the
+    // value it had when it looked clean.
+    ky_block_stats render_adaptive(scene_t* scene, sampler_t* original_sampler, film_t* film, float threshold, float max_fraction_above, int min_batches,
+                                   int min_samples_per_pass, std::vector<int32_t>* sample_counts = nullptr) {
+        if (masked()) throw std::runtime_error("integrator_t::render_adaptive: light classes are rendered by render() only");
+        const ky_render_params p = params_for(original_sampler, film);
+        kyhip_frame* frame = nullptr;
+        if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        ky_block_stats st{};
+        try {
+            int done = 0;
+            if (kyhip_frame_track_noise(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_noise: ") + kyhip_last_error());
+            if (kyhip_frame_track_blocks(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_blocks: ") + kyhip_last_error());
+            if (kyhip_frame_render_adaptive(frame, threshold, max_fraction_above, min_batches, min_samples_per_pass, &done, &st) != KY_OK)
+                throw std::runtime_error(std::string("kyhip_frame_render_adaptive: ") + kyhip_last_error());
+            if (kyhip_frame_resolve(frame, 1, film->target_origin(), film->row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+            if (sample_counts) {
+                sample_counts->assign((size_t)p.width * (size_t)p.height, 0);
+                if (kyhip_frame_sample_map(frame, sample_counts->data(), (size_t)p.width) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_sample_map: ") + kyhip_last_error());
+            }
+        } catch (...) {
+            kyhip_frame_end(frame);
+            throw;
+        }
+        kyhip_frame_end(frame);
+        return st;
+    }
     // integrator_t::debug_area / debug_pixel (ky.cpp:3733-3787), the reference's single-pixel replay: a red frame is ADDED around
     // [begin, end) (color_t{1.f} = (1, 0, 0) on the pixels of [begin - 1, end], 3739-3746), then every pixel of the area is cleared and
     // rendered again on its own (3756-3776): the caller's sampler, the samples summed one after the other in float, one clamp, add_color.

@@ -164,6 +164,38 @@ int kyhost_render_until(void* scene, int integrator_enum, int depth, int direct_
     return rc != 0 ? rc : status;
 }
 
+// create_integrator(...)->render_adaptive(&scene, sampler, &film, threshold, max_fraction_above, min_batches, min_samples_per_pass, &counts) on a film_t of width x
+// height.  `film` is read, added to and written back; sample_counts (may be NULL) receives width x height int32; *stats (may be NULL) the block statistics.
+// Returns 0, -1 on error, -2 when create_integrator returns nullptr.
+int kyhost_render_adaptive(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
+                           float* film, int device, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass, int32_t* sample_counts,
+                           ky_block_stats* stats) {
+    int status = 0;
+    int rc = guarded([&] {
+        std::unique_ptr<ky::integrator_t> integrator;
+        const auto ie = (ky::integrator_enum_t)integrator_enum;
+        if (ie == ky::integrator_enum_t::position || ie == ky::integrator_enum_t::normal || ie == ky::integrator_enum_t::basecolor)
+            integrator = std::make_unique<ky::debug_integrator_t>(ie, device);
+        else
+            integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
+        if (!integrator) { status = -2; return; }
+        std::unique_ptr<ky::sampler_t> sampler;
+        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
+        else sampler = std::make_unique<ky::random_sampler_t>(spp);
+        sampler->set_seed(seed);
+        ky::film_t f(width, height);
+        const size_t n = (size_t)f.get_pixel_num() * 3;
+        std::memcpy(f.data(), film, n * sizeof(float));
+        std::vector<int32_t> counts;
+        const ky_block_stats st = integrator->render_adaptive(&((scene_box*)scene)->scene, sampler.get(), &f, threshold, max_fraction_above, min_batches,
+                                                              min_samples_per_pass, sample_counts ? &counts : nullptr);
+        if (stats) *stats = st;
+        if (sample_counts) std::memcpy(sample_counts, counts.data(), counts.size() * sizeof(int32_t));
+        std::memcpy(film, f.data(), n * sizeof(float));
+    });
+    return rc != 0 ? rc : status;
+}
+
 // create_integrator(...)->debug_area(&scene, sampler, &film, {bx, by}, {ex, ey}) on a film_t of width x height (ky.cpp:3733-3777);
 // `film` is read, modified and written back.  Returns 0, -1 on error, -2 when create_integrator returns nullptr.
 int kyhost_debug_area(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed,
