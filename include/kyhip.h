@@ -204,6 +204,11 @@ int         kyhip_set_specialisation(int on);
    (tests/test_boxes.py: by how much).  on = 1 (default; environment variable KYHIP_BOXES=0 turns it off) / off = 0; needs kyhip_set_specialisation(1).  Returns the
    previous setting.  A tuning knob. */
 int         kyhip_set_boxes(int on);
+/* The screen cull: when a scene is packed the library projects the world bound of its surfaces through the scene's camera and keeps the pixel
+   rectangle around it (kyhip_scene_screen_bound); the lane engine's render kernels take no work for an 8 x 8 pixel block outside it -- every camera ray of such a
+   block misses every surface, and without an environment light a miss adds nothing.  The image does not depend on it, to the bit.  on = 1 (default; environment
+   variable KYHIP_SCREEN_CULL=0 turns it off) / off = 0: the rectangle is the whole frame; -1 (any other value) only queries.  Returns the previous setting.  A tuning knob. */
+int         kyhip_set_screen_cull(int on);
 /* Deferred shadow rays (the render kernels' QUEUE instantiations: light samples wait on a per-wavefront stack until 64 of them fill a traversal).
    mode -1 (default): by the scene -- when its sphere area lights outnumber its point / directional lights by five or more (create_mis_scene's five
    lamps; measured crossing, tools/queue_policy.py); 0: never; 1: for every scene with lights.  The environment variable KYHIP_SHADOW_QUEUE = 0 / 1 sets the
@@ -539,6 +544,12 @@ int kyhip_scene_non_occluders(const ky_scene* scene, int light, int* left_out, i
    plane) when surface i (the caller's index) is such a face, -1 otherwise.  n = entries in box_face, at least scene->surface_count.  Returns the number of boxes
    (0 with kyhip_set_specialisation(0)), or a negative ky_status. */
 int kyhip_scene_boxes(const ky_scene* scene, int* box_face, int n);
+/* Host only (no GPU needed): the scene's live rectangle for the frame of `params` -- rect = {x0, y0, x1, y1}: no camera sample of a pixel outside
+   [x0, x1) x [y0, y1) reaches a surface, so the film is exactly 0 there.  The whole frame {0, 0, width, height} when that cannot be proved (an environment light, a
+   camera inside or beside the scene's bound, coordinates that are not finite, no surfaces) and with kyhip_set_screen_cull(0).  counts (may be NULL): counts[0] = the
+   8 x 8 pixel blocks of the shard `params` names that lie outside the rectangle (the work the render kernels skip), counts[1] = all of the shard's blocks.
+   Returns KY_OK or a negative ky_status. */
+int kyhip_scene_screen_bound(const ky_scene* scene, const ky_render_params* params, int rect[4], long long counts[2]);
 /* Host only: the facts the library finds for a scene when it packs it -- a mask of the KY_FEAT_* values of ky_amd/csrc/ky_scene.hpp (1 exactly one area light, 2 every
    area light samples a rectangle, 4 few carrier surfaces per light, 8 exactly one point / directional light, 16 exactly one environment light, 32 sphere lamps only,
    64 no mirror or glass, 128 at most 16 surfaces and 8 materials, 256 every lamp is its own one carrier, 512 boxes, 1024 every planar surface is a rectangle in an axis

@@ -105,6 +105,7 @@ KYHIP_SYMBOLS = {
     "kyhip_set_engine": (C.c_int, [C.c_int]),
     "kyhip_set_specialisation": (C.c_int, [C.c_int]),
     "kyhip_set_boxes": (C.c_int, [C.c_int]),
+    "kyhip_set_screen_cull": (C.c_int, [C.c_int]),
     "kyhip_set_shadow_queue": (C.c_int, [C.c_int]),
     "kyhip_set_jit": (C.c_int, [C.c_int]),
     "kyhip_jit_status": (C.c_char_p, []),
@@ -170,6 +171,7 @@ KYHIP_SYMBOLS = {
     "kyhip_kat_occluded_between": (C.c_int, [C.c_int, SP, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_scene_non_occluders": (C.c_int, [SP, C.c_int, C.c_void_p, C.c_int]),
     "kyhip_scene_boxes": (C.c_int, [SP, C.c_void_p, C.c_int]),
+    "kyhip_scene_screen_bound": (C.c_int, [SP, PP, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "kyhip_scene_facts": (C.c_int, [SP]),
     "kyhip_kat_li": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }

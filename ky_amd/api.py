@@ -475,6 +475,16 @@ def scene_boxes(scene):
     return rc, out[:n].copy()
 
 
+def scene_screen_bound(scene, params):
+    """kyhip_scene_screen_bound (host only): ((x0, y0, x1, y1), dead, total) -- the scene's live rectangle in the frame of `params` (no camera ray of a pixel outside it
+    reaches a surface), and the 8 x 8 blocks of the params' shard outside it / in all."""
+    lib = A.load_kyhip()
+    rect = (C.c_int * 4)()
+    counts = (C.c_longlong * 2)()
+    _check(lib.kyhip_scene_screen_bound(_scene_ptr(scene), C.byref(params), rect, counts))
+    return tuple(int(v) for v in rect), int(counts[0]), int(counts[1])
+
+
 def kat_li(scene, params, x, y, s0, n, device=0):
     lib = A.load_kyhip()
     out = np.zeros((n, 3), np.float32)

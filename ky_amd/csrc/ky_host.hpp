@@ -94,6 +94,10 @@ struct Boxes {
     std::vector<int> box_of;                            // [surface] -> box, -1: none
 };
 void find_boxes(const ky_scene* in, Boxes& B);
+// The live rectangle of a scene (DScene::live; ky_pack.cpp states the proof): live[0..3] = x0, y0, x1, y1, the whole range when the proof does not hold
+void screen_bound(const ky_scene* in, int32_t live[4]);
+// ... and for a launch's tiling: the 8 x 8 blocks of the shard that lie outside it (the work items a render kernel skips per chunk), and all of them
+void screen_bound_counts(const int32_t live[4], const ky_render_params* p, long long* dead, long long* total);
 int pack_scene(const ky_scene* in, DScene* out);
 uint64_t scene_hash(const DScene& s);
 bool scene_input(const ky_scene* in, std::vector<unsigned char>& out, uint64_t& hash);
@@ -105,6 +109,7 @@ int smallpt_check(const ky_smallpt_sphere* spheres, int n, const ky_smallpt_para
 // ---- launch policies (each has an environment variable and a kyhip_set_* entry) ----
 bool specialisation_enabled();
 bool boxes_enabled();
+bool screen_cull_enabled();
 int shadow_queue_mode();
 bool shadow_queue_wanted(const ky_scene* scene);
 int blocks_per_cu_cap();

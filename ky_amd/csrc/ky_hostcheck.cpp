@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <thread>
 #include <sys/wait.h>
@@ -247,6 +248,87 @@ int kyhostcheck_blocks(const ky_render_params* p, int* out_block, int* out_pixel
     }
     if (!trailer) return KY_OK;
     return block_trailer_check(trailer, trailer_bytes, trailer_offset, sh.n_blocks, p->samples_per_pixel, samples_done, noise_batches);
+}
+
+// The live rectangle (screen_bound, kyhip_scene_screen_bound) on degenerate inputs: a unit box of five matte rectangles (open towards -z) or one sphere, seen by a
+// camera that looks along +z.  Whatever the proof cannot cover must give the whole frame: the camera on the bound's face, inside the bound, a NaN vertex, no surfaces.
+// A sphere of radius zero is a bound that is a point: a rectangle of a few pixels.  Returns 0, or the number of the case that went wrong.
+int kyhostcheck_screen_bound(void) {
+    const float q = std::numeric_limits<float>::quiet_NaN();
+    auto rect_shape = [](const float (&p)[4][3], float nx, float ny, float nz) {
+        ky_shape s{};
+        s.kind = KY_SHAPE_RECTANGLE;
+        std::memcpy(s.p, p, sizeof s.p);
+        s.normal[0] = nx; s.normal[1] = ny; s.normal[2] = nz;
+        return s;
+    };
+    const float back[4][3] = {{-1, -1, 1}, {1, -1, 1}, {1, 1, 1}, {-1, 1, 1}}, floor_[4][3] = {{-1, -1, -1}, {1, -1, -1}, {1, -1, 1}, {-1, -1, 1}},
+                ceil_[4][3] = {{-1, 1, -1}, {1, 1, -1}, {1, 1, 1}, {-1, 1, 1}}, left[4][3] = {{-1, -1, -1}, {-1, -1, 1}, {-1, 1, 1}, {-1, 1, -1}},
+                right[4][3] = {{1, -1, -1}, {1, -1, 1}, {1, 1, 1}, {1, 1, -1}};
+    std::vector<ky_shape> box = {rect_shape(back, 0, 0, -1), rect_shape(floor_, 0, 1, 0), rect_shape(ceil_, 0, -1, 0), rect_shape(left, 1, 0, 0), rect_shape(right, -1, 0, 0)};
+    ky_material matte{};
+    matte.kind = KY_MATERIAL_MATTE; matte.color0[0] = matte.color0[1] = matte.color0[2] = 0.5f;
+    ky_light lamp{};
+    lamp.kind = KY_LIGHT_POINT; lamp.color[0] = lamp.color[1] = lamp.color[2] = 1.f;
+    std::vector<ky_surface> surf;
+    for (int i = 0; i < 5; ++i) surf.push_back(ky_surface{i, 0, -1});
+    ky_render_params p{};
+    p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS; p.samples_per_pixel = 4; p.sampler = KY_SAMPLER_RANDOM;
+    p.width = 256; p.height = 64; p.tile_w = 32; p.tile_h = 32; p.tile_first = 0; p.tile_step = 1;
+    auto scene_at = [&](const std::vector<ky_shape>& shapes, int n_surfaces, float cz) {
+        ky_scene s{};
+        s.shapes = shapes.data(); s.shape_count = (int)shapes.size();
+        s.materials = &matte; s.material_count = 1;
+        s.lights = &lamp; s.light_count = 1;
+        s.surfaces = surf.data(); s.surface_count = n_surfaces;
+        s.environment_light = -1;
+        s.camera.position[2] = cz; s.camera.front[2] = 1.f; s.camera.right[0] = 2.f; s.camera.up[1] = 0.5f;   // a 4 : 1 frame, half a unit high at unit depth
+        s.camera.resolution[0] = 256.f; s.camera.resolution[1] = 64.f;
+        return s;
+    };
+    auto whole = [&](const ky_scene& s) {
+        int r[4] = {-1, -1, -1, -1};
+        long long c[2] = {-1, -1};
+        return kyhip_scene_screen_bound(&s, &p, r, c) == KY_OK && r[0] == 0 && r[1] == 0 && r[2] == p.width && r[3] == p.height && c[0] == 0 && c[1] == 8 * 32;
+    };
+    {   // the box from far in front: columns around the middle, every row, and dead blocks on both sides
+        const ky_scene s = scene_at(box, 5, -5.f);
+        int r[4];
+        long long c[2];
+        if (kyhip_scene_screen_bound(&s, &p, r, c) != KY_OK || !(r[0] > 8 && r[2] < p.width - 8 && r[0] < 128 && r[2] > 128 && r[1] == 0 && r[3] == p.height && c[0] > 0 && c[0] < c[1])) return 1;
+    }
+    if (!whole(scene_at(box, 5, -1.f))) return 2;        // the camera on the bound's open face
+    if (!whole(scene_at(box, 5, 0.f))) return 3;         // ... inside the bound
+    if (!whole(scene_at(box, 0, -5.f))) return 4;        // no surfaces
+    {
+        std::vector<ky_shape> bad = box;
+        bad[2].p[1][0] = q;                               // a NaN vertex
+        if (!whole(scene_at(bad, 5, -5.f))) return 5;
+        bad = box;
+        bad[0].p[3][2] = std::numeric_limits<float>::infinity();
+        if (!whole(scene_at(bad, 5, -5.f))) return 6;
+    }
+    {   // a sphere of radius zero at the origin: a point, a few pixels around the frame's centre
+        ky_shape sp{};
+        sp.kind = KY_SHAPE_SPHERE; sp.radius = 0.f;
+        std::vector<ky_shape> one = {sp};
+        const ky_scene s = scene_at(one, 1, -5.f);
+        int r[4];
+        if (kyhip_scene_screen_bound(&s, &p, r, nullptr) != KY_OK || !(r[0] >= 125 && r[0] <= 127 && r[2] >= 129 && r[2] <= 131 && r[1] >= 29 && r[3] <= 35)) return 7;
+        one[0].radius = q;
+        if (!whole(scene_at(one, 1, -5.f))) return 8;
+    }
+    {   // the switch, and a NULL scene through the internal entry
+        const ky_scene s = scene_at(box, 5, -5.f);
+        const int prev = kyhip_set_screen_cull(0);
+        const bool off = whole(s);
+        kyhip_set_screen_cull(prev);
+        if (!off || kyhip_set_screen_cull(-1) != prev) return 9;
+        int32_t live[4];
+        screen_bound(nullptr, live);
+        if (live[0] != 0 || live[2] != KY_LIVE_MAX) return 10;
+    }
+    return 0;
 }
 
 // ---- the entry points that need a GPU: absent from this build.  They exist as symbols because the host mirror (ky.hpp) and ctypes resolve every

@@ -660,6 +660,127 @@ bool boxes_enabled() {
     return g_boxes != 0;
 }
 
+// The screen cull (screen_bound below) can be switched off: KYHIP_SCREEN_CULL=0 or kyhip_set_screen_cull(0); the packed scene then carries the whole range.  The image
+// does not depend on it (tests/test_screen_cull_gpu.py); the switch exists for that test and for A/B measurements.
+static int g_screen_cull = -1;
+bool screen_cull_enabled() {
+    if (g_screen_cull < 0) {
+        const char* e = std::getenv("KYHIP_SCREEN_CULL");
+        g_screen_cull = (e && std::atoi(e) == 0) ? 0 : 1;
+    }
+    return g_screen_cull != 0;
+}
+
+// Which pixels' camera rays can reach the scene at all (DScene::live): the pixel rectangle [x0, x1) x [y0, y1) around the projection of the surfaces' world bound.
+//
+// The bound B is the axis-aligned box of every surface -- rectangles and general quads by their four corners, triangles by their three (each is the convex hull of
+// its corners), spheres and disks by their sphere (shape_extent does the same) --, grown on every side by 1e-3 of its diagonal (and by 1e-6 of its largest
+// coordinate, for a bound that is a point).  generate_ray (ky.cpp:1884-1892) sends the sample (px, py) along  d = front + sx right + sy up  with
+// sx = px / w - 0.5, sy = 0.5 - py / h  from the camera's position c.  Write a point v - c in the basis (front, right, up): v - c = a front + b right + g up.  The
+// ray of (sx, sy) is the set {t (1, sx, sy), t > 0} in these coordinates, so it passes through v exactly when a > 0, sx = b / a and sy = g / a.  When all eight
+// corners of B have a > 0, every point of B has (a is linear), and on the half-space a > 0 the map (a, b, g) -> (b / a, g / a) is projective: it maps the convex
+// B onto the convex hull of its corners' images.  In exact arithmetic a ray whose (sx, sy) lies outside the axis rectangle of those eight images therefore has no
+// point in B, and so none on a surface.
+// What is not exact: the device forms px = x + u (u < 1, which may round up to x + 1), sx and d in fp32 -- errors of a few 1e-7 of the frame, below 0.01 pixel at
+// the largest width --, and its hit tests accept points within a few ulp of a shape's edge, 1e-6 of the scene's size.  The rectangle is widened by a WHOLE pixel
+// on every side beyond the pixels the exact projection touches (floor - 1, ceil + 1) and B by 1e-3 of its diagonal: three and more orders of magnitude above
+// either error.  Everything here is computed in double from the caller's floats.
+// The whole range is stored -- nothing is culled -- when the proof does not hold:
+//   * the scene has an environment light: a miss adds its radiance (environment_lighting, 3231);
+//   * a corner's depth a is not safely positive (the camera inside or beside B: below 1e-3 of the diagonal in front of it), or the camera's basis is singular --
+//     unless EVERY corner lies safely behind the camera (a < 0 on all of B while a > 0 along every ray): then no ray reaches B and the rectangle is empty;
+//   * a coordinate, the camera or a projected corner is not finite; a shape's kind is unknown (pack_scene refuses the scene);
+//   * there are no surfaces (nothing to bound; such a frame is black however it is rendered).
+// The pixel -> direction map uses the camera's own resolution (cam_inv_w, cam_inv_h), not the launch's: the rectangle is a fact of the scene, in the pixel units of
+// its camera, and clamped to the range of pixels a launch can have rather than to that resolution (a launch wider than its camera's resolution is legal, and its
+// outer pixels see what their rays see).
+void screen_bound(const ky_scene* in, int32_t live[4]) {
+    live[0] = live[1] = 0; live[2] = live[3] = KY_LIVE_MAX;
+    if (!in || !screen_cull_enabled() || in->environment_light >= 0 || in->surface_count <= 0 || !in->surfaces || !in->shapes) return;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    bool first = true;
+    auto add = [&](double x, double y, double z) {
+        const double v[3] = {x, y, z};
+        for (int k = 0; k < 3; ++k) { lo[k] = first ? v[k] : std::min(lo[k], v[k]); hi[k] = first ? v[k] : std::max(hi[k], v[k]); }
+        first = false;
+    };
+    for (int i = 0; i < in->surface_count; ++i) {
+        const int si = in->surfaces[i].shape;
+        if (si < 0 || si >= in->shape_count) return;
+        const ky_shape& sh = in->shapes[si];
+        if (sh.kind == KY_SHAPE_SPHERE || sh.kind == KY_SHAPE_DISK) {
+            const double r = std::fabs((double)sh.radius);
+            if (!std::isfinite(r) || !std::isfinite(sh.p[0][0]) || !std::isfinite(sh.p[0][1]) || !std::isfinite(sh.p[0][2])) return;
+            add(sh.p[0][0] - r, sh.p[0][1] - r, sh.p[0][2] - r);
+            add(sh.p[0][0] + r, sh.p[0][1] + r, sh.p[0][2] + r);
+        } else if (sh.kind == KY_SHAPE_TRIANGLE || sh.kind == KY_SHAPE_RECTANGLE) {
+            const int np = sh.kind == KY_SHAPE_TRIANGLE ? 3 : 4;
+            for (int q = 0; q < np; ++q) {
+                if (!std::isfinite(sh.p[q][0]) || !std::isfinite(sh.p[q][1]) || !std::isfinite(sh.p[q][2])) return;   // (min / max would drop a NaN silently)
+                add(sh.p[q][0], sh.p[q][1], sh.p[q][2]);
+            }
+        } else {
+            return;
+        }
+    }
+    const ky_camera& cam = in->camera;
+    double f[3], r[3], u[3], c[3];
+    for (int k = 0; k < 3; ++k) {
+        f[k] = cam.front[k]; r[k] = cam.right[k]; u[k] = cam.up[k]; c[k] = cam.position[k];
+        if (!std::isfinite(f[k]) || !std::isfinite(r[k]) || !std::isfinite(u[k]) || !std::isfinite(c[k])) return;
+    }
+    const double w = cam.resolution[0], h = cam.resolution[1];
+    if (!std::isfinite(w) || !std::isfinite(h) || !(w > 0) || !(h > 0)) return;
+    double diag = 0, size = 0;
+    for (int k = 0; k < 3; ++k) { diag += (hi[k] - lo[k]) * (hi[k] - lo[k]); size = std::max(size, std::max(std::fabs(lo[k]), std::fabs(hi[k]))); }
+    diag = std::sqrt(diag);
+    const double grow = std::max(1e-3 * diag, 1e-6 * size);
+    if (!std::isfinite(diag) || !std::isfinite(grow)) return;
+    // the dual basis of (front, right, up): a = (v - c) . f*, b = (v - c) . r*, g = (v - c) . u*  (for the reference's orthogonal cameras f* = f / |f|^2, and so on)
+    auto cross3 = [](const double* x, const double* y, double* o) { o[0] = x[1] * y[2] - x[2] * y[1]; o[1] = x[2] * y[0] - x[0] * y[2]; o[2] = x[0] * y[1] - x[1] * y[0]; };
+    auto dot3 = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
+    double fs[3], rs[3], us[3];
+    cross3(r, u, fs); cross3(u, f, rs); cross3(f, r, us);
+    const double det = dot3(f, fs), lf = std::sqrt(dot3(f, f)), lr = std::sqrt(dot3(r, r)), lu = std::sqrt(dot3(u, u));
+    if (!std::isfinite(det) || !(std::fabs(det) > 1e-9 * lf * lr * lu) || !(lf > 0)) return;
+    double X0 = 0, X1 = 0, Y0 = 0, Y1 = 0;
+    int in_front = 0, behind = 0;
+    for (int corner = 0; corner < 8; ++corner) {
+        double v[3];
+        for (int k = 0; k < 3; ++k) v[k] = (((corner >> k) & 1) ? hi[k] + grow : lo[k] - grow) - c[k];
+        const double a = dot3(v, fs) / det, b = dot3(v, rs) / det, g = dot3(v, us) / det;
+        const double depth = a * lf, margin = std::max(grow, 1e-3 * diag);   // along front, in world units
+        if (!std::isfinite(depth)) return;
+        if (depth < -margin) { ++behind; continue; }
+        if (!(depth > margin)) return;   // not safely in front of the camera, nor safely behind it
+        ++in_front;
+        const double x = (b / a + 0.5) * w, y = (0.5 - g / a) * h;
+        if (!std::isfinite(x) || !std::isfinite(y)) return;
+        X0 = in_front > 1 ? std::min(X0, x) : x; X1 = in_front > 1 ? std::max(X1, x) : x;
+        Y0 = in_front > 1 ? std::min(Y0, y) : y; Y1 = in_front > 1 ? std::max(Y1, y) : y;
+    }
+    if (behind == 8) { live[0] = live[1] = live[2] = live[3] = 0; return; }   // the camera looks away from all of B: a < 0 on B, a > 0 on every ray -- no pixel is live
+    if (in_front != 8) return;                                                  // B straddles the camera's plane
+    auto clampi = [](double t) { return (int32_t)std::min((double)KY_LIVE_MAX, std::max(0.0, t)); };
+    live[0] = clampi(std::floor(X0) - 1); live[1] = clampi(std::floor(Y0) - 1);
+    live[2] = clampi(std::ceil(X1) + 1); live[3] = clampi(std::ceil(Y1) + 1);
+}
+
+void screen_bound_counts(const int32_t live[4], const ky_render_params* p, long long* dead, long long* total) {
+    const ShardConst sh = make_shard(p);
+    long long n_dead = 0;
+    for (int b = 0; b < sh.n_blocks; ++b) {   // the render kernels' decoder (ky_render.hpp), block by block
+        const int k = b / sh.blocks_per_tile, inner = b % sh.blocks_per_tile;
+        const int bx = inner % sh.blocks_w, by = inner / sh.blocks_w;
+        const int tile = sh.tile_first + k * sh.tile_step;
+        const int trow = tile / sh.tiles_x, tcol = (tile % sh.tiles_x + trow) % sh.tiles_x;
+        const int x0 = tcol * sh.tile_w + bx * 8, y0 = trow * sh.tile_h + by * 8;
+        n_dead += (x0 + 8 <= live[0] || x0 >= live[2] || y0 + 8 <= live[1] || y0 >= live[3]) ? 1 : 0;
+    }
+    if (dead) *dead = n_dead;
+    if (total) *total = sh.n_blocks;
+}
+
 int pack_scene(const ky_scene* in, DScene* out) {
     if (!in) return fail(KY_ERR_INVALID_VALUE, "scene is NULL");
     if (in->surface_count < 0 || in->shape_count < 0 || in->material_count < 0 || in->light_count < 0)
@@ -780,6 +901,7 @@ int pack_scene(const ky_scene* in, DScene* out) {
     }
     out->occ_deferred_ok = non.deferred_ok ? 1 : 0;
     out->ts_light = non.ts_light;
+    screen_bound(in, out->live);
     out->feat = 0;
     if (specialisation_enabled()) {   // the KY_FEAT_* facts of this scene
         if (in->light_count == 1 && in->lights[0].kind == KY_LIGHT_AREA && in->environment_light < 0) out->feat |= KY_FEAT_SINGLE_AREA;
@@ -963,7 +1085,7 @@ bool scene_input(const ky_scene* in, std::vector<unsigned char>& out, uint64_t& 
         in->shape_count > KYHIP_MAX_SHAPES || in->material_count > KYHIP_MAX_MATERIALS || in->light_count > KYHIP_MAX_LIGHTS)
         return false;   // pack_scene reports what is wrong
     auto put = [&](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; out.insert(out.end(), b, b + n); };
-    const int32_t head[6] = {in->shape_count, in->material_count, in->light_count, in->surface_count, in->environment_light, (specialisation_enabled() ? 1 : 0) | (boxes_enabled() ? 2 : 0)};
+    const int32_t head[6] = {in->shape_count, in->material_count, in->light_count, in->surface_count, in->environment_light, (specialisation_enabled() ? 1 : 0) | (boxes_enabled() ? 2 : 0) | (screen_cull_enabled() ? 4 : 0)};
     put(head, sizeof head);
     put(&in->camera, sizeof in->camera);
     if (in->shape_count) put(in->shapes, sizeof(ky_shape) * (size_t)in->shape_count);
@@ -1080,6 +1202,7 @@ int smallpt_check(const ky_smallpt_sphere* spheres, int n, const ky_smallpt_para
 void set_engine_raw(int v) { g_engine = v; }
 void set_specialise_raw(int v) { g_specialise = v; }
 void set_boxes_raw(int v) { g_boxes = v; }
+void set_screen_cull_raw(int v) { g_screen_cull = v; }
 void set_shadow_queue_raw(int v) { g_shadow_queue = v; }
 }  // namespace kyh
 
@@ -1105,6 +1228,11 @@ int kyhip_set_specialisation(int on) {
 int kyhip_set_boxes(int on) {
     const int prev = boxes_enabled() ? 1 : 0;
     if (on == 0 || on == 1) kyh::set_boxes_raw(on);
+    return prev;
+}
+int kyhip_set_screen_cull(int on) {
+    const int prev = screen_cull_enabled() ? 1 : 0;
+    if (on == 0 || on == 1) kyh::set_screen_cull_raw(on);
     return prev;
 }
 int kyhip_set_shadow_queue(int mode) {
@@ -1198,6 +1326,21 @@ int kyhip_scene_boxes(const ky_scene* scene, int* box_face, int n) {
         }
     }
     return P.boxtrav.n_box;
+}
+
+// host only: the live rectangle pack_scene stores for the scene (screen_bound), cut to the frame of `params`, and the blocks of its shard outside / in all
+int kyhip_scene_screen_bound(const ky_scene* scene, const ky_render_params* params, int rect[4], long long counts[2]) {
+    if (!scene || !rect) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    if (!valid_params(params)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    if (!shard_in_range(params)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices");
+    std::vector<DScene> packed(1);   // pack_scene validates the scene
+    const int rc = pack_scene(scene, &packed[0]);
+    if (rc != KY_OK) return rc;
+    const int32_t* live = packed[0].live;
+    rect[0] = std::min(live[0], params->width); rect[1] = std::min(live[1], params->height);
+    rect[2] = std::min(live[2], params->width); rect[3] = std::min(live[3], params->height);
+    if (counts) screen_bound_counts(live, params, &counts[0], &counts[1]);
+    return KY_OK;
 }
 
 // ---- smallpt's scene in double precision (ky_smallpt.hpp) ----

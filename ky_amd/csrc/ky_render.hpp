@@ -209,14 +209,32 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                 const int k = b / sh.blocks_per_tile, inner = b % sh.blocks_per_tile;
                 const int bx = inner % sh.blocks_w, by = inner / sh.blocks_w;
                 const int tile = sh.tile_first + k * sh.tile_step;
+                // A block outside the scene's live rectangle (DScene::live: none of its camera rays reaches a surface, and nothing else adds to a miss) is no work:
+                // `fetched` does not count it, and its pixels keep the zero they would have received.  Lane 0, which decodes the block's origin anyway, tests it and
+                // the wavefront reads the answer back (one v_readfirstlane).  Two plainer forms were measured on the hot row's listing and not kept: as wave-uniform
+                // code the decoder's four divisions moved to the scalar unit (four more spilled VGPRs, 28 B of scratch per lane against 12), and a slot write under
+                // `if (!dead)` left one more value live across the render loop (the depth limit went to a spill lane that the loop read back twice a turn).
+                // The rectangle is read HERE, by a scalar load behind an offset the compiler cannot see through, so that it is not hoisted and kept in SGPRs across
+                // the render loop ("Range rule": what a kernel argument cost there).
+                // Termination: a turn of this loop with fetched > 0 takes a fresh id from the counter, skipped or not, and an id at or beyond n_items ends the loop.
+                // Only the wavefront's own index is not taken from the counter: when ITS block is dead it counts as fetched and handed out (item 0 of the pool, pairs
+                // 0 .. 63, none of which has been handed out: fetched == 0 implies cursor == 0), so the next turn goes to the counter -- with no flag of its own
+                // carried through the render loop.  Slot 0 of the ring is then never read: every pair handed out from here on is 64 or beyond.
+                int dead = 0;
                 if (lane == 0) {
                     ItemSlot it;
                     const int trow = tile / sh.tiles_x, tcol = (tile % sh.tiles_x + trow) % sh.tiles_x;   // rotated rows
                     it.x0 = tcol * sh.tile_w + bx * 8;
                     it.y0 = trow * sh.tile_h + by * 8;
+                    const int4 live = scene_at<int4>(S, opaque_off((unsigned)__builtin_offsetof(DScene, live)));
+                    dead = (it.x0 + 8 <= live.x || it.x0 >= live.z || it.y0 + 8 <= live.y || it.y0 >= live.w) ? 1 : 0;
                     it.pix0 = (k * sh.tile_h + by * 8) * sh.tile_w + bx * 8;
                     chunk_range(chunk_plan(rc.spp), c, it.s_begin, it.s_end);
-                    my_ring[fetched % KY_RING] = it;
+                    my_ring[fetched % KY_RING] = it;   // (a dead item's record too: into the slot the NEXT item overwrites; pairs are handed out below fetched * 64 only)
+                }
+                if (__builtin_amdgcn_readfirstlane(dead)) {   // (every lane is here: the refill pass is a wave-uniform branch)
+                    if (fetched == 0) { fetched = 1; cursor = 64; }
+                    continue;
                 }
                 ++fetched;
             }

@@ -106,6 +106,7 @@ struct DLight {  // light_t + the shape an area light samples; wave-uniform inde
     DSurf isect;          // traversal record of the sampled shape (pdf_direction re-intersects it, 1057-1061)
 };
 constexpr int KY_MAX_CARRIERS = 4;
+constexpr int KY_LIVE_MAX = 32768;   // beyond every pixel a launch can have (valid_params: width, height <= 32767)
 static_assert(sizeof(DLight) % 16 == 0 && __builtin_offsetof(DLight, p1) % 16 == 0 && __builtin_offsetof(DLight, n) % 16 == 0, "DLight is read in 16-byte groups (shape_sample_position)");
 
 struct DPar {  // planar parallelogram, 48 B: q0 = (n, n.p0), q1 = (a*, a*.p1 + 0.5), q2 = (b*, b*.p1 + 0.5)
@@ -177,6 +178,10 @@ struct DScene {
     // few that are left, under a wave-uniform branch.
     int32_t ts_light, feat, ts_pad[2];   // feat: the KY_FEAT_* facts that hold for this scene (host: pack_scene)
     float ts_plane[4];
+    // The live rectangle (host: screen_bound, which states the proof): pixels [x0, x1) x [y0, y1) in live[0..3] = x0, y0, x1, y1.  No camera sample of a pixel outside
+    // it reaches a surface, and the scene has no environment light, so such a pixel's film value is exactly 0 and the render kernels take no work item whose 8 x 8
+    // block lies outside (ky_render.hpp, the work decoder).  The whole range 0 .. KY_LIVE_MAX wherever the proof does not hold, and with kyhip_set_screen_cull(0).
+    int32_t live[4];
     DTrav occ_front, occ_behind;
     DBoxTrav boxtrav;                   // KY_FEAT_BOXES: the nearest-hit traversal's planar part with the boxes' faces taken out of the rectangle lists
     DSph sph[KYHIP_MAX_SURFACES + 1];
