@@ -26,17 +26,17 @@ $(RTC_INC): $(DEVICE_HDRS) include/kyhip.h tools/embed_sources.py
 #   ky_noise.hip   a frame's noise estimate: film-sized kernels and a deterministic reduction (ky_noise.hpp: their arithmetic, host and device)
 #   ky_blocks.hip  a frame that retires pixel blocks: block state, retire rule, the live list's compaction, per-block resolve (ky_blocks.hpp: their arithmetic)
 # (ky_pack.cpp and ky_jit.cpp make no HIP call: `make sanitize` builds the same files with g++ -fsanitize=...)
-HOST_HDRS := $(CSRC)/ky_host.hpp $(CSRC)/ky_ctx.hpp $(CSRC)/ky_scene.hpp $(CSRC)/ky_shard.hpp $(CSRC)/ky_noise.hpp $(CSRC)/ky_blocks.hpp include/kyhip.h
+HOST_HDRS := $(CSRC)/ky_host.hpp $(CSRC)/ky_ctx.hpp $(CSRC)/ky_scene.hpp $(CSRC)/ky_shard.hpp $(CSRC)/ky_noise.hpp $(CSRC)/ky_blocks.hpp $(CSRC)/ky_checkpoint.hpp include/kyhip.h
 OBJDIR  := build/obj
 KYHIP_OBJS := $(OBJDIR)/ky_launch.o $(OBJDIR)/ky_kat.o $(OBJDIR)/ky_pack.o $(OBJDIR)/ky_jit.o $(OBJDIR)/ky_seam.o $(OBJDIR)/ky_frame.o $(OBJDIR)/ky_noise.o $(OBJDIR)/ky_blocks.o
-$(OBJDIR)/ky_launch.o: $(CSRC)/ky_launch.hip $(DEVICE_HDRS) $(CSRC)/ky_queue.hpp $(CSRC)/ky_smallpt.hpp $(CSRC)/ky_measure.hpp $(HOST_HDRS)
+$(OBJDIR)/ky_launch.o: $(CSRC)/ky_launch.hip $(DEVICE_HDRS) $(CSRC)/ky_queue.hpp $(CSRC)/ky_smallpt.hpp $(CSRC)/ky_measure.hpp $(CSRC)/ky_film_value.hpp $(HOST_HDRS)
 $(OBJDIR)/ky_kat.o: $(CSRC)/ky_kat.hip $(DEVICE_HDRS) $(CSRC)/ky_measure.hpp $(HOST_HDRS)
 $(OBJDIR)/ky_pack.o: $(CSRC)/ky_pack.cpp $(HOST_HDRS)
 $(OBJDIR)/ky_jit.o: $(CSRC)/ky_jit.cpp $(HOST_HDRS) $(RTC_INC)
 $(OBJDIR)/ky_seam.o: $(CSRC)/ky_seam.cpp $(HOST_HDRS)
 $(OBJDIR)/ky_frame.o: $(CSRC)/ky_frame.cpp $(HOST_HDRS)
 $(OBJDIR)/ky_noise.o: $(CSRC)/ky_noise.hip $(HOST_HDRS)
-$(OBJDIR)/ky_blocks.o: $(CSRC)/ky_blocks.hip $(HOST_HDRS)
+$(OBJDIR)/ky_blocks.o: $(CSRC)/ky_blocks.hip $(CSRC)/ky_film_value.hpp $(HOST_HDRS)
 $(OBJDIR)/%.o:
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(KYFLAGS) -c -o $@ $<

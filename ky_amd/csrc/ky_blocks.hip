@@ -8,13 +8,14 @@
  *   blocks_count / _scan / _scatter_kernel   the ascending list of the live blocks: a count per workgroup of 256 blocks, their exclusive prefix by one thread,
  *                          then every live block's place from its workgroup's prefix, the waves before it and the lanes before it.  No atomics: the list is
  *                          the same from run to run;
- *   blocks_resolve_kernel  resolve_frame_kernel's arithmetic (ky_launch.hip) with the scale total / (the block's samples), in double, before the one rounding.
+ *   blocks_resolve_kernel  resolve_frame_kernel's arithmetic (film_value, ky_film_value.hpp) with the scale total / (the block's samples), in double, before the one rounding.
  * gfx950 only.
  */
 #include <hip/hip_runtime.h>
 
 #include "ky_blocks.hpp"
 #include "ky_ctx.hpp"
+#include "ky_film_value.hpp"
 
 using namespace kyb;
 
@@ -112,14 +113,7 @@ __global__ void blocks_resolve_kernel(const unsigned long long* __restrict__ acc
     const double scale = n > 0 ? (double)total_spp / (double)n : 0.0;
     const unsigned fl = flags[i];
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        float v = (float)((double)(long long)accum[3 * (size_t)i + ch] * (1.0 / KY_FIX_SCALE) * scale);
-        const bool nan = (fl >> ch) & 1u, pinf = (fl >> (3 + ch)) & 1u, ninf = (fl >> (6 + ch)) & 1u;
-        if (pinf) v = 1.f;
-        if (ninf) v = 0.f;
-        if (nan || (pinf && ninf)) v = 0.f;
-        tiles[3 * (size_t)i + ch] = fminf(fmaxf(v, 0.f), 1.f);
-    }
+    for (int ch = 0; ch < 3; ++ch) tiles[3 * (size_t)i + ch] = film_value(accum[3 * (size_t)i + ch], fl, ch, scale);
 }
 
 namespace kyb {

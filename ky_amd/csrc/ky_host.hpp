@@ -24,6 +24,12 @@ using namespace kyd;
 // ---- errors: kyhip_last_error() returns the calling thread's last message ----
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 const std::string& last_error();
+// a call that returns a KY_* status (and has set the message): any other than KY_OK is the caller's
+#define KY_TRY(expr)                            \
+    do {                                        \
+        const int rc_ = (expr);                 \
+        if (rc_ != KY_OK) return rc_;           \
+    } while (0)
 
 // ---- parameters and shard geometry ----
 bool valid_params(const ky_render_params* p);
@@ -55,23 +61,12 @@ inline size_t workspace_bytes_for(const ShardConst& s) { return (size_t)s.n_pix 
 
 // ---- passes of a frame (kyhip_frame_*; the chunk arithmetic is ky_shard.hpp's) ----
 int pass_boundaries(int spp, int* bounds, int n);   // kyhip_pass_boundaries
-// A frame's checkpoint (kyhip_frame_save / _load) begins with this header; the accumulators (3 x 64 bits per pixel) and the flag words follow.  Everything in it
-// but samples_done names what the frame IS: a state is loaded only into a frame whose own header agrees in all of that.
-struct FrameHeader {
-    uint64_t magic;            // KY_FRAME_MAGIC
-    uint64_t source_hash;      // kyhip_kernel_source_hash(): another kernel source's chunk sums differ in the last bit
-    ky_render_params params;
-    uint64_t scene_hash;       // scene_hash of the packed scene
-    int32_t samples_done, n_pix;
-};
-constexpr uint64_t KY_FRAME_MAGIC = 0x31454d4152464b59ull;   // "YKFRAME1"
-constexpr uint64_t KY_FRAME_BLOCKS_MAGIC = 0x314b4c4252464b59ull;   // "YKFRBLK1": a frame that retires pixel blocks (ky_blocks.hpp): its accumulators stand at per-block
-                                                                    // sample counts, which a frame that does not track blocks would resolve wrongly
-FrameHeader frame_header(const ky_render_params* p, uint64_t scene_hash, int samples_done);
-// KY_OK and the chunk count the state's samples_done stands for, or KY_ERR_INVALID_VALUE with the message: a short buffer, another frame's state, a
-// samples_done at which no chunk of the frame ends
-int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, int* chunks_done);
-inline size_t frame_state_bytes(const ky_render_params* p) { return sizeof(FrameHeader) + workspace_bytes_for(make_shard(p)); }
+// (a frame's checkpoint: ky_checkpoint.hpp)
+// The stop rule's arguments, refused before a frame or a device is looked at, in this order by every entry that takes them (ky_frame.cpp and the host-only
+// builds' stand-ins, ky_hostcheck.cpp): KY_OK, or KY_ERR_INVALID_VALUE with the message
+int threshold_check(float threshold);                                                  // a noise level is >= 0 (a NaN is not)
+int stop_rule_check(float threshold, float max_fraction_above, int min_batches);      // threshold_check, then the fraction in 0 .. 1, then min_batches >= 2
+int pass_samples_check(int min_samples_per_pass);                                      // >= 1
 
 // ---- scene packing (ky_pack.cpp) ----
 void cp3(float* d, const float* s);

@@ -2,7 +2,9 @@
  * ky_hostcheck.cpp -- entry points of the SANITIZER builds only (`make sanitize`: g++ -fsanitize=address,undefined and -fsanitize=thread over ky_pack.cpp,
  * ky_jit.cpp and this file; never part of libkyhip.so).  They drive the host code that has no C-ABI entry of its own -- scene packing into a heap DScene,
  * the scene cache's keys, the chunk schedule, the banded add, HostPool and the seam's lock order under contention and across a fork -- so that
- * tests/test_sanitize.py can run it under the sanitizers from Python (ctypes) or from the stress binary (tools/sanitize/stress.cpp).
+ * tests/test_sanitize.py can run it under the sanitizers from Python (ctypes) or from the stress binary (tools/sanitize/stress.cpp).  A checkpoint's layout,
+ * writer and check (ky_checkpoint.hpp) and the stop rule's argument checks (ky_host.hpp) are the product's own, defined in ky_pack.cpp: kyhostcheck_checkpoint
+ * and the kyhip_frame_* stand-ins at the end of this file call them and restate nothing.
  */
 #include <atomic>
 #include <cstdlib>
@@ -13,9 +15,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
-#include "ky_blocks.hpp"
-#include "ky_host.hpp"
-#include "ky_noise.hpp"
+#include "ky_checkpoint.hpp"   // ky_host.hpp, ky_blocks.hpp, ky_noise.hpp
 
 using namespace kyh;
 
@@ -70,7 +70,8 @@ int kyhostcheck_frame(const ky_render_params* p, int min_samples) {
     std::vector<int> bounds((size_t)chunk_count(plan));
     if (pass_boundaries(p->samples_per_pixel, bounds.data(), (int)bounds.size()) != (int)bounds.size()) return -10;
     const FrameHeader own = frame_header(p, 0x1234, 0);
-    std::vector<unsigned char> state(frame_state_bytes(p), 0);
+    const size_t state_end = checkpoint_layout(p, false, false).total;
+    std::vector<unsigned char> state(state_end, 0);
     ky_render_params q = *p;
     q.seed ^= 1u;
     int passes = 0, done = 0;
@@ -84,10 +85,10 @@ int kyhostcheck_frame(const ky_render_params* p, int min_samples) {
         FrameHeader h = own;
         h.samples_done = bounds[(size_t)done - 1];
         std::memcpy(state.data(), &h, sizeof h);
-        if (frame_state_check(own, state.data(), state.size(), &back) != KY_OK || back != done) return -13;
-        if (frame_state_check(own, state.data(), state.size() - 1, &back) == KY_OK || frame_state_check(own, state.data(), sizeof h - 1, &back) == KY_OK) return -14;
-        if (frame_state_check(frame_header(&q, 0x1234, 0), state.data(), state.size(), &back) == KY_OK) return -15;
-        if (frame_state_check(frame_header(p, 0x1235, 0), state.data(), state.size(), &back) == KY_OK) return -16;
+        if (frame_state_check(own, state.data(), state.size(), state_end, &back) != KY_OK || back != done) return -13;
+        if (frame_state_check(own, state.data(), state.size() - 1, state_end, &back) == KY_OK || frame_state_check(own, state.data(), sizeof h - 1, state_end, &back) == KY_OK) return -14;
+        if (frame_state_check(frame_header(&q, 0x1234, 0), state.data(), state.size(), state_end, &back) == KY_OK) return -15;
+        if (frame_state_check(frame_header(p, 0x1235, 0), state.data(), state.size(), state_end, &back) == KY_OK) return -16;
     }
     if (chunks_at_sample(plan, 0) != 0 || chunks_at_sample(plan, p->samples_per_pixel + 1) != -1) return -17;
     for (int s = 1, c = 0; s <= p->samples_per_pixel; ++s) {   // every sample count: a chunk count exactly at the boundaries
@@ -96,6 +97,32 @@ int kyhostcheck_frame(const ky_render_params* p, int min_samples) {
         if (is_bound) ++c;
     }
     return passes;
+}
+
+// A whole checkpoint without a device (ky_checkpoint.hpp): the layout of a frame of p that tracks (noise, blocks) -> offsets[6] = where the accumulators, the noise
+// trailer, the noise pixels, the block trailer and the block states begin, and the total; the host-side parts written into a zeroed buffer of that total from
+// counts_in = {samples_done, batches, n_prev, passes} and `states` (n_blocks x {retired_at, batches}; NULL: every block live) -- copied to state_out when its
+// capacity holds it --, then checkpoint_check on the first check_bytes bytes of it (at most the total) by a frame that tracks (noise, check_blocks) ->
+// counts_out = {chunks_done, samples_done, batches, n_prev, passes}.  Returns the check's status, or KY_ERR_INVALID_VALUE for arguments that are none.
+int kyhostcheck_checkpoint(const ky_render_params* p, int noise, int blocks, int check_blocks, const int* counts_in, const int32_t* states, size_t check_bytes,
+                           size_t* offsets, int* counts_out, void* state_out, size_t state_capacity) {
+    if (!valid_params(p) || !shard_in_range(p) || !counts_in || !offsets || !counts_out) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    const CheckpointLayout L = checkpoint_layout(p, noise != 0, blocks != 0);
+    const size_t at[6] = {L.accum, L.noise, L.noise_pixels, L.blocks, L.block_states, L.total};
+    std::memcpy(offsets, at, sizeof at);
+    std::vector<kyb::BlockState> st((size_t)L.n_blocks, kyb::BlockState{-1, 0});
+    for (int b = 0; b < L.n_blocks && states; ++b) st[(size_t)b] = kyb::BlockState{states[2 * b], states[2 * b + 1]};
+    CheckpointCounts n;
+    n.samples_done = counts_in[0]; n.batches = counts_in[1]; n.n_prev = counts_in[2]; n.passes = counts_in[3];
+    const FrameHeader own = frame_header(p, 0x1234, 0);
+    std::vector<unsigned char> buf(L.total, 0);
+    checkpoint_write_host(own, L, n, st.data(), buf.data());
+    if (state_out && state_capacity >= L.total) std::memcpy(state_out, buf.data(), L.total);
+    CheckpointCounts back;
+    KY_TRY(checkpoint_check(own, checkpoint_layout(p, noise != 0, check_blocks != 0), buf.data(), check_bytes < L.total ? check_bytes : L.total, &back));
+    const int got[5] = {back.chunks_done, back.samples_done, back.batches, back.n_prev, back.passes};
+    std::memcpy(counts_out, got, sizeof got);
+    return KY_OK;
 }
 
 // make_shard / shard_in_range / valid_params on the caller's parameters: n_items, or a negative status
@@ -374,42 +401,33 @@ int64_t kyhip_frame_state_bytes(const kyhip_frame*) { return fail(KY_ERR_INVALID
 int kyhip_frame_save(kyhip_frame*, void*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_load(kyhip_frame*, const void*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 void kyhip_frame_end(kyhip_frame*) {}
-// (the noise entries check their other arguments first, like the real ones)
+// (the noise and block entries refuse their other arguments first, by the real ones' own checks in the real ones' order: ky_host.hpp)
+static int no_frame(const void* out) { return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL"); }
 int kyhip_frame_track_noise(kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_noise(kyhip_frame*, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_noise_stats(kyhip_frame*, float threshold, ky_noise_stats* out) {
-    if (!(threshold >= 0.f)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
-    return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+    KY_TRY(threshold_check(threshold));
+    return no_frame(out);
 }
 int kyhip_frame_render_until(kyhip_frame*, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass, int*, ky_noise_stats* out) {
-    if (!(threshold >= 0.f)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
-    if (!(max_fraction_above >= 0.f && max_fraction_above <= 1.f)) return fail(KY_ERR_INVALID_VALUE, "max_fraction_above %g: a fraction of the pixels, 0 .. 1", (double)max_fraction_above);
-    if (min_batches < 2) return fail(KY_ERR_INVALID_VALUE, "min_batches %d: the estimate needs two batches", min_batches);
-    if (min_samples_per_pass < 1) return fail(KY_ERR_INVALID_VALUE, "min_samples_per_pass %d: a pass renders at least one sample per pixel", min_samples_per_pass);
-    return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+    KY_TRY(stop_rule_check(threshold, max_fraction_above, min_batches));
+    KY_TRY(pass_samples_check(min_samples_per_pass));
+    return no_frame(out);
 }
 int kyhip_frame_noise_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
-// (the block entries too)
-static int adaptive_args(float threshold, float max_fraction_above, int min_batches) {
-    if (!(threshold >= 0.f)) return fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);
-    if (!(max_fraction_above >= 0.f && max_fraction_above <= 1.f)) return fail(KY_ERR_INVALID_VALUE, "max_fraction_above %g: a fraction of the pixels, 0 .. 1", (double)max_fraction_above);
-    if (min_batches < 2) return fail(KY_ERR_INVALID_VALUE, "min_batches %d: the estimate needs two batches", min_batches);
-    return KY_OK;
-}
 int kyhip_frame_track_blocks(kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_keep(kyhip_frame*, const unsigned char* mask, size_t) { return fail(KY_ERR_INVALID_VALUE, mask ? "frame is NULL" : "mask is NULL"); }
 int kyhip_frame_retire_noisy(kyhip_frame*, float threshold, float max_fraction_above, int min_batches, ky_block_stats* out) {
-    const int rc = adaptive_args(threshold, max_fraction_above, min_batches);
-    return rc != KY_OK ? rc : fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+    KY_TRY(stop_rule_check(threshold, max_fraction_above, min_batches));
+    return no_frame(out);
 }
 int kyhip_frame_render_adaptive(kyhip_frame*, float threshold, float max_fraction_above, int min_batches, int min_samples_per_pass, int*, ky_block_stats* out) {
-    const int rc = adaptive_args(threshold, max_fraction_above, min_batches);
-    if (rc != KY_OK) return rc;
-    if (min_samples_per_pass < 1) return fail(KY_ERR_INVALID_VALUE, "min_samples_per_pass %d: a pass renders at least one sample per pixel", min_samples_per_pass);
-    return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL");
+    KY_TRY(stop_rule_check(threshold, max_fraction_above, min_batches));
+    KY_TRY(pass_samples_check(min_samples_per_pass));
+    return no_frame(out);
 }
 int kyhip_frame_sample_map(kyhip_frame*, int32_t*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
-int kyhip_frame_block_stats(kyhip_frame*, ky_block_stats* out) { return fail(KY_ERR_INVALID_VALUE, out ? "frame is NULL" : "out is NULL"); }
+int kyhip_frame_block_stats(kyhip_frame*, ky_block_stats* out) { return no_frame(out); }
 int kyhip_frame_blocks_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }

@@ -31,6 +31,7 @@
 #include <cstring>
 
 #include "ky_ctx.hpp"
+#include "ky_film_value.hpp"
 #include "ky_render.hpp"
 #include "ky_smallpt.hpp"
 
@@ -53,18 +54,14 @@ __global__ void resolve_kernel(unsigned long long* __restrict__ accum, unsigned*
     flags[i] = 0u;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        float v = (float)((double)(long long)accum[3 * (size_t)i + ch] * (1.0 / KY_FIX_SCALE));
+        const unsigned long long word = accum[3 * (size_t)i + ch];
         accum[3 * (size_t)i + ch] = 0ull;
-        const bool nan = (fl >> ch) & 1u, pinf = (fl >> (3 + ch)) & 1u, ninf = (fl >> (6 + ch)) & 1u;
-        if (pinf) v = 1.f;
-        if (ninf) v = 0.f;
-        if (nan || (pinf && ninf)) v = 0.f;  // a NaN pixel: clamp01 keeps NaN in the reference and its 8-bit image shows 0
-        tiles[3 * (size_t)i + ch] = fminf(fmaxf(v, 0.f), 1.f);
+        tiles[3 * (size_t)i + ch] = film_value(word, fl, ch, 1.0);
     }
 }
 
 // A frame's accumulators (kyhip_frame_resolve) -> clamp01(value * scale) -> fp32 tile buffer, one thread per pixel: resolve_kernel's conversion and flag rules
-// word for word, but the accumulators, the flag words and every counter stay as they are -- the frame goes on adding to them.  scale is total / done for the
+// (film_value), but the accumulators, the flag words and every counter stay as they are -- the frame goes on adding to them.  scale is total / done for the
 // picture so far (the chunk sums were scaled by 1 / total, ky_render.hpp), applied in double before the one rounding to float; with scale == 1.0 (an exact
 // product) the output is resolve_kernel's bit for bit.
 __global__ void resolve_frame_kernel(const unsigned long long* __restrict__ accum, const unsigned* __restrict__ flags, float* __restrict__ tiles, int n_pix, double scale) {
@@ -72,14 +69,7 @@ __global__ void resolve_frame_kernel(const unsigned long long* __restrict__ accu
     if (i >= n_pix) return;
     const unsigned fl = flags[i];
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        float v = (float)((double)(long long)accum[3 * (size_t)i + ch] * (1.0 / KY_FIX_SCALE) * scale);
-        const bool nan = (fl >> ch) & 1u, pinf = (fl >> (3 + ch)) & 1u, ninf = (fl >> (6 + ch)) & 1u;
-        if (pinf) v = 1.f;
-        if (ninf) v = 0.f;
-        if (nan || (pinf && ninf)) v = 0.f;
-        tiles[3 * (size_t)i + ch] = fminf(fmaxf(v, 0.f), 1.f);
-    }
+    for (int ch = 0; ch < 3; ++ch) tiles[3 * (size_t)i + ch] = film_value(accum[3 * (size_t)i + ch], fl, ch, scale);
 }
 
 __global__ void film_add_kernel(const float* __restrict__ tiles, float* __restrict__ film, size_t stride_px, ShardConst sh, int width, int height) {

@@ -1,7 +1,9 @@
 /*
  * ky_pack.cpp -- the host code of libkyhip.so that needs no GPU: error state, parameter validation and shard geometry, packing a caller's ky_scene
  * into the device layout (DScene: kind-sorted traversal tables, occluder tables, scene facts), the proof of which surfaces a shadow ray never has to
- * test (find_non_occluders), the launch policies, and the CPU side of the host-film seam (HostPool, the banded add).
+ * test (find_non_occluders), the launch policies, the CPU side of the host-film seam (HostPool, the banded add), and what a frame's checkpoint is: its layout,
+ * its host-side parts and the check of a buffer (ky_checkpoint.hpp), next to the stop rule's argument checks (ky_host.hpp) -- shared by ky_frame.cpp's entries and
+ * the host-only builds' stand-ins (ky_hostcheck.cpp).
  * Plain C++17 with no HIP runtime call: hipcc compiles it into the library, and `make sanitize` compiles the very same file with
  * g++ -fsanitize=address,undefined and -fsanitize=thread (round 5; until round 4 all of this lived inside kyhip.hip, out of any sanitizer's reach).
  */
@@ -16,9 +18,7 @@
 #include <sched.h>
 #include <unistd.h>
 
-#include "ky_blocks.hpp"
-#include "ky_host.hpp"
-#include "ky_noise.hpp"
+#include "ky_checkpoint.hpp"   // ky_host.hpp, ky_blocks.hpp, ky_noise.hpp
 
 namespace kyh {
 
@@ -197,7 +197,7 @@ FrameHeader frame_header(const ky_render_params* p, uint64_t hash, int samples_d
     h.n_pix = make_shard(p).n_pix;
     return h;
 }
-int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, int* chunks_done) {
+int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, size_t state_end, int* chunks_done) {
     if (!buf || bytes < sizeof(FrameHeader)) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no header", bytes);
     FrameHeader theirs;
     std::memcpy(&theirs, buf, sizeof theirs);
@@ -210,14 +210,79 @@ int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, int
     FrameHeader same = theirs;
     same.samples_done = own.samples_done;
     if (std::memcmp(&same, &own, sizeof own) != 0) return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its render params, scene or film size differ from this frame's)");
-    if (bytes < frame_state_bytes(&own.params)) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes, the frame's state has %zu", bytes, frame_state_bytes(&own.params));
+    if (bytes < state_end) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes, the frame's state has %zu", bytes, state_end);
     const int c = theirs.samples_done < 0 ? -1 : chunks_at_sample(chunk_plan(own.params.samples_per_pixel), theirs.samples_done);
     if (c < 0) return fail(KY_ERR_INVALID_VALUE, "frame state: no pass of a %d-sample frame ends at %d samples", own.params.samples_per_pixel, theirs.samples_done);
     *chunks_done = c;
     return KY_OK;
 }
+
+// ---- a checkpoint as a whole (ky_checkpoint.hpp) ----
+CheckpointLayout checkpoint_layout(const ky_render_params* p, bool noise, bool blocks) {
+    const ShardConst sh = make_shard(p);
+    CheckpointLayout L;
+    L.n_pix = sh.n_pix; L.n_blocks = sh.n_blocks; L.tracks_noise = noise; L.tracks_blocks = blocks;
+    L.accum = sizeof(FrameHeader);
+    L.noise = L.accum + workspace_bytes_for(sh);
+    L.noise_pixels = L.noise + (noise ? sizeof(kyn::NoiseTrailer) : 0);
+    L.blocks = L.noise_pixels + (noise ? (size_t)sh.n_pix * sizeof(kyn::NoisePixel) : 0);
+    L.block_states = L.blocks + (blocks ? sizeof(kyb::BlockTrailer) : 0);
+    L.total = L.block_states + (blocks ? (size_t)sh.n_blocks * sizeof(kyb::BlockState) : 0);
+    return L;
+}
+// the frame's header as its checkpoints carry it: the magic says whether the layout ends with blocks
+static FrameHeader checkpoint_header(FrameHeader own, const CheckpointLayout& L, int samples_done) {
+    own.magic = L.tracks_blocks ? KY_FRAME_BLOCKS_MAGIC : KY_FRAME_MAGIC;
+    own.samples_done = samples_done;
+    return own;
+}
+void checkpoint_write_host(const FrameHeader& own, const CheckpointLayout& L, const CheckpointCounts& n, const kyb::BlockState* states, void* buf) {
+    char* at = (char*)buf;
+    const FrameHeader h = checkpoint_header(own, L, n.samples_done);
+    std::memcpy(at, &h, sizeof h);
+    if (L.tracks_noise) {
+        const kyn::NoiseTrailer t = {kyn::KY_NOISE_MAGIC, n.batches, n.n_prev};
+        std::memcpy(at + L.noise, &t, sizeof t);
+    }
+    if (L.tracks_blocks) {
+        const kyb::BlockTrailer t = {kyb::KY_BLOCKS_MAGIC, L.n_blocks, n.passes};
+        std::memcpy(at + L.blocks, &t, sizeof t);
+        if (L.n_blocks > 0) std::memcpy(at + L.block_states, states, L.block_states_bytes());
+    }
+}
+int checkpoint_check(const FrameHeader& own, const CheckpointLayout& L, const void* buf, size_t bytes, CheckpointCounts* out) {
+    CheckpointCounts n;
+    KY_TRY(frame_state_check(checkpoint_header(own, L, own.samples_done), buf, bytes, L.noise, &n.chunks_done));
+    n.samples_done = chunk_end(chunk_plan(own.params.samples_per_pixel), n.chunks_done - 1);
+    if (L.tracks_noise) {   // (a frame that does not track accepts a longer buffer and ignores the trailer)
+        kyn::NoiseTrailer t;
+        KY_TRY(kyn::noise_trailer_check(buf, bytes, L.noise, L.n_pix, n.samples_done, &t));
+        n.batches = t.batches; n.n_prev = t.n_prev;
+    }
+    if (L.tracks_blocks) {
+        kyb::BlockTrailer t;
+        KY_TRY(kyb::block_trailer_check(buf, bytes, L.blocks, L.n_blocks, own.params.samples_per_pixel, n.samples_done, n.batches, &t));
+        n.passes = t.passes;
+    }
+    *out = n;
+    return KY_OK;
+}
+
+// ---- the stop rule's arguments (ky_host.hpp) ----
+int threshold_check(float threshold) {
+    return threshold >= 0.f ? KY_OK : fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);   // (a NaN is refused)
+}
+int stop_rule_check(float threshold, float max_fraction_above, int min_batches) {
+    KY_TRY(threshold_check(threshold));
+    if (!(max_fraction_above >= 0.f && max_fraction_above <= 1.f)) return fail(KY_ERR_INVALID_VALUE, "max_fraction_above %g: a fraction of the pixels, 0 .. 1", (double)max_fraction_above);
+    if (min_batches < 2) return fail(KY_ERR_INVALID_VALUE, "min_batches %d: the estimate needs two batches", min_batches);
+    return KY_OK;
+}
+int pass_samples_check(int min_samples_per_pass) {
+    return min_samples_per_pass >= 1 ? KY_OK : fail(KY_ERR_INVALID_VALUE, "min_samples_per_pass %d: a pass renders at least one sample per pixel", min_samples_per_pass);
+}
 }  // namespace kyh
-// A tracking frame's state continues behind the accumulators and flag words (state_bytes) with a NoiseTrailer and n_pix NoisePixel (ky_noise.hpp)
+// the pieces of checkpoint_check: the noise trailer at `state_bytes` (CheckpointLayout::noise) ...
 int kyn::noise_trailer_check(const void* buf, size_t bytes, size_t state_bytes, int n_pix, int samples_done, NoiseTrailer* out) {
     using kyh::fail;
     if (!buf || bytes < state_bytes || bytes - state_bytes < noise_trailer_bytes(n_pix))
@@ -230,7 +295,7 @@ int kyn::noise_trailer_check(const void* buf, size_t bytes, size_t state_bytes, 
     if (out) *out = t;
     return KY_OK;
 }
-// A block-tracking frame's state ends with a BlockTrailer and n_blocks BlockState (ky_blocks.hpp), at `offset`
+// ... and the block trailer at `offset` (CheckpointLayout::blocks)
 int kyb::block_trailer_check(const void* buf, size_t bytes, size_t offset, int n_blocks, int total_spp, int samples_done, int noise_batches, BlockTrailer* out) {
     using kyh::fail;
     if (!buf || bytes < offset || bytes - offset < block_trailer_bytes(n_blocks))

@@ -6,7 +6,7 @@ import struct
 import numpy as np
 
 NOISE_MAGIC = 0x314553494F4E4B59   # "YKNOISE1"
-HEADER_BYTES = 8 + 8 + 12 * 4 + 8 + 4 + 4   # FrameHeader (ky_host.hpp): magic, source hash, ky_render_params, scene hash, samples_done, n_pix
+HEADER_BYTES = 8 + 8 + 12 * 4 + 8 + 4 + 4   # FrameHeader (ky_checkpoint.hpp): magic, source hash, ky_render_params, scene hash, samples_done, n_pix
 TRAILER_BYTES = 16                           # NoiseTrailer: magic, batches, n_prev
 
 
