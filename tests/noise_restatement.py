@@ -69,13 +69,20 @@ def split_state(state, n_pix):
     return samples_done, accum, flags, (batches, n_prev, pairs[:, 0], pairs[:, 1])
 
 
-def pixel_xy(n_pix, width, height, tile=16, tile_first=0, tile_step=1):
-    """Pixel i of a shard's compact tile buffer -> (x, y) in the film (film_add_kernel's de-interleave: tile rows rotated), and whether it lies inside."""
-    tiles_x = (width + tile - 1) // tile
+def tile_size(tile=16, tile_w=None, tile_h=None):
+    """(tile_w, tile_h): `tile` is a square tile; tile_w / tile_h name the sides apart (ShardConst::tile_w, tile_h)."""
+    return (tile if tile_w is None else tile_w), (tile if tile_h is None else tile_h)
+
+
+def pixel_xy(n_pix, width, height, tile=16, tile_first=0, tile_step=1, tile_w=None, tile_h=None):
+    """Pixel i of a shard's compact tile buffer -> (x, y) in the film (noise_pixel_xy, film_add_kernel's de-interleave: tile rows rotated), and whether it
+    lies inside."""
+    tw, th = tile_size(tile, tile_w, tile_h)
+    tiles_x = (width + tw - 1) // tw
     i = np.arange(n_pix)
-    k, r = i // (tile * tile), i % (tile * tile)
+    k, r = i // (tw * th), i % (tw * th)
     t = tile_first + k * tile_step
     trow = t // tiles_x
     tcol = (t % tiles_x + trow) % tiles_x
-    x, y = tcol * tile + r % tile, trow * tile + r // tile
+    x, y = tcol * tw + r % tw, trow * th + r // tw
     return x, y, (x < width) & (y < height)

@@ -49,27 +49,92 @@ def _rule(check, p, state, values, cls, threshold, fraction, min_batches, front,
     return state
 
 
-@pytest.mark.parametrize("tile,shard,n_tiles,n_inside", [(16, {}, 6, 15), (16, dict(tile_first=1, tile_step=2), 3, None), (32, {}, 2, None)])
-def test_pixel_block_map(tile, shard, n_tiles, n_inside, api, check):
-    w, h = 40, 24
-    p = api.make_params(w, h, 500, tile_w=tile, tile_h=tile, **shard)
-    n_pix = n_tiles * tile * tile
+SHARD_1_3 = dict(tile_first=1, tile_step=3)
+# (w, h, tile_w, tile_h, shard, n_tiles, n_inside): n_tiles and n_inside (blocks with a pixel inside the film) where the case pins them, else None
+MAP_CASES = [(40, 24, 16, 16, {}, 6, 15), (40, 24, 16, 16, dict(tile_first=1, tile_step=2), 3, None), (40, 24, 32, 32, {}, 2, None)]
+# tiles that are not square (blocks_w != tile_h / 8) and the tile that is one block (blocks_per_tile == 1), whole and as a shard
+MAP_CASES += [(40, 24, tw, th, shard, None, None) for (tw, th) in ((32, 8), (8, 24), (8, 8)) for shard in ({}, SHARD_1_3)]
+# films that are no multiple of 8: blocks partly inside
+MAP_CASES += [(w, h, tw, th, shard, None, None) for (w, h) in ((44, 21), (33, 17)) for (tw, th) in ((16, 16), (32, 8), (8, 24), (8, 8)) for shard in ({}, SHARD_1_3)]
+# the frame of tests/test_frame_sizes_gpu.py: 544 tiles, 2176 blocks = 8 groups of 256 and one of 128; as a shard 181 tiles
+MAP_CASES += [(264, 512, 16, 16, {}, 544, 2112), (264, 512, 16, 16, SHARD_1_3, 181, None)]
+
+
+def _case_id(c):
+    w, h, tw, th, shard = c[:5]
+    return "%dx%d_tile_%dx%d%s" % (w, h, tw, th, "_shard_%d_%d" % (shard["tile_first"], shard["tile_step"]) if shard else "")
+
+
+# (the first three cases keep the ids they had before the others came: the same tests under the same names)
+MAP_IDS = ["16-shard0-6-15", "16-shard1-3-None", "32-shard2-2-None"] + [_case_id(c) for c in MAP_CASES[3:]]
+
+
+@pytest.mark.parametrize("w,h,tile_w,tile_h,shard,n_tiles,n_inside", MAP_CASES, ids=MAP_IDS)
+def test_pixel_block_map(w, h, tile_w, tile_h, shard, n_tiles, n_inside, api, check):
+    tile = dict(tile_w=tile_w, tile_h=tile_h)
+    p = api.make_params(w, h, 500, **tile, **shard)
+    tiles_film = -(-w // tile_w) * -(-h // tile_h)
+    first, step = shard.get("tile_first", 0), shard.get("tile_step", 1)
+    tiles_own = -(-(tiles_film - first) // step)
+    if n_tiles is not None:
+        assert tiles_own == n_tiles
+    n_pix = tiles_own * tile_w * tile_h
     block, pixel, inside = _geometry(check, p, n_pix)
-    assert np.array_equal(block, B.block_of_pixel(n_pix, tile))
-    assert np.array_equal(pixel, B.pixel_of_block(n_pix // 64, tile))
+    assert np.array_equal(block, B.block_of_pixel(n_pix, **tile))
+    assert np.array_equal(pixel, B.pixel_of_block(n_pix // 64, **tile))
+    if tile_w == tile_h:   # `tile=` means a square tile
+        assert np.array_equal(block, B.block_of_pixel(n_pix, tile_w)) and np.array_equal(pixel, B.pixel_of_block(n_pix // 64, tile_w))
     assert np.array_equal(block[pixel], np.repeat(np.arange(n_pix // 64)[:, None], 64, axis=1))      # the two are inverses
     assert np.array_equal(np.sort(pixel.ravel()), np.arange(n_pix))
-    want_inside = B.inside_count(n_pix, w, h, tile=tile, **shard)
+    want_inside = B.inside_count(n_pix, w, h, **tile, **shard)
     assert np.array_equal(inside, want_inside)
     if n_inside is not None:
-        assert len(inside) == 24 and int((inside > 0).sum()) == n_inside
+        assert len(inside) == {(40, 24): 24, (264, 512): 2176}[(w, h)] and int((inside > 0).sum()) == n_inside
+    if (w, h) == (264, 512) and not shard:   # the padding blocks: two in each of the 32 tiles of the ragged right-hand column (264 = 16 * 16 + 8)
+        assert int((inside == 0).sum()) == 64 and set(inside.tolist()) == {0, 64}
+        assert np.array_equal(np.flatnonzero(inside == 0) % 2, np.tile([1, 1], 32)) and len(set(np.flatnonzero(inside == 0) // 4)) == 32
+    if w % 8 or h % 8:
+        assert ((inside > 0) & (inside < 64)).any()                                                   # a block partly inside the film
     # a block is an 8 x 8 square of the film: its pixels' coordinates span 8 columns and 8 rows from a multiple of 8
-    x, y, _ = R.pixel_xy(n_pix, w, h, tile=tile, **shard)
+    x, y, in_film = R.pixel_xy(n_pix, w, h, **tile, **shard)
     bx, by = x[pixel], y[pixel]
     assert (bx.min(axis=1) % 8 == 0).all() and (by.min(axis=1) % 8 == 0).all()
     assert np.array_equal(bx - bx.min(axis=1, keepdims=True), np.tile(np.arange(64) % 8, (n_pix // 64, 1)))
     assert np.array_equal(by - by.min(axis=1, keepdims=True), np.tile(np.arange(64) // 8, (n_pix // 64, 1)))
-    assert int(B.inside_count((6 if tile == 16 else 2) * tile * tile, w, h, tile=tile).sum()) == w * h   # the whole film's blocks hold every pixel once
+    # every in-film pixel lies in exactly one block: no two compact pixels of the shard share a film pixel, and over the whole film every film pixel is hit
+    hits = np.bincount((y * w + x)[in_film], minlength=w * h)
+    assert hits.max() == 1 and (shard or hits.min() == 1)
+    whole = B.inside_count(tiles_film * tile_w * tile_h, w, h, **tile)
+    assert int(whole.sum()) == w * h                                                                  # the whole film's blocks hold every pixel once
+    if shard:                                                                                         # ... and the shards of one step share them out
+        parts = [B.inside_count(-(-(tiles_film - f) // step) * tile_w * tile_h, w, h, **tile, tile_first=f, tile_step=step) for f in range(step)]
+        assert sum(int(part.sum()) for part in parts) == w * h
+    # the mask of a set of blocks: their in-film pixels and nothing else
+    some = list(range(0, n_pix // 64, 3))
+    mask = B.keep_mask(some, n_pix, w, h, **tile, **shard)
+    assert mask.dtype == np.uint8 and mask.shape == (h, w) and int(mask.sum()) == int(inside[some].sum())
+    assert (mask[y[in_film], x[in_film]] == np.isin(block, some)[in_film]).all()
+
+
+def test_sizes_and_schedule_the_gpu_tests_rely_on(api):
+    """The figures tests/test_frame_sizes_gpu.py stands on, computed here: the 264 x 512 frame's blocks, compaction groups and noise partials, and the chunk
+    schedule restated (B.chunk_ends, B.pass_plan) against kyhip_pass_boundaries."""
+    n_pix = 544 * 256
+    inside = B.inside_count(n_pix, 264, 512)
+    assert (len(inside), int((inside > 0).sum()), int((inside == 0).sum())) == (2176, 2112, 64)
+    assert -(-2176 // 256) == 9 and 2176 % 256 == 128                                   # the compaction: 8 groups of 256 blocks and one of 128
+    partials = -(-n_pix // 256)
+    per = -(-partials // 256)
+    assert (partials, per, -(-partials // per), partials % per) == (544, 3, 182, 1)      # noise_final_kernel: three per thread, the 182nd thread has one
+    assert -(-(181 * 256) // 256) == 181                                                 # the shard 1 of 3: one per thread, 75 threads idle
+    for spp in (500, 512, 64, 25, 7, 1):
+        assert B.chunk_ends(spp) == api.pass_boundaries(spp), spp
+    plan = B.pass_plan(500, 100)
+    assert [p[2] for p in plan] == [112, 224, 324, 428, 500] and [p[1] for p in plan] == [6, 7, 8, 13, 17] and [p[0] for p in plan] == [0, 6, 13, 21, 34]
+    assert [p[2] for p in B.pass_plan(500, 1)] == B.chunk_ends(500) and B.pass_plan(500, 500) == [(0, 51, 500)]
+    assert B.pass_plan(64, 16) == [(0, 4, 16), (4, 4, 32), (8, 4, 48), (12, 4, 64)]
+    # 32 wavefronts x 256 CUs = 8192 slots: every render(100) pass of the whole frame, and of 1313 live blocks in pass 2, has more items
+    assert min(2176 * p[1] for p in plan) > 8192 and 1313 * plan[1][1] > 8192
 
 
 def test_retire_rule(api, check):
@@ -118,6 +183,24 @@ def test_retire_rule(api, check):
             got = _rule(check, q, qlive, values, qcls, 0.5, 0.25, 2, 224, 2)
             assert (got[block, 0] == 224) == retires
             assert np.array_equal(got, B.retire(qlive, values, qcls == 0, 0.5, 0.25, 2, 224, 2))
+    # `counted`, not 64, is what the fraction multiplies: a 44 x 21 film's corner block has 4 x 5 pixels inside.  With fraction 0.10, 0.10 * 20 = 2 lets two pixels
+    # lie above and not three, where 0.10 * 64 = 6.4 would let six: three above keep the corner block live and retire a whole block of the same film.
+    q = api.make_params(44, 21, 500)
+    _, qpixel, qinside = _geometry(check, q, n_pix)
+    _, _, q_in = R.pixel_xy(n_pix, 44, 21)
+    qcls = np.where(q_in, 0, 2).astype(np.uint8)
+    qlive = B.initial_state(qinside)
+    corner, whole = int(np.flatnonzero(qinside == 20)[0]), int(np.flatnonzero(qinside == 64)[0])
+    assert sorted(set(qinside.tolist())) == [0, 20, 32, 40, 64] and (qinside == 20).sum() == 1
+    for above, corner_retires in ((2, True), (3, False)):
+        assert (above <= float(np.float32(0.10)) * 20.0) == corner_retires and above <= float(np.float32(0.10)) * 64.0
+        values = np.zeros(n_pix, np.float32)
+        for block in (corner, whole):
+            values[qpixel[block, np.flatnonzero(q_in[qpixel[block]])[:above]]] = 1.0
+        values[~q_in] = 9.0
+        got = _rule(check, q, qlive, values, qcls, 0.5, 0.10, 2, 224, 2)
+        assert (got[corner, 0] == 224) == corner_retires and got[whole, 0] == 224
+        assert np.array_equal(got, B.retire(qlive, values, qcls == 0, 0.5, 0.10, 2, 224, 2))
     # the threshold itself is not above it
     values = np.full(n_pix, np.float32(0.008), np.float32)
     assert (_rule(check, p, live, values, cls, 0.008, 0.0, 2, 24, 2)[inside > 0, 0] == 24).all()

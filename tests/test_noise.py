@@ -91,6 +91,48 @@ def test_unequal_batches_match_the_numpy_restatement(check):
     assert (state[-1, :, 1] > 0).all() and np.isfinite(out[-1]).all()
 
 
+SHARD_1_3 = dict(tile_first=1, tile_step=3)
+# film, tile: the square tiles the kernels were first tested at, the tiles that are not square, the tile that is one block, films that are no multiple of 8, and
+# the frame of tests/test_frame_sizes_gpu.py (139 264 pixels: 544 partials of the statistics; as the shard 181 tiles, 181 partials)
+XY_CASES = [(40, 24, 16, 16), (40, 24, 32, 32), (40, 24, 32, 8), (40, 24, 8, 24), (40, 24, 8, 8)]
+XY_CASES += [(w, h, tw, th) for (w, h) in ((44, 21), (33, 17)) for (tw, th) in ((16, 16), (32, 8), (8, 24), (8, 8))] + [(264, 512, 16, 16)]
+
+
+@pytest.mark.parametrize("shard", [{}, SHARD_1_3], ids=["whole", "shard_1_3"])
+@pytest.mark.parametrize("w,h,tile_w,tile_h", XY_CASES, ids=["%dx%d_tile_%dx%d" % c for c in XY_CASES])
+def test_pixel_map(w, h, tile_w, tile_h, shard, A, api, check):
+    """noise_pixel_xy as the host runs it (through kyhostcheck_blocks: per block of 64 compact pixels, how many lie inside the film) against R.pixel_xy, and what
+    the map must be whatever the tile: tile by tile a tile_w x tile_h rectangle of the film in row order, no two tiles at one place.  (That the blocks built on
+    this map hold every pixel of the film once is tests/test_blocks.py::test_pixel_block_map's.)"""
+    check.kyhostcheck_blocks.restype, check.kyhostcheck_blocks.argtypes = A.KYHOSTCHECK_SYMBOLS["kyhostcheck_blocks"]
+    tile = dict(tile_w=tile_w, tile_h=tile_h)
+    tiles_x, tiles_y = -(-w // tile_w), -(-h // tile_h)
+    first, step = shard.get("tile_first", 0), shard.get("tile_step", 1)
+    n_tiles = -(-(tiles_x * tiles_y - first) // step)
+    n_pix = n_tiles * tile_w * tile_h
+    if (w, h) == (264, 512):
+        assert (n_tiles, -(-n_pix // 256)) == ((181, 181) if shard else (544, 544))
+    x, y, inside = R.pixel_xy(n_pix, w, h, **tile, **shard)
+    if tile_w == tile_h:   # `tile=` means a square tile
+        assert all(np.array_equal(a, b) for a, b in zip((x, y, inside), R.pixel_xy(n_pix, w, h, tile=tile_w, **shard)))
+    # the host's noise_pixel_xy: the in-film pixels of every block, the blocks' pixels located by the host too
+    p = api.make_params(w, h, 500, **tile, **shard)
+    pixel = np.full((n_pix // 64, 64), -1, np.int32)
+    count = np.full(n_pix // 64, -1, np.int32)
+    assert check.kyhostcheck_blocks(C.byref(p), None, pixel.ctypes.data, count.ctypes.data, None, 0, None, None, 0.0, 0.0, 2, 0, 0, None, 0, 0, 0, 0) == 0
+    assert np.array_equal(count, inside[pixel].sum(axis=1))
+    # a tile is a rectangle of the film in row order, at a tile's place of the grid, and no two tiles of a shard share a place
+    tx, ty = x.reshape(n_tiles, tile_h, tile_w), y.reshape(n_tiles, tile_h, tile_w)
+    assert (tx[:, 0, 0] % tile_w == 0).all() and (ty[:, 0, 0] % tile_h == 0).all()
+    assert np.array_equal(tx - tx[:, :1, :1], np.broadcast_to(np.arange(tile_w)[None, None, :], tx.shape))
+    assert np.array_equal(ty - ty[:, :1, :1], np.broadcast_to(np.arange(tile_h)[None, :, None], ty.shape))
+    place = (ty[:, 0, 0] // tile_h) * tiles_x + tx[:, 0, 0] // tile_w
+    assert len(set(place.tolist())) == n_tiles and place.max() < tiles_x * tiles_y
+    if w % tile_w or h % tile_h:
+        assert not inside.all() or shard                            # a ragged edge tile has padding
+    assert ((x[~inside] >= w) | (y[~inside] >= h)).all() and (x[inside] < w).all() and (y[inside] < h).all()
+
+
 def test_trailer_refusals(A, check):
     n_pix, base, done = 5, 200, 48
     def state(magic=R.NOISE_MAGIC, batches=2, n_prev=done, cut=0):
