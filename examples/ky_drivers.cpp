@@ -25,6 +25,8 @@
  *   ky_drivers adaptive [threshold] [spp] [w] [h]  the same frame rendered adaptively (0.008, 1024 spp, 1024 x 768): passes of 64, and after each the 8 x 8 pixel
  *                                blocks at most a tenth of whose pixels are noisier than the threshold retire (integrator_t::render_adaptive); writes adaptive.bmp:
  *                                the picture and, next to it, the sample-count map (white: the frame's total)
+ *   ky_drivers denoise [low_spp] [spp] [w] [h]  the same frame after its first low_spp samples (64 of 1024, 1024 x 768), in two passes, as the plain mean and through
+ *                                the edge-avoiding filter (integrator_t::render_denoised), next to the complete frame; writes denoise.bmp: raw | denoised | full
  * An optional last argument multiplies every spp (the reference's values are tiny because its CPU path is slow).
  * KY_DEVICES=all (or a count n: devices 0 .. n-1) makes every integrator spread its tiles over that many GPUs of the node
  * (integrator_t::set_devices); the images do not depend on it.
@@ -315,6 +317,25 @@ static void render_adaptive(float threshold, int spp, int width, int height) {
     film.store_image("adaptive");
 }
 
+// The headline frame early on, raw and denoised (integrator_t::render_denoised; include/kyhip.h, kyhip_frame_denoise), and complete: three cells side by side.  The
+// first two are the same samples: the frame's first passes, two of at least low_spp / 2 samples.
+static void render_denoise(int low_spp, int spp, int width, int height) {
+    film_grid_t film(1, 3, width, height);
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, film.get_resolution());
+    std::unique_ptr<sampler_t> sampler = std::make_unique<random_sampler_t>(spp);
+    std::unique_ptr<integrator_t> integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
+    const int per_pass = std::max(1, (low_spp + 1) / 2);
+    int raw_done = 0, passes = 0;
+    integrator->render_passes(&scene, sampler.get(), &film, per_pass, [&](int done, int) { raw_done = done; return ++passes < 2 || done < low_spp; });
+    film.next_subfilm();
+    int done = 0;
+    const double seconds = timing_seconds([&] { done = integrator->render_denoised(&scene, sampler.get(), &film, per_pass, low_spp); });
+    film.next_subfilm();
+    integrator->render(&scene, sampler.get(), &film);
+    std::printf("denoise: %dx%d, raw at %d and denoised at %d of %d spp (%.3f seconds with its passes), then the complete frame\n", width, height, raw_done, done, spp, seconds);
+    film.store_image("denoise");
+}
+
 // BASELINE.json configs[4]: the stress frame
 static void render_stress(int spp, int res) {
     film_t film(res, res);
@@ -345,6 +366,8 @@ int main(int argc, char* argv[]) {
             const float threshold = argc > 2 ? (float)std::atof(argv[2]) : 0.008f;
             if (!(threshold > 0.f)) { std::fprintf(stderr, "adaptive: a threshold above 0\n"); return 2; }
             render_adaptive(threshold, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768);
+        } else if (!std::strcmp(which, "denoise")) {
+            render_denoise(argc > 2 ? std::atoi(argv[2]) : 64, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768);
         } else if (!std::strcmp(which, "lighting_cells")) {
             render_lighting_cells(argc > 2 ? std::atoi(argv[2]) : 10, argc > 3 ? std::atoi(argv[3]) : 256);
         } else if (!std::strcmp(which, "batch")) {

@@ -488,6 +488,33 @@ int     kyhip_frame_block_stats(kyhip_frame* f, ky_block_stats* out);
 int     kyhip_frame_blocks_ms(const kyhip_frame* f, float* retire_ms, float* list_ms);
 
 /*
+ * The denoised picture so far (DESIGN.md section 3 "Denoise"): an edge-avoiding a-trous wavelet filter over the frame's normalised picture
+ * (kyhip_frame_resolve with normalise 1, before its clamp), guided by the per-pixel variance a tracking frame keeps and by the geometry at each pixel's first
+ * hit, which one kernel traces once per frame (the camera ray through the pixel centre; independent of kyhip_set_boxes).  Level k = 0 .. levels - 1 is a
+ * 5 x 5 B3-spline kernel with its taps 2^k pixels apart; a tap's weight is the spline's times max(0, n_p . n_q)^(2^normal_squarings), a plane distance term with
+ * sigma_plane and a luminance term with sigma_luminance against the locally averaged variance, which the filter carries through its levels.  The arithmetic is
+ * double precision without transcendentals (ky_amd/csrc/ky_denoise.hpp); two calls return identical bytes.
+ *
+ * kyhip_denoise_defaults: host only; the parameters a NULL `p` stands for.
+ * kyhip_frame_denoise: ADDS clamp01(filtered value) per pixel to the film exactly as kyhip_frame_resolve does (a sub-film's first pixel and its row stride; a
+ *   pinned film is added to in place).  levels == 0 IS kyhip_frame_resolve(f, 1, ...).  Pixels whose camera ray misses the scene (1), whose first hit carries an
+ *   area light (2) or whose flag word pins their value (3) pass through unfiltered and are no other pixel's tap; every other pixel is class 0.  On a
+ *   block-tracking frame each pixel is scaled and evaluated at its block's counts; blocks at 0 samples are class 1 and add nothing.
+ *   KY_ERR_INVALID_VALUE, before any device work and with the film untouched: levels outside 0 .. 6, normal_squarings outside 0 .. 10, a sigma that is not > 0;
+ *   a frame that does not track noise; a frame whose shard is not the whole film (tile_first 0, tile_step 1: a shard's neighbours live elsewhere); fewer than
+ *   two noise batches (no variance yet).  Nothing a checkpoint holds changes: a frame may be denoised any number of times, rendered further, or be complete.
+ * kyhip_frame_guides: WRITES width x height float4, y down, row_stride_px float4 apart: normal_t4 = {n.x, n.y, n.z, t} (the normal as the integrator sees it
+ *   and the hit distance), position_class4 = {P.x, P.y, P.z, class}; zeros beside the class where there is no hit.  Either pointer may be NULL.  The frame as
+ *   for kyhip_frame_denoise, but any number of batches.
+ * kyhip_frame_denoise_ms: hipEvent spans of the guide trace (set once per frame) and of the last call's gather, levels and add; negative where there was none.
+ */
+typedef struct ky_denoise_params { int32_t levels, normal_squarings; float sigma_luminance, sigma_plane; } ky_denoise_params;
+void    kyhip_denoise_defaults(ky_denoise_params* out);
+int     kyhip_frame_denoise(kyhip_frame* f, const ky_denoise_params* p, float* film_rgb, size_t film_row_stride_px);
+int     kyhip_frame_guides(kyhip_frame* f, float* normal_t4, float* position_class4, size_t row_stride_px);
+int     kyhip_frame_denoise_ms(const kyhip_frame* f, float* guides_ms, float* filter_ms);
+
+/*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent
  * kyhip_render* call on `device`, from hipEvents recorded on the launch stream around that one
  * kernel.  The stream must have been synchronised.  Negative if no timing is available.

@@ -82,6 +82,10 @@ class BlockStats(C.Structure):   # ky_block_stats
                 ("max_samples", C.c_int32), ("pixels", C.c_int64), ("pixel_samples", C.c_int64)]
 
 
+class DenoiseParams(C.Structure):   # ky_denoise_params
+    _fields_ = [("levels", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float)]
+
+
 FP = C.POINTER(C.c_float)
 SP = C.POINTER(Scene)
 PP = C.POINTER(RenderParams)
@@ -152,6 +156,10 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_sample_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "kyhip_frame_block_stats": (C.c_int, [C.c_void_p, C.POINTER(BlockStats)]),
     "kyhip_frame_blocks_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "kyhip_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
+    "kyhip_frame_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_size_t]),
+    "kyhip_frame_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_denoise_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -194,6 +202,8 @@ KYHOST_SYMBOLS = {
                                       C.c_float, C.c_float, C.c_int, C.c_int]),
     "kyhost_render_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                          C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.POINTER(BlockStats)]),
+    "kyhost_render_denoised": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_int, C.POINTER(DenoiseParams)]),
     "kyhost_store_image": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhost_gamma_encoding": (C.c_int, [C.c_float]),
 }
@@ -215,6 +225,7 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
                                     C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int]),
     "kyhostcheck_blocks": (C.c_int, [PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int]),
+    "kyhostcheck_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_double, C.c_void_p]),
     "kyhostcheck_add_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_seam_stress": (C.c_int, [C.c_int]),
     "kyhostcheck_jit_stress": (C.c_int, [C.c_int, C.c_int]),

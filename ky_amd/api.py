@@ -110,12 +110,20 @@ def pass_boundaries(spp):
     return list(out)
 
 
+def denoise_defaults():
+    """kyhip_denoise_defaults (host only) as a ky_denoise_params (_abi.DenoiseParams)."""
+    q = A.DenoiseParams()
+    A.load_kyhip().kyhip_denoise_defaults(C.byref(q))
+    return q
+
+
 class Frame:
     """A frame rendered in passes (kyhip_frame_*): `with Frame(scene, params) as f: f.render(64); preview = f.resolve(normalise=True); ...`.
     params.samples_per_pixel is the frame's total; a complete frame's resolve() is render(scene, params), bit for bit.
     noise=True: the frame keeps a per-pixel noise estimate over its passes (kyhip_frame_track_noise): noise(), noise_stats(threshold), render_until(...).
     blocks=True: the frame retires 8 x 8 pixel blocks between its passes and renders the live ones only (kyhip_frame_track_blocks): keep(mask),
-    retire_noisy(...) and render_adaptive(...) (these two with noise=True), sample_map(), block_stats(); resolve(normalise=True) is then per block."""
+    retire_noisy(...) and render_adaptive(...) (these two with noise=True), sample_map(), block_stats(); resolve(normalise=True) is then per block.
+    A frame with noise=True whose shard is the whole film can be denoised between passes: denoise(), guides(), denoise_ms()."""
 
     def __init__(self, scene, params, device=0, noise=False, blocks=False):
         self._lib = A.load_kyhip()
@@ -246,6 +254,35 @@ class Frame:
         _check(self._lib.kyhip_frame_block_stats(self._f, C.byref(st)), self._lib)
         return st
 
+    def denoise(self, params=None, film=None, row_stride_px=None, origin_px=(0, 0)):
+        """ADDS the denoised picture so far to `film` (a new zero film by default) and returns it (kyhip_frame_denoise): resolve(normalise=True) through an
+        edge-avoiding a-trous filter guided by the frame's variance estimate and its first-hit geometry.  params: a ky_denoise_params (_abi.DenoiseParams) or a dict
+        of its fields over denoise_defaults(); None: the defaults.  levels=0 is resolve(normalise=True)."""
+        if isinstance(params, dict):
+            q = denoise_defaults()
+            for name, value in params.items():
+                setattr(q, name, value)
+            params = q
+        if film is None:
+            film = np.zeros((self.height, self.width, 3), np.float32)
+        stride = film.shape[1] if row_stride_px is None else row_stride_px
+        base = film.ctypes.data + (origin_px[1] * stride + origin_px[0]) * 12
+        _check(self._lib.kyhip_frame_denoise(self._f, None if params is None else C.byref(params), C.c_void_p(base), stride), self._lib)
+        return film
+
+    def guides(self):
+        """kyhip_frame_guides: ((H, W, 4) {n.x, n.y, n.z, t}, (H, W, 4) {P.x, P.y, P.z, class}) float32 of the camera rays through the pixel centres; class 0
+        surface, 1 miss, 2 a surface that carries an area light, 3 flagged."""
+        a, b = np.zeros((self.height, self.width, 4), np.float32), np.zeros((self.height, self.width, 4), np.float32)
+        _check(self._lib.kyhip_frame_guides(self._f, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), self.width), self._lib)
+        return a, b
+
+    def denoise_ms(self):
+        """kyhip_frame_denoise_ms: (the guide trace, the last denoise()'s gather + levels + add) in ms, negative where there was none."""
+        a, b = C.c_float(-1), C.c_float(-1)
+        _check(self._lib.kyhip_frame_denoise_ms(self._f, C.byref(a), C.byref(b)), self._lib)
+        return a.value, b.value
+
     def load(self, state):
         """Continue from a checkpoint of a frame begun with the same scene and params (kyhip_frame_load); any other state raises KyError."""
         state = bytes(state)
@@ -357,6 +394,22 @@ def render_adaptive_host_api(scene, integrator_enum, depth, direct_sample, sampl
     if rc != 0:
         raise KyError("kyhost_render_adaptive failed: " + host.kyhost_last_error().decode())
     return film, counts, st
+
+
+def render_denoised_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, min_samples_per_pass, stop_after_samples, params=None,
+                             seed=1234, film=None, device=0):
+    """create_integrator(...)->render_denoised(&scene, sampler, &film, min_samples_per_pass, stop_after_samples, params) through the C++ host classes: (the film
+    with the denoised picture so far added, the samples done per pixel).  params: an _abi.DenoiseParams, None for the library's defaults."""
+    host = A.load_kyhost()
+    if film is None:
+        film = np.zeros((height, width, 3), np.float32)
+    rc = host.kyhost_render_denoised(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device,
+                                     int(min_samples_per_pass), int(stop_after_samples), None if params is None else C.byref(params))
+    if rc == -2:
+        return None
+    if rc < 0:
+        raise KyError("kyhost_render_denoised failed: " + host.kyhost_last_error().decode())
+    return film, rc
 
 
 def debug_area_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, begin, end, film=None, seed=1234, device=0):

@@ -1,0 +1,134 @@
+/*
+ * ky_denoise.hip -- the kernels of a frame's denoised picture (ky_denoise.hpp; DESIGN.md "Denoise"), film-sized and apart from the render kernels, which they read
+ * a frame between the passes of like noise_map_kernel and blocks_retire_kernel do:
+ *   denoise_guides_kernel   once per frame, one thread per film pixel: the camera ray through the pixel centre (generate_ray) and its nearest hit WITHOUT the box
+ *                           traversal (trace_nearest; the slab test moves t by a few ulp, and the guides do not depend on kyhip_set_boxes) -> {n, t}, {P, class}; the
+ *                           scene's tables staged in LDS as the KAT kernels stage them (the product's device functions, ky_device.hpp, called directly);
+ *   denoise_gather_kernel   one thread per pixel of the compact tile buffer: film_add_kernel's de-interleave (noise_pixel_xy) -> {r, g, b, v} in film order and
+ *                           the pixel's class as the frame's state gives it (flagged: 3; a block at 0 samples: 1); a ragged tile's padding writes nothing;
+ *   denoise_level_kernel    one thread per film pixel, 256-thread workgroups: level_pixel (ky_denoise.hpp) from one film-order buffer into the other; every tap is
+ *                           three 16-byte loads from global memory;
+ *   denoise_add_kernel      clamp01 per channel, then film_t::add_color into a device film or a pinned host film.
+ * No floating-point atomics and no order that depends on scheduling: two calls return identical bytes.  gfx950 only.
+ */
+#include <hip/hip_runtime.h>
+
+#include "ky_device.hpp"
+
+#include "ky_blocks.hpp"
+#include "ky_ctx.hpp"
+#include "ky_denoise.hpp"
+
+using namespace kyd;
+using namespace kyh;
+using namespace kydn;
+using kyb::BlockState;
+using kyn::NoisePixel;
+
+static_assert(sizeof(Px4) == 16 && alignof(Px4) == 16, "a pixel of the filter's buffers is one 16-byte load");
+
+__global__ __launch_bounds__(KY_DN_BLOCK) void denoise_guides_kernel(const DScene* __restrict__ S_, int width, int height, Px4* __restrict__ ga, Px4* __restrict__ gb) {
+    const SceneRef S{S_, true, 0, true};
+    const LdsScene Lds = stage_scene<true>(S);   // the scene-sized dynamic block, as the KAT kernels take it; ends with a barrier
+    const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
+    if (i >= width * height) return;
+    const int x = i % width, y = i / width;
+    f3 o, d;
+    generate_ray(S, (float)x + 0.5f, (float)y + 0.5f, o, d);
+    float t = K_INF;
+    const int hs = trace_nearest(S, o, d, t);
+    Px4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, (float)KY_DN_MISS};
+    if (hs >= 0) {
+        const f3 p = o + t * d;
+        const f3 n = hit_normal(Lds.hit[hs], p, d);
+        a = Px4{n.x, n.y, n.z, t};
+        b = Px4{p.x, p.y, p.z, Lds.hit[hs].area_light >= 0 ? (float)KY_DN_LIGHT : (float)KY_DN_SURFACE};
+    }
+    ga[i] = a;
+    gb[i] = b;
+}
+
+__global__ __launch_bounds__(KY_DN_BLOCK) void denoise_gather_kernel(const unsigned long long* __restrict__ accum, const unsigned* __restrict__ flags,
+                                                                      const NoisePixel* __restrict__ state, const BlockState* __restrict__ blocks, ShardConst sh, int width,
+                                                                      int height, int total_spp, int n_done, int batches, const Px4* __restrict__ gb_traced,
+                                                                      Px4* __restrict__ cv, Px4* __restrict__ gb) {
+    const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
+    if (i >= sh.n_pix) return;
+    int x, y;
+    kyn::noise_pixel_xy(sh, i, x, y);
+    if (x >= width || y >= height) return;
+    if (blocks) {   // a retired block's pixels stand at the counts it retired with
+        const BlockState b = blocks[kyb::block_of_pixel(sh, i)];
+        if (b.retired_at >= 0) { batches = b.batches; n_done = b.retired_at; }
+    }
+    const unsigned fl = flags[i];
+    const size_t at = (size_t)y * (size_t)width + (size_t)x;
+    Px4 g = gb_traced[at];
+    if (n_done <= 0) g.w = (float)KY_DN_MISS;
+    else if (fl & 0x1ffu) g.w = (float)KY_DN_FLAGGED;
+    cv[at] = gather_pixel((long long)accum[3 * (size_t)i], (long long)accum[3 * (size_t)i + 1], (long long)accum[3 * (size_t)i + 2], fl, state[i].m2, total_spp, n_done, batches);
+    gb[at] = g;
+}
+
+__global__ __launch_bounds__(KY_DN_BLOCK) void denoise_level_kernel(const Px4* __restrict__ cv_in, Px4* __restrict__ cv_out, const Px4* __restrict__ ga,
+                                                                     const Px4* __restrict__ gb, int step, LevelConst k) {
+    const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
+    if (i >= k.width * k.height) return;
+    cv_out[i] = level_pixel(cv_in, ga, gb, i % k.width, i / k.width, step, k);
+}
+
+__global__ __launch_bounds__(KY_DN_BLOCK) void denoise_add_kernel(const Px4* __restrict__ cv, float* __restrict__ film, size_t stride_px, int width, int height) {
+    const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
+    if (i >= width * height) return;
+    const int x = i % width, y = i / width;
+    const Px4 c = cv[i];
+    float* px = film + ((size_t)y * stride_px + (size_t)x) * 3;
+    px[0] += fminf(fmaxf(c.x, 0.f), 1.f); px[1] += fminf(fmaxf(c.y, 0.f), 1.f); px[2] += fminf(fmaxf(c.z, 0.f), 1.f);
+}
+
+namespace kydn {
+static dim3 film_grid(int width, int height) { return dim3((unsigned)((width * height + KY_DN_BLOCK - 1) / KY_DN_BLOCK)); }
+
+int denoise_guides_device(int device, const ky_scene* scene, int width, int height, void* ga, void* gb, void* stream_) {
+    if (width <= 0 || height <= 0) return KY_OK;
+    DeviceCtx* c;
+    KY_TRY(get_ctx(device, &c));
+    std::lock_guard<std::mutex> lock(c->m);
+    hipStream_t stream = (hipStream_t)stream_;
+    SceneSlot* sc;
+    KY_TRY(upload_scene(c, scene, stream, &sc));
+    const size_t lds = (size_t)lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
+    hipLaunchKernelGGL(denoise_guides_kernel, film_grid(width, height), dim3(KY_DN_BLOCK), lds, stream, (const DScene*)sc->d, width, height, (Px4*)ga, (Px4*)gb);
+    const hipError_t launched = hipGetLastError();
+    const hipError_t done = hipStreamSynchronize(stream);   // (under the lock: the slot is this kernel's until it is done)
+    HIP_TRY(launched);
+    HIP_TRY(done);
+    return KY_OK;
+}
+
+int denoise_gather_device(const void* ws, const void* noise_state, const void* blocks, const ShardConst& sh, int width, int height, int total_spp, int n_done, int batches,
+                          const void* gb_traced, void* cv, void* gb, void* stream) {
+    if (sh.n_pix <= 0) return KY_OK;
+    const unsigned long long* accum = (const unsigned long long*)ws;
+    const unsigned* flags = (const unsigned*)(accum + (size_t)sh.n_pix * 3);
+    hipLaunchKernelGGL(denoise_gather_kernel, dim3((unsigned)((sh.n_pix + KY_DN_BLOCK - 1) / KY_DN_BLOCK)), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, accum, flags,
+                       (const NoisePixel*)noise_state, (const BlockState*)blocks, sh, width, height, total_spp, n_done, batches, (const Px4*)gb_traced, (Px4*)cv, (Px4*)gb);
+    HIP_TRY(hipGetLastError());
+    return KY_OK;
+}
+
+int denoise_level_device(const void* cv_in, void* cv_out, const void* ga, const void* gb, int step, const LevelConst& k, void* stream) {
+    if (k.width <= 0 || k.height <= 0) return KY_OK;
+    hipLaunchKernelGGL(denoise_level_kernel, film_grid(k.width, k.height), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, (const Px4*)cv_in, (Px4*)cv_out, (const Px4*)ga,
+                       (const Px4*)gb, step, k);
+    HIP_TRY(hipGetLastError());
+    return KY_OK;
+}
+
+int denoise_add_device(const void* cv, float* film, size_t stride_px, int width, int height, void* stream) {
+    if (width <= 0 || height <= 0) return KY_OK;
+    hipLaunchKernelGGL(denoise_add_kernel, film_grid(width, height), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, (const Px4*)cv, film, stride_px, width, height);
+    HIP_TRY(hipGetLastError());
+    return KY_OK;
+}
+}  // namespace kydn

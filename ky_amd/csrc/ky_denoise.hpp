@@ -1,0 +1,145 @@
+/*
+ * ky_denoise.hpp -- the denoised picture of a frame rendered in passes (kyhip_frame_denoise ...; DESIGN.md "Denoise"): an edge-avoiding a-trous wavelet filter
+ * over the frame's normalised picture, guided by the variance of each pixel's mean luminance (the quantity ky_noise.hpp's noise_value takes its square root of)
+ * and by the geometry at the pixel's first hit.  The arithmetic is written ONCE here, as KY_HD functions with floating-point contraction off: the device kernels
+ * (ky_denoise.hip), the host-only builds (kyhostcheck_denoise, ky_hostcheck.cpp) and a NumPy restatement (tests/denoise_restatement.py) round alike.  All of it is
+ * DOUBLE arithmetic on float32 inputs -- + - x /, max and comparisons, nothing transcendental: the library's fp32 division is not correctly rounded and could not
+ * be restated, double division is -- and what one level hands to the next is stored as float32.  Plain C++: part of `make sanitize`.
+ */
+#pragma once
+#include <cstdint>
+
+#include "ky_noise.hpp"   // ky_shard.hpp, KY_NOFMA_*, noise_pixel_xy
+
+namespace kydn {
+// 16 bytes, 16-byte aligned: every buffer of the filter is read and written a whole pixel at a time
+struct alignas(16) Px4 {
+    float x, y, z, w;
+};
+// the three film-order buffers a level reads per tap:
+//   colour / variance  {r, g, b, v}       the normalised picture (unclamped) and the variance of the pixel's mean luminance
+//   guide A            {n.x, n.y, n.z, t} the normal as the integrator sees it and the hit distance
+//   guide B            {P.x, P.y, P.z, class}
+enum { KY_DN_SURFACE = 0, KY_DN_MISS = 1, KY_DN_LIGHT = 2, KY_DN_FLAGGED = 3 };   // a pixel's class; every class but 0 passes through and is nobody's tap
+constexpr int KY_DN_MAX_LEVELS = 6, KY_DN_MAX_SQUARINGS = 10;
+// what a level needs beside its buffers and its step
+struct LevelConst {
+    int width, height;
+    int normal_squarings, pad_;
+    double sigma_l2;        // sigma_luminance^2
+    double sigma_plane;
+    double pix;             // the width of a pixel at unit distance: 2 |camera.right| / width
+};
+
+// the B3 spline's taps (1 4 6 4 1) / 16 and the variance prefilter's (1 2 1) / 4, by distance from the centre (no table: nothing of a level lives in scratch)
+KY_HD inline double tap5(int i) { const int k = i < 0 ? -i : i; return k == 0 ? 0.375 : k == 1 ? 0.25 : 0.0625; }
+KY_HD inline double tap3(int i) { return i == 0 ? 0.5 : 0.25; }
+// color_t::luminance()'s weights (ky.cpp:249-255)
+KY_NOFMA_FN KY_HD inline double luminance(const Px4& c) {
+    KY_NOFMA_BODY
+    return 0.212671 * (double)c.x + 0.715160 * (double)c.y + 0.072169 * (double)c.z;
+}
+
+// One pixel's {r, g, b, v} from its three accumulator words, its flag word and its noise pair: the accumulator x total / n / 2^32 (what resolve_frame_kernel and
+// blocks_resolve_kernel compute before their clamp; n the samples of the pixel's block), v = m2 / (batches - 1) / n with the block's own counts, 0 before the
+// second batch.  A flagged pixel (class 3) holds what the flag rules pin it to (film_value, ky_film_value.hpp): it passes through.
+KY_NOFMA_FN KY_HD inline Px4 gather_pixel(long long r, long long g, long long b, unsigned fl, double m2, int total_spp, int n, int batches) {
+    KY_NOFMA_BODY
+    Px4 o;
+    const double scale = n > 0 ? (double)total_spp / (double)n : 0.0;
+    float c[3] = {(float)((double)r * (1.0 / KY_FIX_SCALE) * scale), (float)((double)g * (1.0 / KY_FIX_SCALE) * scale), (float)((double)b * (1.0 / KY_FIX_SCALE) * scale)};
+    if (fl & 0x1ffu) {
+        for (int ch = 0; ch < 3; ++ch) {
+            const bool nan = (fl >> ch) & 1u, pinf = (fl >> (3 + ch)) & 1u, ninf = (fl >> (6 + ch)) & 1u;
+            float v = c[ch];
+            if (pinf) v = 1.f;
+            if (ninf) v = 0.f;
+            if (nan || (pinf && ninf)) v = 0.f;
+            c[ch] = v < 0.f ? 0.f : v > 1.f ? 1.f : v;
+        }
+    }
+    o.x = c[0]; o.y = c[1]; o.z = c[2];
+    o.w = (batches >= 2 && n > 0) ? (float)(m2 / (double)(batches - 1) / (double)n) : 0.f;
+    return o;
+}
+
+KY_HD inline bool is_surface(const Px4& gb) { return gb.w == (float)KY_DN_SURFACE; }
+
+// One level at pixel (x, y) with its taps `step` pixels apart: the pixel's new {r, g, b, v}.  cv, ga, gb: width x height, film order.
+//   v_bar  the (1 2 1)^T (1 2 1) / 16 average of v over the class-0 neighbours at distance 1 inside the film, renormalised by the weights used
+//   tap q = p + (i, j) step, i, j = -2 .. 2 in row-major (j, i) order, inside the film and class 0:
+//     h  = B[i] B[j]
+//     wn = max(0, n_p . n_q) squared normal_squarings times
+//     wp = 1 / (1 + xp^2)^2,  xp   = n_p . (P_q - P_p) / (sigma_plane t_p pix step)
+//     wl = 1 / (1 + xl2)^2,   xl2  = (Y_p - Y_q)^2 / (sigma_luminance^2 v_bar + 1e-10)
+//     w  = h wn wp wl
+//   c' = sum w c_q / sum w,  v' = sum w^2 v_q / (sum w)^2.  The centre tap has w = 9 / 64: sum w > 0.
+// Pixels that are not class 0 pass through.
+KY_NOFMA_FN KY_HD inline Px4 level_pixel(const Px4* __restrict__ cv, const Px4* __restrict__ ga, const Px4* __restrict__ gb, int x, int y, int step, const LevelConst& k) {
+    KY_NOFMA_BODY
+    const size_t at = (size_t)y * (size_t)k.width + (size_t)x;
+    const Px4 cp = cv[at], bp = gb[at];
+    if (!is_surface(bp)) return cp;
+    const Px4 ap = ga[at];
+    double vw = 0.0, vs = 0.0;
+    for (int j = -1; j <= 1; ++j)
+        for (int i = -1; i <= 1; ++i) {
+            const int qx = x + i, qy = y + j;
+            if (qx < 0 || qy < 0 || qx >= k.width || qy >= k.height) continue;
+            const size_t q = (size_t)qy * (size_t)k.width + (size_t)qx;
+            if (!is_surface(gb[q])) continue;
+            const double h = tap3(i) * tap3(j);
+            vw = vw + h;
+            vs = vs + h * (double)cv[q].w;
+        }
+    const double v_bar = vs / vw;
+    const double lum_den = k.sigma_l2 * v_bar + 1e-10;
+    const double plane_raw = k.sigma_plane * (double)ap.w * k.pix * (double)step;
+    const double plane_den = plane_raw > 1e-300 ? plane_raw : 1e-300;
+    const double yp = luminance(cp);
+    const double npx = (double)ap.x, npy = (double)ap.y, npz = (double)ap.z;
+    double sw = 0.0, sr = 0.0, sg = 0.0, sb = 0.0, sv = 0.0;
+    for (int j = -2; j <= 2; ++j)
+        for (int i = -2; i <= 2; ++i) {
+            const int qx = x + i * step, qy = y + j * step;
+            if (qx < 0 || qy < 0 || qx >= k.width || qy >= k.height) continue;
+            const size_t q = (size_t)qy * (size_t)k.width + (size_t)qx;
+            const Px4 bq = gb[q];
+            if (!is_surface(bq)) continue;
+            const Px4 aq = ga[q], cq = cv[q];
+            const double nd = npx * (double)aq.x + npy * (double)aq.y + npz * (double)aq.z;
+            double wn = nd > 0.0 ? nd : 0.0;
+            for (int s = 0; s < k.normal_squarings; ++s) wn = wn * wn;
+            const double dx = (double)bq.x - (double)bp.x, dy = (double)bq.y - (double)bp.y, dz = (double)bq.z - (double)bp.z;
+            const double xp = (npx * dx + npy * dy + npz * dz) / plane_den;
+            const double pa = 1.0 + xp * xp;
+            const double wp = 1.0 / (pa * pa);
+            const double dl = yp - luminance(cq);
+            const double la = 1.0 + dl * dl / lum_den;
+            const double wl = 1.0 / (la * la);
+            const double w = tap5(i) * tap5(j) * wn * wp * wl;
+            sw = sw + w;
+            sr = sr + w * (double)cq.x;
+            sg = sg + w * (double)cq.y;
+            sb = sb + w * (double)cq.z;
+            sv = sv + w * w * (double)cq.w;
+        }
+    Px4 o;
+    o.x = (float)(sr / sw); o.y = (float)(sg / sw); o.z = (float)(sb / sw);
+    o.w = (float)(sv / (sw * sw));
+    return o;
+}
+
+// ---- the kernels (ky_denoise.hip); every pointer is device memory, `stream` a hipStream_t ----
+constexpr int KY_DN_BLOCK = 256;
+// guides of the whole film, traced once per frame: ga = {n, t}, gb = {P, class 0 / 1 / 2}.  Uploads the scene, enqueues and WAITS (the scene cache's slot is held
+// by the context's lock until the kernel is done).
+int denoise_guides_device(int device, const ky_scene* scene, int width, int height, void* ga, void* gb, void* stream);
+// compact tile order -> film order: cv = gather_pixel, gb = the traced guide with the class the frame's state gives it (3: flagged; 1: a block at 0 samples)
+// (blocks: NULL, or the kyb::BlockState of every block of a frame that retires blocks, whose pixels stand at their block's own counts)
+int denoise_gather_device(const void* ws, const void* noise_state, const void* blocks, const ShardConst& sh, int width, int height, int total_spp, int n_done, int batches,
+                          const void* gb_traced, void* cv, void* gb, void* stream);
+int denoise_level_device(const void* cv_in, void* cv_out, const void* ga, const void* gb, int step, const LevelConst& k, void* stream);
+// clamp01 per channel and ADD into a film (device memory, or the device alias of a pinned host film): film_t::add_color
+int denoise_add_device(const void* cv, float* film, size_t stride_px, int width, int height, void* stream);
+}  // namespace kydn

@@ -15,10 +15,12 @@
 
 #include "ky_checkpoint.hpp"
 #include "ky_ctx.hpp"
+#include "ky_denoise.hpp"
 
 using namespace kyh;
 using namespace kyn;
 using namespace kyb;
+using namespace kydn;
 
 // An event pair around the last kernel of a kind, for the _ms entries: -1 until `valid` is set, behind the wait for a span that was enqueued whole
 struct TimedSpan {
@@ -51,6 +53,13 @@ struct BlockTrack {
     std::vector<int> inside;           // per block, its pixels inside the film
     TimedSpan rule, list;              // the last retire / keep kernel; the last compaction (kyhip_frame_blocks_ms)
 };
+// what kyhip_frame_denoise keeps between calls (no part of a checkpoint): the guides, traced once per frame, and the filter's film-order buffers
+struct DenoiseTrack {
+    bool guides_done = false;
+    DevBuf ga, gb_traced, gb, cv[2];   // width x height Px4 each: {n, t}; {P, class} as traced and as the frame's state classes it now; the levels' ping-pong
+    std::vector<float> hga, hgb;       // host copies of the guides (kyhip_frame_guides)
+    TimedSpan guides, filter;          // the guide trace; the last call's gather, levels and add (kyhip_frame_denoise_ms)
+};
 struct kyhip_frame {
     int device = 0;
     ky_render_params params{};
@@ -71,6 +80,7 @@ struct kyhip_frame {
     std::vector<float> stage;     // ... and its host copy
     NoiseTrack noise;
     BlockTrack blocks;
+    DenoiseTrack denoise;
 };
 
 static int samples_done(const kyhip_frame* f) { return chunk_end(f->plan, f->chunks_done - 1); }
@@ -507,6 +517,121 @@ int kyhip_frame_noise_ms(const kyhip_frame* f, float* update_ms, float* stats_ms
     KY_TRY(frame_tracks(f, false, true));
     if (update_ms) *update_ms = f->noise.update.ms();
     if (stats_ms) *stats_ms = f->noise.stats.ms();
+    return KY_OK;
+}
+
+// ---- the denoised picture (DESIGN.md "Denoise") ----
+// what the denoise entries refuse of a frame, after their other arguments: KY_OK, or KY_ERR_INVALID_VALUE with the message
+static int denoise_frame_check(const kyhip_frame* f, bool needs_variance) {
+    KY_TRY(frame_tracks(f, false, true));
+    if (f->params.tile_first != 0 || f->params.tile_step != 1)
+        return fail(KY_ERR_INVALID_VALUE, "the frame's shard (tile_first %d, tile_step %d) is not the whole film: a shard's neighbours live elsewhere", f->params.tile_first, f->params.tile_step);
+    if (needs_variance && f->noise.batches < 2) return fail(KY_ERR_INVALID_VALUE, "%d noise batches: the filter needs a variance, two passes or more", f->noise.batches);
+    return KY_OK;
+}
+// the filter's buffers, the guides (traced on the first call) and the gather of the frame's state as it stands: enqueued, the trace also waited for
+static int denoise_prepare(kyhip_frame* f, DeviceCtx* c, bool timed) {
+    DenoiseTrack& d = f->denoise;
+    const ky_render_params* p = &f->params;
+    const size_t bytes = (size_t)p->width * (size_t)p->height * sizeof(Px4);
+    for (DevBuf* b : {&d.ga, &d.gb_traced, &d.gb, &d.cv[0], &d.cv[1]})
+        if (!b->p) HIP_TRY(b->alloc(bytes));
+    KY_TRY(d.guides.create());
+    KY_TRY(d.filter.create());
+    if (!d.guides_done) {
+        d.guides.begin(c->stream);
+        const int rcode = denoise_guides_device(f->device, &f->scene, p->width, p->height, d.ga.p, d.gb_traced.p, c->stream);
+        d.guides.end(c->stream);
+        KY_TRY(finish(c->stream, rcode, "denoise guides"));
+        d.guides.valid = d.guides_done = true;
+    }
+    if (timed) {   // (kyhip_frame_denoise: its span begins with the gather)
+        d.filter.valid = false;
+        d.filter.begin(c->stream);
+    }
+    return denoise_gather_device(f->ws.p, f->noise.state.p, block_state_or_null(f), f->sh, p->width, p->height, p->samples_per_pixel, samples_done(f), f->noise.batches,
+                                 d.gb_traced.p, d.cv[0].p, d.gb.p, c->stream);
+}
+
+int kyhip_frame_denoise(kyhip_frame* f, const ky_denoise_params* params, float* film_rgb, size_t stride_px) {
+    ky_denoise_params q;
+    kyhip_denoise_defaults(&q);
+    if (params) q = *params;
+    KY_TRY(denoise_params_check(&q));
+    KY_TRY(denoise_frame_check(f, true));
+    const ky_render_params* p = &f->params;
+    if (!film_rgb || stride_px < (size_t)p->width) return fail(KY_ERR_INVALID_VALUE, "bad film arguments");
+    if (q.levels == 0) return kyhip_frame_resolve(f, 1, film_rgb, stride_px);
+    if (f->sh.n_pix == 0) return KY_OK;
+    DeviceCtx* c;
+    KY_TRY(get_ctx(f->device, &c));
+    DenoiseTrack& d = f->denoise;
+    int rcode = denoise_prepare(f, c, true);
+    if (rcode != KY_OK) return finish(c->stream, rcode, "denoise");   // (nothing of the filter is enqueued; its span stays invalid)
+    LevelConst k{};
+    k.width = p->width; k.height = p->height;
+    k.normal_squarings = q.normal_squarings;
+    k.sigma_l2 = (double)q.sigma_luminance * (double)q.sigma_luminance;
+    k.sigma_plane = (double)q.sigma_plane;
+    k.pix = denoise_pixel_width(f->scene.camera, p->width);
+    for (int l = 0; l < q.levels && rcode == KY_OK; ++l) rcode = denoise_level_device(d.cv[l & 1].p, d.cv[(l + 1) & 1].p, d.ga.p, d.gb.p, 1 << l, k, c->stream);
+    const void* result = d.cv[q.levels & 1].p;
+    const size_t span = ((size_t)(p->height - 1) * stride_px + (size_t)p->width) * 3 * sizeof(float);
+    if (float* alias = film_in_place_alias(film_rgb, span)) {   // a pinned film: added to where it lies
+        if (rcode == KY_OK) rcode = denoise_add_device(result, alias, stride_px, p->width, p->height, c->stream);
+        d.filter.end(c->stream);
+        KY_TRY(finish(c->stream, rcode, "denoise"));
+        d.filter.valid = true;
+        return KY_OK;
+    }
+    // any other film: added into the frame's device film, brought home, added by the host (kyhip_frame_resolve's path)
+    const size_t film_floats = (size_t)p->width * p->height * 3;
+    if (!f->film.p && rcode == KY_OK) {
+        const hipError_t e = f->film.alloc(film_floats * sizeof(float));
+        if (e != hipSuccess) rcode = fail(KY_ERR_DEVICE, "denoise failed: %s", hipGetErrorString(e));
+    }
+    if (rcode == KY_OK) {
+        f->stage.resize(film_floats);
+        const hipError_t e = hipMemsetAsync(f->film.p, 0, film_floats * sizeof(float), c->stream);
+        if (e != hipSuccess) rcode = fail(KY_ERR_DEVICE, "denoise failed: %s", hipGetErrorString(e));
+    }
+    if (rcode == KY_OK) rcode = denoise_add_device(result, f->film.as<float>(), (size_t)p->width, p->width, p->height, c->stream);
+    d.filter.end(c->stream);
+    KY_TRY(finish(c->stream, rcode, "denoise"));
+    d.filter.valid = true;
+    const hipError_t e = hipMemcpy(f->stage.data(), f->film.p, film_floats * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(KY_ERR_DEVICE, "denoise failed: %s", hipGetErrorString(e));
+    host_add_rows(film_rgb, stride_px, f->stage.data(), p->width, 0, p->height);
+    return KY_OK;
+}
+
+int kyhip_frame_guides(kyhip_frame* f, float* normal_t4, float* position_class4, size_t stride_px) {
+    KY_TRY(denoise_frame_check(f, false));
+    const ky_render_params* p = &f->params;
+    if (stride_px < (size_t)p->width) return fail(KY_ERR_INVALID_VALUE, "row_stride_px %zu: the guides' rows are %d pixels", stride_px, p->width);
+    if (f->sh.n_pix == 0) return KY_OK;
+    DeviceCtx* c;
+    KY_TRY(get_ctx(f->device, &c));
+    DenoiseTrack& d = f->denoise;
+    const int rcode = denoise_prepare(f, c, false);
+    KY_TRY(finish(c->stream, rcode, "denoise guides"));
+    const size_t n = (size_t)p->width * (size_t)p->height * 4;
+    d.hga.resize(n);
+    d.hgb.resize(n);
+    HIP_TRY(hipMemcpy(d.hga.data(), d.ga.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(d.hgb.data(), d.gb.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    for (int y = 0; y < p->height; ++y) {
+        const size_t row = (size_t)p->width * 4 * sizeof(float);
+        if (normal_t4) std::memcpy(normal_t4 + (size_t)y * stride_px * 4, d.hga.data() + (size_t)y * p->width * 4, row);
+        if (position_class4) std::memcpy(position_class4 + (size_t)y * stride_px * 4, d.hgb.data() + (size_t)y * p->width * 4, row);
+    }
+    return KY_OK;
+}
+
+int kyhip_frame_denoise_ms(const kyhip_frame* f, float* guides_ms, float* filter_ms) {
+    KY_TRY(frame_tracks(f, false, true));
+    if (guides_ms) *guides_ms = f->denoise.guides.ms();
+    if (filter_ms) *filter_ms = f->denoise.filter.ms();
     return KY_OK;
 }
 

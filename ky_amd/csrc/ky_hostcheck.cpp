@@ -16,6 +16,7 @@
 #include <unistd.h>
 
 #include "ky_checkpoint.hpp"   // ky_host.hpp, ky_blocks.hpp, ky_noise.hpp
+#include "ky_denoise.hpp"
 
 using namespace kyh;
 
@@ -277,6 +278,31 @@ int kyhostcheck_blocks(const ky_render_params* p, int* out_block, int* out_pixel
     return block_trailer_check(trailer, trailer_bytes, trailer_offset, sh.n_blocks, p->samples_per_pixel, samples_done, noise_batches);
 }
 
+// The denoise filter's arithmetic (ky_denoise.hpp: what denoise_level_kernel does per pixel) on the caller's film-order buffers -- cv {r, g, b, v}, ga {n, t},
+// gb {P, class}: width x height x 4 floats each -- for p->levels levels with steps 1, 2, 4 ...; `pix` is the width of a pixel at unit distance.  Writes the last
+// level's {r, g, b, v}, unclamped, to out (width x height x 4).  Returns denoise_params_check's status, or KY_ERR_INVALID_VALUE for arguments that are none.
+int kyhostcheck_denoise(const float* cv, const float* ga, const float* gb, int width, int height, const ky_denoise_params* p, double pix, float* out) {
+    using namespace kydn;
+    if (!cv || !ga || !gb || !p || !out || width < 1 || height < 1) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    KY_TRY(denoise_params_check(p));
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<Px4> c[2] = {std::vector<Px4>(n), std::vector<Px4>(n)}, a(n), b(n);   // (16-byte aligned copies: the caller's arrays need not be)
+    std::memcpy(c[0].data(), cv, n * sizeof(Px4));
+    std::memcpy(a.data(), ga, n * sizeof(Px4));
+    std::memcpy(b.data(), gb, n * sizeof(Px4));
+    LevelConst k{};
+    k.width = width; k.height = height;
+    k.normal_squarings = p->normal_squarings;
+    k.sigma_l2 = (double)p->sigma_luminance * (double)p->sigma_luminance;
+    k.sigma_plane = (double)p->sigma_plane;
+    k.pix = pix;
+    for (int l = 0; l < p->levels; ++l)
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) c[(l + 1) & 1][(size_t)y * width + x] = level_pixel(c[l & 1].data(), a.data(), b.data(), x, y, 1 << l, k);
+    std::memcpy(out, c[p->levels & 1].data(), n * sizeof(Px4));
+    return KY_OK;
+}
+
 // The live rectangle (screen_bound, kyhip_scene_screen_bound) on degenerate inputs: a unit box of five matte rectangles (open towards -z) or one sphere, seen by a
 // camera that looks along +z.  Whatever the proof cannot cover must give the whole frame: the camera on the bound's face, inside the bound, a NaN vertex, no surfaces.
 // A sphere of radius zero is a bound that is a point: a rectangle of a few pixels.  Returns 0, or the number of the case that went wrong.
@@ -429,6 +455,16 @@ int kyhip_frame_render_adaptive(kyhip_frame*, float threshold, float max_fractio
 int kyhip_frame_sample_map(kyhip_frame*, int32_t*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_block_stats(kyhip_frame*, ky_block_stats* out) { return no_frame(out); }
 int kyhip_frame_blocks_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+// (the denoise entries: the parameters first, as the real ones check them; kyhip_denoise_defaults is host code, ky_pack.cpp)
+int kyhip_frame_denoise(kyhip_frame*, const ky_denoise_params* p, float*, size_t) {
+    ky_denoise_params q;
+    kyhip_denoise_defaults(&q);
+    if (p) q = *p;
+    KY_TRY(denoise_params_check(&q));
+    return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+}
+int kyhip_frame_guides(kyhip_frame*, float*, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_denoise_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }
 int kyhip_smallpt_render(int, const ky_smallpt_sphere* spheres, int n, const ky_smallpt_params* p, double* image) {

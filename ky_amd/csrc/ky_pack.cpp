@@ -19,6 +19,7 @@
 #include <unistd.h>
 
 #include "ky_checkpoint.hpp"   // ky_host.hpp, ky_blocks.hpp, ky_noise.hpp
+#include "ky_denoise.hpp"
 
 namespace kyh {
 
@@ -280,6 +281,18 @@ int stop_rule_check(float threshold, float max_fraction_above, int min_batches) 
 }
 int pass_samples_check(int min_samples_per_pass) {
     return min_samples_per_pass >= 1 ? KY_OK : fail(KY_ERR_INVALID_VALUE, "min_samples_per_pass %d: a pass renders at least one sample per pixel", min_samples_per_pass);
+}
+int denoise_params_check(const ky_denoise_params* p) {
+    if (p->levels < 0 || p->levels > kydn::KY_DN_MAX_LEVELS) return fail(KY_ERR_INVALID_VALUE, "levels %d: 0 .. %d", p->levels, kydn::KY_DN_MAX_LEVELS);
+    if (p->normal_squarings < 0 || p->normal_squarings > kydn::KY_DN_MAX_SQUARINGS)
+        return fail(KY_ERR_INVALID_VALUE, "normal_squarings %d: 0 .. %d", p->normal_squarings, kydn::KY_DN_MAX_SQUARINGS);
+    if (!(p->sigma_luminance > 0.f)) return fail(KY_ERR_INVALID_VALUE, "sigma_luminance %g: a width is > 0", (double)p->sigma_luminance);   // (a NaN is refused)
+    if (!(p->sigma_plane > 0.f)) return fail(KY_ERR_INVALID_VALUE, "sigma_plane %g: a width is > 0", (double)p->sigma_plane);
+    return KY_OK;
+}
+double denoise_pixel_width(const ky_camera& camera, int width) {
+    const double x = (double)camera.right[0], y = (double)camera.right[1], z = (double)camera.right[2];
+    return 2.0 * std::sqrt(x * x + y * y + z * z) / (double)width;
 }
 }  // namespace kyh
 // the pieces of checkpoint_check: the noise trailer at `state_bytes` (CheckpointLayout::noise) ...
@@ -1317,6 +1330,12 @@ int kyhip_lighting_plan(const ky_render_params* p, int lighting, int* effective_
 }
 
 int kyhip_pass_boundaries(int spp, int* bounds, int n) { return pass_boundaries(spp, bounds, n); }
+// the filter's defaults: sigma_luminance and sigma_plane as tools/denoise_replay.py settled them (profiles/denoise_replay.txt; DESIGN.md "Denoise")
+void kyhip_denoise_defaults(ky_denoise_params* out) {
+    if (!out) return;
+    out->levels = 5; out->normal_squarings = 7;
+    out->sigma_luminance = 1.5f; out->sigma_plane = 0.25f;
+}
 
 int64_t kyhip_shard_tile_count(const ky_render_params* p) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");

@@ -743,6 +743,33 @@ public:
         kyhip_frame_end(frame);
         return done;
     }
+    // render_passes that ends on the denoised preview (kyhip_frame_denoise, include/kyhip.h): passes of at least min_samples_per_pass until stop_after_samples
+    // samples per pixel are done or the frame is complete -- two passes at least, the filter needs a variance -- then ADDS the picture so far through the
+    // edge-avoiding filter (params NULL: kyhip_denoise_defaults) where render_until adds the plain mean.  A frame that is complete behind its first pass (its total is
+    // at most one pass long) has one batch only: it is added unfiltered, exactly as render() adds it.  Returns the samples done per pixel.
+    int render_denoised(scene_t* scene, sampler_t* original_sampler, film_t* film, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params = nullptr) {
+        if (masked()) throw std::runtime_error("integrator_t::render_denoised: light classes are rendered by render() only");
+        const ky_render_params p = params_for(original_sampler, film);
+        kyhip_frame* frame = nullptr;
+        if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        int done = 0;
+        try {
+            if (kyhip_frame_track_noise(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_noise: ") + kyhip_last_error());
+            int passes = 0;
+            for (; done < p.samples_per_pixel && (passes < 2 || done < stop_after_samples); ++passes)
+                if (kyhip_frame_render(frame, min_samples_per_pass, &done) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_render: ") + kyhip_last_error());
+            if (passes < 2) {   // the frame was complete behind its first pass: one batch, no variance to guide a filter -- the complete frame as render() adds it
+                if (kyhip_frame_resolve(frame, 0, film->target_origin(), film->row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+            } else if (kyhip_frame_denoise(frame, params, film->target_origin(), film->row_stride_px()) != KY_OK) {
+                throw std::runtime_error(std::string("kyhip_frame_denoise: ") + kyhip_last_error());
+            }
+        } catch (...) {
+            kyhip_frame_end(frame);
+            throw;
+        }
+        kyhip_frame_end(frame);
+        return done;
+    }
     // render_until per 8 x 8 pixel block (kyhip_frame_track_blocks ..., include/kyhip.h): after every pass the blocks at most max_fraction_above of whose pixels lie
     // above `threshold` (after min_batches passes or more) retire and are rendered no further; the passes go on over the others until none is left or the frame
     // is complete.  ADDS per pixel the mean of the samples its block received (normalise 1) and returns the block statistics; sample_counts, when given,

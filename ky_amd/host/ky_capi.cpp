@@ -164,6 +164,33 @@ int kyhost_render_until(void* scene, int integrator_enum, int depth, int direct_
     return rc != 0 ? rc : status;
 }
 
+// create_integrator(...)->render_denoised(&scene, sampler, &film, min_samples_per_pass, stop_after_samples, params) on a film_t of width x height; params may be
+// NULL (the library's defaults).  `film` is read, added to and written back.  Returns the samples done per pixel (>= 1), -1 on error, -2 when create_integrator
+// returns nullptr.
+int kyhost_render_denoised(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
+                           float* film, int device, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params) {
+    int status = 0;
+    int rc = guarded([&] {
+        std::unique_ptr<ky::integrator_t> integrator;
+        const auto ie = (ky::integrator_enum_t)integrator_enum;
+        if (ie == ky::integrator_enum_t::position || ie == ky::integrator_enum_t::normal || ie == ky::integrator_enum_t::basecolor)
+            integrator = std::make_unique<ky::debug_integrator_t>(ie, device);
+        else
+            integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
+        if (!integrator) { status = -2; return; }
+        std::unique_ptr<ky::sampler_t> sampler;
+        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
+        else sampler = std::make_unique<ky::random_sampler_t>(spp);
+        sampler->set_seed(seed);
+        ky::film_t f(width, height);
+        const size_t n = (size_t)f.get_pixel_num() * 3;
+        std::memcpy(f.data(), film, n * sizeof(float));
+        status = integrator->render_denoised(&((scene_box*)scene)->scene, sampler.get(), &f, min_samples_per_pass, stop_after_samples, params);
+        std::memcpy(film, f.data(), n * sizeof(float));
+    });
+    return rc != 0 ? rc : status;
+}
+
 // create_integrator(...)->render_adaptive(&scene, sampler, &film, threshold, max_fraction_above, min_batches, min_samples_per_pass, &counts) on a film_t of width x
 // height.  `film` is read, added to and written back; sample_counts (may be NULL) receives width x height int32; *stats (may be NULL) the block statistics.
 // Returns 0, -1 on error, -2 when create_integrator returns nullptr.

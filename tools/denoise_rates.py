@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""The numbers of DESIGN.md "Denoise" (profiles/denoise_rates.txt), table kernels, one GPU.
+  tools/denoise_rates.py cornell [spp]   configs[1]'s geometry (1024 x 768, Cornell box with the lamp, depth 5, both_mis; 512 spp)
+  tools/denoise_rates.py veach [spp]     bench.py --workload veach's geometry (1280 x 720)
+hipEvent time (kyhip_frame_denoise_ms) of the guide trace and of the filter -- gather, levels and add in one span -- for 1 .. 6 levels into a pinned film, so
+that the span holds kernels only: the increment from L - 1 to L levels is the level with step 2^(L - 1), and what one level's span holds beyond an increment is
+the gather and the add.  Next to a 64-sample pass's render kernel (kyhip_kernel_ms) and the noise kernels (kyhip_frame_noise_ms).  Medians of five calls after
+a warm-up."""
+import ctypes as C
+import os
+import sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from ky_amd import api, _abi as A
+
+what = sys.argv[1] if len(sys.argv) > 1 else "cornell"
+spp = int(sys.argv[2]) if len(sys.argv) > 2 else 512
+lib = A.load_kyhip()
+lib.kyhip_set_jit(0)
+W, H = (1024, 768) if what == "cornell" else (1280, 720)
+scene = api.cornell_box_scene(A.CB_DEFAULT_SCENE, W, H) if what == "cornell" else api.mis_scene(W, H)
+p = api.make_params(W, H, spp)
+film = api.PinnedFilm(H, W)
+with api.Frame(scene, p, noise=True) as f:
+    f.render(64)
+    first = api.kernel_ms()
+    f.render(64)
+    print("%s %d x %d, %d spp; passes of 64: render kernel %.3f and %.3f ms  [%s]" % (what, W, H, spp, first, api.kernel_ms(), lib.kyhip_last_kernel(0).decode()), flush=True)
+    f.noise_stats(0.01)
+    up, ms = C.c_float(-1), C.c_float(-1)
+    assert lib.kyhip_frame_noise_ms(f._f, C.byref(up), C.byref(ms)) == A.KY_OK
+    print("noise update %.4f ms, map + statistics %.4f ms" % (up.value, ms.value))
+    f.denoise(film=film.array)   # warm-up; traces the guides
+    print("guide trace, once per frame: %.4f ms (%d pixels)" % (f.denoise_ms()[0], W * H), flush=True)
+    spans = {}
+    for levels in (1, 2, 3, 4, 5, 6):
+        runs = []
+        for _ in range(5):
+            f.denoise(dict(levels=levels), film=film.array)
+            runs.append(f.denoise_ms()[1])
+        spans[levels] = float(np.median(runs))
+        print("filter, %d levels: %.4f ms (five calls: %s)%s" % (levels, spans[levels], " ".join("%.4f" % r for r in runs),
+                                                                "" if levels == 1 else "   the level with step %2d: %.4f ms" % (1 << (levels - 1), spans[levels] - spans[levels - 1])), flush=True)
+    per_level = (spans[6] - spans[1]) / 5
+    print("a level: %.4f ms = %.3f ns per pixel; gather + add: about %.4f ms; the default five levels: %.4f ms = %.3f of a 64-sample pass" % (
+        per_level, per_level * 1e6 / (W * H), spans[1] - per_level, spans[5], spans[5] / first))
+    a = f.denoise(film=np.zeros((H, W, 3), np.float32))
+    b = f.denoise(film=np.zeros((H, W, 3), np.float32))
+    print("a pageable film (device film, copy, host add): two calls identical: %s" % np.array_equal(a, b))

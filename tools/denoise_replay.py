@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""Where the denoise filter's default sigmas come from, and whether it denoises (profiles/denoise_replay.txt; DESIGN.md "Denoise").  No GPU: the samples of the
+tests' Cornell 40 x 24, 500 spp frame (tests/test_denoise_gpu.py; three seeds) are replayed on the CPU oracle (kyo li: the same streams, per-sample radiance), cut
+into the frame's chunks, one chunk per pass, and fed to the NumPy restatements of the noise estimate (tests/noise_restatement.py) and of the filter
+(tests/denoise_restatement.py) at several (sigma_luminance, sigma_plane) pairs.  The guides are the oracle's camera and scene-intersect KATs on the pixel centres.
+Prints the RMSE against a high-sample oracle frame, raw and denoised, at 112, 224 and 500 samples.
+
+usage: tools/denoise_replay.py [truth_spp]"""
+import os
+import sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+from ky_amd import _abi as A, api
+from oracle import kyoracle as O
+import noise_restatement as R
+import denoise_restatement as D
+
+W, H, SPP = 40, 24, 500
+SEEDS = (1234, 101, 202, 303, 404)   # the first three are the GPU test's
+AT = (112, 224, 500)
+PAIRS = [(4.0, 1.0), (1.0, 1.0), (1.5, 1.0), (2.0, 1.0), (1.5, 0.25), (1.5, 0.1), (2.0, 0.25), (3.0, 0.25), (8.0, 1.0)]   # (4, 1): where the scan started; (1.5, 0.25): the defaults
+TRUTH_SPP = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
+
+scene = api.cornell_box_scene(A.CB_DEFAULT_SCENE, W, H)
+truth = O.render(scene, api.make_params(W, H, TRUTH_SPP, seed=987654)).astype(np.float64)
+ga, gb = D.guides_from_hits(scene.c, O.kat_scene_intersect(scene, D.centre_rays(O.kat_camera, scene.c.camera, W, H)), W, H)
+pix = D.pixel_width(scene.c.camera, W)
+bounds = api.pass_boundaries(SPP)
+rmse = lambda film: float(np.sqrt(((np.clip(film.astype(np.float64), 0, 1) - truth) ** 2).mean()))
+print("Cornell %d x %d, %d spp, one chunk per pass; truth: the oracle at %d spp; classes: %s" % (
+    W, H, SPP, TRUTH_SPP, " ".join("%d x %d" % (int((gb[..., 3] == c).sum()), c) for c in (0, 1, 2))))
+print("RMSE of clamp01(picture) against the truth; ratio = denoised / raw.  levels 5, normal_squarings 7")
+print(" seed samples batches      raw   " + "  ".join("sl %-4g sp %-4g" % pr for pr in PAIRS))
+ratios = {pr: [] for pr in PAIRS}
+for seed in SEEDS:
+    p = api.make_params(W, H, SPP, seed=seed)
+    rad = np.stack([O.li(scene, p, i % W, i // W, 0, SPP).astype(np.float64) for i in range(W * H)])   # [pixel (film order), sample, 3]
+    cum = np.cumsum(rad, axis=1)
+    y_prev, m2, n_prev = np.zeros(W * H), np.zeros(W * H), 0
+    for k, d in enumerate(bounds):
+        accum = np.rint(cum[:, d - 1] / SPP * 4294967296.0).astype(np.int64)   # the frame's accumulators: sums scaled by 1 / total, in 2^-32
+        y_prev, m2 = R.update(y_prev, m2, R.luminance(accum, SPP), n_prev, d)
+        n_prev = d
+        if d not in AT:
+            continue
+        flags = np.zeros(W * H, np.uint32)
+        cv = D.gather(accum, flags, m2, SPP, d, k + 1).reshape(H, W, 4)
+        raw = rmse(cv[..., :3])
+        row = []
+        for pr in PAIRS:
+            out = D.denoise(cv, ga, gb, pix, levels=5, normal_squarings=7, sigma_luminance=pr[0], sigma_plane=pr[1])
+            row.append(rmse(out[..., :3]))
+            ratios[pr].append(row[-1] / raw)
+        print("%5d %7d %7d  %.5f   " % (seed, d, k + 1, raw) + "  ".join("%.5f (%.3f)" % (r, r / raw) for r in row))
+print("largest ratio per pair:     " + "  ".join("sl %g sp %g: %.3f" % (pr + (max(ratios[pr]),)) for pr in PAIRS))
+print("mean ratio per pair:        " + "  ".join("sl %g sp %g: %.3f" % (pr + (float(np.mean(ratios[pr])),)) for pr in PAIRS))
