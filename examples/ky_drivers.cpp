@@ -27,6 +27,9 @@
  *                                the picture and, next to it, the sample-count map (white: the frame's total)
  *   ky_drivers denoise [low_spp] [spp] [w] [h]  the same frame after its first low_spp samples (64 of 1024, 1024 x 768), in two passes, as the plain mean and through
  *                                the edge-avoiding filter (integrator_t::render_denoised), next to the complete frame; writes denoise.bmp: raw | denoised | full
+ *   ky_drivers sliced [n] [spp] [w] [h]  the same frame by sample range (3 slices, 512 spp, 1024 x 768; kyhip_frame_begin_slice, kyhip_frame_merge_from): the n slices
+ *                                render on device 0 one after the other, slice 0 merges the rest; prints per slice its samples and kernel time, the merge times, and
+ *                                whether the film is render()'s bit for bit (it must be: exit status 1 otherwise); writes sliced.bmp
  * An optional last argument multiplies every spp (the reference's values are tiny because its CPU path is slow).
  * KY_DEVICES=all (or a count n: devices 0 .. n-1) makes every integrator spread its tiles over that many GPUs of the node
  * (integrator_t::set_devices); the images do not depend on it.
@@ -252,6 +255,49 @@ static void render_progressive(int spp, int width, int height) {
     film.store_image("progressive");
 }
 
+// The headline frame by sample range: n slices of its samples, each over the whole film, merged into slice 0 (include/kyhip.h "Slices").  On one device the slices
+// run one after the other; integrator_t::render_sliced gives each device of a list a thread.  Returns whether the film equals render()'s.
+static bool render_sliced(int n, int spp, int width, int height) {
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, {(float)width, (float)height});
+    ky_render_params p{};
+    p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS;
+    p.samples_per_pixel = spp; p.sampler = KY_SAMPLER_RANDOM; p.seed = random_sampler_t(spp).seed();
+    p.width = width; p.height = height; p.tile_w = 16; p.tile_h = 16; p.tile_first = 0; p.tile_step = 1;
+    std::vector<int> bounds((size_t)(n > 0 ? n : 0) + 1);
+    if (kyhip_slice_bounds(spp, n, bounds.data()) != KY_OK) throw std::runtime_error(std::string("kyhip_slice_bounds: ") + kyhip_last_error());
+    std::vector<kyhip_frame*> frames((size_t)n, nullptr);
+    struct frames_end_t { std::vector<kyhip_frame*>& f; ~frames_end_t() { for (kyhip_frame* x : f) kyhip_frame_end(x); } } frames_end{frames};
+    film_t film(width, height);
+    const double seconds = timing_seconds([&] {
+        for (int k = 0; k < n; ++k) {
+            if (kyhip_frame_begin_slice(0, &scene.flatten(), &p, bounds[(size_t)k], bounds[(size_t)k + 1], &frames[(size_t)k]) != KY_OK)
+                throw std::runtime_error(std::string("kyhip_frame_begin_slice: ") + kyhip_last_error());
+            const int size = bounds[(size_t)k + 1] - bounds[(size_t)k];
+            int done = 0, passes = 0;
+            double kernel_ms = 0;
+            while (done < size) {
+                if (kyhip_frame_render(frames[(size_t)k], 64, &done) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_render: ") + kyhip_last_error());
+                kernel_ms += kyhip_kernel_ms(0);
+                ++passes;
+            }
+            std::printf("slice %d: samples %d..%d (%d) in %d passes, kernels %.3f ms\n", k, bounds[(size_t)k], bounds[(size_t)k + 1], size, passes, kernel_ms);
+        }
+        for (int k = 1; k < n; ++k) {
+            float ms = -1.f;
+            if (kyhip_frame_merge_from(frames[0], frames[(size_t)k]) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_merge_from: ") + kyhip_last_error());
+            kyhip_frame_merge_ms(frames[0], &ms);
+            std::printf("merge of slice %d: %.3f ms\n", k, (double)ms);
+        }
+        if (kyhip_frame_resolve(frames[0], 0, film.target_origin(), film.row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+    });
+    film_t whole(width, height);
+    if (kyhip_render(0, &scene.flatten(), &p, whole.target_origin(), whole.row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_render: ") + kyhip_last_error());
+    const bool same = std::memcmp(film.data(), whole.data(), (size_t)film.get_pixel_num() * 3 * sizeof(float)) == 0;
+    std::printf("sliced: %dx%d, %d spp in %d slices: %.3f seconds; the film %s render()'s\n", width, height, spp, n, seconds, same ? "IS" : "IS NOT");
+    film.store_image("sliced");
+    return same;
+}
+
 // The same frame until it is clean: passes of at least 64 samples until at most 2 % of the pixels have a noise estimate (kyhip_frame_noise: the standard error
 // of the pixel's mean luminance, in units of the film's white) above `threshold`, or the cap is reached.  Writes the mean of the samples done and the noise
 // map scaled by 1 / threshold (white: at or above the threshold).
@@ -358,6 +404,8 @@ int main(int argc, char* argv[]) {
             render_lighting_enum(argc > 2 ? std::atoi(argv[2]) : 1024, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 768);
         } else if (!std::strcmp(which, "progressive")) {
             render_progressive(argc > 2 ? std::atoi(argv[2]) : 512, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 768);
+        } else if (!std::strcmp(which, "sliced")) {
+            if (!render_sliced(argc > 2 ? std::atoi(argv[2]) : 3, argc > 3 ? std::atoi(argv[3]) : 512, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768)) return 1;
         } else if (!std::strcmp(which, "converge")) {
             const float threshold = argc > 2 ? (float)std::atof(argv[2]) : 0.01f;
             if (!(threshold > 0.f)) { std::fprintf(stderr, "converge: a threshold above 0\n"); return 2; }

@@ -515,6 +515,51 @@ int     kyhip_frame_guides(kyhip_frame* f, float* normal_t4, float* position_cla
 int     kyhip_frame_denoise_ms(const kyhip_frame* f, float* guides_ms, float* filter_ms);
 
 /*
+ * Slices: a frame's sample ranges rendered apart and merged, bit for bit (DESIGN.md section 3 "Slices").  A pixel's samples are keyed by their absolute index,
+ * cut into chunks by a schedule of samples_per_pixel alone, and every chunk sum enters a 64-bit integer word scaled by 1 / total under the WHOLE frame's term
+ * limit: frames of one (scene, params) that rendered disjoint sets of chunks hold words whose integer sum is the word of one frame that rendered them all, in
+ * any order, and flag words only gain bits.  A slice is a frame that owns the samples [first_sample, end_sample) of every pixel of its shard; a merge adds
+ * another frame's words, ORs its flag words and pools its noise pairs.  Slices may live on any device, in any process, on any machine.
+ *
+ * kyhip_slice_bounds: host arithmetic.  Writes n_slices + 1 strictly ascending values, bounds[0] = 0 and bounds[n_slices] = spp; inner value k is the value of
+ *   kyhip_pass_boundaries(spp) nearest to k * spp / n_slices (a tie goes to the lower one; moved by as few chunks as it takes to leave every slice one).  Returns KY_OK, or KY_ERR_INVALID_VALUE for an spp that
+ *   kyhip_pass_boundaries refuses, n_slices < 1, a NULL bounds, or a frame of fewer chunks than n_slices.
+ * kyhip_frame_begin_slice: kyhip_frame_begin in every check and status; the frame owns samples [first_sample, end_sample) of the samples_per_pixel-sample frame.
+ *   Both are 0 or a value of kyhip_pass_boundaries and first <= end, else KY_ERR_INVALID_VALUE.  first == end is a collector: it owns and renders nothing and
+ *   exists to receive merges (a preview of all slices as they stand).  (0, samples_per_pixel) IS kyhip_frame_begin: the same frame, the same checkpoint bytes.
+ * A frame holds a coverage: the sample ranges its accumulators contain -- disjoint, ascending, adjacent ones joined, at most KYHIP_SLICE_MAX_RANGES.
+ * kyhip_frame_coverage: returns the number of ranges; writes min(n, count) {first, end} pairs to ranges2 and the owned range to own (either may be NULL).
+ * kyhip_frame_samples' done is the number of samples per pixel HELD, the sum of the coverage (on a frame that never merged: what it always was), and that is
+ *   what kyhip_frame_resolve with normalise 1, the noise estimate and kyhip_frame_denoise divide by.
+ * kyhip_frame_render on a slice renders whole chunks of the owned range from its front; the frame is complete when the owned range is rendered.  The pass note
+ *   of kyhip_last_kernel names absolute chunk and sample indices.  kyhip_frame_render_until works on a slice as on any frame.
+ * kyhip_frame_merge: `state` is what kyhip_frame_save wrote for another frame of the same scene and params.  KY_ERR_INVALID_VALUE, before any device work and
+ *   with dst untouched (its next save returns the bytes it returned before): a short buffer; a header that is no frame state or differs in source hash, params,
+ *   scene hash or pixel count; a coverage that intersects dst's coverage, or dst's owned range whether rendered or not (later passes would count those samples
+ *   twice -- so a kyhip_frame_begin frame, which owns everything, never receives a merge); a dst that tracks noise and a state without a valid noise trailer; a
+ *   block-tracking frame on either side.  KY_ERR_LIMIT: a union of more than KYHIP_SLICE_MAX_RANGES ranges.  A dst that does not track noise ignores the state's
+ *   noise trailer.  Otherwise one kernel merges and the coverage becomes the union.  Blocking.
+ *   Noise pairs: m2 = a.m2 + b.m2 + n_a n_b / (n_a + n_b) (mean_b - mean_a)^2, the batch counts add, and the luminance sum is recomputed from the merged words;
+ *   the last bits of m2 depend on which side is dst and on the order of the merges.  The words and flags do not.
+ * kyhip_frame_merge_from: the same for a frame of this process without a host round trip: on dst's device the kernel reads src's buffers, from another device
+ *   they are copied peer to peer into a buffer dst owns first.  src is unchanged.  src == dst: KY_ERR_INVALID_VALUE.
+ * kyhip_frame_merge_ms: the hipEvent span of the last merge kernel, negative when there was none.
+ * kyhip_frame_track_blocks on a frame whose owned range is not (0, samples_per_pixel) returns KY_ERR_INVALID_VALUE.
+ * Checkpoints: every frame not begun as (0, samples_per_pixel) has a header magic of its own -- plain and block frames refuse its states and it theirs on load --
+ *   whose samples done is the held count, and its state ends, behind the noise trailer, with a slice trailer of fixed size: a magic number, the owned range, the
+ *   front, the range count and KYHIP_SLICE_MAX_RANGES pairs.  All slices of one frame that agree in tracking noise have states of one size.  kyhip_frame_load
+ *   refuses, the frame untouched: another owned range; a front outside the owned range or on no pass boundary; ranges that are not ascending, disjoint and on
+ *   boundaries, or whose part inside the owned range is not exactly [first, front); a held count that disagrees with the header or the noise trailer.
+ */
+#define KYHIP_SLICE_MAX_RANGES 32
+int     kyhip_slice_bounds(int spp, int n_slices, int* bounds);
+int     kyhip_frame_begin_slice(int device, const ky_scene* scene, const ky_render_params* params, int first_sample, int end_sample, kyhip_frame** out);
+int     kyhip_frame_coverage(const kyhip_frame* f, int* ranges2, int n, int own[2]);
+int     kyhip_frame_merge(kyhip_frame* dst, const void* state, size_t bytes);
+int     kyhip_frame_merge_from(kyhip_frame* dst, kyhip_frame* src);
+int     kyhip_frame_merge_ms(const kyhip_frame* f, float* ms);
+
+/*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent
  * kyhip_render* call on `device`, from hipEvents recorded on the launch stream around that one
  * kernel.  The stream must have been synchronised.  Negative if no timing is available.

@@ -104,6 +104,8 @@ SP_DIFF, SP_SPEC, SP_REFR = 0, 1, 2
 SSP = C.POINTER(SmallptSphere)
 SPP = C.POINTER(SmallptParams)
 
+SLICE_MAX_RANGES = 32   # KYHIP_SLICE_MAX_RANGES
+
 KYHIP_SYMBOLS = {
     "kyhip_last_error": (C.c_char_p, []),
     "kyhip_set_engine": (C.c_int, [C.c_int]),
@@ -160,6 +162,12 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.c_size_t]),
     "kyhip_frame_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "kyhip_frame_denoise_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "kyhip_slice_bounds": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "kyhip_frame_begin_slice": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "kyhip_frame_coverage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "kyhip_frame_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_merge_from": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kyhip_frame_merge_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -198,6 +206,8 @@ KYHOST_SYMBOLS = {
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhost_render_passes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
+    "kyhost_render_sliced": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int,
+                                       C.c_int]),
     "kyhost_render_until": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                       C.c_float, C.c_float, C.c_int, C.c_int]),
     "kyhost_render_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -226,6 +236,8 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
     "kyhostcheck_blocks": (C.c_int, [PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int]),
     "kyhostcheck_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_double, C.c_void_p]),
+    "kyhostcheck_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "kyhostcheck_slices": (C.c_int, [C.c_int, PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kyhostcheck_add_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_seam_stress": (C.c_int, [C.c_int]),
     "kyhostcheck_jit_stress": (C.c_int, [C.c_int, C.c_int]),

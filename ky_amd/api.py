@@ -110,6 +110,15 @@ def pass_boundaries(spp):
     return list(out)
 
 
+def slice_bounds(spp, n):
+    """kyhip_slice_bounds (host only): n + 1 ascending pass boundaries from 0 to spp that cut an spp-sample frame into n slices of about equal sample counts;
+    slice k owns samples [bounds[k], bounds[k + 1])."""
+    lib = A.load_kyhip()
+    out = (C.c_int * (max(int(n), 0) + 1))()
+    _check(lib.kyhip_slice_bounds(int(spp), int(n), out), lib)
+    return list(out)
+
+
 def denoise_defaults():
     """kyhip_denoise_defaults (host only) as a ky_denoise_params (_abi.DenoiseParams)."""
     q = A.DenoiseParams()
@@ -123,13 +132,19 @@ class Frame:
     noise=True: the frame keeps a per-pixel noise estimate over its passes (kyhip_frame_track_noise): noise(), noise_stats(threshold), render_until(...).
     blocks=True: the frame retires 8 x 8 pixel blocks between its passes and renders the live ones only (kyhip_frame_track_blocks): keep(mask),
     retire_noisy(...) and render_adaptive(...) (these two with noise=True), sample_map(), block_stats(); resolve(normalise=True) is then per block.
-    A frame with noise=True whose shard is the whole film can be denoised between passes: denoise(), guides(), denoise_ms()."""
+    A frame with noise=True whose shard is the whole film can be denoised between passes: denoise(), guides(), denoise_ms().
+    slice=(first, end): the frame owns and renders samples [first, end) of every pixel only (kyhip_frame_begin_slice; both 0 or a pass boundary, see slice_bounds);
+    first == end is a collector that renders nothing.  merge() adds what another frame of the same scene and params holds, bit for bit: `done` counts the samples
+    held, `coverage` lists them, and slices that cover 0 .. total merged into one of them resolve to render(scene, params)."""
 
-    def __init__(self, scene, params, device=0, noise=False, blocks=False):
+    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
-        _check(self._lib.kyhip_frame_begin(device, _scene_ptr(scene), C.byref(params), C.byref(self._f)), self._lib)
+        if slice is None:
+            _check(self._lib.kyhip_frame_begin(device, _scene_ptr(scene), C.byref(params), C.byref(self._f)), self._lib)
+        else:
+            _check(self._lib.kyhip_frame_begin_slice(device, _scene_ptr(scene), C.byref(params), int(slice[0]), int(slice[1]), C.byref(self._f)), self._lib)
         if noise:
             rc = self._lib.kyhip_frame_track_noise(self._f)
             if rc != A.KY_OK:
@@ -283,10 +298,73 @@ class Frame:
         _check(self._lib.kyhip_frame_denoise_ms(self._f, C.byref(a), C.byref(b)), self._lib)
         return a.value, b.value
 
+    def _coverage(self):
+        ranges, own = (C.c_int * (2 * A.SLICE_MAX_RANGES))(), (C.c_int * 2)()
+        n = self._lib.kyhip_frame_coverage(self._f, ranges, A.SLICE_MAX_RANGES, own)
+        if n < 0:
+            _check(n, self._lib)
+        return [(ranges[2 * i], ranges[2 * i + 1]) for i in range(n)], (own[0], own[1])
+
+    @property
+    def coverage(self):
+        """The sample ranges [(first, end), ...] the frame holds: ascending, disjoint, adjacent ones joined (kyhip_frame_coverage)."""
+        return self._coverage()[0]
+
+    @property
+    def own(self):
+        """The sample range (first, end) the frame owns and renders."""
+        return self._coverage()[1]
+
+    def merge(self, other):
+        """Adds what another frame of the same scene and params holds -- a Frame of this process (kyhip_frame_merge_from: no host round trip) or the bytes its
+        save() returned, from any device, process or machine (kyhip_frame_merge).  Its samples must be disjoint from this frame's coverage and owned range."""
+        if isinstance(other, Frame):
+            _check(self._lib.kyhip_frame_merge_from(self._f, other._f), self._lib)
+        else:
+            state = bytes(other)
+            _check(self._lib.kyhip_frame_merge(self._f, state, len(state)), self._lib)
+
+    def merge_ms(self):
+        """kyhip_frame_merge_ms: the last merge kernel in ms, negative when there was none."""
+        ms = C.c_float(-1)
+        _check(self._lib.kyhip_frame_merge_ms(self._f, C.byref(ms)), self._lib)
+        return ms.value
+
     def load(self, state):
         """Continue from a checkpoint of a frame begun with the same scene and params (kyhip_frame_load); any other state raises KyError."""
         state = bytes(state)
         _check(self._lib.kyhip_frame_load(self._f, state, len(state)), self._lib)
+
+
+def render_sliced(scene, params, devices, min_samples_per_pass, on_pass=None, noise=False, film=None):
+    """The frame in len(devices) slices of its samples (slice_bounds), slice k on devices[k] (a device may repeat); returns the (accumulated) host film, which is
+    render(scene, params) bit for bit.  The slices render in rounds of one pass each, one call after the other (concurrency across devices: ky_amd.dist); after
+    every round on_pass(done, total, preview) is called with the samples per pixel done over all slices, and preview(denoise=False) merges the slices as they stand
+    into a collector and returns its picture: resolve(normalise=True), or with denoise=True (needs noise=True and two rounds) denoise().  At the end slice 0's
+    frame merges the others and resolves."""
+    bounds = slice_bounds(params.samples_per_pixel, len(devices))
+    frames = []
+    try:
+        for k, dev in enumerate(devices):
+            frames.append(Frame(scene, params, device=dev, noise=noise, slice=(bounds[k], bounds[k + 1])))
+
+        def preview(denoise=False):
+            with Frame(scene, params, device=devices[0], noise=noise, slice=(0, 0)) as collector:
+                for f in frames:
+                    collector.merge(f)
+                return collector.denoise() if denoise else collector.resolve(normalise=True)
+
+        while any(f.done < f.own[1] - f.own[0] for f in frames):
+            for f in frames:
+                f.render(min_samples_per_pass)
+            if on_pass is not None:
+                on_pass(sum(f.done for f in frames), params.samples_per_pixel, preview)
+        for f in frames[1:]:
+            frames[0].merge(f)
+        return frames[0].resolve(film=film)
+    finally:
+        for f in frames:
+            f.close()
 
 
 class PinnedFilm:
@@ -358,6 +436,22 @@ def render_passes_host_api(scene, integrator_enum, depth, direct_sample, sampler
         return None
     if rc != 0:
         raise KyError("kyhost_render_passes failed: " + host.kyhost_last_error().decode())
+    return film
+
+
+def render_sliced_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, devices, min_samples_per_pass, seed=1234, film=None):
+    """create_integrator(...)->render_sliced(&scene, sampler, &film, devices, min_samples_per_pass) through the C++ host classes: the frame by sample range, slice k
+    on devices[k], merged on devices[0]; returns the film (render_host_api's, bit for bit)."""
+    host = A.load_kyhost()
+    if film is None:
+        film = np.zeros((height, width, 3), np.float32)
+    devs = (C.c_int * len(devices))(*devices)
+    rc = host.kyhost_render_sliced(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), devs, len(devices),
+                                   int(min_samples_per_pass))
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise KyError("kyhost_render_sliced failed: " + host.kyhost_last_error().decode())
     return film
 
 

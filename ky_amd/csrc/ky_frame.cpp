@@ -7,7 +7,9 @@
  * kernel is defined here.  A frame that tracks noise (kyhip_frame_track_noise; DESIGN.md "Noise") also owns a per-pixel estimate that every pass advances behind its
  * render kernel: the arithmetic is ky_noise.hpp's, the kernels ky_noise.hip's.  A frame that tracks blocks (kyhip_frame_track_blocks; DESIGN.md "Adaptive") retires
  * pixel blocks between its passes and renders the live ones only: the arithmetic is ky_blocks.hpp's, the kernels ky_blocks.hip's, the render kernels' listed form
- * ky_render.hpp's.
+ * ky_render.hpp's.  A frame may own a range of its samples only (kyhip_frame_begin_slice; DESIGN.md "Slices") and receive what other frames of its scene and params
+ * hold (kyhip_frame_merge, _merge_from): what a frame holds is its coverage, the arithmetic of ranges and of a state's acceptance ky_checkpoint.hpp's, the kernel
+ * ky_merge.hip's.
  */
 #include <cstring>
 #include <string>
@@ -73,7 +75,10 @@ struct kyhip_frame {
     ChunkPlan plan{};
     FrameHeader header{};         // with samples_done = 0
     CheckpointLayout layout;      // of what the frame tracks now (retrack)
-    int chunks_done = 0;
+    int own_first = 0, own_end = 0;   // the samples the frame owns and renders, and ...
+    int own_c0 = 0, own_c1 = 0;       // ... the chunks they are
+    int chunks_done = 0;          // the chunks before the frame's front: own_c0 .. own_c1
+    Coverage cov;                 // the samples the accumulators hold: [own_first, front) and what was merged
     bool loaded = false;
     FramePass pass;               // the frame's accumulator block and the kernel its first pass took
     DevBuf ws, tiles, film;       // accumulators + flag words; resolve's compact tile buffer; resolve's device film (pageable host films)
@@ -81,10 +86,16 @@ struct kyhip_frame {
     NoiseTrack noise;
     BlockTrack blocks;
     DenoiseTrack denoise;
+    DevBuf merge_ws, merge_state; // what a merge from a saved state or from another device reads: the other frame's accumulator block and noise pairs
+    TimedSpan merge;              // the last merge kernel (kyhip_frame_merge_ms)
 };
 
+// the frame's front: the absolute sample its owned range is rendered to; and the samples per pixel it holds -- the same for a frame that owns all and merged nothing
 static int samples_done(const kyhip_frame* f) { return chunk_end(f->plan, f->chunks_done - 1); }
-static void retrack(kyhip_frame* f) { f->layout = checkpoint_layout(&f->params, f->noise.on, f->blocks.on); }
+static int samples_held(const kyhip_frame* f) { return f->cov.held(); }
+static bool owned_rendered(const kyhip_frame* f) { return f->chunks_done >= f->own_c1; }
+static bool untouched(const kyhip_frame* f) { return f->chunks_done == f->own_c0 && f->cov.n == 0 && !f->loaded; }
+static void retrack(kyhip_frame* f) { f->layout = checkpoint_layout(&f->params, f->noise.on, f->blocks.on, f->own_first, f->own_end); }
 static const void* block_state_or_null(const kyhip_frame* f) { return f->blocks.on ? f->blocks.state.p : nullptr; }
 
 // Waits for what was enqueued on `stream`, also after a failed enqueue, whose status `rcode` comes first; then the device's, as "<what> failed: <error><tail>"
@@ -153,14 +164,14 @@ static int frame_tracks(const kyhip_frame* f, bool blocks, bool noise) {
     return KY_OK;
 }
 
-extern "C" {
-
-int kyhip_frame_begin(int device, const ky_scene* scene, const ky_render_params* p, kyhip_frame** out) {
+// kyhip_frame_begin and kyhip_frame_begin_slice: the frame that owns samples [first_sample, end_sample)
+static int frame_begin(int device, const ky_scene* scene, const ky_render_params* p, int first_sample, int end_sample, kyhip_frame** out) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
     if (!shard_in_range(p)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices (%d x %d, %d spp)", p->width, p->height, p->samples_per_pixel);
     if (film_range_check(p, scene) != KY_OK) return KY_ERR_LIMIT;
     if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
     *out = nullptr;
+    KY_TRY(slice_range_check(p->samples_per_pixel, first_sample, end_sample));
     DeviceCtx* c;
     KY_TRY(get_ctx(device, &c));
     static thread_local DScene packed;
@@ -176,6 +187,9 @@ int kyhip_frame_begin(int device, const ky_scene* scene, const ky_render_params*
     f->scene.shapes = f->shapes.data(); f->scene.materials = f->materials.data(); f->scene.lights = f->lights.data(); f->scene.surfaces = f->surfaces.data();
     f->sh = make_shard(p);
     f->plan = chunk_plan(p->samples_per_pixel);
+    f->own_first = first_sample; f->own_end = end_sample;
+    f->own_c0 = chunks_at_sample(f->plan, first_sample); f->own_c1 = chunks_at_sample(f->plan, end_sample);
+    f->chunks_done = f->own_c0;
     f->header = frame_header(p, scene_hash(packed), 0);
     if (f->sh.n_pix > 0) {
         const size_t bytes = workspace_bytes_for(f->sh) + blocks_list_bytes(f->sh);   // (the live list of a frame that tracks blocks: behind the flag words)
@@ -190,9 +204,26 @@ int kyhip_frame_begin(int device, const ky_scene* scene, const ky_render_params*
     return KY_OK;
 }
 
+extern "C" {
+
+int kyhip_frame_begin(int device, const ky_scene* scene, const ky_render_params* p, kyhip_frame** out) {
+    return frame_begin(device, scene, p, 0, p ? p->samples_per_pixel : 0, out);   // (invalid params are refused before the range is looked at)
+}
+int kyhip_frame_begin_slice(int device, const ky_scene* scene, const ky_render_params* p, int first_sample, int end_sample, kyhip_frame** out) {
+    return frame_begin(device, scene, p, first_sample, end_sample, out);
+}
+
+int kyhip_frame_coverage(const kyhip_frame* f, int* ranges2, int n, int own[2]) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (n > 0 && !ranges2) return fail(KY_ERR_INVALID_VALUE, "ranges2 is NULL");
+    for (int i = 0; i < f->cov.n && i < n; ++i) { ranges2[2 * i] = f->cov.r[2 * i]; ranges2[2 * i + 1] = f->cov.r[2 * i + 1]; }
+    if (own) { own[0] = f->own_first; own[1] = f->own_end; }
+    return f->cov.n;
+}
+
 int kyhip_frame_samples(const kyhip_frame* f, int* done, int* total) {
     if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
-    if (done) *done = samples_done(f);
+    if (done) *done = samples_held(f);
     if (total) *total = f->params.samples_per_pixel;
     return KY_OK;
 }
@@ -200,13 +231,18 @@ int kyhip_frame_samples(const kyhip_frame* f, int* done, int* total) {
 int kyhip_frame_render(kyhip_frame* f, int min_samples, int* done) {
     if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
     if (min_samples < 1) return fail(KY_ERR_INVALID_VALUE, "min_samples %d: a pass renders at least one sample per pixel", min_samples);
-    const int c1 = pass_chunk_end(f->plan, f->chunks_done, min_samples);
+    int c1 = pass_chunk_end(f->plan, f->chunks_done, min_samples);
+    if (c1 > f->own_c1) c1 = f->own_c1;   // (a slice ends where its owned range does)
     if (nothing_live(f)) {   // every block is retired: nothing is launched and the front stays
-        if (done) *done = samples_done(f);
+        if (done) *done = samples_held(f);
         return KY_OK;
     }
     if (c1 > f->chunks_done) {
-        const int n_now = chunk_end(f->plan, c1 - 1);
+        // what the frame holds behind the pass: its front moves, and the estimate's batch is the samples the pass adds to the held ones
+        Coverage pass_range, held_then;
+        pass_range.n = 1; pass_range.r[0] = samples_done(f); pass_range.r[1] = chunk_end(f->plan, c1 - 1);
+        KY_TRY(coverage_union(f->cov, pass_range, &held_then));
+        const int n_now = held_then.held();
         if (f->sh.n_pix > 0) {
             DeviceCtx* c;
             KY_TRY(get_ctx(f->device, &c));
@@ -225,9 +261,10 @@ int kyhip_frame_render(kyhip_frame* f, int min_samples, int* done) {
         // the bookkeeping, behind the pass's synchronisation (a failed pass is not counted) and alone for a shard without pixels
         if (f->noise.on) { f->noise.batches += 1; f->noise.n_prev = n_now; }
         if (f->blocks.on) f->blocks.passes += 1;
+        f->cov = held_then;
     }
     f->chunks_done = c1;
-    if (done) *done = samples_done(f);
+    if (done) *done = samples_held(f);
     return KY_OK;
 }
 
@@ -236,7 +273,7 @@ int kyhip_frame_resolve(kyhip_frame* f, int normalise, float* film_rgb, size_t s
     if (normalise != 0 && normalise != 1) return fail(KY_ERR_INVALID_VALUE, "normalise %d: 0 (sum / total) or 1 (sum / done)", normalise);
     const ky_render_params* p = &f->params;
     if (!film_rgb || stride_px < (size_t)p->width) return fail(KY_ERR_INVALID_VALUE, "bad film arguments");
-    const int done = samples_done(f);
+    const int done = samples_held(f);
     const BlockTrack& bl = f->blocks;
     if (bl.on && !normalise)
         for (size_t b = 0; b < bl.host.size(); ++b)
@@ -280,7 +317,8 @@ int kyhip_frame_save(kyhip_frame* f, void* buf, size_t bytes) {
     const CheckpointLayout& L = f->layout;
     if (!buf || bytes < L.total) return fail(KY_ERR_INVALID_VALUE, "frame state: a buffer of %zu bytes, the state has %zu", bytes, L.total);
     CheckpointCounts n;
-    n.samples_done = samples_done(f);
+    n.samples_done = samples_held(f);
+    n.front = samples_done(f); n.cov = f->cov;
     n.batches = f->noise.batches; n.n_prev = f->noise.n_prev; n.passes = f->blocks.passes;
     checkpoint_write_host(f->header, L, n, f->blocks.host.data(), buf);   // (the host's block states are current: every call that changes the device's brings them home)
     if (f->sh.n_pix > 0) {
@@ -312,6 +350,7 @@ int kyhip_frame_load(kyhip_frame* f, const void* buf, size_t bytes) {
         KY_TRY(blocks_refresh(f));
     }
     f->chunks_done = n.chunks_done;
+    f->cov = n.cov;
     f->loaded = true;
     return KY_OK;
 }
@@ -321,7 +360,7 @@ int kyhip_frame_track_noise(kyhip_frame* f) {
     if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
     NoiseTrack& t = f->noise;
     if (t.on) return KY_OK;
-    if (f->chunks_done != 0 || f->loaded) return fail(KY_ERR_INVALID_VALUE, "noise is tracked from a frame's first pass: this one has rendered or loaded something");
+    if (!untouched(f)) return fail(KY_ERR_INVALID_VALUE, "noise is tracked from a frame's first pass: this one has rendered, loaded or merged something");
     if (f->sh.n_pix > 0) {
         DeviceCtx* c;
         KY_TRY(get_ctx(f->device, &c));
@@ -386,7 +425,7 @@ int kyhip_frame_noise_stats(kyhip_frame* f, float threshold, ky_noise_stats* out
     }
     std::memset(out, 0, sizeof *out);
     out->batches = f->noise.batches;
-    out->samples_done = samples_done(f);
+    out->samples_done = samples_held(f);
     out->pixels = s.pixels; out->flagged = s.flagged; out->above = s.above;
     out->threshold = threshold;
     out->max = s.max;
@@ -404,7 +443,7 @@ int kyhip_frame_render_until(kyhip_frame* f, float threshold, float max_fraction
         KY_TRY(kyhip_frame_noise_stats(f, threshold, out));
         const bool clean = out->batches >= min_batches && (double)out->above <= (double)max_fraction_above * (double)(out->pixels - out->flagged);
         // (a block-tracking frame without a live block renders no further: its front and its map stay what they are, and so would this verdict)
-        if (clean || samples_done(f) >= f->params.samples_per_pixel || nothing_live(f)) return KY_OK;
+        if (clean || owned_rendered(f) || nothing_live(f)) return KY_OK;
     }
 }
 
@@ -413,7 +452,10 @@ int kyhip_frame_track_blocks(kyhip_frame* f) {
     if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
     BlockTrack& b = f->blocks;
     if (b.on) return KY_OK;
-    if (f->chunks_done != 0 || f->loaded) return fail(KY_ERR_INVALID_VALUE, "blocks are tracked from a frame's first pass: this one has rendered or loaded something");
+    if (f->layout.sliced)
+        return fail(KY_ERR_INVALID_VALUE, "the frame owns samples %d..%d of %d: blocks retire on a frame that owns them all (per-block sample counts across slices are not kept)",
+                    f->own_first, f->own_end, f->params.samples_per_pixel);
+    if (!untouched(f)) return fail(KY_ERR_INVALID_VALUE, "blocks are tracked from a frame's first pass: this one has rendered or loaded something");
     const int nb = f->sh.n_blocks;
     b.host.assign((size_t)nb, BlockState{-1, 0});
     b.inside.assign((size_t)nb, 0);
@@ -549,7 +591,7 @@ static int denoise_prepare(kyhip_frame* f, DeviceCtx* c, bool timed) {
         d.filter.valid = false;
         d.filter.begin(c->stream);
     }
-    return denoise_gather_device(f->ws.p, f->noise.state.p, block_state_or_null(f), f->sh, p->width, p->height, p->samples_per_pixel, samples_done(f), f->noise.batches,
+    return denoise_gather_device(f->ws.p, f->noise.state.p, block_state_or_null(f), f->sh, p->width, p->height, p->samples_per_pixel, samples_held(f), f->noise.batches,
                                  d.gb_traced.p, d.cv[0].p, d.gb.p, c->stream);
 }
 
@@ -632,6 +674,81 @@ int kyhip_frame_denoise_ms(const kyhip_frame* f, float* guides_ms, float* filter
     KY_TRY(frame_tracks(f, false, true));
     if (guides_ms) *guides_ms = f->denoise.guides.ms();
     if (filter_ms) *filter_ms = f->denoise.filter.ms();
+    return KY_OK;
+}
+
+}  // extern "C"
+
+// ---- merging what other frames hold (DESIGN.md "Slices") ----
+// The kernel and, behind it, the bookkeeping: src_ws / src_state are device memory of f's device (src_state is read where f tracks noise), the other frame held
+// n_src samples in src_batches noise batches, `merged` is merge_accept's union.  Blocking; a failed merge is not counted.
+static int merge_apply(kyhip_frame* f, const void* src_ws, const void* src_state, int n_src, int src_batches, const Coverage& merged) {
+    if (f->sh.n_pix > 0) {
+        DeviceCtx* c;
+        KY_TRY(get_ctx(f->device, &c));
+        f->merge.valid = false;
+        f->merge.begin(c->stream);
+        const int rcode = merge_device(f->ws.p, src_ws, f->noise.on ? f->noise.state.p : nullptr, src_state, f->sh.n_pix, f->params.samples_per_pixel, samples_held(f), n_src, c->stream);
+        f->merge.end(c->stream);
+        KY_TRY(finish(c->stream, rcode, "merge", " (the frame's accumulators may hold a part of it)"));
+        f->merge.valid = true;
+    }
+    if (f->noise.on) { f->noise.batches += src_batches; f->noise.n_prev = merged.held(); }
+    f->cov = merged;
+    return KY_OK;
+}
+// the buffers a merge stages the other frame's parts in, allocated on the first merge that needs them (the device is current)
+static int merge_staging(kyhip_frame* f) {
+    if (!f->merge_ws.p) HIP_TRY(f->merge_ws.alloc(workspace_bytes_for(f->sh)));
+    if (f->noise.on && !f->merge_state.p) HIP_TRY(f->merge_state.alloc((size_t)f->sh.n_pix * sizeof(NoisePixel)));
+    return KY_OK;
+}
+extern "C" {
+
+int kyhip_frame_merge(kyhip_frame* f, const void* state, size_t bytes) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    MergeSource m;
+    KY_TRY(merge_source_check(f->header, state, bytes, &m));
+    Coverage merged;
+    KY_TRY(merge_accept(f->cov, f->own_first, f->own_end, f->params.samples_per_pixel, f->noise.on, f->blocks.on, m.cov, m.noise_pixels != 0, &merged));
+    if (f->sh.n_pix > 0) {
+        DeviceCtx* c;
+        KY_TRY(get_ctx(f->device, &c));
+        KY_TRY(f->merge.create());
+        KY_TRY(merge_staging(f));
+        HIP_TRY(hipMemcpy(f->merge_ws.p, (const char*)state + m.accum, workspace_bytes_for(f->sh), hipMemcpyHostToDevice));
+        if (f->noise.on) HIP_TRY(hipMemcpy(f->merge_state.p, (const char*)state + m.noise_pixels, (size_t)f->sh.n_pix * sizeof(NoisePixel), hipMemcpyHostToDevice));
+    }
+    return merge_apply(f, f->merge_ws.p, f->merge_state.p, m.cov.held(), m.batches, merged);
+}
+
+int kyhip_frame_merge_from(kyhip_frame* f, kyhip_frame* src) {
+    if (!f || !src) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (f == src) return fail(KY_ERR_INVALID_VALUE, "merge: a frame holds its own samples already");
+    if (std::memcmp(&f->header, &src->header, sizeof f->header) != 0)
+        return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their render params, scene or film size");
+    if (src->blocks.on) return fail(KY_ERR_INVALID_VALUE, "merge: the other frame retires pixel blocks: its pixels stand at sample counts of their own and merge with nothing");
+    Coverage merged;
+    KY_TRY(merge_accept(f->cov, f->own_first, f->own_end, f->params.samples_per_pixel, f->noise.on, f->blocks.on, src->cov, src->noise.on, &merged));
+    const void* src_ws = src->ws.p;
+    const void* src_state = src->noise.state.p;
+    if (f->sh.n_pix > 0) {
+        DeviceCtx* c;
+        KY_TRY(get_ctx(f->device, &c));
+        KY_TRY(f->merge.create());
+        if (src->device != f->device) {   // (the other frame's calls are blocking: nothing of it is in flight on its device)
+            KY_TRY(merge_staging(f));
+            HIP_TRY(hipMemcpyPeerAsync(f->merge_ws.p, f->device, src->ws.p, src->device, workspace_bytes_for(f->sh), c->stream));
+            if (f->noise.on) HIP_TRY(hipMemcpyPeerAsync(f->merge_state.p, f->device, src->noise.state.p, src->device, (size_t)f->sh.n_pix * sizeof(NoisePixel), c->stream));
+            src_ws = f->merge_ws.p; src_state = f->merge_state.p;
+        }
+    }
+    return merge_apply(f, src_ws, src_state, samples_held(src), src->noise.batches, merged);
+}
+
+int kyhip_frame_merge_ms(const kyhip_frame* f, float* ms) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (ms) *ms = f->merge.ms();
     return KY_OK;
 }
 

@@ -237,6 +237,91 @@ int kyhostcheck_noise(const long long* accum, const int* done, int n_pass, int n
     return noise_trailer_check(state, state_bytes, base_bytes, trailer_n_pix, samples_done, &t);
 }
 
+// A merge's arithmetic (ky_noise.hpp: merge_pixel, what ky_merge.hip's kernel does per pixel) on the caller's arrays: words_a (n_pix x 3), flags_a (n_pix) and,
+// when given, pairs_a (n_pix x {y_prev, m2}; pairs_b then too) receive the frame b, which holds n_b samples, a holding n_a.  Returns KY_OK, or
+// KY_ERR_INVALID_VALUE for arguments that are none.
+int kyhostcheck_merge(long long* words_a, const long long* words_b, unsigned* flags_a, const unsigned* flags_b, double* pairs_a, const double* pairs_b, int n_pix,
+                      int total_spp, int n_a, int n_b) {
+    using namespace kyn;
+    if (n_pix < 0 || n_a < 0 || n_b < 0 || (n_pix > 0 && (!words_a || !words_b || !flags_a || !flags_b || (pairs_a && !pairs_b)))) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    for (int i = 0; i < n_pix; ++i) {
+        NoisePixel a = {0.0, 0.0}, b = {0.0, 0.0};
+        if (pairs_a) { a = NoisePixel{pairs_a[2 * (size_t)i], pairs_a[2 * (size_t)i + 1]}; b = NoisePixel{pairs_b[2 * (size_t)i], pairs_b[2 * (size_t)i + 1]}; }
+        merge_pixel(words_a + 3 * (size_t)i, words_b + 3 * (size_t)i, flags_a[i], flags_b[i], pairs_a ? &a : nullptr, &b, total_spp, n_a, n_b);
+        if (pairs_a) { pairs_a[2 * (size_t)i] = a.y_prev; pairs_a[2 * (size_t)i + 1] = a.m2; }
+    }
+    return KY_OK;
+}
+
+// Slices without a device (ky_checkpoint.hpp), by `mode`; ranges are {first, end} pairs of int, a coverage is built from its pairs one coverage_union at a time:
+//   0  kyhip_slice_bounds(spp = na, n_slices = nb) -> out (nb + 1 values);
+//   1  the coverage of a's na pairs U the coverage of b's nb pairs -> out (pairs), counts[0] = their number.  Returns the first status that is not KY_OK;
+//   2  the host-side parts of the checkpoint of a frame of p that owns a[0] .. a[1], stands at a[2] and holds b's nb pairs (noise = extra[0]: it tracks noise, with
+//      extra[1] batches) into buf, zeroed first, when its `bytes` hold them; counts = {the state's size, where its slice trailer begins, where its noise trailer does};
+//   3  checkpoint_check of buf's first `bytes` bytes by a frame of p that owns a[0] .. a[1] (noise = extra[0]) -> counts = {chunks_done, samples held, batches,
+//      n_prev, front, ranges}, out = the ranges;
+//   4  merge_source_check of buf by a frame of p, then merge_accept by one that owns a[0] .. a[1], holds b's nb pairs and tracks noise (extra[0]) or blocks
+//      (extra[1]) -> out = the union, counts = {its ranges, the samples the state holds, its batches}.
+// Returns the status of what it ran, or KY_ERR_INVALID_VALUE for arguments that are none.
+int kyhostcheck_slices(int mode, const ky_render_params* p, const int* a, int na, const int* b, int nb, int* out, int* counts, void* buf, size_t bytes, const int* extra) {
+    if (mode == 0) return kyhip_slice_bounds(na, nb, out);
+    auto build = [](const int* pairs, int n, Coverage* cov) {
+        for (int i = 0; i < n; ++i) {
+            Coverage one;
+            one.n = 1; one.r[0] = pairs[2 * i]; one.r[1] = pairs[2 * i + 1];
+            KY_TRY(coverage_union(*cov, one, cov));
+        }
+        return (int)KY_OK;
+    };
+    auto give = [&](const Coverage& cov) { for (int i = 0; i < 2 * cov.n; ++i) out[i] = cov.r[i]; };
+    if (na < 0 || nb < 0 || (na > 0 && !a) || (nb > 0 && !b) || !out || !counts) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    if (mode == 1) {
+        Coverage ca, cb, u;
+        KY_TRY(build(a, na, &ca));
+        KY_TRY(build(b, nb, &cb));
+        KY_TRY(coverage_union(ca, cb, &u));
+        give(u);
+        counts[0] = u.n;
+        return KY_OK;
+    }
+    if (!valid_params(p) || !shard_in_range(p) || !extra || !a || !buf) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    const FrameHeader own = frame_header(p, 0x1234, 0);
+    if (mode == 2) {
+        KY_TRY(slice_range_check(p->samples_per_pixel, a[0], a[1]));
+        const CheckpointLayout L = checkpoint_layout(p, extra[0] != 0, false, a[0], a[1]);
+        counts[0] = (int)L.total; counts[1] = (int)L.slice; counts[2] = (int)L.noise;
+        if (bytes < L.total) return KY_OK;
+        CheckpointCounts n;
+        KY_TRY(build(b, nb, &n.cov));
+        n.samples_done = n.n_prev = n.cov.held();
+        n.front = a[2];
+        n.batches = extra[1];
+        std::memset(buf, 0, L.total);
+        checkpoint_write_host(own, L, n, nullptr, buf);
+        return KY_OK;
+    }
+    if (mode == 3) {
+        KY_TRY(slice_range_check(p->samples_per_pixel, a[0], a[1]));
+        CheckpointCounts n;
+        KY_TRY(checkpoint_check(own, checkpoint_layout(p, extra[0] != 0, false, a[0], a[1]), buf, bytes, &n));
+        const int got[6] = {n.chunks_done, n.samples_done, n.batches, n.n_prev, n.front, n.cov.n};
+        std::memcpy(counts, got, sizeof got);
+        give(n.cov);
+        return KY_OK;
+    }
+    if (mode == 4) {
+        MergeSource m;
+        KY_TRY(merge_source_check(own, buf, bytes, &m));
+        Coverage mine, u;
+        KY_TRY(build(b, nb, &mine));
+        KY_TRY(merge_accept(mine, a[0], a[1], p->samples_per_pixel, extra[0] != 0, extra[1] != 0, m.cov, m.noise_pixels != 0, &u));
+        give(u);
+        counts[0] = u.n; counts[1] = m.cov.held(); counts[2] = m.batches;
+        return KY_OK;
+    }
+    return fail(KY_ERR_INVALID_VALUE, "mode %d", mode);
+}
+
 // The block arithmetic of a frame that retires pixel blocks (ky_blocks.hpp: what ky_blocks.hip's kernels do per block) for the shard of p.  Each part runs when its
 // pointers are given:
 //   out_block (n_pix), out_pixel (n_blocks x 64), out_inside (n_blocks): the pixel -> block map, its inverse, and each block's pixels inside the film;
@@ -420,6 +505,16 @@ int kyhip_frame_begin(int, const ky_scene* scene, const ky_render_params* p, kyh
     *out = nullptr;
     return no_gpu();
 }
+int kyhip_frame_begin_slice(int device, const ky_scene* scene, const ky_render_params* p, int first_sample, int end_sample, kyhip_frame** out) {
+    const int rc = kyhip_frame_begin(device, scene, p, out);
+    if (rc != KY_ERR_NO_DEVICE) return rc;
+    KY_TRY(slice_range_check(p->samples_per_pixel, first_sample, end_sample));   // (the range is looked at behind every other argument, before the device)
+    return no_gpu();
+}
+int kyhip_frame_coverage(const kyhip_frame*, int*, int, int*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_merge(kyhip_frame*, const void*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_merge_from(kyhip_frame*, kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_merge_ms(const kyhip_frame*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_render(kyhip_frame*, int, int*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_samples(const kyhip_frame*, int*, int*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_resolve(kyhip_frame*, int, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }

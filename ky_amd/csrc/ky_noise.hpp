@@ -59,6 +59,30 @@ KY_NOFMA_FN KY_HD inline void noise_update(NoisePixel& px, double y_now, int n_p
     }
     px.y_prev = y_now;
 }
+// Two estimates of one pixel over DISJOINT samples become one (a merge of two frames' sample ranges, ky_merge.hip; DESIGN.md "Slices"): a stands at n_a samples,
+// b at n_b, y_merged is noise_luminance of the merged words.  noise_update's step with a batch that has a spread of its own (Chan's pairwise form of West's
+// update): with b.m2 == 0 it IS noise_update(a, a.y_prev + b.y_prev, n_a, n_a + n_b) in m2, bit for bit.  With a count of 0 the other pair's m2 is taken.  y_prev
+// becomes y_merged, not a.y_prev + b.y_prev: the next pass's batch difference is then exact.  Not symmetric in its last bits (mean_b - mean_a, a.m2 + b.m2 first):
+// which frame receives and in which order it merges shows in m2's rounding, never in the words.
+KY_NOFMA_FN KY_HD inline void noise_merge(NoisePixel& a, int n_a, const NoisePixel& b, int n_b, double y_merged) {
+    KY_NOFMA_BODY
+    if (n_a > 0 && n_b > 0) {
+        const double w = (double)n_a * (double)n_b / (double)(n_a + n_b);
+        const double t = b.y_prev / (double)n_b - a.y_prev / (double)n_a;
+        a.m2 = a.m2 + b.m2 + w * (t * t);
+    } else if (n_a <= 0) {
+        a.m2 = b.m2;
+    }
+    a.y_prev = y_merged;
+}
+// One pixel of a merge, as ky_merge.hip's kernel and kyhostcheck_merge run it: the three words add as 64-bit integers (exact: the frame's term limit covers all of
+// the frame's chunks, DESIGN.md "Slices"; written unsigned, two's complement), the flag words OR, and where both frames track noise (pa) the pairs merge at the
+// merged words.
+KY_HD inline void merge_pixel(long long* wa, const long long* wb, unsigned& fa, unsigned fb, NoisePixel* pa, const NoisePixel* pb, int total_spp, int n_a, int n_b) {
+    for (int c = 0; c < 3; ++c) wa[c] = (long long)((unsigned long long)wa[c] + (unsigned long long)wb[c]);
+    fa |= fb;
+    if (pa) noise_merge(*pa, n_a, *pb, n_b, noise_luminance(wa[0], wa[1], wa[2], total_spp));
+}
 // The standard error of the pixel's mean luminance in units of the film's white: se / max(1, mean), se = sqrt(m2 / (batches - 1) / N).  +inf before the second
 // batch; 0 for a pixel whose flag word has a NaN or +-inf bit (its resolved value is pinned by the flag rules).
 KY_NOFMA_FN KY_HD inline float noise_value(const NoisePixel& px, int batches, int n_done, unsigned flags) {
@@ -115,4 +139,7 @@ constexpr int KY_NOISE_BLOCK = 256;
 inline int noise_blocks(int n_pix) { return (n_pix + KY_NOISE_BLOCK - 1) / KY_NOISE_BLOCK; }
 // partials: noise_blocks(n_pix) + 1 NoiseSums; the result is the last one
 int noise_stats_device(const float* map, const unsigned char* cls, int n_pix, float threshold, void* partials, void* stream);
+// ky_merge.hip: merge_pixel over the n_pix pixels of two accumulator blocks of one shard (3 n_pix words, then n_pix flag words; src_ws is read only) and, where
+// dst_state is given, over their n_pix NoisePixel (src_state then too); dst stands at n_dst samples held, src at n_src
+int merge_device(void* dst_ws, const void* src_ws, void* dst_state, const void* src_state, int n_pix, int total_spp, int n_dst, int n_src, void* stream);
 }  // namespace kyn

@@ -80,21 +80,7 @@ def render_shard(scene, params, rank, world, device_index=0, out=None):
     """Render this rank's tiles on its GPU into `out` (default: a fresh zeroed tensor) [max_tiles_per_rank, tile_h, tile_w, 3]
     -- equal sizes on every rank keep the gather a single call."""
     lib = A.load_kyhip()
-    if world > 1:
-        # run-time instantiations across ranks: table and own kernel differ in the last bit of a pixel, so every rank of a frame must be on the same one.
-        # Mode 1 (blocking; the code cache is shared through flock) guarantees that as long as no rank's compile fails; mode 2 switches when each process's
-        # own background compile finishes -- a matter of timing, so it is refused here.
-        mode = lib.kyhip_set_jit(-1)
-        if mode == 2:
-            import os
-            if os.environ.get("KYHIP_JIT") == "2":
-                raise RuntimeError("kyhip_set_jit(2) (asynchronous run-time instantiations) would let the ranks of one frame render on different kernels; use mode 1 with world > 1")
-            # the library's own default (round 6: mode 2 in a single-process job; torchrun's WORLD_SIZE already turns it off): a caller that builds its own
-            # group gets the table's kernels on every rank
-            lib.kyhip_set_jit(0)
-            mode = 0
-        if mode == 1 and lib.kyhip_jit_failures() > 0:
-            raise RuntimeError("a run-time instantiation failed on this rank (%s): its shards would come from another kernel than the other ranks'" % lib.kyhip_jit_status().decode())
+    _same_kernel_on_every_rank(lib, world)
     p = shard_params(params, rank, world)
     dev = torch.device("cuda", device_index)
     tiles = out
@@ -206,3 +192,57 @@ def render_distributed(scene, params, rank, world, device_index=0, film=None, gr
     if pipeline:
         fb.free = torch.cuda.current_stream(dev).record_event()
     return film
+
+
+# ---- the sample-range mode: every rank renders a slice of every pixel's samples over the whole film (api.Frame(slice=...), DESIGN.md "Slices") ----
+def _same_kernel_on_every_rank(lib, world):
+    """Run-time instantiations across ranks (render_shard, render_sliced_distributed): table and own kernel differ in the last bit of a pixel, so every rank of a
+    frame must be on the same one.  Mode 1 (blocking; the code cache is shared through flock) guarantees that as long as no rank's compile fails; mode 2 switches
+    when each process's own background compile finishes -- a matter of timing, so it is refused here."""
+    if world <= 1:
+        return
+    mode = lib.kyhip_set_jit(-1)
+    if mode == 2:
+        import os
+        if os.environ.get("KYHIP_JIT") == "2":
+            raise RuntimeError("kyhip_set_jit(2) (asynchronous run-time instantiations) would let the ranks of one frame render on different kernels; use mode 1 with world > 1")
+        # the library's own default (round 6: mode 2 in a single-process job; torchrun's WORLD_SIZE already turns it off): a caller that builds its own
+        # group gets the table's kernels on every rank
+        lib.kyhip_set_jit(0)
+        mode = 0
+    if mode == 1 and lib.kyhip_jit_failures() > 0:
+        raise RuntimeError("a run-time instantiation failed on this rank (%s): its part of the frame would come from another kernel than the other ranks'" % lib.kyhip_jit_status().decode())
+
+
+def gather_states(state, rank, world, group=None):
+    """One torch.distributed.gather of every rank's saved frame state (bytes of one length on every rank: the slices of one frame that agree in tracking noise) to
+    rank 0 as CPU uint8 tensors.  Returns the list of bytes in rank order on rank 0, None elsewhere."""
+    mine = torch.frombuffer(bytearray(state), dtype=torch.uint8)
+    if world == 1:
+        return [bytes(state)]
+    import torch.distributed as dist
+    if rank != 0:
+        dist.gather(mine, None, dst=0, group=group)
+        return None
+    out = [torch.empty_like(mine) for _ in range(world)]
+    dist.gather(mine, out, dst=0, group=group)
+    return [t.numpy().tobytes() for t in out]
+
+
+def render_sliced_distributed(scene, params, rank, world, device_index=0, min_samples_per_pass=64, film=None, group=None, noise=False):
+    """integrator_t::render over `world` ranks by sample range: rank r renders slice r of api.slice_bounds(samples_per_pixel, world) over the whole film in passes
+    of at least min_samples_per_pass, with no communication while rendering and perfect load balance; ONE gather of the saved states (through host memory: the group
+    may be gloo) at the end, then rank 0 merges them into its own frame and resolves.  Returns the host film (numpy, api.render's bit for bit) on rank 0, None
+    elsewhere.  noise=True: every rank tracks noise and rank 0's merged frame carries the pooled estimate."""
+    lib = A.load_kyhip()
+    _same_kernel_on_every_rank(lib, world)
+    bounds = api.slice_bounds(params.samples_per_pixel, world)
+    with api.Frame(scene, params, device=device_index, noise=noise, slice=(bounds[rank], bounds[rank + 1])) as f:
+        while f.done < bounds[rank + 1] - bounds[rank]:
+            f.render(min_samples_per_pass)
+        states = gather_states(f.save(), rank, world, group)
+        if rank != 0:
+            return None
+        for s in states[1:]:
+            f.merge(s)
+        return f.resolve(film=film)

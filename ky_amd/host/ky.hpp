@@ -18,8 +18,10 @@
 #include <functional>
 #include <limits>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -718,6 +720,79 @@ public:
             throw;
         }
         kyhip_frame_end(frame);
+    }
+    // render() by SAMPLE RANGE over a device list (kyhip_frame_begin_slice, kyhip_frame_merge_from; include/kyhip.h "Slices"): the frame's samples are cut into
+    // devices.size() slices (kyhip_slice_bounds) and slice k renders over the whole film on devices[k], in passes of at least min_samples_per_pass -- one host thread
+    // per distinct device, the slices that share a device one after the other on its thread.  After every pass on_pass(done, total) is called, from the thread that
+    // rendered it and never from two at once, with the samples per pixel done over all slices; when it returns false every thread stops behind its pass.  Then the
+    // slices are merged into slice 0's frame on devices[0] and added to the film like render() adds it: for a complete frame exactly what render() adds, bit for bit,
+    // whatever the list; the mean of the samples done if the frame was stopped early.  An empty on_pass renders to the end.  Light classes are render()'s only.
+    void render_sliced(scene_t* scene, sampler_t* original_sampler, film_t* film, const std::vector<int>& devices, int min_samples_per_pass,
+                       const std::function<bool(int done, int total)>& on_pass = {}) {
+        if (masked()) throw std::runtime_error("integrator_t::render_sliced: light classes are rendered by render() only");
+        if (devices.empty()) throw std::runtime_error("integrator_t::render_sliced: an empty device list");
+        const ky_render_params p = params_for(original_sampler, film);
+        const int n = (int)devices.size();
+        std::vector<int> bounds((size_t)n + 1);
+        if (kyhip_slice_bounds(p.samples_per_pixel, n, bounds.data()) != KY_OK) throw std::runtime_error(std::string("kyhip_slice_bounds: ") + kyhip_last_error());
+        std::vector<kyhip_frame*> frames((size_t)n, nullptr);
+        auto end_all = [&] { for (kyhip_frame*& f : frames) { kyhip_frame_end(f); f = nullptr; } };
+        try {
+            const ky_scene& flat = scene->flatten();
+            std::vector<int> distinct;
+            for (int k = 0; k < n; ++k) {
+                if (kyhip_frame_begin_slice(devices[(size_t)k], &flat, &p, bounds[(size_t)k], bounds[(size_t)k + 1], &frames[(size_t)k]) != KY_OK)
+                    throw std::runtime_error(std::string("kyhip_frame_begin_slice: ") + kyhip_last_error());
+                bool seen = false;
+                for (int d : distinct) seen = seen || d == devices[(size_t)k];
+                if (!seen) distinct.push_back(devices[(size_t)k]);
+            }
+            std::mutex m;   // guards the three below and serialises on_pass
+            int done_all = 0;
+            bool go_on = true;
+            std::string error;
+            auto device_thread = [&](int device) {
+                for (int k = 0; k < n; ++k) {
+                    if (devices[(size_t)k] != device) continue;
+                    const int size = bounds[(size_t)k + 1] - bounds[(size_t)k];
+                    int done = 0;
+                    while (done < size) {
+                        {
+                            std::lock_guard<std::mutex> lock(m);
+                            if (!go_on || !error.empty()) return;
+                        }
+                        const int before = done;
+                        const int rc = kyhip_frame_render(frames[(size_t)k], min_samples_per_pass, &done);
+                        std::lock_guard<std::mutex> lock(m);
+                        if (rc != KY_OK) {
+                            if (error.empty()) error = std::string("kyhip_frame_render: ") + kyhip_last_error();
+                            return;
+                        }
+                        done_all += done - before;
+                        if (!on_pass || !go_on || !error.empty()) continue;
+                        try {
+                            go_on = on_pass(done_all, p.samples_per_pixel);
+                        } catch (const std::exception& e) {
+                            error = e.what();
+                        } catch (...) {
+                            error = "integrator_t::render_sliced: on_pass threw";
+                        }
+                    }
+                }
+            };
+            std::vector<std::thread> threads;
+            for (int d : distinct) threads.emplace_back(device_thread, d);
+            for (std::thread& t : threads) t.join();
+            if (!error.empty()) throw std::runtime_error(error);
+            for (int k = 1; k < n; ++k)
+                if (kyhip_frame_merge_from(frames[0], frames[(size_t)k]) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_merge_from: ") + kyhip_last_error());
+            const int rc = kyhip_frame_resolve(frames[0], done_all < p.samples_per_pixel ? 1 : 0, film->target_origin(), film->row_stride_px());
+            if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+        } catch (...) {
+            end_all();
+            throw;
+        }
+        end_all();
     }
     // render_passes that stops by itself: passes of at least min_samples_per_pass until, after min_batches passes or more, at most max_fraction_above of the
     // pixels have a noise estimate (kyhip_frame_noise: the standard error of the pixel's mean luminance, in units of the film's white) above `threshold`, or the

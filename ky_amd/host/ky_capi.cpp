@@ -138,6 +138,33 @@ int kyhost_render_passes(void* scene, int integrator_enum, int depth, int direct
     return rc != 0 ? rc : status;
 }
 
+// create_integrator(...)->render_sliced(&scene, sampler, &film, {devices[0 .. n_devices)}, min_samples_per_pass, {}) on a film_t of width x height: the frame by
+// sample range, rendered to the end.  `film` is read, added to and written back.  Returns 0, -1 on error, -2 when create_integrator returns nullptr.
+int kyhost_render_sliced(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
+                         float* film, const int* devices, int n_devices, int min_samples_per_pass) {
+    int status = 0;
+    int rc = guarded([&] {
+        if (!devices || n_devices < 1) throw std::runtime_error("kyhost_render_sliced: an empty device list");
+        std::unique_ptr<ky::integrator_t> integrator;
+        const auto ie = (ky::integrator_enum_t)integrator_enum;
+        if (ie == ky::integrator_enum_t::position || ie == ky::integrator_enum_t::normal || ie == ky::integrator_enum_t::basecolor)
+            integrator = std::make_unique<ky::debug_integrator_t>(ie, devices[0]);
+        else
+            integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, devices[0]);
+        if (!integrator) { status = -2; return; }
+        std::unique_ptr<ky::sampler_t> sampler;
+        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
+        else sampler = std::make_unique<ky::random_sampler_t>(spp);
+        sampler->set_seed(seed);
+        ky::film_t f(width, height);
+        const size_t n = (size_t)f.get_pixel_num() * 3;
+        std::memcpy(f.data(), film, n * sizeof(float));
+        integrator->render_sliced(&((scene_box*)scene)->scene, sampler.get(), &f, std::vector<int>(devices, devices + n_devices), min_samples_per_pass);
+        std::memcpy(film, f.data(), n * sizeof(float));
+    });
+    return rc != 0 ? rc : status;
+}
+
 // create_integrator(...)->render_until(&scene, sampler, &film, threshold, max_fraction_above, min_batches, min_samples_per_pass) on a film_t of width x height.
 // `film` is read, added to and written back.  Returns the samples done per pixel (>= 1), -1 on error, -2 when create_integrator returns nullptr.
 int kyhost_render_until(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
