@@ -1,5 +1,5 @@
 # Builds every native piece in-tree:
-#   ky_amd/lib/libkyhip.so   the product: gfx950 kernels + C ABI (include/kyhip.h), ten translation units under ky_amd/csrc
+#   ky_amd/lib/libkyhip.so   the product: gfx950 kernels + C ABI (include/kyhip.h), eleven translation units under ky_amd/csrc
 #   ky_amd/lib/libkyhost.so  host-side C++ API (ky_amd/host/ky.hpp) behind a small C API for Python
 #   oracle/libkyoracle.so    the CPU checker (test infrastructure only)
 HIPCC    ?= hipcc
@@ -19,21 +19,23 @@ DEVICE_HDRS := $(CSRC)/ky_scene.hpp $(CSRC)/ky_shard.hpp $(CSRC)/ky_device.hpp $
 $(RTC_INC): $(DEVICE_HDRS) include/kyhip.h tools/embed_sources.py
 	python3 tools/embed_sources.py $@ ky_scene.hpp=$(CSRC)/ky_scene.hpp ky_shard.hpp=$(CSRC)/ky_shard.hpp ky_device.hpp=$(CSRC)/ky_device.hpp ky_render.hpp=$(CSRC)/ky_render.hpp ../../include/kyhip.h=include/kyhip.h
 
-# libkyhip.so = ten translation units (round 5; one 2100-line kyhip.hip before):
+# libkyhip.so = eleven translation units (round 5; one 2100-line kyhip.hip before):
 #   ky_launch.hip  the render kernels' table + launch path, film kernels, fp64 smallpt      ky_kat.hip   KAT kernels + entries
 #   ky_pack.cpp    host: params, scene packing, occluder proof, policies, HostPool           ky_jit.cpp   run-time instantiations' code cache
-#   ky_seam.cpp    host-film calls (kyhip_render / kyhip_render_multi)                       ky_frame.cpp a frame in passes (kyhip_frame_*)
+#   ky_seam.cpp    host-film calls (kyhip_render / kyhip_render_multi)                       ky_frame.cpp a frame in passes (kyhip_frame_*): its device work
+#   ky_frame_book.cpp  host: a frame's bookkeeping (FrameBook: passes, slices, what it holds and tracks) and its checkpoint (ky_checkpoint.hpp)
 #   ky_noise.hip   a frame's noise estimate: film-sized kernels and a deterministic reduction (ky_noise.hpp: their arithmetic, host and device)
 #   ky_blocks.hip  a frame that retires pixel blocks: block state, retire rule, the live list's compaction, per-block resolve (ky_blocks.hpp: their arithmetic)
 #   ky_denoise.hip a frame's denoised picture: the guide trace, the gather into film order, the a-trous levels, the add (ky_denoise.hpp: their arithmetic)
 #   ky_merge.hip   two frames' disjoint sample ranges become one: the film-sized merge kernel (ky_noise.hpp: its arithmetic)
-# (ky_pack.cpp and ky_jit.cpp make no HIP call: `make sanitize` builds the same files with g++ -fsanitize=...)
-HOST_HDRS := $(CSRC)/ky_host.hpp $(CSRC)/ky_ctx.hpp $(CSRC)/ky_scene.hpp $(CSRC)/ky_shard.hpp $(CSRC)/ky_noise.hpp $(CSRC)/ky_blocks.hpp $(CSRC)/ky_denoise.hpp $(CSRC)/ky_checkpoint.hpp include/kyhip.h
+# (ky_pack.cpp, ky_frame_book.cpp and ky_jit.cpp make no HIP call: `make sanitize` builds the same files with g++ -fsanitize=...)
+HOST_HDRS := $(CSRC)/ky_host.hpp $(CSRC)/ky_ctx.hpp $(CSRC)/ky_scene.hpp $(CSRC)/ky_shard.hpp $(CSRC)/ky_noise.hpp $(CSRC)/ky_blocks.hpp $(CSRC)/ky_denoise.hpp $(CSRC)/ky_checkpoint.hpp $(CSRC)/ky_frame_book.hpp include/kyhip.h
 OBJDIR  := build/obj
-KYHIP_OBJS := $(OBJDIR)/ky_launch.o $(OBJDIR)/ky_kat.o $(OBJDIR)/ky_pack.o $(OBJDIR)/ky_jit.o $(OBJDIR)/ky_seam.o $(OBJDIR)/ky_frame.o $(OBJDIR)/ky_noise.o $(OBJDIR)/ky_blocks.o $(OBJDIR)/ky_denoise.o $(OBJDIR)/ky_merge.o
+KYHIP_OBJS := $(OBJDIR)/ky_launch.o $(OBJDIR)/ky_kat.o $(OBJDIR)/ky_pack.o $(OBJDIR)/ky_frame_book.o $(OBJDIR)/ky_jit.o $(OBJDIR)/ky_seam.o $(OBJDIR)/ky_frame.o $(OBJDIR)/ky_noise.o $(OBJDIR)/ky_blocks.o $(OBJDIR)/ky_denoise.o $(OBJDIR)/ky_merge.o
 $(OBJDIR)/ky_launch.o: $(CSRC)/ky_launch.hip $(DEVICE_HDRS) $(CSRC)/ky_queue.hpp $(CSRC)/ky_smallpt.hpp $(CSRC)/ky_measure.hpp $(CSRC)/ky_film_value.hpp $(HOST_HDRS)
 $(OBJDIR)/ky_kat.o: $(CSRC)/ky_kat.hip $(DEVICE_HDRS) $(CSRC)/ky_measure.hpp $(HOST_HDRS)
 $(OBJDIR)/ky_pack.o: $(CSRC)/ky_pack.cpp $(HOST_HDRS)
+$(OBJDIR)/ky_frame_book.o: $(CSRC)/ky_frame_book.cpp $(HOST_HDRS)
 $(OBJDIR)/ky_jit.o: $(CSRC)/ky_jit.cpp $(HOST_HDRS) $(RTC_INC)
 $(OBJDIR)/ky_seam.o: $(CSRC)/ky_seam.cpp $(HOST_HDRS)
 $(OBJDIR)/ky_frame.o: $(CSRC)/ky_frame.cpp $(HOST_HDRS)
@@ -68,14 +70,14 @@ build_variants/%: tools/ubench/%.hip
 	$(HIPCC) --offload-arch=gfx950 -O2 -Wno-unused-value -o $@ $<
 
 # ---- sanitizers on the CPU build (never on the GPU: the pool has no GPU sanitizers) --------------------------------------------------------
-# The host code that needs no GPU -- ky_pack.cpp (scene packing, occluder proof, HostPool, seam lock order), ky_jit.cpp (code cache, posix_spawn) plus
+# The host code that needs no GPU -- ky_pack.cpp (scene packing, occluder proof, HostPool, seam lock order), ky_frame_book.cpp (a frame's bookkeeping and checkpoint), ky_jit.cpp (code cache, posix_spawn) plus
 # ky_hostcheck.cpp (entry points for them) -- the host mirror's C API (ky.hpp's scene graph) and the oracle, built by g++ with
-# -fsanitize=address,undefined, and the first three again with -fsanitize=thread.  `make sanitize-build` builds them (tests/test_sanitize.py does that
+# -fsanitize=address,undefined, and the first four again with -fsanitize=thread.  `make sanitize-build` builds them (tests/test_sanitize.py does that
 # on demand and runs its checks in sanitized child processes); `make sanitize` also runs the CPU test suite under the address build and writes
 # profiles/<round>_sanitize_summary.txt (tools/sanitize/run.sh).
 SANDIR   := build/san
 SANFLAGS := -O1 -g -std=c++17 -fPIC -fno-omit-frame-pointer -Wall -Wno-unused-function -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include
-HOSTSAN_SRC := $(CSRC)/ky_pack.cpp $(CSRC)/ky_jit.cpp $(CSRC)/ky_hostcheck.cpp
+HOSTSAN_SRC := $(CSRC)/ky_pack.cpp $(CSRC)/ky_frame_book.cpp $(CSRC)/ky_jit.cpp $(CSRC)/ky_hostcheck.cpp
 $(SANDIR)/libkyhip_host_asan.so: $(HOSTSAN_SRC) $(HOST_HDRS) $(RTC_INC)
 	@mkdir -p $(SANDIR)
 	$(CXX) $(SANFLAGS) -fsanitize=address,undefined -shared -o $@ $(HOSTSAN_SRC) -lpthread

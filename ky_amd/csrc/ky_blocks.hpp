@@ -3,7 +3,7 @@
  * is the work decoder's item, a block of 8 x 8 pixels (ShardConst::blocks_per_tile, n_blocks): a block is live, or retired at the sample count it had when it was
  * last rendered.  Live blocks all stand at the frame's front; a pass renders the live ones only, through the ascending list of their indices (ky_render.hpp,
  * LISTED).  The arithmetic is written ONCE here, as KY_HD functions: the pixel <-> block index in compact tile order, the retire rule and the check of a
- * checkpoint's block trailer.  The device kernels (ky_blocks.hip), the host (ky_frame.cpp) and the host-only builds (kyhostcheck_blocks, ky_hostcheck.cpp)
+ * checkpoint's block trailer.  The device kernels (ky_blocks.hip), the host (ky_frame_book.cpp) and the host-only builds (kyhostcheck_blocks, ky_hostcheck.cpp)
  * share it.  Plain C++: part of `make sanitize`.
  */
 #pragma once
@@ -59,7 +59,7 @@ KY_HD inline int block_samples(const BlockState& s, int front) { return s.retire
 inline size_t blocks_list_offset(const ShardConst& sh) { return (size_t)sh.n_pix * (3 * sizeof(unsigned long long) + sizeof(unsigned)); }
 inline size_t blocks_list_bytes(const ShardConst& sh) { return (size_t)sh.n_blocks * sizeof(int); }
 
-// ---- the block trailer of a checkpoint (ky_pack.cpp) ----
+// ---- the block trailer of a checkpoint (ky_frame_book.cpp) ----
 inline size_t block_trailer_bytes(int n_blocks) { return sizeof(BlockTrailer) + (size_t)n_blocks * sizeof(BlockState); }
 // KY_OK, or KY_ERR_INVALID_VALUE with the message: `bytes` after `offset` hold no whole trailer, another magic, another block count, a retirement count that is
 // neither -1 nor a sample count at which a pass of a total_spp-sample frame can end (0 included), or one beyond samples_done; a pass count below 0; a batch count

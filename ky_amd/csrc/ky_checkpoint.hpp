@@ -4,7 +4,8 @@
  * BlockTrailer and n_blocks BlockState (ky_blocks.hpp), then for a frame that owns a sample range other than all of them (a slice, DESIGN.md "Slices") a
  * SliceTrailer.  CheckpointLayout says where each part lies, checkpoint_write_host writes the parts the host holds,
  * checkpoint_check decides what a frame loads; ky_frame.cpp adds the copies of the device parts and nothing else.  Host only, no HIP call: defined in
- * ky_pack.cpp, part of `make sanitize` (kyhostcheck_checkpoint, ky_hostcheck.cpp).
+ * ky_frame_book.cpp next to the frame's book, which asks and writes through it (ky_frame_book.hpp); part of `make sanitize` (kyhostcheck_checkpoint, kyhostcheck_book,
+ * ky_hostcheck.cpp).
  */
 #pragma once
 #include "ky_blocks.hpp"   // ky_noise.hpp, ky_shard.hpp

@@ -1,7 +1,7 @@
 /*
  * ky_host.hpp -- what the host-side translation units of libkyhip.so share that needs NO HIP runtime: error reporting, parameter checks and shard
  * geometry, scene packing and the occluder classification, the launch policies (specialisation, deferred shadow rays, engine), the run-time
- * instantiations' code cache, and the small thread pool of the host-film seam.  Implemented in ky_pack.cpp and ky_jit.cpp, which are plain C++:
+ * instantiations' code cache, and the small thread pool of the host-film seam.  Implemented in ky_pack.cpp, ky_frame_book.cpp (pass_boundaries) and ky_jit.cpp, which are plain C++:
  * `make sanitize` builds them with g++ -fsanitize=address,undefined / thread next to the oracle and runs them through tests/test_sanitize.py.
  * (The HIP side -- device contexts, streams, the scene cache -- is ky_ctx.hpp.)
  */
@@ -61,7 +61,7 @@ inline size_t workspace_bytes_for(const ShardConst& s) { return (size_t)s.n_pix 
 
 // ---- passes of a frame (kyhip_frame_*; the chunk arithmetic is ky_shard.hpp's) ----
 int pass_boundaries(int spp, int* bounds, int n);   // kyhip_pass_boundaries
-// (a frame's checkpoint: ky_checkpoint.hpp)
+// (a frame's checkpoint: ky_checkpoint.hpp; its bookkeeping: ky_frame_book.hpp)
 // The stop rule's arguments, refused before a frame or a device is looked at, in this order by every entry that takes them (ky_frame.cpp and the host-only
 // builds' stand-ins, ky_hostcheck.cpp): KY_OK, or KY_ERR_INVALID_VALUE with the message
 int threshold_check(float threshold);                                                  // a noise level is >= 0 (a NaN is not)

@@ -2,9 +2,10 @@
  * ky_hostcheck.cpp -- entry points of the SANITIZER builds only (`make sanitize`: g++ -fsanitize=address,undefined and -fsanitize=thread over ky_pack.cpp,
  * ky_jit.cpp and this file; never part of libkyhip.so).  They drive the host code that has no C-ABI entry of its own -- scene packing into a heap DScene,
  * the scene cache's keys, the chunk schedule, the banded add, HostPool and the seam's lock order under contention and across a fork -- so that
- * tests/test_sanitize.py can run it under the sanitizers from Python (ctypes) or from the stress binary (tools/sanitize/stress.cpp).  A checkpoint's layout,
- * writer and check (ky_checkpoint.hpp) and the stop rule's argument checks (ky_host.hpp) are the product's own, defined in ky_pack.cpp: kyhostcheck_checkpoint
- * and the kyhip_frame_* stand-ins at the end of this file call them and restate nothing.
+ * tests/test_sanitize.py can run it under the sanitizers from Python (ctypes) or from the stress binary (tools/sanitize/stress.cpp).  A frame's bookkeeping
+ * (FrameBook, ky_frame_book.hpp), a checkpoint's layout, writer and check (ky_checkpoint.hpp; both ky_frame_book.cpp) and the stop rule's argument checks
+ * (ky_host.hpp, ky_pack.cpp) are the product's own: kyhostcheck_frame and kyhostcheck_book drive the book through whole life cycles, kyhostcheck_checkpoint and
+ * the kyhip_frame_* stand-ins at the end of this file call the rest, and nothing of it is restated here.
  */
 #include <atomic>
 #include <cstdlib>
@@ -15,7 +16,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
-#include "ky_checkpoint.hpp"   // ky_host.hpp, ky_blocks.hpp, ky_noise.hpp
+#include "ky_frame_book.hpp"   // ky_checkpoint.hpp, ky_host.hpp, ky_blocks.hpp, ky_noise.hpp
 #include "ky_denoise.hpp"
 
 using namespace kyh;
@@ -62,31 +63,36 @@ int kyhostcheck_chunks(int spp) {
     return next == spp ? n : -1;
 }
 
-// A frame's host bookkeeping (kyhip_frame_*) on the caller's parameters, without a device: passes of at least min_samples from the first chunk to the last
-// cover every chunk once, in order, each ending at a value of pass_boundaries; a checkpoint written at every such point is accepted and gives the chunk count
-// back, and one cut short, of another seed, or with a sample count no chunk ends at is refused.  Returns the number of passes, or a negative number.
+// A frame's host bookkeeping on the caller's parameters, without a device: the passes of at least min_samples that the book of a frame that owns everything takes
+// (FrameBook::next_pass / commit_pass, what kyhip_frame_render asks and commits) cover every chunk once, in order, each ending at a value of pass_boundaries; a
+// checkpoint written at every such point is accepted and gives the chunk count back, and one cut short, of another seed, or with a sample count no chunk ends at is
+// refused.  Returns the number of passes, or a negative number.
 int kyhostcheck_frame(const ky_render_params* p, int min_samples) {
     if (!valid_params(p) || min_samples < 1) return KY_ERR_INVALID_VALUE;
     const ChunkPlan plan = chunk_plan(p->samples_per_pixel);
     std::vector<int> bounds((size_t)chunk_count(plan));
     if (pass_boundaries(p->samples_per_pixel, bounds.data(), (int)bounds.size()) != (int)bounds.size()) return -10;
-    const FrameHeader own = frame_header(p, 0x1234, 0);
-    const size_t state_end = checkpoint_layout(p, false, false).total;
+    FrameBook book;
+    book.begin(p, 0x1234, 0, p->samples_per_pixel);
+    const FrameHeader own = book.header;
+    const size_t state_end = book.layout.total;
     std::vector<unsigned char> state(state_end, 0);
     ky_render_params q = *p;
     q.seed ^= 1u;
-    int passes = 0, done = 0;
-    while (done < (int)bounds.size()) {
-        const int next = pass_chunk_end(plan, done, min_samples);
-        if (next <= done || next > (int)bounds.size()) return -11;
-        if (next < (int)bounds.size() && bounds[(size_t)next - 1] - chunk_end(plan, done - 1) < min_samples) return -12;
-        done = next;
+    int passes = 0;
+    while (!book.owned_rendered()) {
+        const int done = book.chunks_done, before = book.front();
+        PassStep step;
+        if (book.next_pass(min_samples, &step) != KY_OK || step.chunk_first != done || step.chunk_count <= 0 || done + step.chunk_count > (int)bounds.size()) return -11;
+        book.commit_pass(step);
+        if (book.chunks_done != done + step.chunk_count || book.front() != bounds[(size_t)book.chunks_done - 1] || book.held() != book.front()) return -11;
+        if (!book.owned_rendered() && book.front() - before < min_samples) return -12;
         ++passes;
         int back = -1;
         FrameHeader h = own;
-        h.samples_done = bounds[(size_t)done - 1];
+        h.samples_done = book.front();
         std::memcpy(state.data(), &h, sizeof h);
-        if (frame_state_check(own, state.data(), state.size(), state_end, &back) != KY_OK || back != done) return -13;
+        if (frame_state_check(own, state.data(), state.size(), state_end, &back) != KY_OK || back != book.chunks_done) return -13;
         if (frame_state_check(own, state.data(), state.size() - 1, state_end, &back) == KY_OK || frame_state_check(own, state.data(), sizeof h - 1, state_end, &back) == KY_OK) return -14;
         if (frame_state_check(frame_header(&q, 0x1234, 0), state.data(), state.size(), state_end, &back) == KY_OK) return -15;
         if (frame_state_check(frame_header(p, 0x1235, 0), state.data(), state.size(), state_end, &back) == KY_OK) return -16;
@@ -98,6 +104,121 @@ int kyhostcheck_frame(const ky_render_params* p, int min_samples) {
         if (is_bound) ++c;
     }
     return passes;
+}
+
+// blocks_init_kernel's rule (ky_blocks.hip) for a block with `inside` pixels inside the film, and what blocks_refresh (ky_frame.cpp) counts when the states come home
+static kyb::BlockState block_init_state(int inside) { return inside > 0 ? kyb::BlockState{-1, 0} : kyb::BlockState{0, 0}; }
+static int blocks_come_home(FrameBook* book) {
+    int n_live = 0;
+    for (const kyb::BlockState& s : book->blocks.host) n_live += s.retired_at < 0;
+    return book->blocks_home(n_live);
+}
+// one operation of kyhostcheck_book on `book`: what the kyhip_frame_* entry of that name does (ky_frame.cpp) without its device work -- ask the book, commit
+static int book_op(FrameBook* books, int n_books, std::vector<unsigned char>* slots, int op, int at, int arg, int arg2) {
+    FrameBook& book = books[at];
+    auto slot_of = [&](std::vector<unsigned char>** out) {
+        if (arg < 0 || arg >= 4) return fail(KY_ERR_INVALID_VALUE, "slot %d", arg);
+        *out = &slots[arg];
+        return (int)KY_OK;
+    };
+    std::vector<unsigned char>* slot = nullptr;
+    switch (op) {
+    case 0: {   // kyhip_frame_render
+        PassStep step;
+        KY_TRY(book.next_pass(arg, &step));
+        book.commit_pass(step);
+        return KY_OK;
+    }
+    case 1: {   // kyhip_frame_save: the host parts into a zeroed buffer
+        KY_TRY(slot_of(&slot));
+        std::vector<unsigned char> buf(book.layout.total, 0);
+        KY_TRY(book.save_host(buf.data(), buf.size()));
+        slot->swap(buf);
+        return KY_OK;
+    }
+    case 2: {   // kyhip_frame_load of the slot's bytes but the last arg2
+        KY_TRY(slot_of(&slot));
+        const size_t bytes = slot->size() - ((size_t)arg2 < slot->size() ? (size_t)arg2 : slot->size());
+        CheckpointCounts n;
+        KY_TRY(book.load_check(slot->data(), bytes, &n));
+        if (book.blocks.on && book.sh.n_blocks > 0) {
+            std::memcpy(book.blocks.host.data(), slot->data() + book.layout.block_states, book.layout.block_states_bytes());
+            KY_TRY(blocks_come_home(&book));
+        }
+        book.commit_load(n);
+        return KY_OK;
+    }
+    case 3: {   // kyhip_frame_merge of the slot's bytes but the last arg2
+        KY_TRY(slot_of(&slot));
+        const size_t bytes = slot->size() - ((size_t)arg2 < slot->size() ? (size_t)arg2 : slot->size());
+        MergeStep step;
+        KY_TRY(book.merge_state(slot->data(), bytes, &step));
+        book.commit_merge(step);
+        return KY_OK;
+    }
+    case 4: {   // kyhip_frame_merge_from book arg
+        if (arg < 0 || arg >= n_books) return fail(KY_ERR_INVALID_VALUE, "book %d", arg);
+        MergeStep step;
+        KY_TRY(book.merge_book(books[arg], &step));
+        book.commit_merge(step);
+        return KY_OK;
+    }
+    case 5:   // kyhip_frame_track_noise
+        if (book.noise.on) return KY_OK;
+        KY_TRY(book.can_track_noise());
+        book.track_noise();
+        return KY_OK;
+    case 6:   // kyhip_frame_track_blocks
+        if (book.blocks.on) return KY_OK;
+        KY_TRY(book.can_track_blocks());
+        book.size_blocks();
+        for (size_t b = 0; b < book.blocks.host.size(); ++b) book.blocks.host[b] = block_init_state(book.blocks.inside[b]);
+        KY_TRY(blocks_come_home(&book));
+        book.track_blocks();
+        return KY_OK;
+    case 7: return KY_OK;   // nothing: the book as it stands is recorded
+    default: return fail(KY_ERR_INVALID_VALUE, "operation %d", op);
+    }
+}
+
+// Whole life cycles of up to five frames of one ky_render_params and one scene hash (source_hash, when not 0: the kernel source hash their headers carry instead of
+// this build's, which another compiler made -- a caller that holds the books' states against libkyhip.so's passes that library's), without a device: books[i] = {own_first, own_end} opens book i (begin_check,
+// FrameBook::begin), then ops[k] = {operation, book, arg, arg2} run in order on the books and on four state slots:
+//   0 a pass of at least arg samples      1 save into slot arg            2 load from slot arg (without its last arg2 bytes)      3 merge slot arg's state (likewise)
+//   4 merge from book arg                 5 track noise                   6 track blocks                                          7 nothing
+// (kyhip_frame_keep has no operation: the rule of ky_blocks.hip's keep kernel is no function of ky_blocks.hpp, and it is not restated here.)
+// Behind every operation records[k] (KY_BOOK_RECORD ints) = {status, front, held, coverage ranges, own_first, own_end, batches, n_prev, passes, n_live,
+// state_bytes, then the coverage's pairs, zeros behind them} of the book it addressed.  At the end slot i's bytes lie at slots_out + i * slot_capacity when they
+// fit, and slot_bytes[i] is their number.  Returns KY_OK when the script ran (a refused operation shows in its record and leaves the message), or the status of
+// arguments or of a book that is none.
+constexpr int KY_BOOK_RECORD = 11 + 2 * KY_SLICE_MAX_RANGES, KY_BOOK_MAX = 5;   // (five: three slices, a collector and a fresh collector that loads its state)
+int kyhostcheck_book(const ky_render_params* p, uint64_t scene_hash, uint64_t source_hash, const int* books, int n_books, const int* ops, int n_ops, int* records, unsigned char* slots_out,
+                     size_t slot_capacity, size_t* slot_bytes) {
+    if (n_books < 1 || n_books > KY_BOOK_MAX || n_ops < 0 || !books || (n_ops > 0 && (!ops || !records))) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    FrameBook book[KY_BOOK_MAX];
+    std::vector<unsigned char> slots[4];
+    for (int i = 0; i < n_books; ++i) {
+        kyhip_frame* none;
+        KY_TRY(begin_check(nullptr, p, books[2 * i], books[2 * i + 1], &none));
+        book[i].begin(p, scene_hash, books[2 * i], books[2 * i + 1]);
+        if (source_hash) book[i].header.source_hash = source_hash;
+    }
+    for (int k = 0; k < n_ops; ++k) {
+        const int* op = ops + 4 * (size_t)k;
+        if (op[1] < 0 || op[1] >= n_books) return fail(KY_ERR_INVALID_VALUE, "operation %d: book %d", k, op[1]);
+        const FrameBook& b = book[op[1]];
+        int* r = records + (size_t)KY_BOOK_RECORD * (size_t)k;
+        std::memset(r, 0, sizeof(int) * KY_BOOK_RECORD);
+        r[0] = book_op(book, n_books, slots, op[0], op[1], op[2], op[3]);
+        const int after[10] = {b.front(), b.held(), b.cov.n, b.own_first, b.own_end, b.noise.batches, b.noise.n_prev, b.blocks.passes, b.blocks.n_live, (int)b.layout.total};
+        std::memcpy(r + 1, after, sizeof after);
+        b.coverage(r + 11, KY_SLICE_MAX_RANGES, nullptr);
+    }
+    for (int i = 0; i < 4; ++i) {
+        if (slot_bytes) slot_bytes[i] = slots[i].size();
+        if (slots_out && !slots[i].empty() && slots[i].size() <= slot_capacity) std::memcpy(slots_out + (size_t)i * slot_capacity, slots[i].data(), slots[i].size());
+    }
+    return KY_OK;
 }
 
 // A whole checkpoint without a device (ky_checkpoint.hpp): the layout of a frame of p that tracks (noise, blocks) -> offsets[6] = where the accumulators, the noise
@@ -346,7 +467,7 @@ int kyhostcheck_blocks(const ky_render_params* p, int* out_block, int* out_pixel
         if (out_inside) out_inside[b] = inside;
         if (!state) continue;
         BlockState s = {state[2 * b], state[2 * b + 1]};
-        if (init) s = inside > 0 ? BlockState{-1, 0} : BlockState{0, 0};
+        if (init) s = block_init_state(inside);
         if (map && s.retired_at < 0) {
             int counted = 0, above = 0;
             for (int lane = 0; lane < KY_BLOCK_PIXELS; ++lane) {
@@ -496,19 +617,13 @@ int kyhip_kat_li(int, const ky_scene*, const ky_render_params*, int, int, int, i
 // (the masked entries refuse an invalid mask before they look for a device, like the real ones: lighting_plan is host code)
 int kyhip_render_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, float*, size_t) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
 int kyhip_kat_li_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, int, int, int, int, float*) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
-// (a frame refuses what kyhip_render refuses, in its order, before it looks for a device; no frame ever exists here, so the other entries see NULL only)
+// (a frame refuses what the real entries refuse, by their own check, before it looks for a device; no frame ever exists here, so the other entries see NULL only)
 int kyhip_frame_begin(int, const ky_scene* scene, const ky_render_params* p, kyhip_frame** out) {
-    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params (integrator %d, direct_sample %d)", p ? p->integrator : -1, p ? p->direct_sample : -1);
-    if (!shard_in_range(p)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices");
-    if (film_range_check(p, scene) != KY_OK) return KY_ERR_LIMIT;
-    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
-    *out = nullptr;
+    KY_TRY(begin_check(scene, p, 0, p ? p->samples_per_pixel : 0, out));
     return no_gpu();
 }
-int kyhip_frame_begin_slice(int device, const ky_scene* scene, const ky_render_params* p, int first_sample, int end_sample, kyhip_frame** out) {
-    const int rc = kyhip_frame_begin(device, scene, p, out);
-    if (rc != KY_ERR_NO_DEVICE) return rc;
-    KY_TRY(slice_range_check(p->samples_per_pixel, first_sample, end_sample));   // (the range is looked at behind every other argument, before the device)
+int kyhip_frame_begin_slice(int, const ky_scene* scene, const ky_render_params* p, int first_sample, int end_sample, kyhip_frame** out) {
+    KY_TRY(begin_check(scene, p, first_sample, end_sample, out));
     return no_gpu();
 }
 int kyhip_frame_coverage(const kyhip_frame*, int*, int, int*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }

@@ -123,7 +123,7 @@ KY_HD inline NoiseSums noise_sums_of(float v, int cls, float threshold) {
     return s;
 }
 
-// ---- the trailer of a tracking frame's checkpoint (ky_pack.cpp, next to frame_state_check) ----
+// ---- the trailer of a tracking frame's checkpoint (ky_frame_book.cpp, next to frame_state_check) ----
 inline size_t noise_trailer_bytes(int n_pix) { return sizeof(NoiseTrailer) + (size_t)n_pix * sizeof(NoisePixel); }
 // KY_OK and the trailer, or KY_ERR_INVALID_VALUE with the message: `bytes` after `state_bytes` hold no whole trailer, another magic, a batch count below 0,
 // an n_prev that is not the header's samples done

@@ -1,9 +1,9 @@
 /*
  * ky_pack.cpp -- the host code of libkyhip.so that needs no GPU: error state, parameter validation and shard geometry, packing a caller's ky_scene
  * into the device layout (DScene: kind-sorted traversal tables, occluder tables, scene facts), the proof of which surfaces a shadow ray never has to
- * test (find_non_occluders), the launch policies, the CPU side of the host-film seam (HostPool, the banded add), and what a frame's checkpoint is: its layout,
- * its host-side parts and the check of a buffer (ky_checkpoint.hpp), next to the stop rule's argument checks (ky_host.hpp) -- shared by ky_frame.cpp's entries and
- * the host-only builds' stand-ins (ky_hostcheck.cpp).
+ * test (find_non_occluders), the launch policies, the CPU side of the host-film seam (HostPool, the banded add), and the stop rule's and the denoiser's argument
+ * checks (ky_host.hpp) -- shared by ky_frame.cpp's entries and the host-only builds' stand-ins (ky_hostcheck.cpp).  Nothing of a frame's bookkeeping or of its
+ * checkpoint lives here: that is ky_frame_book.cpp.
  * Plain C++17 with no HIP runtime call: hipcc compiles it into the library, and `make sanitize` compiles the very same file with
  * g++ -fsanitize=address,undefined and -fsanitize=thread (round 5; until round 4 all of this lived inside kyhip.hip, out of any sanitizer's reach).
  */
@@ -18,7 +18,7 @@
 #include <sched.h>
 #include <unistd.h>
 
-#include "ky_checkpoint.hpp"   // ky_host.hpp, ky_blocks.hpp, ky_noise.hpp
+#include "ky_host.hpp"
 #include "ky_denoise.hpp"
 
 namespace kyh {
@@ -178,273 +178,6 @@ std::string lighting_note(const ky_render_params* p, int lighting, const Lightin
     return s;
 }
 
-// The sample counts at which a pass of an spp-sample frame can end: the ends of the chunks of chunk_plan(spp)
-int pass_boundaries(int spp, int* bounds, int n) {
-    if (spp < 1 || spp > (1 << 24)) return fail(KY_ERR_INVALID_VALUE, "pass boundaries of %d samples per pixel (1 .. 2^24)", spp);
-    if (n > 0 && !bounds) return fail(KY_ERR_INVALID_VALUE, "bounds is NULL");
-    const ChunkPlan plan = chunk_plan(spp);
-    const int count = chunk_count(plan);
-    for (int c = 0; c < count && c < n; ++c) bounds[c] = chunk_end(plan, c);
-    return count;
-}
-FrameHeader frame_header(const ky_render_params* p, uint64_t hash, int samples_done) {
-    FrameHeader h;
-    std::memset(&h, 0, sizeof h);   // (padding too: headers are compared and saved as bytes)
-    h.magic = KY_FRAME_MAGIC;
-    h.source_hash = kyjit::source_hash();
-    h.params = *p;
-    h.scene_hash = hash;
-    h.samples_done = samples_done;
-    h.n_pix = make_shard(p).n_pix;
-    return h;
-}
-static const char* magic_kind(uint64_t magic) {
-    return magic == KY_FRAME_BLOCKS_MAGIC ? "retires pixel blocks" : magic == KY_FRAME_SLICE_MAGIC ? "owns a slice of its samples" : "does neither";
-}
-// what every reader of a state asks of its header: a frame state of own's identity, long enough; any_kind: whatever its magic, else own's
-static int frame_header_check(const FrameHeader& own, const void* buf, size_t bytes, size_t state_end, bool any_kind, FrameHeader* out) {
-    if (!buf || bytes < sizeof(FrameHeader)) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no header", bytes);
-    FrameHeader theirs;
-    std::memcpy(&theirs, buf, sizeof theirs);
-    if (theirs.magic != KY_FRAME_MAGIC && theirs.magic != KY_FRAME_BLOCKS_MAGIC && theirs.magic != KY_FRAME_SLICE_MAGIC)
-        return fail(KY_ERR_INVALID_VALUE, "frame state: not a kyhip_frame_save buffer");
-    if (!any_kind && theirs.magic != own.magic)
-        return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame that %s, this one %s (kyhip_frame_track_blocks, kyhip_frame_begin_slice)", magic_kind(theirs.magic),
-                    magic_kind(own.magic));
-    if (theirs.source_hash != own.source_hash) return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a library with other kernel sources (%016llx, this one %016llx)",
-                                                          (unsigned long long)theirs.source_hash, (unsigned long long)own.source_hash);
-    FrameHeader same = theirs;
-    same.samples_done = own.samples_done;
-    same.magic = own.magic;
-    if (std::memcmp(&same, &own, sizeof own) != 0) return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its render params, scene or film size differ from this frame's)");
-    if (bytes < state_end) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes, the frame's state has %zu", bytes, state_end);
-    *out = theirs;
-    return KY_OK;
-}
-int frame_state_check(const FrameHeader& own, const void* buf, size_t bytes, size_t state_end, int* chunks_done) {
-    FrameHeader theirs;
-    KY_TRY(frame_header_check(own, buf, bytes, state_end, false, &theirs));
-    const int c = theirs.samples_done < 0 ? -1 : chunks_at_sample(chunk_plan(own.params.samples_per_pixel), theirs.samples_done);
-    if (c < 0) return fail(KY_ERR_INVALID_VALUE, "frame state: no pass of a %d-sample frame ends at %d samples", own.params.samples_per_pixel, theirs.samples_done);
-    *chunks_done = c;
-    return KY_OK;
-}
-
-// ---- a checkpoint as a whole (ky_checkpoint.hpp) ----
-CheckpointLayout checkpoint_layout(const ky_render_params* p, bool noise, bool blocks, int own_first, int own_end) {
-    const ShardConst sh = make_shard(p);
-    CheckpointLayout L;
-    L.n_pix = sh.n_pix; L.n_blocks = sh.n_blocks; L.tracks_noise = noise; L.tracks_blocks = blocks;
-    L.own_first = own_end < 0 ? 0 : own_first;
-    L.own_end = own_end < 0 ? p->samples_per_pixel : own_end;
-    L.sliced = !(L.own_first == 0 && L.own_end == p->samples_per_pixel);
-    L.accum = sizeof(FrameHeader);
-    L.noise = L.accum + workspace_bytes_for(sh);
-    L.noise_pixels = L.noise + (noise ? sizeof(kyn::NoiseTrailer) : 0);
-    L.blocks = L.noise_pixels + (noise ? (size_t)sh.n_pix * sizeof(kyn::NoisePixel) : 0);
-    L.block_states = L.blocks + (blocks ? sizeof(kyb::BlockTrailer) : 0);
-    L.slice = L.block_states + (blocks ? (size_t)sh.n_blocks * sizeof(kyb::BlockState) : 0);
-    L.total = L.slice + (L.sliced ? sizeof(SliceTrailer) : 0);
-    return L;
-}
-// the frame's header as its checkpoints carry it: the magic says whether the layout ends with blocks or with a slice trailer (never both: a slice tracks no blocks)
-static FrameHeader checkpoint_header(FrameHeader own, const CheckpointLayout& L, int samples_done) {
-    own.magic = L.sliced ? KY_FRAME_SLICE_MAGIC : L.tracks_blocks ? KY_FRAME_BLOCKS_MAGIC : KY_FRAME_MAGIC;
-    own.samples_done = samples_done;
-    return own;
-}
-void checkpoint_write_host(const FrameHeader& own, const CheckpointLayout& L, const CheckpointCounts& n, const kyb::BlockState* states, void* buf) {
-    char* at = (char*)buf;
-    const FrameHeader h = checkpoint_header(own, L, n.samples_done);
-    std::memcpy(at, &h, sizeof h);
-    if (L.tracks_noise) {
-        const kyn::NoiseTrailer t = {kyn::KY_NOISE_MAGIC, n.batches, n.n_prev};
-        std::memcpy(at + L.noise, &t, sizeof t);
-    }
-    if (L.tracks_blocks) {
-        const kyb::BlockTrailer t = {kyb::KY_BLOCKS_MAGIC, L.n_blocks, n.passes};
-        std::memcpy(at + L.blocks, &t, sizeof t);
-        if (L.n_blocks > 0) std::memcpy(at + L.block_states, states, L.block_states_bytes());
-    }
-    if (L.sliced) {
-        SliceTrailer t;
-        std::memset(&t, 0, sizeof t);
-        t.magic = KY_SLICE_MAGIC;
-        t.own_first = L.own_first; t.own_end = L.own_end; t.front = n.front;
-        t.n_ranges = n.cov.n;
-        std::memcpy(t.ranges, n.cov.r, sizeof(int32_t) * 2 * (size_t)n.cov.n);
-        std::memcpy(at + L.slice, &t, sizeof t);
-    }
-}
-int checkpoint_check(const FrameHeader& own, const CheckpointLayout& L, const void* buf, size_t bytes, CheckpointCounts* out) {
-    CheckpointCounts n;
-    if (L.sliced) {   // the header's samples_done is the held count: checked against the trailers, not against a chunk end
-        FrameHeader theirs;
-        KY_TRY(frame_header_check(checkpoint_header(own, L, own.samples_done), buf, bytes, L.noise, false, &theirs));
-        n.samples_done = theirs.samples_done;
-        if (L.tracks_noise) {
-            kyn::NoiseTrailer t;
-            KY_TRY(kyn::noise_trailer_check(buf, bytes, L.noise, L.n_pix, n.samples_done, &t));
-            n.batches = t.batches; n.n_prev = t.n_prev;
-        }
-        SliceTrailer s;
-        KY_TRY(slice_trailer_check(buf, bytes, L.slice, own.params.samples_per_pixel, n.samples_done, L.own_first, L.own_end, &s));
-        n.front = s.front;
-        n.chunks_done = chunks_at_sample(chunk_plan(own.params.samples_per_pixel), s.front);
-        n.cov.n = s.n_ranges;
-        std::memcpy(n.cov.r, s.ranges, sizeof s.ranges);
-        *out = n;
-        return KY_OK;
-    }
-    KY_TRY(frame_state_check(checkpoint_header(own, L, own.samples_done), buf, bytes, L.noise, &n.chunks_done));
-    n.samples_done = chunk_end(chunk_plan(own.params.samples_per_pixel), n.chunks_done - 1);
-    n.front = n.samples_done;
-    if (n.samples_done > 0) { n.cov.n = 1; n.cov.r[0] = 0; n.cov.r[1] = n.samples_done; }
-    if (L.tracks_noise) {   // (a frame that does not track accepts a longer buffer and ignores the trailer)
-        kyn::NoiseTrailer t;
-        KY_TRY(kyn::noise_trailer_check(buf, bytes, L.noise, L.n_pix, n.samples_done, &t));
-        n.batches = t.batches; n.n_prev = t.n_prev;
-    }
-    if (L.tracks_blocks) {
-        kyb::BlockTrailer t;
-        KY_TRY(kyb::block_trailer_check(buf, bytes, L.blocks, L.n_blocks, own.params.samples_per_pixel, n.samples_done, n.batches, &t));
-        n.passes = t.passes;
-    }
-    *out = n;
-    return KY_OK;
-}
-
-// ---- slices (ky_checkpoint.hpp; DESIGN.md "Slices") ----
-int slice_bounds(int spp, int n_slices, int* bounds) {
-    const int count = pass_boundaries(spp, nullptr, 0);
-    if (count < 0) return count;
-    if (n_slices < 1 || !bounds) return fail(KY_ERR_INVALID_VALUE, "slice bounds: %d slices into %s", n_slices, bounds ? "bounds" : "a NULL bounds");
-    if (count < n_slices) return fail(KY_ERR_INVALID_VALUE, "slice bounds: a %d-sample frame has %d chunks, fewer than %d slices", spp, count, n_slices);
-    const ChunkPlan plan = chunk_plan(spp);
-    bounds[0] = 0;
-    int prev = -1;   // the chunk whose end the last bound is
-    for (int k = 1; k < n_slices; ++k) {
-        // the chunk end nearest to k * spp / n_slices, compared as integers times n_slices; the lower one on a tie ...
-        const long long want = (long long)k * spp;
-        int best = 0;
-        long long best_d = -1;
-        for (int c = 0; c < count; ++c) {
-            long long d = (long long)chunk_end(plan, c) * n_slices - want;
-            if (d < 0) d = -d;
-            if (best_d < 0 || d < best_d) { best = c; best_d = d; }
-        }
-        // ... moved as little as it takes to leave a chunk to every slice before and behind it
-        const int lo = prev + 1, hi = count - 1 - (n_slices - k);
-        prev = best < lo ? lo : best > hi ? hi : best;
-        bounds[k] = chunk_end(plan, prev);
-    }
-    bounds[n_slices] = spp;
-    return KY_OK;
-}
-int slice_range_check(int spp, int first_sample, int end_sample) {
-    const ChunkPlan plan = chunk_plan(spp);
-    const bool ok = first_sample >= 0 && first_sample <= end_sample && end_sample <= spp && chunks_at_sample(plan, first_sample) >= 0 && chunks_at_sample(plan, end_sample) >= 0;
-    return ok ? KY_OK : fail(KY_ERR_INVALID_VALUE, "a slice of samples %d..%d of %d: both are 0 or a pass boundary (kyhip_pass_boundaries), the first not beyond the end",
-                             first_sample, end_sample, spp);
-}
-int coverage_union(const Coverage& a, const Coverage& b, Coverage* out) {
-    int r[4 * KY_SLICE_MAX_RANGES + 2];
-    int n = 0, i = 0, j = 0;
-    while (i < a.n || j < b.n) {   // both ascending: the one that begins first is next
-        const bool from_a = j >= b.n || (i < a.n && a.r[2 * i] <= b.r[2 * j]);
-        const int first = from_a ? a.r[2 * i] : b.r[2 * j], end = from_a ? a.r[2 * i + 1] : b.r[2 * j + 1];
-        if (from_a) ++i; else ++j;
-        if (n > 0 && first < r[2 * n - 1])
-            return fail(KY_ERR_INVALID_VALUE, "samples %d..%d are held twice: merged sample ranges must not intersect", first, end < r[2 * n - 1] ? end : r[2 * n - 1]);
-        if (n > 0 && first == r[2 * n - 1]) r[2 * n - 1] = end;   // adjacent: joined
-        else { r[2 * n] = first; r[2 * n + 1] = end; ++n; }
-    }
-    if (n > KY_SLICE_MAX_RANGES) return fail(KY_ERR_LIMIT, "%d sample ranges: a frame's coverage holds at most %d", n, KY_SLICE_MAX_RANGES);
-    Coverage u;
-    u.n = n;
-    std::memcpy(u.r, r, sizeof(int) * 2 * (size_t)n);
-    *out = u;
-    return KY_OK;
-}
-int slice_trailer_check(const void* buf, size_t bytes, size_t offset, int total_spp, int samples_done, int own_first, int own_end, SliceTrailer* out) {
-    if (!buf || bytes < offset || bytes - offset < sizeof(SliceTrailer))
-        return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no slice trailer (the state of this frame has %zu)", bytes, offset + sizeof(SliceTrailer));
-    SliceTrailer t;
-    std::memcpy(&t, (const char*)buf + offset, sizeof t);
-    if (t.magic != KY_SLICE_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: no slice trailer where this frame's state has one");
-    const ChunkPlan plan = chunk_plan(total_spp);
-    auto boundary = [&](int s) { return s >= 0 && s <= total_spp && chunks_at_sample(plan, s) >= 0; };
-    if (!boundary(t.own_first) || !boundary(t.own_end) || t.own_first > t.own_end)
-        return fail(KY_ERR_INVALID_VALUE, "frame state: a slice of samples %d..%d of %d: not a range between pass boundaries", t.own_first, t.own_end, total_spp);
-    if (own_end >= 0 && (t.own_first != own_first || t.own_end != own_end))
-        return fail(KY_ERR_INVALID_VALUE, "frame state: saved by the slice of samples %d..%d, this frame owns %d..%d", t.own_first, t.own_end, own_first, own_end);
-    if (t.front < t.own_first || t.front > t.own_end || !boundary(t.front))
-        return fail(KY_ERR_INVALID_VALUE, "frame state: the slice %d..%d stands at sample %d: outside it or on no pass boundary", t.own_first, t.own_end, t.front);
-    if (t.n_ranges < 0 || t.n_ranges > KY_SLICE_MAX_RANGES) return fail(KY_ERR_INVALID_VALUE, "frame state: a coverage of %d sample ranges", t.n_ranges);
-    int held = 0, last = -1, in_first = -1, in_end = -1, inside = 0;
-    for (int i = 0; i < t.n_ranges; ++i) {
-        const int first = t.ranges[2 * i], end = t.ranges[2 * i + 1];
-        // (last: the end of the range before; equality would be two adjacent ranges that were not joined)
-        if (!boundary(first) || !boundary(end) || first >= end || first <= last)
-            return fail(KY_ERR_INVALID_VALUE, "frame state: sample range %d (%d..%d) of the coverage is not ascending, disjoint and between pass boundaries", i, first, end);
-        last = end;
-        held += end - first;
-        const int a = first > t.own_first ? first : t.own_first, b = end < t.own_end ? end : t.own_end;   // its part inside the owned range
-        if (a < b) { ++inside; in_first = a; in_end = b; }
-    }
-    const bool rendered_part_right = t.front == t.own_first ? inside == 0 : (inside == 1 && in_first == t.own_first && in_end == t.front);
-    if (!rendered_part_right)
-        return fail(KY_ERR_INVALID_VALUE, "frame state: the coverage inside the slice %d..%d is not the rendered part %d..%d", t.own_first, t.own_end, t.own_first, t.front);
-    if (held != samples_done) return fail(KY_ERR_INVALID_VALUE, "frame state: the coverage holds %d samples, the header says %d", held, samples_done);
-    if (out) *out = t;
-    return KY_OK;
-}
-int merge_source_check(const FrameHeader& own, const void* buf, size_t bytes, MergeSource* out) {
-    const ShardConst sh = make_shard(&own.params);
-    MergeSource m;
-    m.accum = sizeof(FrameHeader);
-    const size_t noise = m.accum + workspace_bytes_for(sh);
-    FrameHeader theirs;
-    KY_TRY(frame_header_check(own, buf, bytes, noise, true, &theirs));
-    if (theirs.magic == KY_FRAME_BLOCKS_MAGIC)
-        return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame that retires pixel blocks: its pixels stand at sample counts of their own and merge with nothing");
-    const int spp = own.params.samples_per_pixel;
-    // a noise trailer counts when it is valid as a whole: it is there, it is long enough and it stands at the header's samples
-    size_t behind = noise;
-    uint64_t magic = 0;
-    if (bytes - noise >= sizeof magic) std::memcpy(&magic, (const char*)buf + noise, sizeof magic);
-    if (magic == kyn::KY_NOISE_MAGIC) {
-        kyn::NoiseTrailer t;
-        KY_TRY(kyn::noise_trailer_check(buf, bytes, noise, sh.n_pix, theirs.samples_done, &t));
-        m.noise_pixels = noise + sizeof t;
-        m.batches = t.batches;
-        behind = noise + kyn::noise_trailer_bytes(sh.n_pix);
-    }
-    if (theirs.magic == KY_FRAME_SLICE_MAGIC) {
-        SliceTrailer s;
-        KY_TRY(slice_trailer_check(buf, bytes, behind, spp, theirs.samples_done, 0, -1, &s));
-        m.cov.n = s.n_ranges;
-        std::memcpy(m.cov.r, s.ranges, sizeof s.ranges);
-    } else {
-        if (theirs.samples_done < 0 || chunks_at_sample(chunk_plan(spp), theirs.samples_done) < 0)
-            return fail(KY_ERR_INVALID_VALUE, "frame state: no pass of a %d-sample frame ends at %d samples", spp, theirs.samples_done);
-        if (theirs.samples_done > 0) { m.cov.n = 1; m.cov.r[0] = 0; m.cov.r[1] = theirs.samples_done; }
-    }
-    *out = m;
-    return KY_OK;
-}
-int merge_accept(const Coverage& mine, int own_first, int own_end, int total_spp, bool tracks_noise, bool tracks_blocks, const Coverage& theirs, bool has_noise, Coverage* merged) {
-    if (tracks_blocks) return fail(KY_ERR_INVALID_VALUE, "merge: the receiving frame retires pixel blocks: its pixels stand at sample counts of their own");
-    if (own_first == 0 && own_end == total_spp)
-        return fail(KY_ERR_INVALID_VALUE, "merge: the receiving frame owns all %d samples and renders them itself (kyhip_frame_begin_slice: a slice, or a collector)", total_spp);
-    for (int i = 0; i < theirs.n; ++i)
-        if (theirs.r[2 * i] < own_end && own_first < theirs.r[2 * i + 1])
-            return fail(KY_ERR_INVALID_VALUE, "merge: the state holds samples %d..%d, the receiving frame owns %d..%d and would count them twice", theirs.r[2 * i], theirs.r[2 * i + 1],
-                        own_first, own_end);
-    if (tracks_noise && !has_noise) return fail(KY_ERR_INVALID_VALUE, "merge: the receiving frame tracks noise, the state carries no valid noise trailer");
-    return coverage_union(mine, theirs, merged);
-}
-
 // ---- the stop rule's arguments (ky_host.hpp) ----
 int threshold_check(float threshold) {
     return threshold >= 0.f ? KY_OK : fail(KY_ERR_INVALID_VALUE, "threshold %g: a noise level is >= 0", (double)threshold);   // (a NaN is refused)
@@ -470,46 +203,6 @@ double denoise_pixel_width(const ky_camera& camera, int width) {
     const double x = (double)camera.right[0], y = (double)camera.right[1], z = (double)camera.right[2];
     return 2.0 * std::sqrt(x * x + y * y + z * z) / (double)width;
 }
-}  // namespace kyh
-// the pieces of checkpoint_check: the noise trailer at `state_bytes` (CheckpointLayout::noise) ...
-int kyn::noise_trailer_check(const void* buf, size_t bytes, size_t state_bytes, int n_pix, int samples_done, NoiseTrailer* out) {
-    using kyh::fail;
-    if (!buf || bytes < state_bytes || bytes - state_bytes < noise_trailer_bytes(n_pix))
-        return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no noise trailer (the state of a frame that tracks noise has %zu)", bytes, state_bytes + noise_trailer_bytes(n_pix));
-    NoiseTrailer t;
-    std::memcpy(&t, (const char*)buf + state_bytes, sizeof t);
-    if (t.magic != KY_NOISE_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: no noise trailer behind the accumulators (saved by a frame that does not track noise?)");
-    if (t.batches < 0 || t.n_prev != samples_done)
-        return fail(KY_ERR_INVALID_VALUE, "frame state: the noise estimate stands at %d samples in %d batches, the accumulators at %d", t.n_prev, t.batches, samples_done);
-    if (out) *out = t;
-    return KY_OK;
-}
-// ... and the block trailer at `offset` (CheckpointLayout::blocks)
-int kyb::block_trailer_check(const void* buf, size_t bytes, size_t offset, int n_blocks, int total_spp, int samples_done, int noise_batches, BlockTrailer* out) {
-    using kyh::fail;
-    if (!buf || bytes < offset || bytes - offset < block_trailer_bytes(n_blocks))
-        return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes hold no block trailer (the state of this frame has %zu)", bytes, offset + block_trailer_bytes(n_blocks));
-    BlockTrailer t;
-    std::memcpy(&t, (const char*)buf + offset, sizeof t);
-    if (t.magic != KY_BLOCKS_MAGIC) return fail(KY_ERR_INVALID_VALUE, "frame state: no block trailer where this frame's state has one");
-    if (t.n_blocks != n_blocks) return fail(KY_ERR_INVALID_VALUE, "frame state: the block trailer counts %d blocks, the frame has %d", t.n_blocks, n_blocks);
-    if (t.passes < 0) return fail(KY_ERR_INVALID_VALUE, "frame state: the block trailer counts %d passes", t.passes);
-    const ChunkPlan plan = chunk_plan(total_spp);
-    for (int b = 0; b < n_blocks; ++b) {
-        BlockState s;
-        std::memcpy(&s, (const char*)buf + offset + sizeof t + (size_t)b * sizeof s, sizeof s);
-        // (a block's batch count is the frame's when it retired: at most the noise trailer's, and 0 where nothing was rendered yet and for a live block)
-        if (s.batches < 0 || s.batches > noise_batches || (s.retired_at <= 0 && s.batches != 0))
-            return fail(KY_ERR_INVALID_VALUE, "frame state: block %d (retired at %d) has %d batches, the noise estimate %d", b, s.retired_at, s.batches, noise_batches);
-        if (s.retired_at == -1) continue;
-        if (s.retired_at < 0 || s.retired_at > samples_done || chunks_at_sample(plan, s.retired_at) < 0)
-            return fail(KY_ERR_INVALID_VALUE, "frame state: block %d retired at %d samples: no pass of a %d-sample frame that stands at %d ends there", b, s.retired_at,
-                        total_spp, samples_done);
-    }
-    if (out) *out = t;
-    return KY_OK;
-}
-namespace kyh {
 
 RenderConst make_rc(const ky_render_params* p) {
     RenderConst rc{};
@@ -1505,8 +1198,6 @@ int kyhip_lighting_plan(const ky_render_params* p, int lighting, int* effective_
     return KY_OK;
 }
 
-int kyhip_pass_boundaries(int spp, int* bounds, int n) { return pass_boundaries(spp, bounds, n); }
-int kyhip_slice_bounds(int spp, int n_slices, int* bounds) { return slice_bounds(spp, n_slices, bounds); }
 // the filter's defaults: sigma_luminance and sigma_plane as tools/denoise_replay.py settled them (profiles/denoise_replay.txt; DESIGN.md "Denoise")
 void kyhip_denoise_defaults(ky_denoise_params* out) {
     if (!out) return;
