@@ -507,12 +507,30 @@ int     kyhip_frame_blocks_ms(const kyhip_frame* f, float* retire_ms, float* lis
  *   and the hit distance), position_class4 = {P.x, P.y, P.z, class}; zeros beside the class where there is no hit.  Either pointer may be NULL.  The frame as
  *   for kyhip_frame_denoise, but any number of batches.
  * kyhip_frame_denoise_ms: hipEvent spans of the guide trace (set once per frame) and of the last call's gather, levels and add; negative where there was none.
+ *
+ * Guides beyond the first hit (opt-in; the default, 0 bounces, is everything above).  With guide bounces B = 1 .. KYHIP_GUIDE_MAX_BOUNCES the guide kernel
+ * follows the camera ray through mirrors and glass the way the debug sampler walks it (every number 0.5: glass takes the likelier of reflection and
+ * refraction, total internal reflection reflects) for up to B specular vertices, and a pixel takes the guides of the first vertex that is neither -- its normal
+ * and position, t summed along the chain, class 2 if it carries an area light, class 1 with zeros if the chain leaves the scene.  Each pixel also gets a KEY:
+ * 10 bits per specular vertex k at bit 10 k, ((surface + 1) << 1) | (1 if transmitted), the caller's surface index; 0 where the first hit is not specular.  A
+ * chain with more than B specular vertices is unresolved: bit 62 plus its first digit, the first hit's guides, class 0.  The filter then takes a class-0
+ * pixel's taps, and its variance prefilter's neighbours, from the class-0 pixels with the SAME key only: what a mirror shows is filtered by the geometry it
+ * shows, and neither ball is a tap of the walls around it.  Where it helps and where it does not: DESIGN.md "Denoise".
+ * kyhip_frame_set_guide_bounces: 0 .. KYHIP_GUIDE_MAX_BOUNCES, else KY_ERR_INVALID_VALUE; KY_ERR_INVALID_VALUE with the frame untouched once its guides have been
+ *   traced (the first kyhip_frame_denoise / _guides / _guide_chains call that reaches the device), unless the value is the one it has.  No part of a checkpoint.
+ * kyhip_frame_guide_bounces: the value, or KY_ERR_INVALID_VALUE for a NULL frame.
+ * kyhip_frame_guide_chains: WRITES width x height keys, y down, row_stride_px keys apart (all 0 at 0 bounces); the frame as for kyhip_frame_guides, which
+ *   returns the chain-end guides.
  */
+#define KYHIP_GUIDE_MAX_BOUNCES 4
 typedef struct ky_denoise_params { int32_t levels, normal_squarings; float sigma_luminance, sigma_plane; } ky_denoise_params;
 void    kyhip_denoise_defaults(ky_denoise_params* out);
 int     kyhip_frame_denoise(kyhip_frame* f, const ky_denoise_params* p, float* film_rgb, size_t film_row_stride_px);
 int     kyhip_frame_guides(kyhip_frame* f, float* normal_t4, float* position_class4, size_t row_stride_px);
 int     kyhip_frame_denoise_ms(const kyhip_frame* f, float* guides_ms, float* filter_ms);
+int     kyhip_frame_set_guide_bounces(kyhip_frame* f, int bounces);
+int     kyhip_frame_guide_bounces(const kyhip_frame* f);
+int     kyhip_frame_guide_chains(kyhip_frame* f, uint64_t* keys, size_t row_stride_px);
 
 /*
  * Slices: a frame's sample ranges rendered apart and merged, bit for bit (DESIGN.md section 3 "Slices").  A pixel's samples are keyed by their absolute index,

@@ -133,11 +133,14 @@ class Frame:
     blocks=True: the frame retires 8 x 8 pixel blocks between its passes and renders the live ones only (kyhip_frame_track_blocks): keep(mask),
     retire_noisy(...) and render_adaptive(...) (these two with noise=True), sample_map(), block_stats(); resolve(normalise=True) is then per block.
     A frame with noise=True whose shard is the whole film can be denoised between passes: denoise(), guides(), denoise_ms().
+    guide_bounces=1 .. 4: the denoiser's guides follow mirrors and glass for that many specular vertices behind the first hit, and a pixel's taps are the pixels
+    with the same chain (guide_chains()); 0, the default: first-hit guides.  A win at preview sample counts on the Cornell box with its two balls, mixed at 224
+    samples and more and behind a large curved mirror (DESIGN.md "Denoise").
     slice=(first, end): the frame owns and renders samples [first, end) of every pixel only (kyhip_frame_begin_slice; both 0 or a pass boundary, see slice_bounds);
     first == end is a collector that renders nothing.  merge() adds what another frame of the same scene and params holds, bit for bit: `done` counts the samples
     held, `coverage` lists them, and slices that cover 0 .. total merged into one of them resolve to render(scene, params)."""
 
-    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None):
+    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
@@ -155,6 +158,22 @@ class Frame:
             if rc != A.KY_OK:
                 self.close()
                 _check(rc, self._lib)
+        if guide_bounces:
+            rc = self._lib.kyhip_frame_set_guide_bounces(self._f, int(guide_bounces))
+            if rc != A.KY_OK:
+                self.close()
+                _check(rc, self._lib)
+
+    def set_guide_bounces(self, bounces):
+        """kyhip_frame_set_guide_bounces: 0 .. 4 specular vertices the denoiser's guides follow behind the first hit; refused once the guides are traced."""
+        _check(self._lib.kyhip_frame_set_guide_bounces(self._f, int(bounces)), self._lib)
+
+    @property
+    def guide_bounces(self):
+        n = self._lib.kyhip_frame_guide_bounces(self._f)
+        if n < 0:
+            _check(n, self._lib)
+        return n
 
     def close(self):
         if getattr(self, "_f", None):
@@ -271,7 +290,7 @@ class Frame:
 
     def denoise(self, params=None, film=None, row_stride_px=None, origin_px=(0, 0)):
         """ADDS the denoised picture so far to `film` (a new zero film by default) and returns it (kyhip_frame_denoise): resolve(normalise=True) through an
-        edge-avoiding a-trous filter guided by the frame's variance estimate and its first-hit geometry.  params: a ky_denoise_params (_abi.DenoiseParams) or a dict
+        edge-avoiding a-trous filter guided by the frame's variance estimate and its first-hit geometry (guide_bounces: the geometry its specular chains end on).  params: a ky_denoise_params (_abi.DenoiseParams) or a dict
         of its fields over denoise_defaults(); None: the defaults.  levels=0 is resolve(normalise=True)."""
         if isinstance(params, dict):
             q = denoise_defaults()
@@ -287,10 +306,19 @@ class Frame:
 
     def guides(self):
         """kyhip_frame_guides: ((H, W, 4) {n.x, n.y, n.z, t}, (H, W, 4) {P.x, P.y, P.z, class}) float32 of the camera rays through the pixel centres; class 0
-        surface, 1 miss, 2 a surface that carries an area light, 3 flagged."""
+        surface, 1 miss, 2 a surface that carries an area light, 3 flagged.  With guide_bounces: of the vertex the pixel's specular chain ends on, t summed
+        along the chain (an unresolved chain: the first hit's)."""
         a, b = np.zeros((self.height, self.width, 4), np.float32), np.zeros((self.height, self.width, 4), np.float32)
         _check(self._lib.kyhip_frame_guides(self._f, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), self.width), self._lib)
         return a, b
+
+    def guide_chains(self):
+        """kyhip_frame_guide_chains: the (H, W) uint64 chain keys: 10 bits per specular vertex k at bit 10 k, ((surface + 1) << 1) | (1 if transmitted); 0 where
+        the first hit is neither mirror nor glass (everywhere at guide_bounces=0); bit 62 (_abi.GUIDE_KEY_UNRESOLVED) plus the first digit where the chain
+        has more specular vertices than guide_bounces."""
+        keys = np.zeros((self.height, self.width), np.uint64)
+        _check(self._lib.kyhip_frame_guide_chains(self._f, C.c_void_p(keys.ctypes.data), self.width), self._lib)
+        return keys
 
     def denoise_ms(self):
         """kyhip_frame_denoise_ms: (the guide trace, the last denoise()'s gather + levels + add) in ms, negative where there was none."""
@@ -491,14 +519,16 @@ def render_adaptive_host_api(scene, integrator_enum, depth, direct_sample, sampl
 
 
 def render_denoised_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, min_samples_per_pass, stop_after_samples, params=None,
-                             seed=1234, film=None, device=0):
+                             seed=1234, film=None, device=0, guide_bounces=None):
     """create_integrator(...)->render_denoised(&scene, sampler, &film, min_samples_per_pass, stop_after_samples, params) through the C++ host classes: (the film
-    with the denoised picture so far added, the samples done per pixel).  params: an _abi.DenoiseParams, None for the library's defaults."""
+    with the denoised picture so far added, the samples done per pixel).  params: an _abi.DenoiseParams, None for the library's defaults.  guide_bounces: None,
+    or render_denoised's last argument (kyhost_render_denoised_chains)."""
     host = A.load_kyhost()
     if film is None:
         film = np.zeros((height, width, 3), np.float32)
-    rc = host.kyhost_render_denoised(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device,
-                                     int(min_samples_per_pass), int(stop_after_samples), None if params is None else C.byref(params))
+    args = (scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device, int(min_samples_per_pass),
+            int(stop_after_samples), None if params is None else C.byref(params))
+    rc = host.kyhost_render_denoised(*args) if guide_bounces is None else host.kyhost_render_denoised_chains(*args, int(guide_bounces))
     if rc == -2:
         return None
     if rc < 0:

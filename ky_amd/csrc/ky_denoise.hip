@@ -4,11 +4,14 @@
  *   denoise_guides_kernel   once per frame, one thread per film pixel: the camera ray through the pixel centre (generate_ray) and its nearest hit WITHOUT the box
  *                           traversal (trace_nearest; the slab test moves t by a few ulp, and the guides do not depend on kyhip_set_boxes) -> {n, t}, {P, class}; the
  *                           scene's tables staged in LDS as the KAT kernels stage them (the product's device functions, ky_device.hpp, called directly);
+ *   denoise_chain_guides_kernel   the same for a frame with guide bounces (kyhip_frame_set_guide_bounces): the ray followed through mirrors and glass, every sampler
+ *                           number 0.5, to the first vertex that is neither -> its {n, t summed}, {P, class} and the chain's key, one uint64_t per pixel;
  *   denoise_gather_kernel   one thread per pixel of the compact tile buffer: film_add_kernel's de-interleave (noise_pixel_xy) -> {r, g, b, v} in film order and
  *                           the pixel's class as the frame's state gives it (flagged: 3; a block at 0 samples: 1); a ragged tile's padding writes nothing;
  *   denoise_level_kernel    one thread per film pixel, 256-thread workgroups: level_pixel (ky_denoise.hpp) from one film-order buffer into the other; every tap is
  *                           three 16-byte loads from global memory;
- *   denoise_add_kernel      clamp01 per channel, then film_t::add_color into a device film or a pinned host film.
+ *   denoise_level_keyed_kernel   ... with the taps that share the pixel's chain key only (level_pixel_t<true>): 8 more bytes per tap;
+ *   denoise_add_kernel     clamp01 per channel, then film_t::add_color into a device film or a pinned host film.
  * No floating-point atomics and no order that depends on scheduling: two calls return identical bytes.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
@@ -48,6 +51,60 @@ __global__ __launch_bounds__(KY_DN_BLOCK) void denoise_guides_kernel(const DScen
     gb[i] = b;
 }
 
+// The guides of a frame with guide bounces (DESIGN.md "Denoise", "Guides beyond the first hit"): the camera ray through the pixel centre followed through mirrors
+// and glass as the debug sampler walks it -- every number 0.5, so glass takes its likelier branch (bsdf_sample_delta) -- to the first vertex that is neither, a
+// lamp, or nothing.  Every vertex is the one the render kernels build at that hit (path_intersect / path_shade: position, hit_normal, the material's lobe, the
+// offset origin of the next ray).  At most bounces + 1 traversals per lane (bounces <= KYHIP_GUIDE_MAX_BOUNCES): the loop's last turn has k == bounces and leaves.
+__global__ __launch_bounds__(KY_DN_BLOCK) void denoise_chain_guides_kernel(const DScene* __restrict__ S_, int width, int height, int bounces, Px4* __restrict__ ga,
+                                                                            Px4* __restrict__ gb, uint64_t* __restrict__ key) {
+    const SceneRef S{S_, true, 0, true};
+    const LdsScene Lds = stage_scene<true>(S);   // the scene-sized dynamic block, as denoise_guides_kernel takes it; ends with a barrier
+    const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
+    if (i >= width * height) return;
+    const int x = i % width, y = i / width;
+    f3 o, d;
+    generate_ray(S, (float)x + 0.5f, (float)y + 0.5f, o, d);
+    float t_sum = 0.f;
+    uint64_t kk = 0;
+    Px4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, (float)KY_DN_MISS};
+    Px4 a0 = a, b0 = b;   // the first hit's guides: what an unresolved chain keeps
+    for (int k = 0; k <= bounces; ++k) {
+        float t = K_INF;
+        const int hs = trace_nearest(S, o, d, t);
+        if (hs < 0) {   // the chain leaves the scene: class 1, nobody's tap
+            a = Px4{0.f, 0.f, 0.f, 0.f};
+            b = Px4{0.f, 0.f, 0.f, (float)KY_DN_MISS};
+            break;
+        }
+        t_sum += t;
+        const DHit& H = Lds.hit[hs];
+        Vertex v;
+        v.t = t;
+        v.position = o + t * d;
+        v.normal = hit_normal(H, v.position, d);
+        v.surface = hs;
+        v.bsdf = make_bsdf(Lds.mat[H.material], 0.5f);   // (a plastic surface's draw: either of its lobes ends the chain)
+        const bool lamp = H.area_light >= 0;
+        a = Px4{v.normal.x, v.normal.y, v.normal.z, t_sum};
+        b = Px4{v.position.x, v.position.y, v.position.z, lamp ? (float)KY_DN_LIGHT : (float)KY_DN_SURFACE};
+        if (k == 0) { a0 = a; b0 = b; }
+        if (lamp || !bsdf_is_delta(v.bsdf)) break;
+        if (k == bounces) {   // unresolved: the first hit's guides (a mirror or glass that carries no lamp: class 0) and the first digit
+            a = a0;
+            b = b0;
+            kk = chain_unresolved(kk);
+            break;
+        }
+        const DeltaSample s = bsdf_sample_delta(v, -d, 0.5f);
+        kk |= chain_digit(S->orig[hs], s.reflected) << (KY_DN_KEY_DIGIT_BITS * k);
+        o = offset_ray_origin(v.position, v.normal, s.wi);
+        d = s.wi;
+    }
+    ga[i] = a;
+    gb[i] = b;
+    key[i] = kk;
+}
+
 __global__ __launch_bounds__(KY_DN_BLOCK) void denoise_gather_kernel(const unsigned long long* __restrict__ accum, const unsigned* __restrict__ flags,
                                                                       const NoisePixel* __restrict__ state, const BlockState* __restrict__ blocks, ShardConst sh, int width,
                                                                       int height, int total_spp, int n_done, int batches, const Px4* __restrict__ gb_traced,
@@ -77,6 +134,14 @@ __global__ __launch_bounds__(KY_DN_BLOCK) void denoise_level_kernel(const Px4* _
     cv_out[i] = level_pixel(cv_in, ga, gb, i % k.width, i / k.width, step, k);
 }
 
+// ... of a frame with guide bounces: taps share the pixel's chain key (level_pixel_t<true>; 8 more bytes per tap)
+__global__ __launch_bounds__(KY_DN_BLOCK) void denoise_level_keyed_kernel(const Px4* __restrict__ cv_in, Px4* __restrict__ cv_out, const Px4* __restrict__ ga,
+                                                                           const Px4* __restrict__ gb, const uint64_t* __restrict__ key, int step, LevelConst k) {
+    const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
+    if (i >= k.width * k.height) return;
+    cv_out[i] = level_pixel_t<true>(cv_in, ga, gb, key, i % k.width, i / k.width, step, k);
+}
+
 __global__ __launch_bounds__(KY_DN_BLOCK) void denoise_add_kernel(const Px4* __restrict__ cv, float* __restrict__ film, size_t stride_px, int width, int height) {
     const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
     if (i >= width * height) return;
@@ -89,21 +154,38 @@ __global__ __launch_bounds__(KY_DN_BLOCK) void denoise_add_kernel(const Px4* __r
 namespace kydn {
 static dim3 film_grid(int width, int height) { return dim3((unsigned)((width * height + KY_DN_BLOCK - 1) / KY_DN_BLOCK)); }
 
-int denoise_guides_device(int device, const ky_scene* scene, int width, int height, void* ga, void* gb, void* stream_) {
-    if (width <= 0 || height <= 0) return KY_OK;
+// The scene on the device, `launch(scene, lds_bytes)` on the stream, and the WAIT: the scene cache's slot is the kernel's until it is done, so all under the context's lock
+template <class Launch>
+static int trace_guides(int device, const ky_scene* scene, void* stream_, Launch launch) {
     DeviceCtx* c;
     KY_TRY(get_ctx(device, &c));
     std::lock_guard<std::mutex> lock(c->m);
     hipStream_t stream = (hipStream_t)stream_;
     SceneSlot* sc;
     KY_TRY(upload_scene(c, scene, stream, &sc));
-    const size_t lds = (size_t)lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
-    hipLaunchKernelGGL(denoise_guides_kernel, film_grid(width, height), dim3(KY_DN_BLOCK), lds, stream, (const DScene*)sc->d, width, height, (Px4*)ga, (Px4*)gb);
+    launch((const DScene*)sc->d, (size_t)lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), stream);
     const hipError_t launched = hipGetLastError();
-    const hipError_t done = hipStreamSynchronize(stream);   // (under the lock: the slot is this kernel's until it is done)
+    const hipError_t done = hipStreamSynchronize(stream);
     HIP_TRY(launched);
     HIP_TRY(done);
     return KY_OK;
+}
+
+int denoise_guides_device(int device, const ky_scene* scene, int width, int height, void* ga, void* gb, void* stream) {
+    if (width <= 0 || height <= 0) return KY_OK;
+    return trace_guides(device, scene, stream, [&](const DScene* S, size_t lds, hipStream_t s) {
+        hipLaunchKernelGGL(denoise_guides_kernel, film_grid(width, height), dim3(KY_DN_BLOCK), lds, s, S, width, height, (Px4*)ga, (Px4*)gb);
+    });
+}
+
+static_assert(((KYHIP_MAX_SURFACES + 1) << 1 | 1) < (1 << KY_DN_KEY_DIGIT_BITS) && KY_DN_KEY_DIGIT_BITS * KYHIP_GUIDE_MAX_BOUNCES <= 62, "a chain's digits fit its key");
+
+int denoise_chain_guides_device(int device, const ky_scene* scene, int width, int height, int bounces, void* ga, void* gb, void* key, void* stream) {
+    if (bounces < 1 || bounces > KYHIP_GUIDE_MAX_BOUNCES) return fail(KY_ERR_INVALID_VALUE, "guide bounces %d: 1 .. %d", bounces, KYHIP_GUIDE_MAX_BOUNCES);
+    if (width <= 0 || height <= 0) return KY_OK;
+    return trace_guides(device, scene, stream, [&](const DScene* S, size_t lds, hipStream_t s) {
+        hipLaunchKernelGGL(denoise_chain_guides_kernel, film_grid(width, height), dim3(KY_DN_BLOCK), lds, s, S, width, height, bounces, (Px4*)ga, (Px4*)gb, (uint64_t*)key);
+    });
 }
 
 int denoise_gather_device(const void* ws, const void* noise_state, const void* blocks, const ShardConst& sh, int width, int height, int total_spp, int n_done, int batches,
@@ -121,6 +203,14 @@ int denoise_level_device(const void* cv_in, void* cv_out, const void* ga, const 
     if (k.width <= 0 || k.height <= 0) return KY_OK;
     hipLaunchKernelGGL(denoise_level_kernel, film_grid(k.width, k.height), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, (const Px4*)cv_in, (Px4*)cv_out, (const Px4*)ga,
                        (const Px4*)gb, step, k);
+    HIP_TRY(hipGetLastError());
+    return KY_OK;
+}
+
+int denoise_level_keyed_device(const void* cv_in, void* cv_out, const void* ga, const void* gb, const void* key, int step, const LevelConst& k, void* stream) {
+    if (k.width <= 0 || k.height <= 0) return KY_OK;
+    hipLaunchKernelGGL(denoise_level_keyed_kernel, film_grid(k.width, k.height), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, (const Px4*)cv_in, (Px4*)cv_out,
+                       (const Px4*)ga, (const Px4*)gb, (const uint64_t*)key, step, k);
     HIP_TRY(hipGetLastError());
     return KY_OK;
 }

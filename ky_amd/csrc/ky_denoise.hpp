@@ -1,7 +1,7 @@
 /*
  * ky_denoise.hpp -- the denoised picture of a frame rendered in passes (kyhip_frame_denoise ...; DESIGN.md "Denoise"): an edge-avoiding a-trous wavelet filter
  * over the frame's normalised picture, guided by the variance of each pixel's mean luminance (the quantity ky_noise.hpp's noise_value takes its square root of)
- * and by the geometry at the pixel's first hit.  The arithmetic is written ONCE here, as KY_HD functions with floating-point contraction off: the device kernels
+ * and by the geometry at the pixel's first hit -- or, with guide bounces, at the vertex its specular chain ends on, taps sharing the chain's key.  The arithmetic is written ONCE here, as KY_HD functions with floating-point contraction off: the device kernels
  * (ky_denoise.hip), the host-only builds (kyhostcheck_denoise, ky_hostcheck.cpp) and a NumPy restatement (tests/denoise_restatement.py) round alike.  All of it is
  * DOUBLE arithmetic on float32 inputs -- + - x /, max and comparisons, nothing transcendental: the library's fp32 division is not correctly rounded and could not
  * be restated, double division is -- and what one level hands to the next is stored as float32.  Plain C++: part of `make sanitize`.
@@ -75,12 +75,18 @@ KY_HD inline bool is_surface(const Px4& gb) { return gb.w == (float)KY_DN_SURFAC
 //     w  = h wn wp wl
 //   c' = sum w c_q / sum w,  v' = sum w^2 v_q / (sum w)^2.  The centre tap has w = 9 / 64: sum w > 0.
 // Pixels that are not class 0 pass through.
-KY_NOFMA_FN KY_HD inline Px4 level_pixel(const Px4* __restrict__ cv, const Px4* __restrict__ ga, const Px4* __restrict__ gb, int x, int y, int step, const LevelConst& k) {
+// KEYED (a frame with guide bounces, kyhip_frame_set_guide_bounces): `key` holds one specular-chain key per pixel in film order, and a class-0 pixel's taps and
+// its variance prefilter's neighbours are the class-0 pixels with THE SAME KEY -- one more condition on who is a tap, no other arithmetic.  !KEYED: `key` is not
+// read, and the body is what it was before keys existed.
+template <bool KEYED>
+KY_NOFMA_FN KY_HD inline Px4 level_pixel_t(const Px4* __restrict__ cv, const Px4* __restrict__ ga, const Px4* __restrict__ gb, const uint64_t* __restrict__ key, int x,
+                                           int y, int step, const LevelConst& k) {
     KY_NOFMA_BODY
     const size_t at = (size_t)y * (size_t)k.width + (size_t)x;
     const Px4 cp = cv[at], bp = gb[at];
     if (!is_surface(bp)) return cp;
     const Px4 ap = ga[at];
+    const uint64_t kp = KEYED ? key[at] : 0;
     double vw = 0.0, vs = 0.0;
     for (int j = -1; j <= 1; ++j)
         for (int i = -1; i <= 1; ++i) {
@@ -88,6 +94,7 @@ KY_NOFMA_FN KY_HD inline Px4 level_pixel(const Px4* __restrict__ cv, const Px4* 
             if (qx < 0 || qy < 0 || qx >= k.width || qy >= k.height) continue;
             const size_t q = (size_t)qy * (size_t)k.width + (size_t)qx;
             if (!is_surface(gb[q])) continue;
+            if (KEYED && key[q] != kp) continue;
             const double h = tap3(i) * tap3(j);
             vw = vw + h;
             vs = vs + h * (double)cv[q].w;
@@ -106,6 +113,7 @@ KY_NOFMA_FN KY_HD inline Px4 level_pixel(const Px4* __restrict__ cv, const Px4* 
             const size_t q = (size_t)qy * (size_t)k.width + (size_t)qx;
             const Px4 bq = gb[q];
             if (!is_surface(bq)) continue;
+            if (KEYED && key[q] != kp) continue;
             const Px4 aq = ga[q], cq = cv[q];
             const double nd = npx * (double)aq.x + npy * (double)aq.y + npz * (double)aq.z;
             double wn = nd > 0.0 ? nd : 0.0;
@@ -129,17 +137,34 @@ KY_NOFMA_FN KY_HD inline Px4 level_pixel(const Px4* __restrict__ cv, const Px4* 
     o.w = (float)(sv / (sw * sw));
     return o;
 }
+KY_NOFMA_FN KY_HD inline Px4 level_pixel(const Px4* __restrict__ cv, const Px4* __restrict__ ga, const Px4* __restrict__ gb, int x, int y, int step, const LevelConst& k) {
+    KY_NOFMA_BODY
+    return level_pixel_t<false>(cv, ga, gb, nullptr, x, y, step, k);
+}
+
+// ---- specular-chain keys (DESIGN.md "Denoise", "Guides beyond the first hit") ----
+// A pixel's key: digit k, 10 bits at 10 k, is ((surface + 1) << 1) | (transmitted ? 1 : 0) of the chain's k-th delta vertex (the caller's surface index); bit 62
+// marks a chain the frame's guide bounces did not resolve, which keeps its first digit only and the first hit's guides.  0: the first hit is no mirror and no glass.
+constexpr int KY_DN_KEY_DIGIT_BITS = 10;
+constexpr uint64_t KY_DN_KEY_UNRESOLVED = (uint64_t)1 << 62;
+KY_HD inline uint64_t chain_digit(int surface, bool reflected) { return ((uint64_t)(surface + 1) << 1) | (reflected ? 0u : 1u); }
+KY_HD inline uint64_t chain_unresolved(uint64_t key) { return KY_DN_KEY_UNRESOLVED | (key & (((uint64_t)1 << KY_DN_KEY_DIGIT_BITS) - 1)); }
 
 // ---- the kernels (ky_denoise.hip); every pointer is device memory, `stream` a hipStream_t ----
 constexpr int KY_DN_BLOCK = 256;
 // guides of the whole film, traced once per frame: ga = {n, t}, gb = {P, class 0 / 1 / 2}.  Uploads the scene, enqueues and WAITS (the scene cache's slot is held
 // by the context's lock until the kernel is done).
 int denoise_guides_device(int device, const ky_scene* scene, int width, int height, void* ga, void* gb, void* stream);
+// ... of a frame with guide bounces 1 .. KYHIP_GUIDE_MAX_BOUNCES: the camera ray followed through mirrors and glass (every sampler number 0.5) to the first surface
+// that is neither, whose guides the pixel takes with t summed along the chain; `key`: width x height uint64_t, the chain's key.  Uploads, enqueues and WAITS alike.
+int denoise_chain_guides_device(int device, const ky_scene* scene, int width, int height, int bounces, void* ga, void* gb, void* key, void* stream);
 // compact tile order -> film order: cv = gather_pixel, gb = the traced guide with the class the frame's state gives it (3: flagged; 1: a block at 0 samples)
 // (blocks: NULL, or the kyb::BlockState of every block of a frame that retires blocks, whose pixels stand at their block's own counts)
 int denoise_gather_device(const void* ws, const void* noise_state, const void* blocks, const ShardConst& sh, int width, int height, int total_spp, int n_done, int batches,
                           const void* gb_traced, void* cv, void* gb, void* stream);
 int denoise_level_device(const void* cv_in, void* cv_out, const void* ga, const void* gb, int step, const LevelConst& k, void* stream);
+// the keyed level (level_pixel_t<true>): 8 more bytes per tap
+int denoise_level_keyed_device(const void* cv_in, void* cv_out, const void* ga, const void* gb, const void* key, int step, const LevelConst& k, void* stream);
 // clamp01 per channel and ADD into a film (device memory, or the device alias of a pinned host film): film_t::add_color
 int denoise_add_device(const void* cv, float* film, size_t stride_px, int width, int height, void* stream);
 }  // namespace kydn

@@ -50,8 +50,11 @@ struct BlockTrack {
 // what kyhip_frame_denoise keeps between calls (no part of a checkpoint): the guides, traced once per frame, and the filter's film-order buffers
 struct DenoiseTrack {
     bool guides_done = false;
+    int guide_bounces = 0;             // kyhip_frame_set_guide_bounces: fixed once the guides are traced
     DevBuf ga, gb_traced, gb, cv[2];   // width x height Px4 each: {n, t}; {P, class} as traced and as the frame's state classes it now; the levels' ping-pong
+    DevBuf key;                        // width x height uint64_t, the chain keys of a frame with guide bounces (none at 0 bounces: every key is 0)
     std::vector<float> hga, hgb;       // host copies of the guides (kyhip_frame_guides)
+    std::vector<uint64_t> hkey;        // ... and of the keys (kyhip_frame_guide_chains)
     TimedSpan guides, filter;          // the guide trace; the last call's gather, levels and add (kyhip_frame_denoise_ms)
 };
 struct kyhip_frame {
@@ -493,10 +496,14 @@ static int denoise_prepare(kyhip_frame* f, DeviceCtx* c, bool timed_filter) {
     const size_t bytes = (size_t)p->width * (size_t)p->height * sizeof(Px4);
     for (DevBuf* b : {&d.ga, &d.gb_traced, &d.gb, &d.cv[0], &d.cv[1]})
         if (!b->p) HIP_TRY(b->alloc(bytes));
+    if (d.guide_bounces > 0 && !d.key.p) HIP_TRY(d.key.alloc((size_t)p->width * (size_t)p->height * sizeof(uint64_t)));
     KY_TRY(d.guides.create());
     KY_TRY(d.filter.create());
     if (!d.guides_done) {
-        KY_TRY(timed(d.guides, c->stream, "denoise guides", "", [&] { return denoise_guides_device(f->device, &f->scene, p->width, p->height, d.ga.p, d.gb_traced.p, c->stream); }));
+        KY_TRY(timed(d.guides, c->stream, "denoise guides", "", [&] {
+            if (d.guide_bounces > 0) return denoise_chain_guides_device(f->device, &f->scene, p->width, p->height, d.guide_bounces, d.ga.p, d.gb_traced.p, d.key.p, c->stream);
+            return denoise_guides_device(f->device, &f->scene, p->width, p->height, d.ga.p, d.gb_traced.p, c->stream);
+        }));
         d.guides_done = true;
     }
     if (timed_filter) d.filter.begin(c->stream);   // (kyhip_frame_denoise: its span begins with the gather and ends behind the delivery's add)
@@ -525,7 +532,9 @@ int kyhip_frame_denoise(kyhip_frame* f, const ky_denoise_params* params, float* 
     k.sigma_l2 = (double)q.sigma_luminance * (double)q.sigma_luminance;
     k.sigma_plane = (double)q.sigma_plane;
     k.pix = denoise_pixel_width(f->scene.camera, p->width);
-    for (int l = 0; l < q.levels && rcode == KY_OK; ++l) rcode = denoise_level_device(d.cv[l & 1].p, d.cv[(l + 1) & 1].p, d.ga.p, d.gb.p, 1 << l, k, c->stream);
+    for (int l = 0; l < q.levels && rcode == KY_OK; ++l)
+        rcode = d.guide_bounces > 0 ? denoise_level_keyed_device(d.cv[l & 1].p, d.cv[(l + 1) & 1].p, d.ga.p, d.gb.p, d.key.p, 1 << l, k, c->stream)
+                                    : denoise_level_device(d.cv[l & 1].p, d.cv[(l + 1) & 1].p, d.ga.p, d.gb.p, 1 << l, k, c->stream);
     const void* result = d.cv[q.levels & 1].p;
     return deliver(f, c->stream, rcode, "denoise", &d.filter, film_rgb, stride_px, [&](float* dst, size_t dst_stride) {
         return denoise_add_device(result, dst, dst_stride, p->width, p->height, c->stream);   // film order already
@@ -552,6 +561,39 @@ int kyhip_frame_guides(kyhip_frame* f, float* normal_t4, float* position_class4,
         if (normal_t4) std::memcpy(normal_t4 + (size_t)y * stride_px * 4, d.hga.data() + (size_t)y * p->width * 4, row);
         if (position_class4) std::memcpy(position_class4 + (size_t)y * stride_px * 4, d.hgb.data() + (size_t)y * p->width * 4, row);
     }
+    return KY_OK;
+}
+
+int kyhip_frame_set_guide_bounces(kyhip_frame* f, int bounces) {
+    if (bounces < 0 || bounces > KYHIP_GUIDE_MAX_BOUNCES) return fail(KY_ERR_INVALID_VALUE, "guide bounces %d: 0 .. %d", bounces, KYHIP_GUIDE_MAX_BOUNCES);
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    DenoiseTrack& d = f->denoise;
+    if (bounces == d.guide_bounces) return KY_OK;
+    if (d.guides_done) return fail(KY_ERR_INVALID_VALUE, "guide bounces %d: the frame's guides are traced, with %d", bounces, d.guide_bounces);
+    d.guide_bounces = bounces;
+    return KY_OK;
+}
+
+int kyhip_frame_guide_bounces(const kyhip_frame* f) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    return f->denoise.guide_bounces;
+}
+
+int kyhip_frame_guide_chains(kyhip_frame* f, uint64_t* keys, size_t stride_px) {
+    KY_TRY(denoise_frame_check(f, false));
+    const ky_render_params* p = &f->book.params;
+    if (!keys) return fail(KY_ERR_INVALID_VALUE, "keys is NULL");
+    if (stride_px < (size_t)p->width) return fail(KY_ERR_INVALID_VALUE, "row_stride_px %zu: the keys' rows are %d pixels", stride_px, p->width);
+    if (f->book.sh.n_pix == 0) return KY_OK;
+    DeviceCtx* c;
+    KY_TRY(get_ctx(f->device, &c));
+    DenoiseTrack& d = f->denoise;
+    const int rcode = denoise_prepare(f, c, false);
+    KY_TRY(finish(c->stream, rcode, "denoise guides"));
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    d.hkey.assign(n, 0);
+    if (d.guide_bounces > 0) HIP_TRY(hipMemcpy(d.hkey.data(), d.key.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (int y = 0; y < p->height; ++y) std::memcpy(keys + (size_t)y * stride_px, d.hkey.data() + (size_t)y * p->width, (size_t)p->width * sizeof(uint64_t));
     return KY_OK;
 }
 

@@ -487,11 +487,14 @@ int kyhostcheck_blocks(const ky_render_params* p, int* out_block, int* out_pixel
 // The denoise filter's arithmetic (ky_denoise.hpp: what denoise_level_kernel does per pixel) on the caller's film-order buffers -- cv {r, g, b, v}, ga {n, t},
 // gb {P, class}: width x height x 4 floats each -- for p->levels levels with steps 1, 2, 4 ...; `pix` is the width of a pixel at unit distance.  Writes the last
 // level's {r, g, b, v}, unclamped, to out (width x height x 4).  Returns denoise_params_check's status, or KY_ERR_INVALID_VALUE for arguments that are none.
-int kyhostcheck_denoise(const float* cv, const float* ga, const float* gb, int width, int height, const ky_denoise_params* p, double pix, float* out) {
+// `key`: NULL (level_pixel, the filter of a frame without guide bounces), or width x height chain keys (level_pixel_t<true>: taps share the pixel's key).
+static int denoise_on_host(const float* cv, const float* ga, const float* gb, const uint64_t* key, int width, int height, const ky_denoise_params* p, double pix, float* out) {
     using namespace kydn;
     if (!cv || !ga || !gb || !p || !out || width < 1 || height < 1) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
     KY_TRY(denoise_params_check(p));
     const size_t n = (size_t)width * (size_t)height;
+    std::vector<uint64_t> keys(key ? n : 0);
+    if (key) std::memcpy(keys.data(), key, n * sizeof(uint64_t));
     std::vector<Px4> c[2] = {std::vector<Px4>(n), std::vector<Px4>(n)}, a(n), b(n);   // (16-byte aligned copies: the caller's arrays need not be)
     std::memcpy(c[0].data(), cv, n * sizeof(Px4));
     std::memcpy(a.data(), ga, n * sizeof(Px4));
@@ -504,9 +507,20 @@ int kyhostcheck_denoise(const float* cv, const float* ga, const float* gb, int w
     k.pix = pix;
     for (int l = 0; l < p->levels; ++l)
         for (int y = 0; y < height; ++y)
-            for (int x = 0; x < width; ++x) c[(l + 1) & 1][(size_t)y * width + x] = level_pixel(c[l & 1].data(), a.data(), b.data(), x, y, 1 << l, k);
+            for (int x = 0; x < width; ++x)
+                c[(l + 1) & 1][(size_t)y * width + x] = key ? level_pixel_t<true>(c[l & 1].data(), a.data(), b.data(), keys.data(), x, y, 1 << l, k)
+                                                            : level_pixel(c[l & 1].data(), a.data(), b.data(), x, y, 1 << l, k);
     std::memcpy(out, c[p->levels & 1].data(), n * sizeof(Px4));
     return KY_OK;
+}
+int kyhostcheck_denoise(const float* cv, const float* ga, const float* gb, int width, int height, const ky_denoise_params* p, double pix, float* out) {
+    return denoise_on_host(cv, ga, gb, nullptr, width, height, p, pix, out);
+}
+// ... with one chain key per pixel (width x height uint64_t, film order): the filter of a frame with guide bounces
+int kyhostcheck_denoise_keyed(const float* cv, const float* ga, const float* gb, const uint64_t* key, int width, int height, const ky_denoise_params* p, double pix,
+                              float* out) {
+    if (!key) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    return denoise_on_host(cv, ga, gb, key, width, height, p, pix, out);
 }
 
 // The live rectangle (screen_bound, kyhip_scene_screen_bound) on degenerate inputs: a unit box of five matte rectangles (open towards -z) or one sphere, seen by a
@@ -675,6 +689,12 @@ int kyhip_frame_denoise(kyhip_frame*, const ky_denoise_params* p, float*, size_t
 }
 int kyhip_frame_guides(kyhip_frame*, float*, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_denoise_ms(const kyhip_frame*, float*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_set_guide_bounces(kyhip_frame*, int bounces) {
+    if (bounces < 0 || bounces > KYHIP_GUIDE_MAX_BOUNCES) return fail(KY_ERR_INVALID_VALUE, "guide bounces %d: 0 .. %d", bounces, KYHIP_GUIDE_MAX_BOUNCES);
+    return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+}
+int kyhip_frame_guide_bounces(const kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_guide_chains(kyhip_frame*, uint64_t*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }
 int kyhip_smallpt_render(int, const ky_smallpt_sphere* spheres, int n, const ky_smallpt_params* p, double* image) {

@@ -5,7 +5,7 @@
 hipEvent time (kyhip_frame_denoise_ms) of the guide trace and of the filter -- gather, levels and add in one span -- for 1 .. 6 levels into a pinned film, so
 that the span holds kernels only: the increment from L - 1 to L levels is the level with step 2^(L - 1), and what one level's span holds beyond an increment is
 the gather and the add.  Next to a 64-sample pass's render kernel (kyhip_kernel_ms) and the noise kernels (kyhip_frame_noise_ms).  Medians of five calls after
-a warm-up."""
+a warm-up.  Then, per guide bounce count 1 .. 4 (kyhip_frame_set_guide_bounces), a frame of its own: the chain trace and the keyed filter the same way."""
 import ctypes as C
 import os
 import sys
@@ -47,3 +47,23 @@ with api.Frame(scene, p, noise=True) as f:
     a = f.denoise(film=np.zeros((H, W, 3), np.float32))
     b = f.denoise(film=np.zeros((H, W, 3), np.float32))
     print("a pageable film (device film, copy, host add): two calls identical: %s" % np.array_equal(a, b))
+# guides beyond the first hit: the chain trace at 1 .. 4 guide bounces, and the keyed level next to the plain one (spans[...] above)
+for bounces in range(0, A.GUIDE_MAX_BOUNCES + 1):   # (0: the first-hit trace and the plain filter once more, on a scene that is on the device already)
+    with api.Frame(scene, p, noise=True, guide_bounces=bounces) as f:
+        f.render(64)
+        f.render(64)
+        f.denoise(film=film.array)   # warm-up; traces the chains
+        keys = f.guide_chains()
+        keyed = {}
+        for levels in (1, 5, 6):
+            runs = []
+            for _ in range(5):
+                f.denoise(dict(levels=levels), film=film.array)
+                runs.append(f.denoise_ms()[1])
+            keyed[levels] = float(np.median(runs))
+        per_level = (keyed[6] - keyed[1]) / 5
+        print("%d guide bounces: %s trace, once per frame: %.4f ms (%d chain pixels, %d unresolved); %s filter, 1 / 5 / 6 levels: %.4f %.4f %.4f ms; a level: "
+              "%.4f ms = %.3f ns per pixel (plain, above: %.4f ms); the default five levels: %.4f ms (plain, above: %.4f ms)" % (
+                  bounces, "chain" if bounces else "first-hit", f.denoise_ms()[0], int((keys != 0).sum()), int((keys >> np.uint64(62)).sum()),
+                  "keyed" if bounces else "plain", keyed[1], keyed[5], keyed[6], per_level,
+                  per_level * 1e6 / (W * H), (spans[6] - spans[1]) / 5, keyed[5], spans[5]), flush=True)

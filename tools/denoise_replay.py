@@ -5,7 +5,12 @@ into the frame's chunks, one chunk per pass, and fed to the NumPy restatements o
 (tests/denoise_restatement.py) at several (sigma_luminance, sigma_plane) pairs.  The guides are the oracle's camera and scene-intersect KATs on the pixel centres.
 Prints the RMSE against a high-sample oracle frame, raw and denoised, at 112, 224 and 500 samples.
 
-usage: tools/denoise_replay.py [truth_spp]"""
+`chains` (profiles/denoise_chains_replay.txt; DESIGN.md "Denoise", "Guides beyond the first hit"): the same replay at the default sigmas with first-hit guides and
+with specular-chain guides (four guide bounces: the oracle's trace_li under the debug sampler fed to tests/denoise_chains_restatement.py, taps of the same key
+only), for the default scene and for the large mirror ball, at 48, 112, 224 and 500 samples: RMSE over the whole film and over the pixels whose key is not 0.
+
+usage: tools/denoise_replay.py [truth_spp]
+       tools/denoise_replay.py chains [truth_spp]"""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,9 +26,62 @@ W, H, SPP = 40, 24, 500
 SEEDS = (1234, 101, 202, 303, 404)   # the first three are the GPU test's
 AT = (112, 224, 500)
 PAIRS = [(4.0, 1.0), (1.0, 1.0), (1.5, 1.0), (2.0, 1.0), (1.5, 0.25), (1.5, 0.1), (2.0, 0.25), (3.0, 0.25), (8.0, 1.0)]   # (4, 1): where the scan started; (1.5, 0.25): the defaults
+CHAINS = sys.argv[1:2] == ["chains"]
+if CHAINS:
+    del sys.argv[1]
 TRUTH_SPP = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 
-scene = api.cornell_box_scene(A.CB_DEFAULT_SCENE, W, H)
+
+def replay_chains():
+    import denoise_chains_restatement as DC
+    at = (48, 112, 224, 500)
+    bounds = api.pass_boundaries(SPP)
+    debug = api.make_params(W, H, 1, max_path_depth=8, sampler=A.SAMPLER_DEBUG)
+    print("Cornell %d x %d, %d spp, one chunk per pass; truth: the oracle at %d spp; D.DEFAULTS; chain guides: %d guide bounces, taps of the same key only" % (
+        W, H, SPP, TRUTH_SPP, DC.MAX_BOUNCES))
+    print("RMSE of clamp01(picture) against the truth, over the whole film and over the pixels whose key is not 0 (\"chain\"); ratio = chain guides / first-hit guides")
+    for name, flags in (("CB_DEFAULT_SCENE", A.CB_DEFAULT_SCENE), ("CB_LARGE_MIRROR | CB_LIGHT_AREA", A.CB_LARGE_MIRROR | A.CB_LIGHT_AREA)):
+        scene = api.cornell_box_scene(flags, W, H)
+        truth = O.render(scene, api.make_params(W, H, TRUTH_SPP, seed=987654)).astype(np.float64)
+        ga0, gb0 = D.guides_from_hits(scene.c, O.kat_scene_intersect(scene, D.centre_rays(O.kat_camera, scene.c.camera, W, H)), W, H)
+        cls, key, ga1, gb1 = DC.chains(lambda x, y: O.trace_li(scene, debug, x, y, 0), scene.c, W, H, DC.MAX_BOUNCES)
+        on = key != 0
+        pix = D.pixel_width(scene.c.camera, W)
+        rmse = lambda film, sel: float(np.sqrt((((np.clip(film.astype(np.float64), 0, 1) - truth) ** 2)[sel]).mean()))
+        print("\n== %s: %d of %d pixels first hit a mirror or glass: %d chains end on a surface, %d leave the box, %d distinct keys on the film" % (
+            (name, int(on.sum()), W * H) + DC.counts(cls, key)[1:3] + (len(np.unique(key)),)))
+        print(" seed samples batches | whole film: raw  first-hit     chains  ratio | chain pixels: raw  first-hit     chains  ratio | other pixels: first-hit     chains")
+        ratios = {d: [] for d in at}
+        for seed in SEEDS:
+            p = api.make_params(W, H, SPP, seed=seed)
+            rad = np.stack([O.li(scene, p, i % W, i // W, 0, SPP).astype(np.float64) for i in range(W * H)])
+            cum = np.cumsum(rad, axis=1)
+            y_prev, m2, n_prev = np.zeros(W * H), np.zeros(W * H), 0
+            for k, d in enumerate(bounds):
+                accum = np.rint(cum[:, d - 1] / SPP * 4294967296.0).astype(np.int64)
+                y_prev, m2 = R.update(y_prev, m2, R.luminance(accum, SPP), n_prev, d)
+                n_prev = d
+                if d not in at:
+                    continue
+                cv = D.gather(accum, np.zeros(W * H, np.uint32), m2, SPP, d, k + 1).reshape(H, W, 4)
+                first = D.denoise(cv, ga0, gb0, pix, **D.DEFAULTS)[..., :3]
+                chain = DC.denoise(cv, ga1, gb1, key, pix, **D.DEFAULTS)[..., :3]
+                everywhere = np.ones((H, W), bool)
+                w3, c3 = [rmse(f, everywhere) for f in (cv[..., :3], first, chain)], [rmse(f, on) for f in (cv[..., :3], first, chain)]
+                ratios[d].append((w3[2] / w3[1], c3[2] / c3[1]))
+                print("%5d %7d %7d |          %.5f    %.5f    %.5f  %.3f |            %.5f    %.5f    %.5f  %.3f |                 %.5f    %.5f" % (
+                    seed, d, k + 1, w3[0], w3[1], w3[2], w3[2] / w3[1], c3[0], c3[1], c3[2], c3[2] / c3[1], rmse(first, ~on), rmse(chain, ~on)))
+        for d in at:
+            r = np.array(ratios[d])
+            print("at %3d samples: whole-film ratio %.3f .. %.3f, %d of %d seeds below 1; chain-pixel ratio %.3f .. %.3f, %d of %d below 1" % (
+                d, r[:, 0].min(), r[:, 0].max(), int((r[:, 0] < 1).sum()), len(r), r[:, 1].min(), r[:, 1].max(), int((r[:, 1] < 1).sum()), len(r)))
+
+
+if CHAINS:
+    replay_chains()
+    sys.exit(0)
+
+scene =api.cornell_box_scene(A.CB_DEFAULT_SCENE, W, H)
 truth = O.render(scene, api.make_params(W, H, TRUTH_SPP, seed=987654)).astype(np.float64)
 ga, gb = D.guides_from_hits(scene.c, O.kat_scene_intersect(scene, D.centre_rays(O.kat_camera, scene.c.camera, W, H)), W, H)
 pix = D.pixel_width(scene.c.camera, W)
