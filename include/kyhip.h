@@ -603,6 +603,12 @@ int kyhip_kat_camera(int device, const ky_camera* camera, const float* p_film2, 
 /* surface_t::intersect + material_t::scattering + bsdf_t::{sample, eval, pdf} (3077, 2587-2671, 2162-2179).
    in: n x {normal[3], wo[3], u[2], wi_eval[3], lobe_u}.  out: n x {f[3], wi[3], pdf, flags, eval[3], pdf_eval, is_delta}. */
 int kyhip_kat_bsdf(int device, const ky_material* material, const float* in12, int n, float* out13);
+/* The same rows through the lobe code the render kernels execute: what path_tracing_iteration_t makes of its BSDF sample (4586-4597: the direction, the
+   factor f |n.wi| / pdf its throughput is multiplied by, whether the path goes on, whether the lobe is specular) and the light-sampling estimators' evaluation
+   of wi_eval as colour x scale.  flat_phong != 0: the variant of scenes whose plastic surfaces are all rectangles (no flip behind a Phong lobe); the same
+   result wherever n.wo >= 0.  Rows are taken 256 per workgroup in order, so 64 consecutive rows share a wavefront.
+   out: n x {wi[3], weight[3], ok(0/1), specular(0/1), eval[3], pdf_eval}. */
+int kyhip_kat_bsdf_continue(int device, const ky_material* material, const float* in12, int n, int flat_phong, float* out12);
 
 /* light_t::sample_Li / pdf_Li (2825, 2891, 2964, 3026).
    in: n x {p[3], normal[3], u[2], wi[3]}.  out: n x {position[3], wi[3], pdf, Li[3], pdf_Li}. */

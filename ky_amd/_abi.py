@@ -185,6 +185,7 @@ KYHIP_SYMBOLS = {
     "kyhip_kat_intersect": (C.c_int, [C.c_int, C.POINTER(Shape), C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_camera": (C.c_int, [C.c_int, C.POINTER(Camera), C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_bsdf": (C.c_int, [C.c_int, C.POINTER(Material), C.c_void_p, C.c_int, C.c_void_p]),
+    "kyhip_kat_bsdf_continue": (C.c_int, [C.c_int, C.POINTER(Material), C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "kyhip_kat_light": (C.c_int, [C.c_int, SP, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_scene_intersect": (C.c_int, [C.c_int, SP, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_occluded": (C.c_int, [C.c_int, SP, C.c_void_p, C.c_int, C.c_void_p]),
@@ -235,6 +236,7 @@ SAN_DIR = os.path.join(REPO_ROOT, "build", "san")
 
 KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitizer builds only
     "kyhostcheck_pack": (C.c_int, [SP, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kyhostcheck_material": (C.c_int, [C.POINTER(Material), C.POINTER(C.c_int32), C.c_void_p]),
     "kyhostcheck_chunks": (C.c_int, [C.c_int]),
     "kyhostcheck_shard": (C.c_longlong, [PP]),
     "kyhostcheck_frame": (C.c_int, [PP, C.c_int]),

@@ -581,6 +581,15 @@ def kat_bsdf(material, in12, device=0):
     return out
 
 
+def kat_bsdf_continue(material, in12, flat_phong=False, device=0):
+    """kyhip_kat_bsdf_continue: kat_bsdf's rows through the render kernels' lobe code -> n x {wi[3], weight[3], ok, specular, col * scale [3], pdf}."""
+    lib = A.load_kyhip()
+    in12 = np.ascontiguousarray(in12, np.float32)
+    out = np.zeros((in12.shape[0], 12), np.float32)
+    _check(lib.kyhip_kat_bsdf_continue(device, C.byref(material), _fptr(in12), in12.shape[0], 1 if flat_phong else 0, _fptr(out)))
+    return out
+
+
 def kat_light(scene, light, in11, device=0):
     lib = A.load_kyhip()
     in11 = np.ascontiguousarray(in11, np.float32)

@@ -49,6 +49,17 @@ int kyhostcheck_pack(const ky_scene* scene, int* feat, uint64_t* packed_hash, ui
     return KY_OK;
 }
 
+// pack_material on the caller's material: DMat::exp_flags (integral / odd exponent, the two not-black bits, the Phong power's zero bound) and the two colours as
+// packed (colours6: c0 then c1; plastic divides by the lobe probabilities there)
+int kyhostcheck_material(const ky_material* m, int32_t* exp_flags, float* colours6) {
+    if (!m || !exp_flags) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    DMat d;
+    pack_material(*m, &d);
+    *exp_flags = d.exp_flags;
+    if (colours6) { cp3(colours6, d.c0); cp3(colours6 + 3, d.c1); }
+    return KY_OK;
+}
+
 // the chunk schedule of `spp` samples covers [0, spp) exactly once, in order; returns the chunk count or -1
 int kyhostcheck_chunks(int spp) {
     const ChunkPlan p = chunk_plan(spp);
@@ -622,6 +633,7 @@ void kyhip_film_free(void*) {}
 int kyhip_kat_intersect(int, const ky_shape*, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_camera(int, const ky_camera*, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_bsdf(int, const ky_material*, const float*, int, float*) { return no_gpu(); }
+int kyhip_kat_bsdf_continue(int, const ky_material*, const float*, int, int, float*) { return no_gpu(); }
 int kyhip_kat_light(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_scene_intersect(int, const ky_scene*, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_occluded(int, const ky_scene*, const float*, int, float*) { return no_gpu(); }

@@ -234,6 +234,28 @@ __global__ void kat_li_trace_kernel(const DScene* __restrict__ S_, RenderConst r
     if (threadIdx.x == 0) { out[0] = (float)tr.n; out[1] = ps.Lo.x; out[2] = ps.Lo.y; out[3] = ps.Lo.z; }
 }
 
+// the same rows and the same vertex through what the render kernels execute: bsdf_continue (the iterative integrator's sample: direction, value |cos| / pdf in one
+// factor, whether the path goes on) and bsdf_eval_parts (the light-sampling estimators' evaluation as two factors).  256 rows per workgroup in order: a wave is 64
+// consecutive rows, which is what phong_pow_lobe's vote sees.  FLAT_PHONG: a compile-time fact here as in the render kernels (KY_FEAT_FLAT_PHONG).
+template <bool FLAT_PHONG>
+__global__ void kat_bsdf_continue_kernel(DMat M, const float* __restrict__ in12, int n, float* __restrict__ out12) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* r = in12 + 12 * (size_t)i;
+    const f3 normal = ld3(r), wo = ld3(r + 3), wi_eval = ld3(r + 8);
+    Vertex v;
+    v.normal = normal;
+    v.bsdf = make_bsdf(M, r[11]);
+    vertex_prepare(v, wo);
+    const BsdfContinue c = bsdf_continue(v, wo, r[6], r[7], FLAT_PHONG);
+    f3 col; float scale, pd, abs_cos_i;
+    bsdf_eval_parts(v, wo, wi_eval, col, scale, pd, abs_cos_i);
+    const f3 ev = col * scale;
+    float* q = out12 + 12 * (size_t)i;
+    q[0] = c.wi.x; q[1] = c.wi.y; q[2] = c.wi.z; q[3] = c.weight.x; q[4] = c.weight.y; q[5] = c.weight.z;
+    q[6] = c.ok ? 1.f : 0.f; q[7] = c.specular ? 1.f : 0.f; q[8] = ev.x; q[9] = ev.y; q[10] = ev.z; q[11] = pd;
+}
+
 // shared driver of the KAT entry points
 template <typename F>
 static int kat_run(int device, const void* in, size_t in_bytes, void* out, size_t out_bytes, F launch) {
@@ -457,6 +479,19 @@ int kyhip_kat_li_trace(int device, const ky_scene* scene, const ky_render_params
     std::memcpy(rows26, host.data() + 4, (size_t)n * 26 * sizeof(float));
     if (li3) { li3[0] = host[1]; li3[1] = host[2]; li3[2] = host[3]; }
     return n;
+}
+
+// kyhip_kat_bsdf's rows through bsdf_continue and bsdf_eval_parts (the last entry: its kernels are instantiated behind the others, whose listings keep their text)
+int kyhip_kat_bsdf_continue(int device, const ky_material* m, const float* in12, int n, int flat_phong, float* out12) {
+    if (!m || !in12 || !out12 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (m->kind < KY_MATERIAL_MATTE || m->kind > KY_MATERIAL_PLASTIC) return fail(KY_ERR_INVALID_VALUE, "unknown material kind");
+    DMat d{};
+    pack_material(*m, &d);
+    return kat_run(device, in12, (size_t)n * 12 * 4, out12, (size_t)n * 12 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        if (flat_phong) hipLaunchKernelGGL(kat_bsdf_continue_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
+        else hipLaunchKernelGGL(kat_bsdf_continue_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
+        return (int)KY_OK;
+    });
 }
 
 }  // extern "C"

@@ -338,7 +338,7 @@ void pack_material(const ky_material& m, DMat* d) {
         for (int j = 0; j < 3; ++j) d->c1[j] = (d->cs[j] * d->inv_eta) / d->phong_pdf_norm;
     }
     const float e = m.exponent;
-    const bool integral = std::isfinite(e) && std::fabs(e) < 16777216.f && std::floor(e) == e;
+    const bool integral = std::isfinite(e) && std::floor(e) == e;   // (every float from 2^24 on is an even integer: std::pow of a negative base is positive there, not NaN)
     d->exp_flags = (integral ? 1 : 0) | ((integral && std::fmod(std::fabs(e), 2.f) == 1.f) ? 2 : 0);
     // bits 2 / 3: c0 / c1 as packed above is not black (color_t::is_black, 258: every channel <= 0) -- the test of 4588 on a colour that is a constant of the material
     if (!(d->c0[0] <= 0 && d->c0[1] <= 0 && d->c0[2] <= 0)) d->exp_flags |= 4;
