@@ -677,6 +677,11 @@ int kyhip_kat_single_light(int device, const ky_scene* scene, const float* in16,
 int kyhip_kat_li_trace(int device, const ky_scene* scene, const ky_render_params* params, int x, int y, int s,
                        float* rows26, int max_rows, float* li3);
 
+/* The random-number streams of the render kernels by key.  keys2: n x {pixel_index (y * width + x), sample_index} as uint32;
+   out: n x k uint32, the BIT PATTERNS of the first k floats the stream of (seed, pixel_index, sample_index) hands out, in order.  1 <= k <= 256.
+   debug != 0: the debug sampler's stream (0.5 everywhere). */
+int kyhip_kat_sampler(int device, uint32_t seed, const uint32_t* keys2, int n, int k, int debug, uint32_t* out);
+
 /* ---- the smallpt lineage's own scene, in double precision -----------------------------------------
    smallpt2pbrt/smallpt.cpp is the 99-line path tracer ky grew out of (smallpt_milo.cpp is its 256 x 256 build):
    9 spheres -- the walls are spheres of radius 1e5, which is why ky's fp32 sphere test cannot render this scene
@@ -728,6 +733,10 @@ int kyhip_smallpt_render(int device, const ky_smallpt_sphere* spheres, int n_sph
    pixel (x, y): 3 doubles per sample, unclamped. */
 int kyhip_smallpt_kat_radiance(int device, const ky_smallpt_sphere* spheres, int n_spheres, const ky_smallpt_params* params,
                                int x, int y, int sx, int sy, int s0, int n, double* out3);
+
+/* The fp64 path's random-number streams by key.  keys2: n x {subpixel_index ((y * width + x) * 4 + sy * 2 + sx; variant 1: y * width + x), sample}
+   as uint32; out: n x k uint64, the bit patterns of the first k doubles of the stream of (seed, subpixel_index, sample).  1 <= k <= 256. */
+int kyhip_smallpt_kat_rng(int device, uint32_t seed, const uint32_t* keys2, int n, int k, uint64_t* out);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,8 @@ KYHIP_SYMBOLS = {
     "kyhip_scene_screen_bound": (C.c_int, [SP, PP, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "kyhip_scene_facts": (C.c_int, [SP]),
     "kyhip_kat_li": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "kyhip_kat_sampler": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "kyhip_smallpt_kat_rng": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 
 KYHOST_SYMBOLS = {

@@ -714,6 +714,17 @@ def kat_li_trace(scene, params, x, y, s, max_rows=64, device=0):
     return rows[:n], li
 
 
+def kat_sampler(seed, keys2, k, debug=False, device=0):
+    """kyhip_kat_sampler: keys2 [n, 2] uint32 {pixel_index, sample_index} -> [n, k] uint32, the bit patterns of each stream's first k floats."""
+    lib = A.load_kyhip()
+    keys2 = np.ascontiguousarray(keys2, np.uint32)
+    assert keys2.ndim == 2 and keys2.shape[1] == 2
+    out = np.zeros((keys2.shape[0], k), np.uint32)
+    _check(lib.kyhip_kat_sampler(device, int(seed) & 0xFFFFFFFF, keys2.ctypes.data_as(C.c_void_p), keys2.shape[0], k, int(bool(debug)),
+                                 out.ctypes.data_as(C.c_void_p)), lib)
+    return out
+
+
 # ---- SURVEY 8(f)4: smallpt's own scene in double precision --------------------------------------
 
 def smallpt_scene():
@@ -749,6 +760,17 @@ def smallpt_kat_radiance(spheres, params, x, y, sx, sy, s0, n, device=0):
     out = np.zeros((n, 3), np.float64)
     _check(lib.kyhip_smallpt_kat_radiance(device, spheres, len(spheres), C.byref(params), x, y, sx, sy, s0, n,
                                           out.ctypes.data_as(C.c_void_p)), lib)
+    return out
+
+
+def smallpt_kat_rng(seed, keys2, k, device=0):
+    """kyhip_smallpt_kat_rng: keys2 [n, 2] uint32 {subpixel_index, sample} -> [n, k] uint64, the bit patterns of each stream's first k doubles."""
+    lib = A.load_kyhip()
+    keys2 = np.ascontiguousarray(keys2, np.uint32)
+    assert keys2.ndim == 2 and keys2.shape[1] == 2
+    out = np.zeros((keys2.shape[0], k), np.uint64)
+    _check(lib.kyhip_smallpt_kat_rng(device, int(seed) & 0xFFFFFFFF, keys2.ctypes.data_as(C.c_void_p), keys2.shape[0], k,
+                                     out.ctypes.data_as(C.c_void_p)), lib)
     return out
 
 

@@ -721,5 +721,7 @@ int kyhip_smallpt_kat_radiance(int, const ky_smallpt_sphere* spheres, int n, con
     if (p->variant == KY_SP_VARIANT_REWRITE && (sx | sy) != 0) return fail(KY_ERR_INVALID_VALUE, "variant 1 has no subpixels: sx = sy = 0");
     return no_gpu();
 }
+int kyhip_kat_sampler(int, uint32_t, const uint32_t*, int, int, int, uint32_t*) { return no_gpu(); }
+int kyhip_smallpt_kat_rng(int, uint32_t, const uint32_t*, int, int, uint64_t*) { return no_gpu(); }
 
 }  // extern "C"

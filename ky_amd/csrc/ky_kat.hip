@@ -1,7 +1,8 @@
 /*
  * ky_kat.hip -- function-level known-answer-test kernels and their C-ABI entry points (include/kyhip.h, "KAT entry points"): each runs ONE function
  * of the path -- a shape test, the camera, a BSDF lobe, a light, the scene traversal, an occlusion query, one estimator, one camera sample's
- * radiance with or without a vertex trace -- on caller-supplied inputs, for tests/test_parity_gpu.py to compare with the oracle.  Test surface
+ * radiance with or without a vertex trace, the random-number streams by key -- on caller-supplied inputs, for tests/test_parity_gpu.py to compare with the
+ * oracle (the streams: tests/test_sampler_gpu.py, with a restatement that shares no code with either).  Test surface
  * of the library, not part of a render; the kernels are the product's device functions (ky_device.hpp) called directly.
  */
 #include <cstring>
@@ -256,6 +257,18 @@ __global__ void kat_bsdf_continue_kernel(DMat M, const float* __restrict__ in12,
     q[6] = c.ok ? 1.f : 0.f; q[7] = c.specular ? 1.f : 0.f; q[8] = ev.x; q[9] = ev.y; q[10] = ev.z; q[11] = pd;
 }
 
+// the bit patterns of the first k numbers of the stream the render kernels give the key (seed, pixel_index, sample_index): sampler_pixel_key, sampler_start
+// and sampler_next as path_begin calls them.  One thread per key; its k words lie together.
+template <bool DEBUG_SAMPLER>
+__global__ void kat_sampler_kernel(uint32_t seed, const uint32_t* __restrict__ keys2, int n, int k, uint32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Sampler smp;
+    sampler_start(smp, sampler_pixel_key(seed, keys2[2 * (size_t)i]), keys2[2 * (size_t)i + 1]);
+    uint32_t* q = out + (size_t)i * (size_t)k;
+    for (int j = 0; j < k; ++j) q[j] = __float_as_uint(sampler_next<DEBUG_SAMPLER>(smp));
+}
+
 // shared driver of the KAT entry points
 template <typename F>
 static int kat_run(int device, const void* in, size_t in_bytes, void* out, size_t out_bytes, F launch) {
@@ -490,6 +503,17 @@ int kyhip_kat_bsdf_continue(int device, const ky_material* m, const float* in12,
     return kat_run(device, in12, (size_t)n * 12 * 4, out12, (size_t)n * 12 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
         if (flat_phong) hipLaunchKernelGGL(kat_bsdf_continue_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
         else hipLaunchKernelGGL(kat_bsdf_continue_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
+        return (int)KY_OK;
+    });
+}
+
+// the render kernels' random-number streams by key (behind the other entries, like kyhip_kat_bsdf_continue)
+int kyhip_kat_sampler(int device, uint32_t seed, const uint32_t* keys2, int n, int k, int debug, uint32_t* out) {
+    if (!keys2 || !out || n <= 0 || k < 1 || k > 256 || (size_t)n * (size_t)k > ((size_t)1 << 28)) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    return kat_run(device, keys2, (size_t)n * 2 * 4, out, (size_t)n * (size_t)k * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        const dim3 grid((n + 255) / 256), block(256);
+        if (debug) hipLaunchKernelGGL(kat_sampler_kernel<true>, grid, block, 0, 0, seed, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
+        else hipLaunchKernelGGL(kat_sampler_kernel<false>, grid, block, 0, 0, seed, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
         return (int)KY_OK;
     });
 }

@@ -843,4 +843,21 @@ int kyhip_smallpt_kat_radiance(int device, const ky_smallpt_sphere* spheres, int
     return KY_OK;
 }
 
+int kyhip_smallpt_kat_rng(int device, uint32_t seed, const uint32_t* keys2, int n, int k, uint64_t* out) {
+    if (!keys2 || !out || n <= 0 || k < 1 || k > 256 || (size_t)n * (size_t)k > ((size_t)1 << 27)) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    DeviceCtx* c = nullptr;
+    int rcode = get_ctx(device, &c);
+    if (rcode != KY_OK) return rcode;
+    std::lock_guard<std::mutex> lock(c->m);
+    const size_t out_bytes = (size_t)n * (size_t)k * sizeof(uint64_t);
+    DevBuf d_keys, d_out;
+    HIP_TRY(d_keys.alloc((size_t)n * 2 * sizeof(uint32_t)));
+    HIP_TRY(d_out.alloc(out_bytes));
+    HIP_TRY(hipMemcpy(d_keys.p, keys2, (size_t)n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(kysp::smallpt_kat_rng_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, seed, d_keys.as<const uint32_t>(), n, k, d_out.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return KY_OK;
+}
+
 }  // extern "C"

@@ -397,6 +397,16 @@ __global__ void smallpt_kat_kernel(const SpSphere* __restrict__ sph, SpConst k, 
     out3[3 * i] = L.x; out3[3 * i + 1] = L.y; out3[3 * i + 2] = L.z;
 }
 
+// the bit patterns of the first k doubles of the stream of the key (seed, subpixel_index, sample): sp_rng_start and sp_next as the kernels above call them
+__global__ void smallpt_kat_rng_kernel(uint32_t seed, const uint32_t* __restrict__ keys2, int n, int k, uint64_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    SpRng rng;
+    sp_rng_start(rng, seed, keys2[2 * (size_t)i], keys2[2 * (size_t)i + 1]);
+    uint64_t* q = out + (size_t)i * (size_t)k;
+    for (int j = 0; j < k; ++j) q[j] = (uint64_t)__double_as_longlong(sp_next(rng));
+}
+
 // ---- host side ----------------------------------------------------------------------------------
 // Ray cam(Vec(50,52,295.6), Vec(0,-0.042612,-1).norm()); cx = Vec(w*.5135/h); cy = (cx % cam.d).norm() * .5135  (93-94)
 inline void sp_make_const(const ky_smallpt_params* p, int n, SpConst& k) {

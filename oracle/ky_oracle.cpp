@@ -226,7 +226,7 @@ struct sampler_t {
     int      kind = KY_SAMPLER_RANDOM;
     uint32_t s0 = 0, s1 = 1;
     const float* tape = nullptr;   // function-level KATs: the next numbers to hand out, instead of the generator's
-    int tape_pos = 0;
+    int tape_pos = 0, tape_len = 0x7fffffff;   // past tape_len the tape hands out 0.5 and goes on counting (kyo_li_tape reports the overrun)
     // one camera sample = one stream; sampler_t::start_pixel / next_sample (900-908) select it.
     // (s0, s1) made from (seed, pixel, sample) is the state of a xoroshiro64+ generator (Blackman / Vigna, a = 26, b = 9, c = 13;
     // s1 is made odd, which excludes the all-zero state): s0 a hash of the pixel's key and the sample index, s1 = rotl(s0, 16) ^ key,
@@ -240,7 +240,7 @@ struct sampler_t {
         s1 = (rotl(s0, 16) ^ h) | 1u;   // round 5: one hash per sample (the device's sampler_start, ky_amd/csrc/ky_device.hpp); two before
     }
     float get_float() {                                                                   // 960
-        if (tape) return tape[tape_pos++];
+        if (tape) { const int at = tape_pos++; return at < tape_len ? tape[at] : 0.5f; }
         if (kind == KY_SAMPLER_DEBUG) return 0.5f;                                        // 933-941
         const uint32_t word = s0 + s1;
         s1 ^= s0;
@@ -1149,6 +1149,43 @@ int kyo_li(const ky_scene* cscene, const ky_render_params* p, int x, int y, int 
         ray_t ray = generate_ray(scene.camera, cs);
         color_t L = integrator.Li(ray, sampler, nullptr);
         out3[3 * i] = L.r; out3[3 * i + 1] = L.g; out3[3 * i + 2] = L.b;
+    }
+    return KY_OK;
+}
+
+// kyo_li with each sample's numbers taken from the caller's rows instead of the generator's (sampler_t::tape): sample i reads tape[i * stride ...] in the
+// order of consumption, camera sample first.  used[i]: how many it consumed; a sample that needs more than its row is handed 0.5 for the rest and ends the call with -2.
+// The rows may come from any generator: this is how the tests put a foreign one under the whole path.
+int kyo_li_tape(const ky_scene* cscene, const ky_render_params* p, int x, int y, const float* tape, int stride, int n, float* out3, int* used) {
+    if (!cscene || !p || !tape || !out3 || !used || stride < 2 || n <= 0) return KY_ERR_INVALID_VALUE;
+    if (!valid_integrator(p->integrator) || !valid_direct_sample(p->direct_sample)) return KY_ERR_INVALID_VALUE;
+    scene_t scene(*cscene);
+    integrator_t integrator{&scene, p->integrator, p->max_path_depth, p->direct_sample};
+    for (int i = 0; i < n; ++i) {
+        sampler_t sampler;
+        sampler.tape = tape + (size_t)i * stride;
+        sampler.tape_len = stride;
+        vec2_t cs = sampler.get_camera_sample({(float)x, (float)y});
+        ray_t ray = generate_ray(scene.camera, cs);
+        color_t L = integrator.Li(ray, sampler, nullptr);
+        out3[3 * i] = L.r; out3[3 * i + 1] = L.g; out3[3 * i + 2] = L.b;
+        used[i] = sampler.tape_pos;
+        if (sampler.tape_pos > stride) return -2;
+    }
+    return KY_OK;
+}
+
+// the bit patterns of the first k numbers of sampler_t's stream for each key {pixel_index, sample_index} (kyhip_kat_sampler's twin)
+int kyo_kat_sampler(uint32_t seed, const uint32_t* keys2, int n, int k, int debug, uint32_t* out) {
+    if (!keys2 || !out || n <= 0 || k < 1) return KY_ERR_INVALID_VALUE;
+    for (int i = 0; i < n; ++i) {
+        sampler_t sampler;
+        sampler.kind = debug ? KY_SAMPLER_DEBUG : KY_SAMPLER_RANDOM;
+        sampler.start_sample(seed, keys2[2 * (size_t)i], keys2[2 * (size_t)i + 1]);
+        for (int j = 0; j < k; ++j) {
+            const float f = sampler.get_float();
+            std::memcpy(out + (size_t)i * k + j, &f, 4);
+        }
     }
     return KY_OK;
 }

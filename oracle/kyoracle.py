@@ -105,6 +105,33 @@ def li(scene, params, x, y, s0, n):
     return out
 
 
+def li_tape(scene, params, x, y, tape):
+    """kyo_li_tape: li() with sample i's numbers read from tape[i] (float32 [n, stride]) in the order of consumption -> (li [n, 3], used [n]).
+    Raises if a sample needed more numbers than its row holds."""
+    tape = np.ascontiguousarray(tape, np.float32)
+    n, stride = tape.shape
+    out = np.zeros((n, 3), np.float32)
+    used = np.zeros(n, np.int32)
+    lib = load()
+    lib.kyo_li_tape.argtypes = [A.SP, A.PP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    rc = lib.kyo_li_tape(_sp(scene), C.byref(params), x, y, _f(tape), stride, n, _f(out), used.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"kyo_li_tape returned {rc} (-2: a sample needed more than {stride} numbers; most used {int(used.max())})")
+    return out, used
+
+
+def kat_sampler(seed, keys2, k, debug=False):
+    """kyo_kat_sampler: keys2 [n, 2] uint32 {pixel_index, sample_index} -> [n, k] uint32, the bit patterns of each stream's first k floats."""
+    keys2 = np.ascontiguousarray(keys2, np.uint32)
+    out = np.zeros((keys2.shape[0], k), np.uint32)
+    lib = load()
+    lib.kyo_kat_sampler.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    rc = lib.kyo_kat_sampler(int(seed) & 0xFFFFFFFF, keys2.ctypes.data_as(C.c_void_p), keys2.shape[0], k, int(bool(debug)), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"kyo_kat_sampler returned {rc}")
+    return out
+
+
 def trace_li(scene, params, x, y, s, max_rows=64):
     rows = np.zeros((max_rows, 26), np.float32)
     lib = load()
@@ -206,6 +233,18 @@ def smallpt_radiance(spheres, params, x, y, sx, sy, s0, n):
     rc = load().kyo_smallpt_radiance(spheres, len(spheres), C.byref(params), x, y, sx, sy, s0, n, out.ctypes.data_as(C.c_void_p))
     if rc != 0:
         raise ValueError(f"kyo_smallpt_radiance returned {rc}")
+    return out
+
+
+def smallpt_kat_rng(seed, keys2, k):
+    """kyo_smallpt_kat_rng: keys2 [n, 2] uint32 {subpixel_index, sample} -> [n, k] uint64, the bit patterns of each stream's first k doubles."""
+    keys2 = np.ascontiguousarray(keys2, np.uint32)
+    out = np.zeros((keys2.shape[0], k), np.uint64)
+    lib = load()
+    lib.kyo_smallpt_kat_rng.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    rc = lib.kyo_smallpt_kat_rng(int(seed) & 0xFFFFFFFF, keys2.ctypes.data_as(C.c_void_p), keys2.shape[0], k, out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError(f"kyo_smallpt_kat_rng returned {rc}")
     return out
 
 

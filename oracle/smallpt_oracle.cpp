@@ -195,6 +195,20 @@ int kyo_smallpt_radiance(const ky_smallpt_sphere* spheres, int n, const ky_small
     return 0;
 }
 
+// the bit patterns of the first k doubles of the rng_mode 0 stream of each key {subpixel_index, sample} (kyhip_smallpt_kat_rng's twin)
+int kyo_smallpt_kat_rng(uint32_t seed, const uint32_t* keys2, int n, int k, uint64_t* out) {
+    if (!keys2 || !out || n <= 0 || k < 1) return -1;
+    for (int i = 0; i < n; ++i) {
+        Rng rng;
+        rng_start(rng, seed, keys2[2 * (size_t)i], keys2[2 * (size_t)i + 1]);
+        for (int j = 0; j < k; ++j) {
+            const double d = rnd(rng);
+            std::memcpy(out + (size_t)i * k + j, &d, 8);
+        }
+    }
+    return 0;
+}
+
 // the scene table, restated independently of the product's kyhip_smallpt_scene (smallpt.cpp:42-52)
 int kyo_smallpt_scene(ky_smallpt_sphere* out) {
     const double rows[9][10] = {{1e5, 1e5 + 1, 40.8, 81.6, 0, 0, 0, .75, .25, .25},     {1e5, -1e5 + 99, 40.8, 81.6, 0, 0, 0, .25, .25, .75},
