@@ -31,6 +31,9 @@
  *   ky_drivers sliced [n] [spp] [w] [h]  the same frame by sample range (3 slices, 512 spp, 1024 x 768; kyhip_frame_begin_slice, kyhip_frame_merge_from): the n slices
  *                                render on device 0 one after the other, slice 0 merges the rest; prints per slice its samples and kernel time, the merge times, and
  *                                whether the film is render()'s bit for bit (it must be: exit status 1 otherwise); writes sliced.bmp
+ *   ky_drivers stratified [scene] [spp] [cell]  one scene (cornell, the default, or veach) under the random and the stratified sampler side by side at equal spp
+ *                                (16; cells of 256, the Veach scene 256 x 144), path_tracing_iteration d5 both_mis into a film_grid_t(1, 2, ...); prints both
+ *                                kernel times and writes stratified.bmp: random | stratified
  * An optional last argument multiplies every spp (the reference's values are tiny because its CPU path is slow).
  * KY_DEVICES=all (or a count n: devices 0 .. n-1) makes every integrator spread its tiles over that many GPUs of the node
  * (integrator_t::set_devices); the images do not depend on it.
@@ -223,6 +226,26 @@ static void render_lighting_cells(int spp, int cell) {
     }
     std::printf("lighting_cells: 4 cells %dx%d, %d spp: kernels %.3f ms\n", cell, cell, spp, kernel_ms);
     film.store_image("lighting_cells");
+}
+
+// One scene under random_sampler_t and stratified_sampler_t (ky.cpp:977, a stub there) at equal spp: what the strata buy at a preview's sample count.
+static void render_stratified(bool veach, int spp, int cell) {
+    const int width = cell, height = veach ? cell * 9 / 16 : cell;
+    film_grid_t film(1, 2, width, height);
+    scene_t scene = veach ? scene_t::create_mis_scene(film.get_resolution())
+                          : scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, film.get_resolution());
+    double ms[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        std::unique_ptr<sampler_t> sampler;
+        if (k == 0) sampler = std::make_unique<random_sampler_t>(spp);
+        else sampler = std::make_unique<stratified_sampler_t>(spp);
+        auto integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
+        use_devices(*integrator); integrator->render(&scene, sampler.get(), &film);
+        ms[k] = integrator->last_kernel_ms();
+        film.next_subfilm();
+    }
+    std::printf("stratified: %s %dx%d, %d spp: kernel %.3f ms random, %.3f ms stratified\n", veach ? "veach" : "cornell", width, height, spp, ms[0], ms[1]);
+    film.store_image("stratified");
 }
 
 // The headline frame in passes: a picture after the first 64 samples, the reference's progress line (3703) after every pass, and a final image that is
@@ -424,6 +447,12 @@ int main(int argc, char* argv[]) {
         } else if (!std::strcmp(which, "denoise")) {
             render_denoise(argc > 2 ? std::atoi(argv[2]) : 64, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768,
                            argc > 6 ? std::atoi(argv[6]) : 0);
+        } else if (!std::strcmp(which, "stratified")) {
+            const bool veach = argc > 2 && !std::strcmp(argv[2], "veach");
+            if (argc > 2 && !veach && std::strcmp(argv[2], "cornell")) { std::fprintf(stderr, "stratified: cornell or veach\n"); return 2; }
+            const int spp = argc > 3 ? std::atoi(argv[3]) : 16, cell = argc > 4 ? std::atoi(argv[4]) : 256;
+            if (spp < 1 || spp > (1 << 24) || cell < 16) { std::fprintf(stderr, "stratified: 1 .. 2^24 samples per pixel, cells of 16 or more\n"); return 2; }
+            render_stratified(veach, spp, cell);
         } else if (!std::strcmp(which, "lighting_cells")) {
             render_lighting_cells(argc > 2 ? std::atoi(argv[2]) : 10, argc > 3 ? std::atoi(argv[3]) : 256);
         } else if (!std::strcmp(which, "batch")) {

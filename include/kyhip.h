@@ -152,9 +152,13 @@ typedef enum ky_direct_sample {
 /* sampler_t subclasses that can be instantiated (ky.cpp:922, 949). */
 typedef enum ky_sampler_kind {
     KY_SAMPLER_DEBUG  = 0,  /* debug_sampler_t: every number 0.5, camera sample = pixel centre (933-946) */
-    KY_SAMPLER_RANDOM = 1   /* random_sampler_t semantics (uniform [0,1) fp32) on a counter-based generator
+    KY_SAMPLER_RANDOM = 1,  /* random_sampler_t semantics (uniform [0,1) fp32) on a counter-based generator
                                keyed (seed, pixel, sample, dimension); see DESIGN.md "Random numbers" */
+    KY_SAMPLER_STRATIFIED = 2   /* stratified_sampler_t, which ky.cpp:977 declares and leaves a stub: the camera sample multi-jittered, the next
+                               KYHIP_STRATIFIED_DIMS - 2 draws of a sample Latin-hypercube strata over the pixel's samples_per_pixel samples, every later
+                               draw the random sampler's; samples_per_pixel <= 2^24.  DESIGN.md "Random numbers" has the definition */
 } ky_sampler_kind;
+#define KYHIP_STRATIFIED_DIMS 16   /* the draws of a camera sample that KY_SAMPLER_STRATIFIED stratifies (the camera's two among them) */
 
 typedef struct ky_render_params {
     int32_t  integrator;         /* ky_integrator_kind */
@@ -681,6 +685,9 @@ int kyhip_kat_li_trace(int device, const ky_scene* scene, const ky_render_params
    out: n x k uint32, the BIT PATTERNS of the first k floats the stream of (seed, pixel_index, sample_index) hands out, in order.  1 <= k <= 256.
    debug != 0: the debug sampler's stream (0.5 everywhere). */
 int kyhip_kat_sampler(int device, uint32_t seed, const uint32_t* keys2, int n, int k, int debug, uint32_t* out);
+/* The same for any ky_sampler_kind, through the device functions the render kernels draw with.  spp: the frame's samples_per_pixel, which the stratified
+   sampler's strata depend on (the other kinds ignore it); under KY_SAMPLER_STRATIFIED 1 <= spp <= 2^24 and a key whose sample_index is >= spp is refused. */
+int kyhip_kat_sampler_kind(int device, int kind, uint32_t seed, int spp, const uint32_t* keys2, int n, int k, uint32_t* out);
 
 /* ---- the smallpt lineage's own scene, in double precision -----------------------------------------
    smallpt2pbrt/smallpt.cpp is the 99-line path tracer ky grew out of (smallpt_milo.cpp is its 256 x 256 build):

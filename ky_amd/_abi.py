@@ -19,7 +19,8 @@ INTEGRATOR_DIRECT_LIGHTING, INTEGRATOR_PATH_TRACING_ITERATION = 6, 11
 INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION, INTEGRATOR_PATH_TRACING_RECURSION, INTEGRATOR_PATH_TRACING_RECURSION_DEFERED = 8, 9, 10
 DIRECT_IDLE, DIRECT_BSDF, DIRECT_LIGHT, DIRECT_BSDF_MIS, DIRECT_LIGHT_MIS, DIRECT_BOTH_MIS = 0, 4, 8, 16, 32, 48
 DIRECT_SINGLE_LIGHT, DIRECT_SINGLE_BOTH_MIS = 1, 49   # sample_single_light: accepted as 1 | 48 only
-SAMPLER_DEBUG, SAMPLER_RANDOM = 0, 1
+SAMPLER_DEBUG, SAMPLER_RANDOM, SAMPLER_STRATIFIED = 0, 1, 2
+STRATIFIED_DIMS = 16   # KYHIP_STRATIFIED_DIMS
 LIGHTING_EMIT, LIGHTING_DIRECT, LIGHTING_INDIRECT, LIGHTING_ALL = 1, 2, 4, 7   # ky_lighting (lighting_enum_t, ky.cpp:3591-3603)
 SP_VARIANT_SMALLPT, SP_VARIANT_REWRITE = 0, 1
 KY_OK, KY_ERR_INVALID_VALUE, KY_ERR_LIMIT, KY_ERR_DEVICE, KY_ERR_NO_DEVICE = 0, -1, -2, -3, -4
@@ -197,6 +198,7 @@ KYHIP_SYMBOLS = {
     "kyhip_scene_facts": (C.c_int, [SP]),
     "kyhip_kat_li": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhip_kat_sampler": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "kyhip_kat_sampler_kind": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "kyhip_smallpt_kat_rng": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }
 

@@ -725,6 +725,17 @@ def kat_sampler(seed, keys2, k, debug=False, device=0):
     return out
 
 
+def kat_sampler_kind(kind, seed, spp, keys2, k, device=0, lib=None):
+    """kyhip_kat_sampler_kind: kat_sampler for any sampler kind; spp is the frame's samples_per_pixel, which the stratified sampler's strata depend on."""
+    lib = lib or A.load_kyhip()
+    keys2 = np.ascontiguousarray(keys2, np.uint32)
+    assert keys2.ndim == 2 and keys2.shape[1] == 2
+    out = np.zeros((keys2.shape[0], k), np.uint32)
+    _check(lib.kyhip_kat_sampler_kind(device, int(kind), int(seed) & 0xFFFFFFFF, int(spp), keys2.ctypes.data_as(C.c_void_p), keys2.shape[0], k,
+                                      out.ctypes.data_as(C.c_void_p)), lib)
+    return out
+
+
 # ---- SURVEY 8(f)4: smallpt's own scene in double precision --------------------------------------
 
 def smallpt_scene():

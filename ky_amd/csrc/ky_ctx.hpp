@@ -68,7 +68,7 @@ struct SceneSlot {
     hipStream_t upload_stream = nullptr;
     unsigned long long last_use = 0;
 };
-constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8, KY_MAX_VARIANTS = 96;
+constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8, KY_MAX_VARIANTS = 128;
 // what kyhip_render / kyhip_render_multi keep between calls (the host-film seam); `m` serialises such calls per device, it is never
 // taken while a context's enqueue mutex is held
 // (measured on configs[1]'s 9.4 MB film, tools/seam_trace.py: what a call costs beyond its kernel -- the film's pinned download alone is 0.18 ms -- is

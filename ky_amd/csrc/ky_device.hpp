@@ -250,6 +250,16 @@ KY_DEV uint32_t mix32(uint32_t x) {
 struct Sampler {
     uint32_t s0, s1;
 };
+// KY_SMP_STRATIFIED's state, a type of its own so that the other kinds' code is what it was: the stream, the pixel's key, the sample's index, how many numbers the
+// sample has drawn, and the launch's strata (wave-uniform: bound once per kernel by sampler_bind, never per path).  Functions that only pass a sampler on take it as
+// the state type of their kind (SamplerFor).
+struct StratSampler : Sampler {
+    uint32_t h, s, d;
+    int N;
+    StratConst k;
+};
+template <int SAMPLER> struct SamplerFor { typedef Sampler type; };
+template <> struct SamplerFor<KY_SMP_STRATIFIED> { typedef StratSampler type; };
 // the state of a sample's xoroshiro64+ stream from (seed, pixel, sample) (s1 is made odd: the all-zero state is excluded)
 KY_DEV uint32_t sampler_pixel_key(uint32_t seed, uint32_t pixel_index) { return mix32(pixel_index ^ mix32(seed)); }  // constant per pixel
 // One hash per sample (round 5; two before): the second state word is the first one rotated by half a word, xor the pixel's key, made odd -- three full-rate
@@ -263,9 +273,7 @@ KY_DEV uint32_t rotl32(uint32_t x, int k) { return __builtin_amdgcn_alignbit(x, 
 // xoroshiro64+ (Blackman / Vigna; a = 26, b = 9, c = 13): eight full-rate VALU instructions per number with the conversion -- a xor, a three-way xor
 // (v_bitop3_b32), two v_alignbit, a shift, an add; v_alignbit, subtract -- against eleven for rounds 1-3's PCG-RXS-M-XS-32 with its two slow integer multiplies
 // (v_mul_lo_u32, v_mad_u64_u32).  The sum's weak low bits are among the nine the conversion drops.
-template <bool DEBUG_SAMPLER>
-KY_DEV float sampler_next(Sampler& s) {
-    if (DEBUG_SAMPLER) return 0.5f;  // debug_sampler_t, 933-941
+KY_DEV float sampler_raw(Sampler& s) {
     const uint32_t r = s.s0 + s.s1;
     s.s1 ^= s.s0;
     s.s0 = __builtin_amdgcn_bitop3_b32(rotl32(s.s0, 26), s.s1, s.s1 << 9, 0x96);   // a ^ b ^ c in one v_bitop3_b32 (gfx950; the compiler writes two v_xor for the C expression)
@@ -273,6 +281,86 @@ KY_DEV float sampler_next(Sampler& s) {
     // the sum's upper 23 bits as the mantissa of a float in [1, 2), minus one: v_alignbit_b32 (0x7f : r) >> 9, v_sub -- two instructions where
     // shift, convert, scale were three; the value is (r >> 9) 2^-23 exactly, which is how the oracle writes it
     return __uint_as_float(__builtin_amdgcn_alignbit(0x7fu, r, 9)) - 1.0f;
+}
+
+// ---- KY_SAMPLER_STRATIFIED: DESIGN.md section 5, "The stratified sampler", is the definition; tests/stratified_restatement.py restates it bit for bit ----
+// perm(i, n, key): a keyed bijection of [0, n), 0 <= i < n <= 2^24.  Cycle-walking on [0, 2^b), b the bit length of n - 1: every step is a bijection of the low b
+// bits (xor with key bits, a product with an odd constant cut to b bits, x ^= x >> ceil(b / 2)), so the walk from a value below n comes back below n -- after fewer
+// than two turns on average, 2^b < 2 n.  Two slow integer multiplies (v_mul_lo_u32) per turn; mask and shift are wave-uniform where n is.
+KY_DEV uint32_t strat_perm(uint32_t i, uint32_t n, uint32_t key) {
+    const int b = 32 - __clz((int)(n - 1u));
+    const uint32_t mask = n > 1u ? 0xffffffffu >> (32 - b) : 0u;
+    const int h = (b + 1) >> 1;
+    const uint32_t key1 = __builtin_amdgcn_alignbit(key, key, 11), key2 = __builtin_amdgcn_alignbit(key, key, 22);   // the key rotated right
+    do {
+        i = ((i ^ key) * 0x9E3779B1u) & mask;
+        i ^= i >> h;
+        i = ((i ^ key1) * 0x85EBCA6Bu) & mask;
+        i ^= i >> h;
+        i = (i ^ key2) & mask;
+    } while (i >= n);
+    return i;
+}
+// the key of purpose j of a pixel: draw positions 2 .. 15 are their own purposes; 0, 1 and 16 are the camera sample's cell, column and row permutations
+KY_DEV uint32_t strat_key(uint32_t h, uint32_t j) { return mix32(h ^ ((j + 1u) * 0x85EBCA77u)); }
+// one rounding per operation: a + b and a * b written so that no multiply-add is contracted from them under the compiler's default for HIP, -ffp-contract=fast-honor-pragmas,
+// which the Makefile and the run-time instantiations' flags leave in force (a build with -ffp-contract=fast would fuse regardless: tests/test_stratified_gpu.py would say so)
+KY_DEV float strat_fadd(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+KY_DEV float strat_fmul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+constexpr float K_BELOW_ONE = 0x1.fffffep-1f;
+// draw position 0 or 1 of the sample whose cell is c = perm(s, N, k_c): the multi-jittered camera sample
+KY_DEV float strat_camera(const StratSampler& s, uint32_t c, uint32_t d, float r) {
+    const uint32_t cy = c / (uint32_t)s.k.m, cx = c - cy * (uint32_t)s.k.m;
+    float x;
+    if (d == 0) x = strat_fmul(strat_fadd((float)cx, strat_fmul(strat_fadd((float)strat_perm(cy, (uint32_t)s.k.n, strat_key(s.h, 1u)), r), s.k.inv_n)), s.k.inv_m);
+    else x = strat_fmul(strat_fadd((float)cy, strat_fmul(strat_fadd((float)strat_perm(cx, (uint32_t)s.k.m, strat_key(s.h, 16u)), r), s.k.inv_m)), s.k.inv_n);
+    return fminf(x, K_BELOW_ONE);
+}
+KY_DEV float strat_next(StratSampler& s) {
+    const uint32_t d = s.d;
+    s.d = d + 1u;
+    const float r = sampler_raw(s);   // the stream is stepped once per draw whatever becomes of the number
+    // (s < N always, for a path: the second test only keeps a lane whose state is not a sample's -- "any register content", path_state_dead -- from walking a
+    // cycle of perm that has no value below n, should such a lane ever draw)
+    if (d >= (uint32_t)KYHIP_STRATIFIED_DIMS || s.s >= (uint32_t)s.N) return r;
+    if (d < 2u) return strat_camera(s, strat_perm(s.s, (uint32_t)s.N, strat_key(s.h, 0u)), d, r);
+    return fminf(strat_fmul(strat_fadd((float)strat_perm(s.s, (uint32_t)s.N, strat_key(s.h, d)), r), s.k.inv_N), K_BELOW_ONE);   // Latin hypercube
+}
+
+template <int SAMPLER>
+KY_DEV float sampler_next(typename SamplerFor<SAMPLER>::type& s) {   // (the state's type goes with the kind: a stratified draw on a plain Sampler does not compile)
+    if (SAMPLER == KY_SMP_DEBUG) return 0.5f;  // debug_sampler_t, 933-941
+    if constexpr (SAMPLER == KY_SMP_STRATIFIED) return strat_next(s);
+    else return sampler_raw(s);
+}
+// sampler_start for a kind: the stratified sampler remembers whose sample this is and that it has drawn nothing
+template <int SAMPLER>
+KY_DEV void sampler_start_kind(typename SamplerFor<SAMPLER>::type& s, uint32_t h, uint32_t sample_index) {
+    sampler_start(s, h, sample_index);
+    if constexpr (SAMPLER == KY_SMP_STRATIFIED) { s.h = h; s.s = sample_index; s.d = 0u; }
+}
+// the launch's strata into a sampler, once per kernel and outside every divergent branch: they stay wave-uniform (scalar registers)
+KY_DEV void sampler_bind(Sampler&, const RenderConst&) {}
+KY_DEV void sampler_bind(StratSampler& s, const RenderConstS& rc) { s.N = rc.spp; s.k = rc.strat; }
+// get_camera_sample (943-946 / 971-974): a sample's first two numbers.  The stratified pair shares one cell permutation.
+template <int SAMPLER>
+KY_DEV void sampler_camera(typename SamplerFor<SAMPLER>::type& s, float& u0, float& u1) {
+    if constexpr (SAMPLER == KY_SMP_STRATIFIED) {
+        StratSampler& t = s;
+        const float r0 = sampler_raw(t), r1 = sampler_raw(t);
+        t.d = 2u;
+        if (t.s >= (uint32_t)t.N) { u0 = r0; u1 = r1; return; }   // (never, for a path: strat_next's note)
+        const uint32_t c = strat_perm(t.s, (uint32_t)t.N, strat_key(t.h, 0u));
+        u0 = strat_camera(t, c, 0u, r0); u1 = strat_camera(t, c, 1u, r1);
+    } else {
+        u0 = sampler_next<SAMPLER>(s); u1 = sampler_next<SAMPLER>(s);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1996,22 +2084,22 @@ KY_DEV void estimate_env_both(SceneRef S, const Vertex& v, f3 wo, float ub0, flo
 // estimate was non-black, bit 16 + li = its light half.
 // `sq` (the QUEUE instantiations of the lane engine: strategies both_mis, light_mis, light): the light-sampling halves are not added but
 // pushed on the wave's shadow-ray stack with beta x weight (x 0.5 under both_mis) as their weight in the pixel's sum.
-template <bool DEBUG_SAMPLER>
-KY_DEV void sample_all_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, Sampler& smp, int strategy, bool active, f3& Lo, f3 beta,
+template <int SAMPLER>
+KY_DEV void sample_all_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, typename SamplerFor<SAMPLER>::type& smp, int strategy, bool active, f3& Lo, f3 beta,
                              unsigned* decisions = nullptr, ShadowQueue* sq = nullptr, float weight = 0.f, unsigned tag = 0, RideAlong* ra = nullptr) {
     const int nl = S.single_light() ? 1 : S->n_lights;
     const f3 w = strategy == KY_DIRECT_BOTH_MIS ? beta * 0.5f : beta;
     for (int li = 0; li < nl; ++li) {
         // the reference's GCC build draws random_bsdf first, then random_light (3866-3868), for every light and strategy
         float ub0 = any_f(), ub1 = any_f(), ul0 = any_f(), ul1 = any_f();   // drawn, and read, by the active lanes only
-        if (active) { ub0 = sampler_next<DEBUG_SAMPLER>(smp); ub1 = sampler_next<DEBUG_SAMPLER>(smp); }
+        if (active) { ub0 = sampler_next<SAMPLER>(smp); ub1 = sampler_next<SAMPLER>(smp); }
         f3 Lb = mk3(0, 0, 0), Ll = mk3(0, 0, 0);      // tracing only: the two halves on their own
         f3& ab = decisions ? Lb : Lo;
         f3& al = decisions ? Ll : Lo;
         const f3 wt = decisions ? mk3(1, 1, 1) : w;
         if (strategy == KY_DIRECT_BOTH_MIS && (S.feat & KY_FEAT_SINGLE_ENV) && !sq && !ra) {   // (compile-time) one environment light: both halves in one pass
             if (active) {
-                ul0 = sampler_next<DEBUG_SAMPLER>(smp); ul1 = sampler_next<DEBUG_SAMPLER>(smp);
+                ul0 = sampler_next<SAMPLER>(smp); ul1 = sampler_next<SAMPLER>(smp);
                 estimate_env_both(S, v, wo, ub0, ub1, ul0, ul1, ab, al, wt);
             }
         } else if (strategy == KY_DIRECT_BOTH_MIS) {  // 4076-4088
@@ -2019,12 +2107,12 @@ KY_DEV void sample_all_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f
             estimate_by_bsdf<true>(S, Lds, v, wo, li, ub0, ub1, active, ab, wt, sq, beta, weight * 0.5f, tag, ra);   // draws nothing itself
             KY_CLK(4);
             // random_light is drawn here, after the BSDF half: same stream position, two registers fewer across it
-            if (active) { ul0 = sampler_next<DEBUG_SAMPLER>(smp); ul1 = sampler_next<DEBUG_SAMPLER>(smp); }
+            if (active) { ul0 = sampler_next<SAMPLER>(smp); ul1 = sampler_next<SAMPLER>(smp); }
             if (sq) estimate_by_emitter_deferred<true>(S, v, wo, li, ul0, ul1, active, beta, weight * 0.5f, tag, *sq);
             else if (ra) estimate_by_emitter_ride<true>(S, Lds, v, wo, li, ul0, ul1, active, *ra, al, wt);
             else if (active) estimate_by_emitter<true>(S, Lds, v, wo, li, ul0, ul1, al, wt);
         } else {
-            if (active) { ul0 = sampler_next<DEBUG_SAMPLER>(smp); ul1 = sampler_next<DEBUG_SAMPLER>(smp); }
+            if (active) { ul0 = sampler_next<SAMPLER>(smp); ul1 = sampler_next<SAMPLER>(smp); }
             KY_CLK(3);
             if (strategy == KY_DIRECT_BSDF_MIS) {
                 estimate_by_bsdf<true>(S, Lds, v, wo, li, ub0, ub1, active, ab, wt);
@@ -2038,7 +2126,7 @@ KY_DEV void sample_all_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f
                 const int lk = S->light[li].kind;
                 if (!S.is_delta(lk)) {  // the third float2 is drawn after the delta test (3894-3900)
                     float u0 = any_f(), u1 = any_f();
-                    if (active) { u0 = sampler_next<DEBUG_SAMPLER>(smp); u1 = sampler_next<DEBUG_SAMPLER>(smp); }
+                    if (active) { u0 = sampler_next<SAMPLER>(smp); u1 = sampler_next<SAMPLER>(smp); }
                     estimate_by_bsdf<false>(S, Lds, v, wo, li, u0, u1, active, ab, wt);
                 }
             }
@@ -2065,18 +2153,18 @@ KY_DEV void sample_all_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f
 // A kernel whose facts name ONE light (KY_FEAT_SINGLE_LIGHT) picks index 0 with probability 1 -- it still draws the pick -- and runs that light's
 // wave-uniform estimators as they are.
 // `decisions`: bit li = the BSDF half of the PICKED light was non-black, bit 16 + li its light half; no other light's bits are set.
-template <bool DEBUG_SAMPLER>
-KY_DEV void sample_single_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, Sampler& smp, bool active, f3& Lo, f3 beta,
+template <int SAMPLER>
+KY_DEV void sample_single_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, typename SamplerFor<SAMPLER>::type& smp, bool active, f3& Lo, f3 beta,
                                 unsigned* decisions = nullptr, ShadowQueue* sq = nullptr, float weight = 0.f, unsigned tag = 0, RideAlong* ra = nullptr) {
     const int nl = S.single_light() ? 1 : S->n_lights;
     if (nl == 0) return;   // 3816-3818
     int li = 0;
     float ub0 = any_f(), ub1 = any_f(), ul0 = any_f(), ul1 = any_f();   // drawn, and read, by the active lanes only
     if (active) {
-        const float u = sampler_next<DEBUG_SAMPLER>(smp);
+        const float u = sampler_next<SAMPLER>(smp);
         li = min((int)(u * (float)nl), nl - 1);   // 3821
-        ul0 = sampler_next<DEBUG_SAMPLER>(smp); ul1 = sampler_next<DEBUG_SAMPLER>(smp);   // random_light, 3824
-        ub0 = sampler_next<DEBUG_SAMPLER>(smp); ub1 = sampler_next<DEBUG_SAMPLER>(smp);   // random_bsdf, 3825
+        ul0 = sampler_next<SAMPLER>(smp); ul1 = sampler_next<SAMPLER>(smp);   // random_light, 3824
+        ub0 = sampler_next<SAMPLER>(smp); ub1 = sampler_next<SAMPLER>(smp);   // random_bsdf, 3825
     }
     const float fn = (float)nl;   // 1 / pick probability, 3830
     const f3 w = beta * (0.5f * fn);
@@ -2110,15 +2198,15 @@ KY_DEV void sample_single_light(SceneRef S, const LdsScene& Lds, const Vertex& v
 // What a vertex's light estimate draws from the sample's stream, drawn and thrown away: the vertex whose estimate a masked render drops (light classes,
 // DESIGN.md section 3) traces none of its rays and pushes none, and every later draw of the sample stays where it was.  sample_all_light: four numbers per light,
 // two more under the plain bsdf strategy for a light that is not a delta light (3894-3900); sample_single_light: the pick and four, nothing without lights.
-template <bool DEBUG_SAMPLER>
-KY_DEV void light_estimate_draws(SceneRef S, Sampler& smp, int strategy, bool active) {
+template <int SAMPLER>
+KY_DEV void light_estimate_draws(SceneRef S, typename SamplerFor<SAMPLER>::type& smp, int strategy, bool active) {
     if (!active) return;
     const int nl = S.single_light() ? 1 : S->n_lights;
     int n = 4 * nl;
     if (strategy == KY_DIRECT_SINGLE_BOTH_MIS) n = nl > 0 ? 5 : 0;
     else if (strategy == KY_DIRECT_BSDF)
         for (int li = 0; li < nl; ++li) n += S.is_delta(S->light[li].kind) ? 0 : 2;
-    for (int i = 0; i < n; ++i) (void)sampler_next<DEBUG_SAMPLER>(smp);
+    for (int i = 0; i < n; ++i) (void)sampler_next<SAMPLER>(smp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2126,28 +2214,34 @@ KY_DEV void light_estimate_draws(SceneRef S, Sampler& smp, int strategy, bool ac
 // (4136-4154) and debug_integrator_t::Li (4105-4122) share this state machine: step() advances
 // the path by one vertex and returns false when the path has ended (radiance complete in Lo).
 // ---------------------------------------------------------------------------------------------
-struct PathState {
+template <typename SMP>
+struct PathStateT {
     f3 o, d;  // current ray
     f3 beta, Lo;
-    Sampler smp;
+    SMP smp;
     int bounces;
     bool prev_specular;
 };
+typedef PathStateT<Sampler> PathState;
+template <int SAMPLER> using PathStateFor = PathStateT<typename SamplerFor<SAMPLER>::type>;
 
 // everything of a path's state but Lo becomes "any register content" (callers: lanes that hold no path)
-KY_DEV void path_state_dead(PathState& ps) {
+template <typename SMP>
+KY_DEV void path_state_dead(PathStateT<SMP>& ps) {
     ps.o = mk3(any_reg(), any_reg(), any_reg()); ps.d = mk3(any_reg(), any_reg(), any_reg()); ps.beta = mk3(any_reg(), any_reg(), any_reg());
     ps.smp.s0 = any_reg_u(); ps.smp.s1 = any_reg_u(); ps.bounces = (int)any_reg_u(); ps.prev_specular = any_reg_u() != 0;
+    if constexpr (std::is_same<SMP, StratSampler>::value) { ps.smp.h = any_reg_u(); ps.smp.s = any_reg_u(); ps.smp.d = any_reg_u(); }   // (not the strata: they are the launch's)
 }
 
 
 // KEEP_LO (render_kernel): ps.Lo is not the sample's radiance but the running sum of the lane's pixel chunk -- every contribution of every
 // path of the chunk is added to it, the kernel scales and flushes it once per chunk -- so a new path leaves it alone.
-template <bool DEBUG_SAMPLER, bool KEEP_LO = false>
-KY_DEV void path_begin(PathState& ps, SceneRef S, uint32_t pixel_key, int x, int y, int sample) {
-    sampler_start(ps.smp, pixel_key, (uint32_t)sample);
+template <int SAMPLER, bool KEEP_LO = false>
+KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key, int x, int y, int sample) {
+    sampler_start_kind<SAMPLER>(ps.smp, pixel_key, (uint32_t)sample);
     // get_camera_sample, 943-946 / 971-974
-    const float u0 = sampler_next<DEBUG_SAMPLER>(ps.smp), u1 = sampler_next<DEBUG_SAMPLER>(ps.smp);
+    float u0, u1;
+    sampler_camera<SAMPLER>(ps.smp, u0, u1);
     generate_ray(S, (float)x + u0, (float)y + u1, ps.o, ps.d);
     ps.beta = mk3(1, 1, 1);
     if (!KEEP_LO) ps.Lo = mk3(0, 0, 0);
@@ -2160,8 +2254,8 @@ KY_DEV void path_begin(PathState& ps, SceneRef S, uint32_t pixel_key, int x, int
 // DROP (light classes, lighting_enum_t 3591-3603): bit 0 -- nothing the camera ray's own hit or miss emits is added (class k = 0); bit 1 -- no
 // class k = 1 term: here the emission a path finds at bounces == 1, which it reads after a delta bounce only (the look-up goes with the add), in path_shade the
 // first vertex's light estimate.  0: nothing dropped, and the code of every instantiation that does not name DROP is what it was.  -1: the bits are `drop_rt`.
-template <bool DEBUG_SAMPLER, int DROP = 0>
-KY_DEV bool path_intersect(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc, int drop_rt = 0) {
+template <int SAMPLER, int DROP = 0>
+KY_DEV bool path_intersect(PathStateFor<SAMPLER>& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc, int drop_rt = 0) {
     const int drop = DROP >= 0 ? DROP : drop_rt;
     float t = K_INF;
     KY_PROBE(0);
@@ -2206,11 +2300,11 @@ KY_DEV bool path_intersect(PathState& ps, Vertex& v, SceneRef S, const LdsScene&
 }
 
 // material->scattering's lobe decision on its own (3083, 2663): draws the plastic lobe number from the path's stream
-template <bool DEBUG_SAMPLER>
-KY_DEV int path_pick_lobe(PathState& ps, int surface, const LdsScene& Lds) {
+template <int SAMPLER>
+KY_DEV int path_pick_lobe(PathStateFor<SAMPLER>& ps, int surface, const LdsScene& Lds) {
     const DMat& M = Lds.mat[Lds.hit[surface].material];
     float lobe_u = 0.f;
-    if (M.kind == KY_MATERIAL_PLASTIC) lobe_u = sampler_next<DEBUG_SAMPLER>(ps.smp);
+    if (M.kind == KY_MATERIAL_PLASTIC) lobe_u = sampler_next<SAMPLER>(ps.smp);
     return pick_lobe(M, lobe_u);
 }
 
@@ -2224,8 +2318,8 @@ struct VertexTrace {
 
 // `tr` is a null constant everywhere but in the trace KAT kernel, which removes the tracing code.
 // DROP / drop_rt: path_intersect's; bit 1 drops the light estimate of the vertex at bounces == 0, whose draws are still made (light_estimate_draws).
-template <bool DEBUG_SAMPLER, int DROP = 0>
-KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc, bool active,
+template <int SAMPLER, int DROP = 0>
+KY_DEV bool path_shade(PathStateFor<SAMPLER>& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc, bool active,
                        int lobe = -1, VertexTrace* tr = nullptr, ShadowQueue* sq = nullptr, unsigned tag = 0, bool ride_along = false, bool free_state = false,
                        int drop_rt = 0) {
     const int drop = DROP >= 0 ? DROP : drop_rt;
@@ -2235,7 +2329,7 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
         const DMat& M = Lds.mat[Lds.hit[v.surface].material];
         if (lobe < 0) {
             float lobe_u = 0.f;
-            if (M.kind == KY_MATERIAL_PLASTIC) lobe_u = sampler_next<DEBUG_SAMPLER>(ps.smp);
+            if (M.kind == KY_MATERIAL_PLASTIC) lobe_u = sampler_next<SAMPLER>(ps.smp);
             v.bsdf = make_bsdf(M, lobe_u, (S.feat & KY_FEAT_NO_DELTA) != 0);
         } else {
             v.bsdf = make_bsdf_for_lobe(M, lobe);
@@ -2277,7 +2371,7 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
     f3 es_f = any3();
     float es_k = any_f();
     if (riding && active && delta) {
-        const float e0 = sampler_next<DEBUG_SAMPLER>(ps.smp), e1 = sampler_next<DEBUG_SAMPLER>(ps.smp);
+        const float e0 = sampler_next<SAMPLER>(ps.smp), e1 = sampler_next<SAMPLER>(ps.smp);
         const BsdfSample es = bsdf_sample(v, wo, e0, e1);
         ra.want = true;
         ra.o = v.position;
@@ -2286,13 +2380,13 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
         es_k = fabsf(dot(es.wi, v.normal)) / es.pdf;
     }
     if (!simple && rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS) {   // sample_single_light: one light per vertex
-        sample_single_light<DEBUG_SAMPLER>(S, Lds, v, wo, ps.smp, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag, riding ? &ra : nullptr);
+        sample_single_light<SAMPLER>(S, Lds, v, wo, ps.smp, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag, riding ? &ra : nullptr);
     } else
     if (!simple) {  // simple_path_tracing_recursion_t samples the BSDF only
-        sample_all_light<DEBUG_SAMPLER>(S, Lds, v, wo, ps.smp, rc.strategy, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag,
+        sample_all_light<SAMPLER>(S, Lds, v, wo, ps.smp, rc.strategy, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag,
                                         riding ? &ra : nullptr);  // 4575 / 4337 / 4458
     }
-    if ((drop & 2) != 0 && !simple) light_estimate_draws<DEBUG_SAMPLER>(S, ps.smp, rc.strategy, unlit);
+    if ((drop & 2) != 0 && !simple) light_estimate_draws<SAMPLER>(S, ps.smp, rc.strategy, unlit);
     KY_CLK(8);
     if (rc.integrator == KY_INTEGRATOR_DIRECT_LIGHTING) return false;  // 4153
     if (!active) {
@@ -2305,7 +2399,7 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
 
     if (recursion && delta) {
         if (!riding) {
-            const float e0 = sampler_next<DEBUG_SAMPLER>(ps.smp), e1 = sampler_next<DEBUG_SAMPLER>(ps.smp);
+            const float e0 = sampler_next<SAMPLER>(ps.smp), e1 = sampler_next<SAMPLER>(ps.smp);
             const BsdfSample es = bsdf_sample(v, wo, e0, e1);
             ra.o = v.position;
             ra.d = es.wi;
@@ -2322,13 +2416,13 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
             const f3 hp = ra.o + ra.t * ra.d;
             Le = surface_emission(Lds, ra.hs, hit_normal(Lds.hit[ra.hs], hp, ra.d), -ra.d);
             // scene->intersect builds the hit's BSDF: a plastic surface draws its lobe number (2663)
-            if (Lds.mat[Lds.hit[ra.hs].material].kind == KY_MATERIAL_PLASTIC) (void)sampler_next<DEBUG_SAMPLER>(ps.smp);
+            if (Lds.mat[Lds.hit[ra.hs].material].kind == KY_MATERIAL_PLASTIC) (void)sampler_next<SAMPLER>(ps.smp);
         }
         ps.Lo = ps.Lo + ps.beta * ((es_f * Le) * es_k);  // 0/0 = NaN on total internal reflection, as in 4349
     }
 
     // sample BSDF to get the new path direction, 4586 / 4213 / 4383 / 4495
-    const float u0 = sampler_next<DEBUG_SAMPLER>(ps.smp), u1 = sampler_next<DEBUG_SAMPLER>(ps.smp);
+    const float u0 = sampler_next<SAMPLER>(ps.smp), u1 = sampler_next<SAMPLER>(ps.smp);
     KY_PROBE(7);
     if (rc.integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !tr) {
         // path_tracing_iteration_t, 4586-4616, with the sample's value, cosine and pdf folded into one factor (bsdf_continue).
@@ -2342,7 +2436,7 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
         ps.d = c.wi;
         if (ps.bounces > 3) {  // Russian roulette, 4601-4612 (the number is drawn by the paths that get here only: the stream of the others must not move)
             const float q = fmaxf(0.05f, 1 - max3(ps.beta));
-            const float u = sampler_next<DEBUG_SAMPLER>(ps.smp);
+            const float u = sampler_next<SAMPLER>(ps.smp);
             cont = cont && !(u < q);
             ps.beta = ps.beta * rcp(1 - q);
         }
@@ -2369,7 +2463,7 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
         ps.d = bs.wi;
         if (ps.bounces > 3) {  // Russian roulette, 4601-4612
             const float q = fmaxf(0.05f, 1 - max3(ps.beta));
-            const float u = sampler_next<DEBUG_SAMPLER>(ps.smp);
+            const float u = sampler_next<SAMPLER>(ps.smp);
             if (u < q) return false;
             ps.beta = ps.beta * rcp(1 - q);
         }
@@ -2382,7 +2476,7 @@ KY_DEV bool path_shade(PathState& ps, Vertex& v, SceneRef S, const LdsScene& Lds
     // the recursive integrators: roulette on the BSDF value once ++depth > 3 (4219-4226, 4389-4397, 4501-4509)
     if (ps.bounces + 1 > 3) {
         const float m = max3(bs.f);
-        const float u = sampler_next<DEBUG_SAMPLER>(ps.smp);
+        const float u = sampler_next<SAMPLER>(ps.smp);
         if (!(u < m)) return false;
         bs.f = bs.f * (1 / m);
     }

@@ -35,7 +35,11 @@ const std::string& last_error();
 bool valid_params(const ky_render_params* p);
 bool shard_in_range(const ky_render_params* p);
 ShardConst make_shard(const ky_render_params* p);
-RenderConst make_rc(const ky_render_params* p);
+RenderConstS make_rc(const ky_render_params* p);   // the launch constants with the stratified sampler's strata; every other kernel takes its RenderConst (ky_scene.hpp)
+// The stratified sampler has strata for the frame's own samples only: what the KAT entries refuse before any device work.
+// strat_samples_check: samples s0 .. s0 + n - 1 of a launch of p (every other sampler: any index).  kat_sampler_kind_check: kyhip_kat_sampler_kind's arguments.
+int strat_samples_check(const ky_render_params* p, int s0, int n);
+int kat_sampler_kind_check(int kind, int spp, const uint32_t* keys2, int n, int k, const uint32_t* out);
 // The film's range rule (DESIGN.md "Film"): N = the most terms one accumulator word can receive in a launch of p (n_lights lights, on the queue engine or
 // the lane engine with or without deferred shadow rays), and the term limit T = min(2e9, 2^31 / N) as a float rounded down (0 when it is below 1:
 // such a launch is refused with KY_ERR_LIMIT).  n_lights: 0 .. KYHIP_MAX_LIGHTS.

@@ -639,7 +639,12 @@ int kyhip_kat_scene_intersect(int, const ky_scene*, const float*, int, float*) {
 int kyhip_kat_occluded(int, const ky_scene*, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_any_pair(int, const ky_scene*, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_occluded_between(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }
-int kyhip_kat_li(int, const ky_scene*, const ky_render_params*, int, int, int, int, float*) { return no_gpu(); }
+// (the stratified sampler's sample range is refused before any device work, like the real entry's: strat_samples_check is host code)
+int kyhip_kat_li(int, const ky_scene*, const ky_render_params* p, int, int, int s0, int n, float*) {
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    KY_TRY(strat_samples_check(p, s0, n));
+    return no_gpu();
+}
 // (the masked entries refuse an invalid mask before they look for a device, like the real ones: lighting_plan is host code)
 int kyhip_render_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, float*, size_t) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
 int kyhip_kat_li_lighting(int, const ky_scene*, const ky_render_params* p, int lighting, int, int, int, int, float*) { LightingPlan pl; const int rc = lighting_plan(p, lighting, &pl); return rc != KY_OK ? rc : no_gpu(); }
@@ -722,6 +727,10 @@ int kyhip_smallpt_kat_radiance(int, const ky_smallpt_sphere* spheres, int n, con
     return no_gpu();
 }
 int kyhip_kat_sampler(int, uint32_t, const uint32_t*, int, int, int, uint32_t*) { return no_gpu(); }
+int kyhip_kat_sampler_kind(int, int kind, uint32_t, int spp, const uint32_t* keys2, int n, int k, uint32_t* out) {
+    KY_TRY(kat_sampler_kind_check(kind, spp, keys2, n, k, out));
+    return no_gpu();
+}
 int kyhip_smallpt_kat_rng(int, uint32_t, const uint32_t*, int, int, uint64_t*) { return no_gpu(); }
 
 }  // extern "C"

@@ -238,7 +238,7 @@ bool build(const std::string& args, std::vector<char>& object_out, std::string& 
     }
     const std::string tu = root + "/ky_amd/csrc/jit" + tag + ".hip", tmp = object + ".tmp" + tag, log = object + tag + ".log";
     const std::string text = "#include \"ky_render.hpp\"\nextern \"C\" __global__ __launch_bounds__(256, (ky_waves_per_eu<" + args + ">())) void " + k_entry +
-                             "(const kyd::DScene* __restrict__ S, kyd::RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, "
+                             "(const kyd::DScene* __restrict__ S, kyd::RenderConstFor<" + args.substr(0, args.find(',')) + ">::type rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, "
                              "unsigned* __restrict__ flags, float4* __restrict__ queue_mem) {\n    render_kernel_body<" + args + ">(S, rc, sh, counter, accum, flags, queue_mem);\n}\n";
     ok = ok && write_once(tu, text.c_str(), tag);
     if (!ok) { status = "cannot write the sources under " + dir; return false; }

@@ -155,6 +155,27 @@ __global__ void kat_li_lighting_kernel(const DScene* __restrict__ S_, RenderCons
     if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
 }
 
+// kat_li_kernel and kat_li_lighting_kernel under the stratified sampler (KY_SAMPLER_STRATIFIED), whose launch constants carry the strata (RenderConstS): the same walk,
+// the drop bits read at run time (0 for kyhip_kat_li)
+template <bool BOXES>
+__global__ void kat_li_stratified_kernel(const DScene* __restrict__ S_, RenderConstS rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env, int drop) {
+    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    PathStateFor<KY_SMP_STRATIFIED> ps;
+    sampler_bind(ps.smp, rc);
+    bool alive = i < n;
+    if (alive) path_begin<KY_SMP_STRATIFIED>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i);
+    while (__any(alive)) {  // path_shade is a wave-uniform call
+        Vertex v;
+        bool have_vertex = false;
+        if (alive) have_vertex = path_intersect<KY_SMP_STRATIFIED, -1>(ps, v, S, Lds, rc, drop);
+        const bool cont = path_shade<KY_SMP_STRATIFIED, -1>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, nullptr, 0, false, false, drop);
+        alive = have_vertex && cont;
+    }
+    if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
+}
+
 // one light's direct-lighting estimate at given vertices with given random numbers (estimate_direct_lighting_*, 3889-4088)
 __global__ void kat_nee_kernel(const DScene* __restrict__ S, int strategy, int li, const float* __restrict__ in15, int n, float* __restrict__ out6) {
     const LdsScene Lds = stage_scene<true>(S);   // KAT kernels: always the scene-sized dynamic block
@@ -235,6 +256,26 @@ __global__ void kat_li_trace_kernel(const DScene* __restrict__ S_, RenderConst r
     if (threadIdx.x == 0) { out[0] = (float)tr.n; out[1] = ps.Lo.x; out[2] = ps.Lo.y; out[3] = ps.Lo.z; }
 }
 
+// kat_li_trace_kernel under the stratified sampler
+template <bool BOXES>
+__global__ void kat_li_trace_stratified_kernel(const DScene* __restrict__ S_, RenderConstS rc, int x, int y, int s, int max_rows, float* __restrict__ out, int single_env) {
+    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    PathStateFor<KY_SMP_STRATIFIED> ps;
+    sampler_bind(ps.smp, rc);
+    bool alive = threadIdx.x == 0;
+    VertexTrace tr{out + 4, max_rows, 0};
+    if (alive) path_begin<KY_SMP_STRATIFIED>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s);
+    while (__any(alive)) {
+        Vertex v;
+        bool have_vertex = false;
+        if (alive) have_vertex = path_intersect<KY_SMP_STRATIFIED>(ps, v, S, Lds, rc);
+        const bool cont = path_shade<KY_SMP_STRATIFIED>(ps, v, S, Lds, rc, have_vertex, -1, &tr);
+        alive = have_vertex && cont;
+    }
+    if (threadIdx.x == 0) { out[0] = (float)tr.n; out[1] = ps.Lo.x; out[2] = ps.Lo.y; out[3] = ps.Lo.z; }
+}
+
 // the same rows and the same vertex through what the render kernels execute: bsdf_continue (the iterative integrator's sample: direction, value |cos| / pdf in one
 // factor, whether the path goes on) and bsdf_eval_parts (the light-sampling estimators' evaluation as two factors).  256 rows per workgroup in order: a wave is 64
 // consecutive rows, which is what phong_pow_lobe's vote sees.  FLAT_PHONG: a compile-time fact here as in the render kernels (KY_FEAT_FLAT_PHONG).
@@ -267,6 +308,24 @@ __global__ void kat_sampler_kernel(uint32_t seed, const uint32_t* __restrict__ k
     sampler_start(smp, sampler_pixel_key(seed, keys2[2 * (size_t)i]), keys2[2 * (size_t)i + 1]);
     uint32_t* q = out + (size_t)i * (size_t)k;
     for (int j = 0; j < k; ++j) q[j] = __float_as_uint(sampler_next<DEBUG_SAMPLER>(smp));
+}
+// ... of the stratified sampler: sampler_start_kind and sampler_next as the render kernels' later draws call them, or -- camera != 0 -- the first two through
+// sampler_camera, which is how path_begin draws them
+__global__ void kat_sampler_stratified_kernel(uint32_t seed, RenderConstS rc, int camera, const uint32_t* __restrict__ keys2, int n, int k, uint32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    StratSampler smp;
+    sampler_bind(smp, rc);
+    sampler_start_kind<KY_SMP_STRATIFIED>(smp, sampler_pixel_key(seed, keys2[2 * (size_t)i]), keys2[2 * (size_t)i + 1]);
+    uint32_t* q = out + (size_t)i * (size_t)k;
+    int j = 0;
+    if (camera && k >= 2) {
+        float u0, u1;
+        sampler_camera<KY_SMP_STRATIFIED>(smp, u0, u1);
+        q[0] = __float_as_uint(u0); q[1] = __float_as_uint(u1);
+        j = 2;
+    }
+    for (; j < k; ++j) q[j] = __float_as_uint(sampler_next<KY_SMP_STRATIFIED>(smp));
 }
 
 // shared driver of the KAT entry points
@@ -384,8 +443,10 @@ int kyhip_kat_occluded_between(int device, const ky_scene* scene, int light, con
 int kyhip_kat_li(int device, const ky_scene* scene, const ky_render_params* p, int x, int y, int s0, int n, float* out3) {
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
     if (!scene || !out3 || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    const RenderConst rc = make_rc(p);
-    const bool dbg = p->sampler == KY_SAMPLER_DEBUG;
+    KY_TRY(strat_samples_check(p, s0, n));
+    const RenderConstS rcs = make_rc(p);
+    const RenderConst rc = rcs;
+    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
     float dummy = 0.f;
     return kat_run(device, &dummy, 4, out3, (size_t)n * 3 * 4, [&](DeviceCtx* c, const float*, float* d_out) {
         SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
@@ -395,7 +456,9 @@ int kyhip_kat_li(int device, const ky_scene* scene, const ky_render_params* p, i
         const int rf = render_replay_feat(scene, p, sc->h);
         const bool boxes = (rf & KY_FEAT_BOXES) != 0;
         const int env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
-        if (dbg && boxes) hipLaunchKernelGGL((kat_li_kernel<true, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
+        if (strat && boxes) hipLaunchKernelGGL((kat_li_stratified_kernel<true>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, 0);
+        else if (strat) hipLaunchKernelGGL((kat_li_stratified_kernel<false>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, 0);
+        else if (dbg && boxes) hipLaunchKernelGGL((kat_li_kernel<true, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
         else if (dbg) hipLaunchKernelGGL((kat_li_kernel<true, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
         else if (boxes) hipLaunchKernelGGL((kat_li_kernel<false, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
         else hipLaunchKernelGGL((kat_li_kernel<false, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
@@ -410,11 +473,13 @@ int kyhip_kat_li_lighting(int device, const ky_scene* scene, const ky_render_par
     if (rcode != KY_OK) return rcode;
     if (plan.plain) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);
     if (!scene || !out3 || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    KY_TRY(strat_samples_check(p, s0, n));
     if (plan.nothing) { std::memset(out3, 0, (size_t)n * 3 * sizeof(float)); return KY_OK; }
     ky_render_params q = *p;
     q.max_path_depth = plan.effective_depth;
-    const RenderConst rc = make_rc(&q);
-    const bool dbg = p->sampler == KY_SAMPLER_DEBUG;
+    const RenderConstS rcs = make_rc(&q);
+    const RenderConst rc = rcs;
+    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
     const int drop = plan.dropped;
     float dummy = 0.f;
     return kat_run(device, &dummy, 4, out3, (size_t)n * 3 * 4, [&](DeviceCtx* c, const float*, float* d_out) {
@@ -425,7 +490,9 @@ int kyhip_kat_li_lighting(int device, const ky_scene* scene, const ky_render_par
         const int rf = render_replay_feat(scene, &q, sc->h, drop);
         const bool boxes = (rf & KY_FEAT_BOXES) != 0;
         const int env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
-        if (dbg && boxes) hipLaunchKernelGGL((kat_li_lighting_kernel<true, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
+        if (strat && boxes) hipLaunchKernelGGL((kat_li_stratified_kernel<true>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, drop);
+        else if (strat) hipLaunchKernelGGL((kat_li_stratified_kernel<false>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, drop);
+        else if (dbg && boxes) hipLaunchKernelGGL((kat_li_lighting_kernel<true, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
         else if (dbg) hipLaunchKernelGGL((kat_li_lighting_kernel<true, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
         else if (boxes) hipLaunchKernelGGL((kat_li_lighting_kernel<false, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
         else hipLaunchKernelGGL((kat_li_lighting_kernel<false, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
@@ -470,8 +537,10 @@ int kyhip_kat_li_trace(int device, const ky_scene* scene, const ky_render_params
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
     if (p->integrator != KY_INTEGRATOR_PATH_TRACING_ITERATION) return fail(KY_ERR_INVALID_VALUE, "the vertex trace follows path_tracing_iteration_t");
     if (!scene || !rows26 || max_rows <= 0 || max_rows > 4096 || s < 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    const RenderConst rc = make_rc(p);
-    const bool dbg = p->sampler == KY_SAMPLER_DEBUG;
+    KY_TRY(strat_samples_check(p, s, 1));
+    const RenderConstS rcs = make_rc(p);
+    const RenderConst rc = rcs;
+    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
     std::vector<float> host((size_t)4 + (size_t)max_rows * 26, 0.f);
     float dummy = 0.f;
     const int rcode = kat_run(device, &dummy, 4, host.data(), host.size() * 4, [&](DeviceCtx* c, const float*, float* d_out) {
@@ -481,7 +550,9 @@ int kyhip_kat_li_trace(int device, const ky_scene* scene, const ky_render_params
         const int rf = render_replay_feat(scene, p, sc->h);
         const bool boxes = (rf & KY_FEAT_BOXES) != 0;
         const int env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
-        if (dbg && boxes) hipLaunchKernelGGL((kat_li_trace_kernel<true, true>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
+        if (strat && boxes) hipLaunchKernelGGL((kat_li_trace_stratified_kernel<true>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rcs, x, y, s, max_rows, d_out, env);
+        else if (strat) hipLaunchKernelGGL((kat_li_trace_stratified_kernel<false>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rcs, x, y, s, max_rows, d_out, env);
+        else if (dbg && boxes) hipLaunchKernelGGL((kat_li_trace_kernel<true, true>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
         else if (dbg) hipLaunchKernelGGL((kat_li_trace_kernel<true, false>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
         else if (boxes) hipLaunchKernelGGL((kat_li_trace_kernel<false, true>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
         else hipLaunchKernelGGL((kat_li_trace_kernel<false, false>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
@@ -516,6 +587,27 @@ int kyhip_kat_sampler(int device, uint32_t seed, const uint32_t* keys2, int n, i
         else hipLaunchKernelGGL(kat_sampler_kernel<false>, grid, block, 0, 0, seed, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
         return (int)KY_OK;
     });
+}
+
+// ... for any ky_sampler_kind.  The stratified sampler's first two numbers are drawn twice, draw by draw and as path_begin draws them (sampler_camera), and the entry
+// fails with KY_ERR_DEVICE if the two disagree: there is one stream per key, however it is read.
+int kyhip_kat_sampler_kind(int device, int kind, uint32_t seed, int spp, const uint32_t* keys2, int n, int k, uint32_t* out) {
+    KY_TRY(kat_sampler_kind_check(kind, spp, keys2, n, k, out));
+    if (kind != KY_SAMPLER_STRATIFIED) return kyhip_kat_sampler(device, seed, keys2, n, k, kind == KY_SAMPLER_DEBUG, out);
+    ky_render_params q{};
+    q.samples_per_pixel = spp;
+    const RenderConstS rc = make_rc(&q);
+    std::vector<uint32_t> first(k >= 2 ? (size_t)n * (size_t)k : 0);
+    for (int camera = k >= 2 ? 1 : 0; camera >= 0; --camera) {
+        const int rcode = kat_run(device, keys2, (size_t)n * 2 * 4, out, (size_t)n * (size_t)k * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+            hipLaunchKernelGGL(kat_sampler_stratified_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, seed, rc, camera, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
+            return (int)KY_OK;
+        });
+        if (rcode != KY_OK) return rcode;
+        if (camera) std::memcpy(first.data(), out, first.size() * sizeof(uint32_t));
+    }
+    if (!first.empty() && std::memcmp(first.data(), out, first.size() * sizeof(uint32_t)) != 0) return fail(KY_ERR_DEVICE, "the stratified camera sample differs between sampler_camera and sampler_next");
+    return KY_OK;
 }
 
 }  // extern "C"

@@ -264,13 +264,14 @@ int kyhip_device_count(void) {
 }
 
 // The render-kernel instantiations of the lane engine, most specific first; a launch takes the first whose assumptions hold.
-//   sampler   debug_sampler_t or random_sampler_t
+//   sampler   debug_sampler_t, random_sampler_t or the stratified sampler (its rows: `fn_s`, a kernel template and launch constants of their own, ky_render.hpp)
 //   strategy  -1: direct_sample_enum_t and integrator are read at run time (11 000 instructions, five waves per SIMD); otherwise both are
 //             compile-time constants of the instantiation
 //   queue     deferred shadow rays (scenes with two or more lights)
 //   general   carries the reference's own formulations for quads that are not parallelograms, triangles and disks
 //   feat      the KY_FEAT_* facts of the scene the instantiation assumes
 using RenderFn = void (*)(const DScene*, RenderConst, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);
+using RenderFnS = void (*)(const DScene*, RenderConstS, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a stratified row's kernel: the launch constants carry the strata
 struct Variant {
     bool dbg;
     int strategy;
@@ -280,6 +281,7 @@ struct Variant {
     RenderFn fn;
     int drop;   // light classes (kyhip_render_lighting): 0 the unmasked kernel, 1 / 2 / 3 these drop bits at compile time, -1 the launch's bits read at run time
     bool listed;   // passes of a block-tracking frame (kyhip_frame_track_blocks): the work decoder reads the block from the frame's live list (ky_render.hpp, LISTED)
+    RenderFnS fn_s;   // KY_SAMPLER_STRATIFIED (dbg is false, fn is null): render_kernel_stratified, which takes RenderConstS; null in every other row
 };
 #define KY_VARIANT(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel<D, S, Q, G, F, I>, 0}
 #define KY_VARIANT_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel<D, S, Q, G, F, I, true>, 0}
@@ -287,6 +289,8 @@ struct Variant {
 #define KY_VARIANT_MASKED_LARGE(DROP, D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel_masked<DROP, D, S, Q, G, F, I, true>, DROP}
 #define KY_VARIANT_LISTED(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel_listed<D, S, Q, G, F, I>, 0, true}
 #define KY_VARIANT_LISTED_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel_listed<D, S, Q, G, F, I, true>, 0, true}
+// a stratified row: the strategy, queue, general, feat, integrator of the others, then large, drop and listed as the kernel template takes them
+#define KY_VARIANT_STRAT(S, Q, G, F, I, L, DROP, LISTED) Variant{false, S, Q, G, F, I, L, nullptr, DROP, LISTED, render_kernel_stratified<S, Q, G, F, I, L, DROP, LISTED>}
 // a row's three masked twins: emission at the first vertex dropped (lighting 2, 6), the k = 1 terms (5), both (4)
 #define KY_VARIANT_MASKED3(D, S, Q, G, F, I) KY_VARIANT_MASKED(1, D, S, Q, G, F, I), KY_VARIANT_MASKED(2, D, S, Q, G, F, I), KY_VARIANT_MASKED(3, D, S, Q, G, F, I)
 constexpr int IT = KY_INTEGRATOR_PATH_TRACING_ITERATION;
@@ -391,6 +395,20 @@ static const Variant g_variants[] = {
     KY_VARIANT_LISTED(true, -1, false, true, 0, IT),
     KY_VARIANT_LISTED_LARGE(false, -1, false, true, 0, IT),
     KY_VARIANT_LISTED_LARGE(true, -1, false, true, 0, IT),
+    // the stratified sampler (KY_SAMPLER_STRATIFIED): the top both_mis rows of the Cornell lamp, the sphere lights and one environment light, then the twins of every
+    // row the debug sampler has -- masked, listed and plain; run-time instantiations serve every other launch that asks for its own kernel
+    KY_VARIANT_STRAT(KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_CORNELL | KY_FEAT_SMALL_TABLES | KY_FEAT_BOXES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT, false, 0, false),
+    KY_VARIANT_STRAT(KY_DIRECT_BOTH_MIS, true, false, KY_FEAT_VEACH | KY_FEAT_FLAT_PHONG | KY_FEAT_X_PLANKS, IT, false, 0, false),
+    KY_VARIANT_STRAT(KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV | KY_FEAT_SMALL_TABLES | KY_FEAT_BOXES | KY_FEAT_AXIS_ALIGNED | KY_FEAT_FLAT_PHONG, IT, false, 0, false),
+    KY_VARIANT_STRAT(-1, false, false, 0, IT, false, -1, false),
+    KY_VARIANT_STRAT(-1, false, true, 0, IT, false, -1, false),
+    KY_VARIANT_STRAT(-1, false, true, 0, IT, true, -1, false),
+    KY_VARIANT_STRAT(-1, false, false, 0, IT, false, 0, true),
+    KY_VARIANT_STRAT(-1, false, true, 0, IT, false, 0, true),
+    KY_VARIANT_STRAT(-1, false, true, 0, IT, true, 0, true),
+    KY_VARIANT_STRAT(-1, false, false, 0, IT, false, 0, false),
+    KY_VARIANT_STRAT(-1, false, true, 0, IT, false, 0, false),
+    KY_VARIANT_STRAT(-1, false, true, 0, IT, true, 0, false),
     // everything else: strategy and integrator at run time; the debug sampler; scenes with general shapes
     KY_VARIANT(false, -1, false, false, 0, IT),
     KY_VARIANT(true, -1, false, false, 0, IT),
@@ -405,11 +423,11 @@ constexpr int KY_N_VARIANTS = (int)(sizeof g_variants / sizeof g_variants[0]);
 static_assert(KY_N_VARIANTS <= KY_MAX_VARIANTS, "DeviceCtx::variant_blocks");
 
 static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0, bool listed = false) {
-    const bool dbg = p->sampler == KY_SAMPLER_DEBUG;
+    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
     const bool general = packed->general != 0;
     const bool large = packed->n_surfaces > KY_LDS_SURFACES || packed->n_materials > KY_LDS_MATERIALS;
     for (const Variant& v : g_variants) {
-        if (v.dbg != dbg || v.large != large || v.listed != listed) continue;
+        if (v.dbg != dbg || (v.fn_s != nullptr) != strat || v.large != large || v.listed != listed) continue;
         if (v.drop != drop && !(v.drop < 0 && drop != 0)) continue;
         if (general && !v.general) continue;
         if (v.strategy >= 0) {
@@ -475,7 +493,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         }
         sh.n_items = (unsigned)sh.n_blocks * (unsigned)pass->chunk_count;
     }
-    const RenderConst rc = make_rc(p);
+    const RenderConstS rc = make_rc(p);   // (the stratified kernels read all of it, the others its RenderConst)
+    const bool strat = p->sampler == KY_SAMPLER_STRATIFIED;
     StreamState* st;
     rcode = get_stream_state(c, stream, &st);
     if (rcode != KY_OK) return rcode;
@@ -516,7 +535,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     const bool single = p->direct_sample == KY_DIRECT_SINGLE_BOTH_MIS;
     // (... nor a masked form: a lighting launch runs on the lane engine too)
     // (... nor passes: a frame's pass runs on the lane engine)
-    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single && drop == 0 && !pass) {
+    // (... nor the stratified sampler)
+    if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single && drop == 0 && !pass && !strat) {
         const int variant = p->sampler == KY_SAMPLER_DEBUG ? 2 : (p->direct_sample == KY_DIRECT_BOTH_MIS ? 0 : 1);
         const int per_cu = c->q_blocks_per_cu[variant] > 0 ? c->q_blocks_per_cu[variant] : 1;
         unsigned grid = (unsigned)(c->cus * per_cu);
@@ -570,11 +590,11 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
             if (!((feat & (KY_FEAT_SINGLE_AREA | KY_FEAT_SINGLE_DELTA)) || env_pair)) feat &= ~KY_FEAT_BOXES;
             const bool want_queue = (p->direct_sample == KY_DIRECT_BOTH_MIS || single || p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) &&
                                     p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && sh.n_pix < (1 << 26) && !general && shadow_queue_wanted(scene);
-            const bool same = v->dbg == dbg && v->strategy == p->direct_sample && v->queue == want_queue && v->general == general && v->feat == feat &&
+            const bool same = v->dbg == dbg && (v->fn_s != nullptr) == strat && v->strategy == p->direct_sample && v->queue == want_queue && v->general == general && v->feat == feat &&
                               v->integrator == p->integrator && v->large == large_scene && v->drop == drop && v->listed == listed;
             if (!same) {
                 char expr[192];   // (an unmasked launch's key is what it was: the drop bits are named only where there are some)
-                int en = snprintf(expr, sizeof expr, "%s, %d, %s, %s, %d, %d, %s", dbg ? "true" : "false", p->direct_sample, want_queue ? "true" : "false",
+                int en = snprintf(expr, sizeof expr, "%s, %d, %s, %s, %d, %d, %s", strat ? "2" : (dbg ? "true" : "false"), p->direct_sample, want_queue ? "true" : "false",
                                   general ? "true" : "false", feat, p->integrator, large_scene ? "true" : "false");
                 if (drop != 0) snprintf(expr + en, sizeof expr - en, ", %d", drop);
                 else if (listed) snprintf(expr + en, sizeof expr - en, ", 0, true");   // (the form is part of the key: a listed pass never runs an unlisted kernel)
@@ -606,7 +626,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
                     jk = &k;
                     queue = want_queue;
                     char desc[224];   // the table's way of naming a kernel, then the template arguments it was compiled with
-                    snprintf(desc, sizeof desc, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d> = render_kernel<", dbg ? "debug sampler, " : "", p->direct_sample,
+                    snprintf(desc, sizeof desc, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d> = render_kernel<", dbg ? "debug sampler, " : (strat ? "stratified sampler, " : ""), p->direct_sample,
                              want_queue ? ", deferred shadow rays" : "", general ? ", general shapes" : "", large_scene ? ", scene-sized LDS block" : "", feat, p->integrator);
                     c->last_jit = std::string(desc) + expr + ">";
                     if (pass) { pass->jit_expr = expr; pass->jit_desc = c->last_jit; }
@@ -615,7 +635,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         }
         if (!jk && (c->variant_blocks[vi] == 0 || c->variant_lds[vi] != lds_bytes)) {   // resident workgroups per CU: depends on the scene's LDS block
             int per_cu = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn, 256, lds_bytes));
+            if (v->fn_s) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_s, 256, lds_bytes));
+            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn, 256, lds_bytes));
             c->variant_blocks[vi] = per_cu > 0 ? per_cu : 1;
             c->variant_lds[vi] = lds_bytes;
         }
@@ -649,6 +670,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         }
         if (drop != 0 && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no masked form]";
         if (pass && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine renders no passes]";
+        if (strat && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no stratified sampler]";
         if (pass) { pass->kernel = jk ? -3 : vi; pass->queue = queue; }
         if (!jk && v->drop < 0 && st->counter_drop != drop) {   // the drop bits of a run-time-dispatched masked kernel: word 2 of the counter block, written when they change
             HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(st->d_counter + 2), drop, 1, stream));
@@ -656,16 +678,19 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         }
         HIP_TRY(hipEventRecord(st->ev0, stream));
         float4* queue_mem = queue ? st->d_shadow_queue : (float4*)nullptr;
+        const RenderConst rc_plain = rc;   // the launch constants as every kernel but the stratified ones declares them
         if (jk) {
             const DScene* a_scene = sc->d;
-            RenderConst a_rc = rc;
+            RenderConstS a_rcs = rc;
+            RenderConst a_rc = rc_plain;
             ShardConst a_sh = sh;
             unsigned* a_counter = st->d_counter;
-            void* args[] = {&a_scene, &a_rc, &a_sh, &a_counter, &accum, &flags, &queue_mem};
+            void* args[] = {&a_scene, strat ? (void*)&a_rcs : (void*)&a_rc, &a_sh, &a_counter, &accum, &flags, &queue_mem};   // (the instantiation's first template argument says which)
             HIP_TRY(hipModuleLaunchKernel(jk->fn, grid, 1, 1, 256, 1, 1, (unsigned)lds_bytes, stream, args, nullptr));
             c->last_variant = -3;
         } else {
-            hipLaunchKernelGGL(v->fn, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc, sh, st->d_counter, accum, flags, queue_mem);
+            if (v->fn_s) hipLaunchKernelGGL(v->fn_s, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc, sh, st->d_counter, accum, flags, queue_mem);
+            else hipLaunchKernelGGL(v->fn, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc_plain, sh, st->d_counter, accum, flags, queue_mem);
             c->last_variant = vi;
         }
     }
@@ -735,11 +760,11 @@ const char* kyhip_last_kernel(int device) {
     if (!c) return name.c_str();
     std::lock_guard<std::mutex> lock(c->m);
     if (c->last_variant == -2) name = "render_kernel_q (queue engine)";
-    else if (c->last_variant == -3) name = c->last_jit + " (run-time instantiation; template arguments: DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE[, DROP[, LISTED]])";
+    else if (c->last_variant == -3) name = c->last_jit + " (run-time instantiation; template arguments: DEBUG_SAMPLER (or 2: the stratified sampler), STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE[, DROP[, LISTED]])";
     else if (c->last_variant >= 0) {
         const Variant& v = g_variants[c->last_variant];
         char buf[160];
-        snprintf(buf, sizeof buf, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d>", v.dbg ? "debug sampler, " : "", v.strategy, v.queue ? ", deferred shadow rays" : "",
+        snprintf(buf, sizeof buf, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d>", v.dbg ? "debug sampler, " : (v.fn_s ? "stratified sampler, " : ""), v.strategy, v.queue ? ", deferred shadow rays" : "",
                  v.general ? ", general shapes" : "", v.large ? ", scene-sized LDS block" : "", v.feat, v.integrator);
         name = buf;
         if (v.listed) name.insert(name.size() - 1, ", listed blocks");

@@ -62,7 +62,8 @@ bool valid_params(const ky_render_params* p) {
     case KY_DIRECT_SINGLE_BOTH_MIS: break;   // sample_single_light (3813-3832), which is fixed to both_mis: flag 1 alone or on another strategy stays refused
     default: return false;   // empty std::function -> bad_function_call (ky.cpp:3860)
     }
-    if (p->sampler != KY_SAMPLER_DEBUG && p->sampler != KY_SAMPLER_RANDOM) return false;
+    if (p->sampler != KY_SAMPLER_DEBUG && p->sampler != KY_SAMPLER_RANDOM && p->sampler != KY_SAMPLER_STRATIFIED) return false;
+    if (p->sampler == KY_SAMPLER_STRATIFIED && p->samples_per_pixel > (1 << 24)) return false;   // a stratum's index plus its jitter is an fp32 sum: this sampler's own reason for the limit the packed fields set above
     return true;
 }
 
@@ -204,12 +205,34 @@ double denoise_pixel_width(const ky_camera& camera, int width) {
     return 2.0 * std::sqrt(x * x + y * y + z * z) / (double)width;
 }
 
-RenderConst make_rc(const ky_render_params* p) {
-    RenderConst rc{};
+RenderConstS make_rc(const ky_render_params* p) {
+    RenderConstS rc{};
     rc.integrator = p->integrator; rc.max_path_depth = p->max_path_depth; rc.strategy = p->direct_sample; rc.seed = p->seed;
     rc.width = p->width; rc.height = p->height; rc.spp = p->samples_per_pixel;
     rc.inv_spp = (float)(1. / p->samples_per_pixel);  // ky.cpp:3717
+    // the stratified sampler's camera grid, m = floor(sqrt(N)) columns by n = ceil(N / m) rows in integers, and the reciprocals its strata are scaled by: the device
+    // multiplies by exactly these (its own division is not correctly rounded, and the restatement has to reproduce every bit)
+    const int N = p->samples_per_pixel;
+    int m = (int)std::sqrt((double)N);
+    while ((long long)m * m > N) --m;
+    while ((long long)(m + 1) * (m + 1) <= N) ++m;
+    rc.strat.m = m; rc.strat.n = (N + m - 1) / m;
+    rc.strat.inv_N = 1.0f / (float)N; rc.strat.inv_m = 1.0f / (float)rc.strat.m; rc.strat.inv_n = 1.0f / (float)rc.strat.n;
     return rc;
+}
+
+int strat_samples_check(const ky_render_params* p, int s0, int n) {
+    if (p->sampler != KY_SAMPLER_STRATIFIED || (s0 >= 0 && (long long)s0 + n <= p->samples_per_pixel)) return KY_OK;
+    return fail(KY_ERR_INVALID_VALUE, "samples %d .. %lld: the stratified sampler has strata for samples_per_pixel = %d samples", s0, (long long)s0 + n - 1, p->samples_per_pixel);
+}
+int kat_sampler_kind_check(int kind, int spp, const uint32_t* keys2, int n, int k, const uint32_t* out) {
+    if (kind != KY_SAMPLER_DEBUG && kind != KY_SAMPLER_RANDOM && kind != KY_SAMPLER_STRATIFIED) return fail(KY_ERR_INVALID_VALUE, "sampler kind %d", kind);
+    if (!keys2 || !out || n <= 0 || k < 1 || k > 256 || (size_t)n * (size_t)k > ((size_t)1 << 28)) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (kind != KY_SAMPLER_STRATIFIED) return KY_OK;
+    if (spp < 1 || spp > (1 << 24)) return fail(KY_ERR_INVALID_VALUE, "the stratified sampler takes 1 .. 2^24 samples per pixel, not %d", spp);
+    for (int i = 0; i < n; ++i)
+        if (keys2[2 * (size_t)i + 1] >= (uint32_t)spp) return fail(KY_ERR_INVALID_VALUE, "key %d: sample %u of %d samples per pixel", i, keys2[2 * (size_t)i + 1], spp);
+    return KY_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -78,7 +78,7 @@ struct ItemSlot {  // one fetched work item, decoded once (wave-uniform) and rea
 // (flags + sh.n_pix).  One wave-uniform (scalar) load per fetched item; false -- every instantiation that does not name it -- decodes the block from the id alone.
 // resident wavefronts per SIMD an instantiation is compiled for (its register budget): measured per family, see the KY_WAVES_PER_EU_* notes above
 // (a masked instantiation starts from its twin's: it is the twin with a term less; a listed one is compiled for its twin's: it is the twin with one load more per item)
-template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE, int DROP = 0, bool LISTED = false>
+template <int SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE, int DROP = 0, bool LISTED = false>
 constexpr int ky_waves_per_eu() {
     return STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS ? KY_WAVES_PER_EU_SINGLE :
            STRATEGY >= 0 ? (QUEUE ? (FEAT ? KY_WAVES_PER_EU_QUEUE_FEAT : KY_WAVES_PER_EU_QUEUE)
@@ -89,12 +89,14 @@ constexpr int ky_waves_per_eu() {
 
 // The kernel's body is a device function so that two kinds of __global__ entry can wrap it: the template render_kernel below (the library's table
 // of instantiations) and the extern "C" kernel of a run-time instantiation (ky_jit.cpp).
-template <bool DEBUG_SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false>
-KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
+// SAMPLER: KY_SMP_RANDOM, KY_SMP_DEBUG (what the `bool DEBUG_SAMPLER` of the kernel templates below converts to) or KY_SMP_STRATIFIED, whose launch constants are the
+// wider RenderConstS.
+template <int SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false>
+KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderConstFor<SAMPLER>::type rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
                                unsigned* __restrict__ flags, float4* __restrict__ queue_mem) {
     static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
                   "the deferred shadow rays belong to the iterative integrator's strategies with a light-sampling half");
-    static_assert(FEAT == 0 || (STRATEGY >= 0 && !GENERAL && !DEBUG_SAMPLER), "scene facts are instantiated for kernels with a fixed strategy only");
+    static_assert(FEAT == 0 || (STRATEGY >= 0 && !GENERAL && SAMPLER != KY_SMP_DEBUG), "scene facts are instantiated for kernels with a fixed strategy only");
     static_assert(STRATEGY >= 0 || INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION, "the run-time-dispatched kernel reads the integrator from rc");
     static_assert(DROP >= -1 && DROP <= 3, "two drop bits, or -1: read per launch");
     const SceneRef S{S_, GENERAL, FEAT, LARGE};
@@ -136,8 +138,9 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
     bool open = false;        // the chunk has samples left to start (s < s_end)
     bool has_item = false, done = false, alive = false;
     int waited = 0;           // turns the longest-waiting lane has waited for a refill (wave-uniform)
-    PathState ps;
+    PathStateFor<SAMPLER> ps;
     ps.Lo = mk3(0, 0, 0);
+    sampler_bind(ps.smp, rc);
 
     KY_CLK(-1);
     for (;;) {
@@ -272,7 +275,7 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
                 const int xy = c_xy[tid];
                 const unsigned se = c_se[tid];
                 const uint32_t key = QUEUE ? sampler_pixel_key(rc.seed, (uint32_t)((xy >> 16) * rc.width + (xy & 0xffff))) : c_key[tid];
-                path_begin<DEBUG_SAMPLER, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7));
+                path_begin<SAMPLER, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7));
                 c_se[tid] = se + 127;             // next sample + 1, samples left - 1
                 open = (se & 127) > 1;
                 alive = true;
@@ -280,7 +283,7 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
             const bool tracing = alive && !have_vertex;
             if (!__any(tracing)) break;
             if (tracing) {
-                const bool ended = !path_intersect<DEBUG_SAMPLER, DROP>(ps, v, S, Lds, rc, drop_rt);
+                const bool ended = !path_intersect<SAMPLER, DROP>(ps, v, S, Lds, rc, drop_rt);
                 if (!ended) have_vertex = true;
                 if (ended) {
                     alive = false;
@@ -304,7 +307,7 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, RenderConst rc, Sh
         if (QUEUE) tag = ((unsigned)c_pix[tid] << 6) | (unsigned)lane;
         // ---- (3) shade the vertex: direct lighting, continuation ----
         {
-            const bool cont = path_shade<DEBUG_SAMPLER, DROP>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, QUEUE ? &sq : nullptr, tag,
+            const bool cont = path_shade<SAMPLER, DROP>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, QUEUE ? &sq : nullptr, tag,
                                                               STRATEGY >= 0 && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_RECURSION, true, drop_rt);  // wave-uniform call
             if (have_vertex && !cont) {
                 alive = false;
@@ -339,4 +342,13 @@ __global__ __launch_bounds__(256, (ky_waves_per_eu<DEBUG_SAMPLER, STRATEGY, QUEU
     const DScene* __restrict__ S_, RenderConst rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
     float4* __restrict__ queue_mem) {
     render_kernel_body<DEBUG_SAMPLER, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, 0, true>(S_, rc, sh, counter, accum, flags, queue_mem);
+}
+
+// The stratified sampler's instantiations (KY_SAMPLER_STRATIFIED), plain, masked and listed: a kernel template of their own as well, whose launch constants carry
+// the strata (RenderConstS).
+template <int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false>
+__global__ __launch_bounds__(256, (ky_waves_per_eu<KY_SMP_STRATIFIED, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, DROP, LISTED>())) void render_kernel_stratified(
+    const DScene* __restrict__ S_, RenderConstS rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
+    float4* __restrict__ queue_mem) {
+    render_kernel_body<KY_SMP_STRATIFIED, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, DROP, LISTED>(S_, rc, sh, counter, accum, flags, queue_mem);
 }

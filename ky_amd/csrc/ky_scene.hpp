@@ -253,5 +253,18 @@ struct RenderConst {  // wave-uniform launch constants
     int width, height, spp;
     float inv_spp;
 };
+// What KY_SAMPLER_STRATIFIED's strata need beside rc.spp = N: the camera sample's m x n grid and the three reciprocals as the host rounds
+// them, 1.0f / (float)k.  Only the stratified kernels take the wider block: every other kernel's arguments stay where they were.
+struct StratConst {
+    int m, n;
+    float inv_N, inv_m, inv_n;
+};
+struct RenderConstS : RenderConst {
+    StratConst strat;
+};
+// the sampler kinds as template arguments: what a `bool DEBUG_SAMPLER` converts to, so that an instantiation expression written for the two older kinds means what it meant
+enum : int { KY_SMP_RANDOM = 0, KY_SMP_DEBUG = 1, KY_SMP_STRATIFIED = 2 };
+template <int SAMPLER> struct RenderConstFor { typedef RenderConst type; };
+template <> struct RenderConstFor<KY_SMP_STRATIFIED> { typedef RenderConstS type; };
 
 }  // namespace kyd

@@ -664,6 +664,14 @@ public:
     std::unique_ptr<sampler_t> clone() override { auto s = std::make_unique<random_sampler_t>(samples_per_pixel_); s->set_seed(seed_); return s; }
     ky_sampler_kind kind() const override { return KY_SAMPLER_RANDOM; }
 };
+// stratified_sampler_t, which ky.cpp:977-985 declares and leaves a stub: the camera sample multi-jittered, the sample's next draws Latin-hypercube strata over the
+// pixel's samples_per_pixel samples (at most 2^24), every later draw the random sampler's -- DESIGN.md "Random numbers"
+class stratified_sampler_t : public sampler_t {
+public:
+    using sampler_t::sampler_t;
+    std::unique_ptr<sampler_t> clone() override { auto s = std::make_unique<stratified_sampler_t>(samples_per_pixel_); s->set_seed(seed_); return s; }
+    ky_sampler_kind kind() const override { return KY_SAMPLER_STRATIFIED; }
+};
 
 // ---------------------------------------------------------------------------------------------
 // integrators (ky.cpp:3608-3654, 3679-3729, 4621-4639)

@@ -54,6 +54,16 @@ const ky_scene* kyhost_scene_flatten(void* scene) {
     return flat;
 }
 
+// the sampler_t of a ky_sampler_kind (every other value: the random sampler, as before the stratified one existed)
+static std::unique_ptr<ky::sampler_t> make_sampler(int kind, int spp, unsigned seed) {
+    std::unique_ptr<ky::sampler_t> sampler;
+    if (kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
+    else if (kind == KY_SAMPLER_STRATIFIED) sampler = std::make_unique<ky::stratified_sampler_t>(spp);
+    else sampler = std::make_unique<ky::random_sampler_t>(spp);
+    sampler->set_seed(seed);
+    return sampler;
+}
+
 // create_integrator(enum, depth, direct_sample)->render(&scene, sampler, &film) on a film_t (grid_rows = 0)
 // or on cell `cell` of a film_grid_t(grid_rows, grid_cols, width, height): the call shape of every
 // reference driver (ky.cpp:4697, 4732, 4770, 4810, 4851, 4899).  film points at the WHOLE film
@@ -79,10 +89,7 @@ static int render_impl(void* scene, int integrator_enum, int depth, int direct_s
         // multi-device path (shards, gather, one add) on a single GPU
         if (device == -1) integrator->set_devices(ky::integrator_t::all_devices());
         else if (device < -1) integrator->set_devices(std::vector<int>((size_t)-device, 0));
-        std::unique_ptr<ky::sampler_t> sampler;
-        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
-        else sampler = std::make_unique<ky::random_sampler_t>(spp);
-        sampler->set_seed(seed);
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
         std::unique_ptr<ky::film_t> f;
         if (grid_rows > 0) {
             auto grid = std::make_unique<ky::film_grid_t>(grid_rows, grid_cols, width, height);
@@ -123,10 +130,7 @@ int kyhost_render_passes(void* scene, int integrator_enum, int depth, int direct
         else
             integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
         if (!integrator) { status = -2; return; }
-        std::unique_ptr<ky::sampler_t> sampler;
-        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
-        else sampler = std::make_unique<ky::random_sampler_t>(spp);
-        sampler->set_seed(seed);
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
         ky::film_t f(width, height);
         const size_t n = (size_t)f.get_pixel_num() * 3;
         std::memcpy(f.data(), film, n * sizeof(float));
@@ -152,10 +156,7 @@ int kyhost_render_sliced(void* scene, int integrator_enum, int depth, int direct
         else
             integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, devices[0]);
         if (!integrator) { status = -2; return; }
-        std::unique_ptr<ky::sampler_t> sampler;
-        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
-        else sampler = std::make_unique<ky::random_sampler_t>(spp);
-        sampler->set_seed(seed);
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
         ky::film_t f(width, height);
         const size_t n = (size_t)f.get_pixel_num() * 3;
         std::memcpy(f.data(), film, n * sizeof(float));
@@ -178,10 +179,7 @@ int kyhost_render_until(void* scene, int integrator_enum, int depth, int direct_
         else
             integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
         if (!integrator) { status = -2; return; }
-        std::unique_ptr<ky::sampler_t> sampler;
-        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
-        else sampler = std::make_unique<ky::random_sampler_t>(spp);
-        sampler->set_seed(seed);
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
         ky::film_t f(width, height);
         const size_t n = (size_t)f.get_pixel_num() * 3;
         std::memcpy(f.data(), film, n * sizeof(float));
@@ -212,10 +210,7 @@ int kyhost_render_denoised_chains(void* scene, int integrator_enum, int depth, i
         else
             integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
         if (!integrator) { status = -2; return; }
-        std::unique_ptr<ky::sampler_t> sampler;
-        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
-        else sampler = std::make_unique<ky::random_sampler_t>(spp);
-        sampler->set_seed(seed);
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
         ky::film_t f(width, height);
         const size_t n = (size_t)f.get_pixel_num() * 3;
         std::memcpy(f.data(), film, n * sizeof(float));
@@ -240,10 +235,7 @@ int kyhost_render_adaptive(void* scene, int integrator_enum, int depth, int dire
         else
             integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
         if (!integrator) { status = -2; return; }
-        std::unique_ptr<ky::sampler_t> sampler;
-        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
-        else sampler = std::make_unique<ky::random_sampler_t>(spp);
-        sampler->set_seed(seed);
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
         ky::film_t f(width, height);
         const size_t n = (size_t)f.get_pixel_num() * 3;
         std::memcpy(f.data(), film, n * sizeof(float));
@@ -270,10 +262,7 @@ int kyhost_debug_area(void* scene, int integrator_enum, int depth, int direct_sa
         else
             integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
         if (!integrator) { status = -2; return; }
-        std::unique_ptr<ky::sampler_t> sampler;
-        if (sampler_kind == KY_SAMPLER_DEBUG) sampler = std::make_unique<ky::debug_sampler_t>(spp);
-        else sampler = std::make_unique<ky::random_sampler_t>(spp);
-        sampler->set_seed(seed);
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
         ky::film_t f(width, height);
         const size_t n = (size_t)f.get_pixel_num() * 3;
         std::memcpy(f.data(), film, n * sizeof(float));
