@@ -100,8 +100,11 @@ $(SANDIR)/stress_tsan: tools/sanitize/stress.cpp $(HOSTSAN_SRC) $(HOST_HDRS) $(R
 $(SANDIR)/stress_asan: tools/sanitize/stress.cpp $(HOSTSAN_SRC) $(HOST_HDRS) $(RTC_INC)
 	@mkdir -p $(SANDIR)
 	$(CXX) $(SANFLAGS) -fsanitize=address,undefined -o $@ tools/sanitize/stress.cpp $(HOSTSAN_SRC) -lpthread
+$(SANDIR)/light_pick_asan: tools/sanitize/light_pick.cpp $(HOSTSAN_SRC) $(HOST_HDRS) $(RTC_INC)
+	@mkdir -p $(SANDIR)
+	$(CXX) $(SANFLAGS) -fsanitize=address,undefined -o $@ tools/sanitize/light_pick.cpp $(HOSTSAN_SRC) -lpthread
 sanitize-build: $(SANDIR)/libkyhip_host_asan.so $(SANDIR)/libkyhip_host_tsan.so $(SANDIR)/libkyhost_asan.so $(SANDIR)/libkyoracle_asan.so $(SANDIR)/stress_tsan $(SANDIR)/stress_asan
-sanitize: sanitize-build
+sanitize: sanitize-build $(SANDIR)/light_pick_asan
 	bash tools/sanitize/run.sh
 
 clean:

@@ -34,6 +34,9 @@
  *   ky_drivers stratified [scene] [spp] [cell]  one scene (cornell, the default, or veach) under the random and the stratified sampler side by side at equal spp
  *                                (16; cells of 256, the Veach scene 256 x 144), path_tracing_iteration d5 both_mis into a film_grid_t(1, 2, ...); prints both
  *                                kernel times and writes stratified.bmp: random | stratified
+ *   ky_drivers pick [spp] [w] [h]    the Veach frame under sample_single_light with its light picked uniformly (49), by power (113) and by position at the vertex
+ *                                (177) side by side at equal spp (16; cells of 512 x 288), path_tracing_iteration d5 into a film_grid_t(1, 3, ...); writes pick.bmp:
+ *                                uniform | power | spatial
  * An optional last argument multiplies every spp (the reference's values are tiny because its CPU path is slow).
  * KY_DEVICES=all (or a count n: devices 0 .. n-1) makes every integrator spread its tiles over that many GPUs of the node
  * (integrator_t::set_devices); the images do not depend on it.
@@ -166,6 +169,20 @@ static void render_mis_scene() {
         film.next_subfilm();
     }
     film.store_image("veach_mis");
+}
+
+// sample_single_light's three picks on the scene that tells them apart: one lamp holds 95 % of the power and lights a pixel about as much as each of the row's
+static void render_pick(int spp, int width, int height) {
+    film_grid_t film(1, 3, width, height);
+    std::unique_ptr<sampler_t> sampler = std::make_unique<random_sampler_t>(spp);
+    scene_t scene = scene_t::create_mis_scene(film.get_resolution());
+    const direct_sample_enum_t single = direct_sample_enum_t::sample_single_light | direct_sample_enum_t::both_mis;
+    for (auto sample_enum : {single, single | direct_sample_enum_t::pick_power, single | direct_sample_enum_t::pick_spatial}) {
+        std::unique_ptr<integrator_t> integrator = std::make_unique<path_tracing_iteration_t>(5, sample_enum);
+        use_devices(*integrator); integrator->render(&scene, sampler.get(), &film);
+        film.next_subfilm();
+    }
+    film.store_image("pick");
 }
 
 // BASELINE.json configs[3]: the batch of render_multiple_scene (4819-4876) at production size -- one film_grid_t, one
@@ -453,6 +470,10 @@ int main(int argc, char* argv[]) {
             const int spp = argc > 3 ? std::atoi(argv[3]) : 16, cell = argc > 4 ? std::atoi(argv[4]) : 256;
             if (spp < 1 || spp > (1 << 24) || cell < 16) { std::fprintf(stderr, "stratified: 1 .. 2^24 samples per pixel, cells of 16 or more\n"); return 2; }
             render_stratified(veach, spp, cell);
+        } else if (!std::strcmp(which, "pick")) {
+            const int spp = argc > 2 ? std::atoi(argv[2]) : 16, w = argc > 3 ? std::atoi(argv[3]) : 512, h = argc > 4 ? std::atoi(argv[4]) : 288;
+            if (spp < 1 || w < 16 || h < 16) { std::fprintf(stderr, "pick: at least one sample per pixel, cells of 16 x 16 or more\n"); return 2; }
+            render_pick(spp, w, h);
         } else if (!std::strcmp(which, "lighting_cells")) {
             render_lighting_cells(argc > 2 ? std::atoi(argv[2]) : 10, argc > 3 ? std::atoi(argv[3]) : 256);
         } else if (!std::strcmp(which, "batch")) {

@@ -146,7 +146,24 @@ typedef enum ky_direct_sample {
     KY_DIRECT_BSDF_MIS  = 16,
     KY_DIRECT_LIGHT_MIS = 32,
     KY_DIRECT_BOTH_MIS  = 48,
-    KY_DIRECT_SINGLE_BOTH_MIS = 49   /* KY_DIRECT_SINGLE_LIGHT | KY_DIRECT_BOTH_MIS */
+    KY_DIRECT_SINGLE_BOTH_MIS = 49,  /* KY_DIRECT_SINGLE_LIGHT | KY_DIRECT_BOTH_MIS */
+    /* How sample_single_light picks its light: two flags on free bits of the reference's enum, which marks the spot `// TODO: power based, spatial based` (3805,
+       3821).  Accepted only on KY_DIRECT_SINGLE_BOTH_MIS, one at a time; every other value that carries one is refused with KY_ERR_INVALID_VALUE.
+       The picked light's estimate is divided by its probability p[li] = a / n + (1 - a) w[li] / W, a = 1/4 the share of the uniform pick (so the estimate stays
+       unbiased whatever the weights, and p = 1 / n when they are all zero), n the light count, W the sum of the weights w:
+         power    w = the light's power: pi e A for an area light (e the luminance of its colour, A the sampled shape's area), 4 pi e for a point light,
+                  pi R^2 e for a directional one and pi^2 R^2 e for the environment (R = world_radius);
+         spatial  w = the sum over the light's emitter proxies of clamp(e Om m, 0, 1e30) at the vertex (NaN counts as 0): Om the solid angle of the proxy seen
+                  from the vertex -- a sphere's cone, a planar shape's A cos_l / max(d^2, r^2) on its emitting side, 1 / d^2 for a point light, 1 for a directional
+                  one --, m the material's response towards it: a cosine that a lamp straddling the horizon keeps, c = clamp(N.om + sin_t, 1/64, 1) (the floor keeps the weights of a vertex with every lamp below its horizon off the rounding of that sum), times, for a
+                  plastic material, Kd_lum / pi + Ks_lum min(Nn t^exponent, 1 / Om) with the Phong lobe evaluated at the point of the lamp nearest the mirror
+                  direction.  The environment's w = e (Kd_lum + Ks_lum).  DESIGN.md section 3, "One light per vertex", has the definition operation by operation.
+       A proxy is the shape a light samples, and one more per carrier surface of another shape (kyhip_scene_light_pick lists them).
+       A scene with one light renders the film of 49 bit for bit under either rule. */
+    KY_DIRECT_PICK_POWER      = 64,
+    KY_DIRECT_PICK_SPATIAL    = 128,
+    KY_DIRECT_SINGLE_POWER    = 113, /* KY_DIRECT_SINGLE_BOTH_MIS | KY_DIRECT_PICK_POWER */
+    KY_DIRECT_SINGLE_SPATIAL  = 177  /* KY_DIRECT_SINGLE_BOTH_MIS | KY_DIRECT_PICK_SPATIAL */
 } ky_direct_sample;
 
 /* sampler_t subclasses that can be instantiated (ky.cpp:922, 949). */
@@ -260,7 +277,9 @@ int64_t kyhip_shard_float_count(const ky_render_params* params);
    0 .. KYHIP_MAX_LIGHTS.  Every term at or beyond +-T, T = min(2e9, 2^31 / N) as a float rounded down, sets the pixel's +inf / -inf flag instead of
    being added, so the word never wraps; *limit (may be NULL) receives T.  Returns N, or KY_ERR_LIMIT when T would be below 1.  kyhip_render and its
    device variants refuse with KY_ERR_LIMIT, before any device work, a launch whose count with deferred shadow rays (the largest of its counts) is
-   such.  Pure host arithmetic. */
+   such.  A single-light strategy (49, 113, 177) counts both_mis's terms -- it adds fewer --, but one of its terms is up to n / a times one light's estimate
+   (n the light count, a = 1/4 the uniform share of the power and spatial picks; n times under 49): the counts are the same for all three, the terms that reach
+   T are not.  Pure host arithmetic. */
 int64_t kyhip_film_term_limit(const ky_render_params* params, int n_lights, int engine, int deferred, float* limit);
 
 /*
@@ -655,6 +674,12 @@ int kyhip_scene_screen_bound(const ky_scene* scene, const ky_render_params* para
    64 no mirror or glass, 128 at most 16 surfaces and 8 materials, 256 every lamp is its own one carrier, 512 boxes, 1024 every planar surface is a rectangle in an axis
    plane, 2048 every plastic surface is a rectangle, 4096 every tilted rectangle is a plank about the x axis) -- which decide the render-kernel instantiation a launch takes (kyhip_last_kernel names it).  0 with kyhip_set_specialisation(0); negative: a ky_status. */
 int kyhip_scene_facts(const ky_scene* scene);
+/* Host only: what sample_single_light's power and spatial picks (KY_DIRECT_SINGLE_POWER / _SPATIAL) know of the scene's lights.  power_p16 (may be NULL): the 16
+   probabilities of the power rule, defensive share included, zeros behind the light count.  proxies (may be NULL with max_proxies 0): up to max_proxies emitter
+   proxies of 11 floats {light (the caller's index), kind (0 sphere, 1 planar, 2 point, 3 direction, 4 environment), c[3], r, n[3], A, e}; a light's proxies are
+   contiguous: the shape it samples, then its carrier surfaces of other shapes; the table holds at most 32, carrier proxies dropped from the last light backwards.
+   `rule`: 1 or 2 (both tables are the same for either; anything else is refused).  Returns the proxy count, or a negative ky_status. */
+int kyhip_scene_light_pick(const ky_scene* scene, int rule, float* power_p16, float* proxies, int max_proxies);
 
 /* integrator_t::Li per camera sample (3714-3717): for pixel (x, y) and samples [s0, s0+n) writes the
    unclamped radiance Li (3 floats per sample) -- the quantity `dL` is built from. */
@@ -671,6 +696,12 @@ int kyhip_kat_nee(int device, const ky_scene* scene, int direct_sample, int ligh
  * min((int)(pick_u * light_count), light_count - 1) in fp32.  out6: the picked light's two both_mis halves (BSDF half, light half), each already
  * divided by the pick probability 1 / light_count, and -- like kyhip_kat_nee's -- not weighted by the 0.5 of 4083.  A scene without lights is refused. */
 int kyhip_kat_single_light(int device, const ky_scene* scene, const float* in16, int n, float* out6);
+/* sample_single_light's pick under `rule` (0 uniform, 1 power, 2 spatial) at kyhip_kat_single_light's rows, through the device function the render kernels
+ * call.  out18: n x {the picked light's index, its probability, p[0 .. 15] -- every light's probability at the row's vertex, from the same weight function one
+ * light at a time; zeros behind the light count}.  Vertices on mirror or glass surfaces take no estimate in a render; their rows are computed all the same. */
+int kyhip_kat_light_pick(int device, const ky_scene* scene, int rule, const float* in16, int n, float* out18);
+/* kyhip_kat_single_light with the light picked under `rule` and the two halves divided by that light's probability; rule 0 is kyhip_kat_single_light. */
+int kyhip_kat_single_light_rule(int device, const ky_scene* scene, int rule, const float* in16, int n, float* out6);
 
 /* The same sample of path_tracing_iteration_t vertex by vertex (the reference's LOG_VAST at ky.cpp:4578 prints the same facts):
    one row of 26 floats per vertex that reaches the continuation sample (4586):

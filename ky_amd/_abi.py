@@ -19,6 +19,11 @@ INTEGRATOR_DIRECT_LIGHTING, INTEGRATOR_PATH_TRACING_ITERATION = 6, 11
 INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION, INTEGRATOR_PATH_TRACING_RECURSION, INTEGRATOR_PATH_TRACING_RECURSION_DEFERED = 8, 9, 10
 DIRECT_IDLE, DIRECT_BSDF, DIRECT_LIGHT, DIRECT_BSDF_MIS, DIRECT_LIGHT_MIS, DIRECT_BOTH_MIS = 0, 4, 8, 16, 32, 48
 DIRECT_SINGLE_LIGHT, DIRECT_SINGLE_BOTH_MIS = 1, 49   # sample_single_light: accepted as 1 | 48 only
+DIRECT_PICK_POWER, DIRECT_PICK_SPATIAL = 64, 128       # ... its light picked by power / by position at the vertex: accepted on 49 only, one at a time
+DIRECT_SINGLE_POWER, DIRECT_SINGLE_SPATIAL = 113, 177
+PICK_UNIFORM, PICK_POWER, PICK_SPATIAL = 0, 1, 2       # the pick rule as the function-level entries take it
+PICK_UNIFORM_SHARE = 0.25                              # KY_PICK_UNIFORM_SHARE: every light keeps p >= share / light count
+MAX_PROXIES = 32                                       # the emitter-proxy table (kyhip_scene_light_pick)
 SAMPLER_DEBUG, SAMPLER_RANDOM, SAMPLER_STRATIFIED = 0, 1, 2
 STRATIFIED_DIMS = 16   # KYHIP_STRATIFIED_DIMS
 LIGHTING_EMIT, LIGHTING_DIRECT, LIGHTING_INDIRECT, LIGHTING_ALL = 1, 2, 4, 7   # ky_lighting (lighting_enum_t, ky.cpp:3591-3603)
@@ -196,6 +201,9 @@ KYHIP_SYMBOLS = {
     "kyhip_scene_boxes": (C.c_int, [SP, C.c_void_p, C.c_int]),
     "kyhip_scene_screen_bound": (C.c_int, [SP, PP, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "kyhip_scene_facts": (C.c_int, [SP]),
+    "kyhip_scene_light_pick": (C.c_int, [SP, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "kyhip_kat_light_pick": (C.c_int, [C.c_int, SP, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "kyhip_kat_single_light_rule": (C.c_int, [C.c_int, SP, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_li": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhip_kat_sampler": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhip_kat_sampler_kind": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -703,6 +703,36 @@ def kat_single_light(scene, in16, device=0):
     return out
 
 
+def scene_light_pick(scene, rule=A.PICK_SPATIAL):
+    """kyhip_scene_light_pick (host only): (the power rule's 16 probabilities, the emitter proxies [n, 11] = {light, kind, c[3], r, n[3], A, e}) that
+    sample_single_light's power and spatial picks (direct_sample 113 / 177) read."""
+    lib = A.load_kyhip()
+    power = np.zeros(A.MAX_LIGHTS, np.float32)
+    proxies = np.zeros((A.MAX_PROXIES, 11), np.float32)
+    rc = lib.kyhip_scene_light_pick(_scene_ptr(scene), int(rule), _fptr(power), _fptr(proxies), A.MAX_PROXIES)
+    if rc < 0:
+        _check(rc)
+    return power, proxies[:rc].copy()
+
+
+def kat_light_pick(scene, rule, in16, device=0):
+    """kyhip_kat_light_pick: kat_single_light's rows -> [n, 18] = {the picked light, its probability, every light's probability at the row's vertex}."""
+    lib = A.load_kyhip()
+    in16 = np.ascontiguousarray(in16, np.float32)
+    out = np.zeros((in16.shape[0], 18), np.float32)
+    _check(lib.kyhip_kat_light_pick(device, _scene_ptr(scene), int(rule), _fptr(in16), in16.shape[0], _fptr(out)))
+    return out
+
+
+def kat_single_light_rule(scene, rule, in16, device=0):
+    """kyhip_kat_single_light_rule: kat_single_light with the light picked under `rule` (0 uniform, 1 power, 2 spatial), the halves over its probability."""
+    lib = A.load_kyhip()
+    in16 = np.ascontiguousarray(in16, np.float32)
+    out = np.zeros((in16.shape[0], 6), np.float32)
+    _check(lib.kyhip_kat_single_light_rule(device, _scene_ptr(scene), int(rule), _fptr(in16), in16.shape[0], _fptr(out)))
+    return out
+
+
 def kat_li_trace(scene, params, x, y, s, max_rows=64, device=0):
     """kyhip_kat_li_trace: (rows [n, 26], li [3]) of one camera sample of path_tracing_iteration_t."""
     lib = A.load_kyhip()

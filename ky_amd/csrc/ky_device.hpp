@@ -2153,20 +2153,145 @@ KY_DEV void sample_all_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f
 // A kernel whose facts name ONE light (KY_FEAT_SINGLE_LIGHT) picks index 0 with probability 1 -- it still draws the pick -- and runs that light's
 // wave-uniform estimators as they are.
 // `decisions`: bit li = the BSDF half of the PICKED light was non-black, bit 16 + li its light half; no other light's bits are set.
+//
+// The pick by power or by position (`rule`: KY_PICK_POWER / KY_PICK_SPATIAL, strategies 113 / 177; DESIGN.md section 3 has the definition): light li with probability
+// p[li] = a / n + (1 - a) w[li] / W, a = KY_PICK_UNIFORM_SHARE, and the estimate times 1 / p[li] in place of n.  p depends on the vertex and the scene only.
+// What the spatial rule keeps of a vertex: made once, read by every proxy
+struct PickVertex {
+    f3 P, N, R;       // position, the normal as the integrator sees it, the mirror direction 2 (N.wo) N - wo
+    float kd, ks;     // a plastic material's lobe colours as luminances, each times its lobe's probability; matte: kd = 1, ks = 0
+    bool plastic;
+    const DMat* m;
+};
+KY_DEV float pick_luminance(const float* c) { return 0.212671f * c[0] + 0.715160f * c[1] + 0.072169f * c[2]; }   // color_t::luminance, 249
+KY_DEV PickVertex pick_vertex(const Vertex& v, f3 wo) {
+    PickVertex pv;
+    const DMat* M = v.bsdf.m;
+    pv.P = v.position; pv.N = v.normal;
+    pv.R = (2.f * dot(v.normal, wo)) * v.normal - wo;
+    pv.plastic = M->kind == KY_MATERIAL_PLASTIC;
+    pv.kd = pv.plastic ? (1.f - M->p_specular) * pick_luminance(M->c0) : 1.f;
+    pv.ks = pv.plastic ? M->p_specular * pick_luminance(M->cs) : 0.f;
+    pv.m = M;
+    return pv;
+}
+// one proxy's share of its light's weight: clamp(e Om m, 0, 1e30), NaN counting as 0.  `q` is read with a wave-uniform index: its fields are scalar operands and the
+// branches on its kind scalar branches; only the plastic material's lobe is a divergent region.
+KY_DEV float pick_proxy_weight(const DProxy& q, const PickVertex& pv) {
+    float w;
+    if (q.kind == KY_PROXY_ENVIRONMENT) {
+        w = q.e * (pv.kd + pv.ks);
+    } else {
+        f3 om = ld3(q.c);
+        float sin_t = 0.f, cos_t = 1.f, Om = 1.f;
+        if (q.kind != KY_PROXY_DIRECTION) {
+            const f3 d = ld3(q.c) - pv.P;
+            const float d2 = fmaxf(length_sq(d), 1e-12f);
+            const float inv_d = rsq(d2);
+            om = d * inv_d;
+            if (q.kind == KY_PROXY_POINT) {
+                Om = inv_d * inv_d;
+            } else {
+                sin_t = fminf(1.f, q.r * inv_d);
+                cos_t = fsqrt(1.f - sin_t * sin_t);
+                if (q.kind == KY_PROXY_SPHERE) Om = ((2.f * K_PI) * (sin_t * sin_t)) * rcp(1.f + cos_t);   // 2 pi (1 - cos_t) without the cancellation: a far lamp's 1 - cos_t is a few ulp of 1
+                else Om = (q.area * fmaxf(0.f, -dot(ld3(q.n), om))) * rcp(fmaxf(d2, q.r * q.r));
+            }
+        }
+        const float c = fminf(fmaxf(dot(pv.N, om) + sin_t, KY_PICK_COS_FLOOR), 1.f);   // the floor: see ky_scene.hpp
+        float m = c;
+        if (pv.plastic) {
+            const float cos_a = dot(pv.R, om);
+            const float sin_a = fsqrt(length_sq(cross(pv.R, om)));   // (not sqrt(1 - cos_a^2): near the mirror direction that loses half the digits, and t^exponent multiplies the error by the exponent)
+            const float t = cos_a >= cos_t ? 1.f : fmaxf(0.f, cos_a * cos_t + sin_a * sin_t);   // the lobe at the point of the lamp nearest the mirror direction
+            float lobe = pv.m->inv_eta * phong_pow_lobe(t, *pv.m);                              // (exponent + 2) / 2 pi x t^exponent
+            if (q.kind <= KY_PROXY_PLANAR) lobe = fminf(lobe, rcp(Om));                         // a lobe narrower than the lamp integrates to at most 1
+            m = c * (pv.kd * K_INV_PI + pv.ks * lobe);
+        }
+        w = (q.e * Om) * m;
+    }
+    return w > 0.f ? fminf(w, 1e30f) : 0.f;
+}
+KY_DEV float pick_light_weight(SceneRef S, const PickVertex& pv, int i) {   // light i's spatial weight: the sum over its proxies (i: wave-uniform)
+    const DLightPick& K = S->pick;
+    float w = 0.f;
+    for (int k = K.first[i]; k < K.first[i + 1]; ++k) w += pick_proxy_weight(K.proxy[k], pv);
+    return w;
+}
+// The pick itself, for the lane's own number u: li and p[li].  One pass over the lights, wave-uniform in its index; the lane keeps O(1) state.
+//  power    the host's 16 probabilities (DLightPick::power_p); the lane inverts their running sum.
+//  spatial  u < a: the uniform branch, index min((int)((u / a) n), n - 1), whose weight is noted as the loop passes it.  Otherwise u' = (u - a) / (1 - a) selects while
+//           the weights are summed: at light i with weight w > 0 and running sums W' before and W = W' + w after it, t = u' W; t < w (or W' = 0: the first light that weighs anything) takes i and leaves
+//           u' = t / w, otherwise u' = (t - w) / W' -- the selection u' < w / W and its two rescalings with one reciprocal; u' stays below 1.
+//           All weights zero: the uniform pick of 3821 on u itself, p = 1 / n.
+template <int RULE>
+KY_DEV void pick_light(SceneRef S, const Vertex& v, f3 wo, float u, int nl, int& li, float& p) {
+    static_assert(RULE == KY_PICK_POWER || RULE == KY_PICK_SPATIAL, "the uniform pick is sample_single_light's own line");
+    const DLightPick& K = S->pick;
+    if (nl == 1) { li = 0; p = 1.f; return; }
+    if constexpr (RULE == KY_PICK_POWER) {
+        float cum = 0.f;
+        bool open = true;
+        li = nl - 1; p = K.power_p[nl - 1];   // (a running sum that ends below u: the last light)
+        for (int i = 0; i < nl - 1; ++i) {
+            const float pi = K.power_p[i];
+            cum += pi;
+            const bool take = open & (u < cum);
+            li = take ? i : li; p = take ? pi : p;
+            open = open & !take;
+        }
+    } else {
+        constexpr float a = KY_PICK_UNIFORM_SHARE;
+        const PickVertex pv = pick_vertex(v, wo);
+        const float fn = (float)nl;
+        const bool uniform = u < a;
+        const int iu = min((int)((u * (1.f / a)) * fn), nl - 1);
+        float up = fminf((u - a) * (1.f / (1.f - a)), K_BELOW_ONE);
+        float Wp = 0.f, w_sel = 0.f, w_uni = 0.f;
+        int sel = 0;
+        for (int i = 0; i < nl; ++i) {
+            const float w = pick_light_weight(S, pv, i);
+            const float W = Wp + w;
+            const float t = up * W;
+            const bool some = w > 0.f;
+            const bool take = some & ((t < w) | !(Wp > 0.f));   // (the first light that weighs anything is taken whatever u' W rounds to: nothing before it could be)
+            const float next = fminf((take ? t : t - w) * rcp(take ? w : Wp), K_BELOW_ONE);
+            up = some ? next : up;
+            sel = take ? i : sel; w_sel = take ? w : w_sel;
+            w_uni = i == iu ? w : w_uni;
+            Wp = W;
+        }
+        const float inv_n = rcp(fn);
+        if (Wp > 0.f) {
+            li = uniform ? iu : sel;
+            p = a * inv_n + (1.f - a) * ((uniform ? w_uni : w_sel) * rcp(Wp));
+        } else {
+            li = min((int)(u * fn), nl - 1);
+            p = inv_n;
+        }
+    }
+}
 template <int SAMPLER>
 KY_DEV void sample_single_light(SceneRef S, const LdsScene& Lds, const Vertex& v, f3 wo, typename SamplerFor<SAMPLER>::type& smp, bool active, f3& Lo, f3 beta,
-                                unsigned* decisions = nullptr, ShadowQueue* sq = nullptr, float weight = 0.f, unsigned tag = 0, RideAlong* ra = nullptr) {
+                                unsigned* decisions = nullptr, ShadowQueue* sq = nullptr, float weight = 0.f, unsigned tag = 0, RideAlong* ra = nullptr,
+                                int rule = KY_PICK_UNIFORM) {
     const int nl = S.single_light() ? 1 : S->n_lights;
     if (nl == 0) return;   // 3816-3818
     int li = 0;
+    float p = 1.f;   // (read under the power and spatial rules only)
     float ub0 = any_f(), ub1 = any_f(), ul0 = any_f(), ul1 = any_f();   // drawn, and read, by the active lanes only
     if (active) {
         const float u = sampler_next<SAMPLER>(smp);
-        li = min((int)(u * (float)nl), nl - 1);   // 3821
+        // `rule` is a constant of every instantiation with a fixed strategy: one arm is left.  The run-time-dispatched kernels branch here (wave-uniform).
+        // (As a template argument -- through path_shade, which would take it too -- the rule compiles 49's two inline-shadow-ray rows to other listings than the
+        // commit before's: measured with tools/asm_same.py.  As an argument that folds, every row of 49 keeps its listing.)
+        if (rule == KY_PICK_POWER) pick_light<KY_PICK_POWER>(S, v, wo, u, nl, li, p);
+        else if (rule == KY_PICK_SPATIAL) pick_light<KY_PICK_SPATIAL>(S, v, wo, u, nl, li, p);
+        else li = min((int)(u * (float)nl), nl - 1);   // 3821
         ul0 = sampler_next<SAMPLER>(smp); ul1 = sampler_next<SAMPLER>(smp);   // random_light, 3824
         ub0 = sampler_next<SAMPLER>(smp); ub1 = sampler_next<SAMPLER>(smp);   // random_bsdf, 3825
     }
-    const float fn = (float)nl;   // 1 / pick probability, 3830
+    const float fn = rule == KY_PICK_UNIFORM ? (float)nl : rcp(p);   // 1 / pick probability, 3830
     const f3 w = beta * (0.5f * fn);
     const float wq = weight * (0.5f * fn);
     f3 Lb = mk3(0, 0, 0), Ll = mk3(0, 0, 0);      // tracing only: the two halves on their own
@@ -2203,7 +2328,7 @@ KY_DEV void light_estimate_draws(SceneRef S, typename SamplerFor<SAMPLER>::type&
     if (!active) return;
     const int nl = S.single_light() ? 1 : S->n_lights;
     int n = 4 * nl;
-    if (strategy == KY_DIRECT_SINGLE_BOTH_MIS) n = nl > 0 ? 5 : 0;
+    if (ky_direct_is_single(strategy)) n = nl > 0 ? 5 : 0;   // (whichever rule picks: the pick is one number)
     else if (strategy == KY_DIRECT_BSDF)
         for (int li = 0; li < nl; ++li) n += S.is_delta(S->light[li].kind) ? 0 : 2;
     for (int i = 0; i < n; ++i) (void)sampler_next<SAMPLER>(smp);
@@ -2379,8 +2504,9 @@ KY_DEV bool path_shade(PathStateFor<SAMPLER>& ps, Vertex& v, SceneRef S, const L
         es_f = es.f;
         es_k = fabsf(dot(es.wi, v.normal)) / es.pdf;
     }
-    if (!simple && rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS) {   // sample_single_light: one light per vertex
-        sample_single_light<SAMPLER>(S, Lds, v, wo, ps.smp, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag, riding ? &ra : nullptr);
+    if (!simple && ky_direct_is_single(rc.strategy)) {   // sample_single_light: one light per vertex
+        sample_single_light<SAMPLER>(S, Lds, v, wo, ps.smp, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag, riding ? &ra : nullptr,
+                                     ky_direct_pick_rule(rc.strategy));
     } else
     if (!simple) {  // simple_path_tracing_recursion_t samples the BSDF only
         sample_all_light<SAMPLER>(S, Lds, v, wo, ps.smp, rc.strategy, nee, ps.Lo, ps.beta, tr ? &decisions : nullptr, sq, rc.inv_spp, tag,

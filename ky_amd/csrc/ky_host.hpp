@@ -100,6 +100,7 @@ void screen_bound(const ky_scene* in, int32_t live[4]);
 // ... and for a launch's tiling: the 8 x 8 blocks of the shard that lie outside it (the work items a render kernel skips per chunk), and all of them
 void screen_bound_counts(const int32_t live[4], const ky_render_params* p, long long* dead, long long* total);
 int pack_scene(const ky_scene* in, DScene* out);
+void pack_light_pick(const ky_scene* in, DLightPick* out);   // sample_single_light's power and spatial picks: the emitter proxies and the power rule's probabilities (a scene pack_scene accepts)
 uint64_t scene_hash(const DScene& s);
 bool scene_input(const ky_scene* in, std::vector<unsigned char>& out, uint64_t& hash);
 

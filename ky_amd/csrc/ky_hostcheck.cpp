@@ -713,6 +713,8 @@ int kyhip_frame_set_guide_bounces(kyhip_frame*, int bounces) {
 int kyhip_frame_guide_bounces(const kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_guide_chains(kyhip_frame*, uint64_t*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
+int kyhip_kat_light_pick(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }   // (kyhip_scene_light_pick is host code: ky_pack.cpp)
+int kyhip_kat_single_light_rule(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_li_trace(int, const ky_scene*, const ky_render_params*, int, int, int, float*, int, float*) { return no_gpu(); }
 int kyhip_smallpt_render(int, const ky_smallpt_sphere* spheres, int n, const ky_smallpt_params* p, double* image) {
     const int rc = smallpt_check(spheres, n, p);

@@ -121,7 +121,7 @@ __global__ void kat_any_pair_kernel(const DScene* __restrict__ S_, const float* 
 template <bool DEBUG_SAMPLER, bool BOXES>
 __global__ void kat_li_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env) {
     const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);   // KAT kernels: always the scene-sized dynamic block
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));   // KAT kernels: always the scene-sized dynamic block
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     PathState ps;
     bool alive = i < n;
@@ -140,7 +140,7 @@ __global__ void kat_li_kernel(const DScene* __restrict__ S_, RenderConst rc, int
 template <bool DEBUG_SAMPLER, bool BOXES>
 __global__ void kat_li_lighting_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env, int drop) {
     const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     PathState ps;
     bool alive = i < n;
@@ -160,7 +160,7 @@ __global__ void kat_li_lighting_kernel(const DScene* __restrict__ S_, RenderCons
 template <bool BOXES>
 __global__ void kat_li_stratified_kernel(const DScene* __restrict__ S_, RenderConstS rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env, int drop) {
     const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     PathStateFor<KY_SMP_STRATIFIED> ps;
     sampler_bind(ps.smp, rc);
@@ -241,7 +241,7 @@ __global__ void kat_single_light_kernel(const DScene* __restrict__ S, const floa
 template <bool DEBUG_SAMPLER, bool BOXES>
 __global__ void kat_li_trace_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s, int max_rows, float* __restrict__ out, int single_env) {
     const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);   // KAT kernels: always the scene-sized dynamic block
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));   // KAT kernels: always the scene-sized dynamic block
     PathState ps;
     bool alive = threadIdx.x == 0;
     VertexTrace tr{out + 4, max_rows, 0};
@@ -260,7 +260,7 @@ __global__ void kat_li_trace_kernel(const DScene* __restrict__ S_, RenderConst r
 template <bool BOXES>
 __global__ void kat_li_trace_stratified_kernel(const DScene* __restrict__ S_, RenderConstS rc, int x, int y, int s, int max_rows, float* __restrict__ out, int single_env) {
     const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
     PathStateFor<KY_SMP_STRATIFIED> ps;
     sampler_bind(ps.smp, rc);
     bool alive = threadIdx.x == 0;
@@ -608,6 +608,99 @@ int kyhip_kat_sampler_kind(int device, int kind, uint32_t seed, int spp, const u
     }
     if (!first.empty() && std::memcmp(first.data(), out, first.size() * sizeof(uint32_t)) != 0) return fail(KY_ERR_DEVICE, "the stratified camera sample differs between sampler_camera and sampler_next");
     return KY_OK;
+}
+
+}  // extern "C"
+
+// sample_single_light's pick by power and by position (behind the other entries, like kyhip_kat_bsdf_continue): kat_single_light_kernel's rows, the light picked by
+// pick_light as the render kernels call it.  `out18` (may be null): {li, p[li], every light's p from the same weight function one light at a time}; `out6` (may be
+// null): the picked light's two both_mis halves over p[li].
+static __device__ Vertex kat_pick_vertex(const DScene* __restrict__ S, const LdsScene& Lds, const float* r) {
+    Vertex v;
+    v.position = ld3(r); v.normal = ld3(r + 3);
+    v.t = 0.f;
+    v.surface = 0;
+    for (int j = 0; j < S->n_surfaces; ++j)
+        if (S->orig[j] == (int)r[9]) v.surface = j;          // the caller's surface index -> the device's sorted index
+    v.bsdf = make_bsdf(Lds.mat[Lds.hit[v.surface].material], r[10]);
+    vertex_prepare(v, ld3(r + 6));
+    return v;
+}
+__global__ void kat_light_pick_kernel(const DScene* __restrict__ S, int rule, const float* __restrict__ in16, int n, float* __restrict__ out18, float* __restrict__ out6) {
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), true);   // KAT kernels: always the scene-sized dynamic block
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = i < n;
+    const float* r = in16 + 16 * (size_t)(active ? i : 0);
+    const Vertex v = kat_pick_vertex(S, Lds, r);
+    const f3 wo = ld3(r + 6);
+    const int nl = S->n_lights;
+    const float u = r[15];
+    int li = min((int)(u * (float)nl), nl - 1);   // 3821
+    float p = rcp((float)nl);
+    if (rule == KY_PICK_POWER) pick_light<KY_PICK_POWER>(S, v, wo, u, nl, li, p);
+    else if (rule == KY_PICK_SPATIAL) pick_light<KY_PICK_SPATIAL>(S, v, wo, u, nl, li, p);
+    if (out18 && active) {
+        float* o = out18 + 18 * (size_t)i;
+        o[0] = (float)li; o[1] = p;
+        for (int k = 0; k < KYHIP_MAX_LIGHTS; ++k) o[2 + k] = 0.f;
+        if (rule == KY_PICK_SPATIAL && nl > 1) {
+            const PickVertex pv = pick_vertex(v, wo);
+            float W = 0.f;
+            for (int k = 0; k < nl; ++k) W += pick_light_weight(S, pv, k);
+            for (int k = 0; k < nl; ++k)
+                o[2 + k] = W > 0.f ? KY_PICK_UNIFORM_SHARE * rcp((float)nl) + (1.f - KY_PICK_UNIFORM_SHARE) * (pick_light_weight(S, pv, k) * rcp(W)) : rcp((float)nl);
+        } else {
+            for (int k = 0; k < nl; ++k) o[2 + k] = nl == 1 ? 1.f : (rule == KY_PICK_POWER ? S->pick.power_p[k] : rcp((float)nl));
+        }
+    }
+    if (out6) {
+        const DLight* Lp = Lds.light + (active ? li : 0);
+        f3 Lb = mk3(0, 0, 0), Ll = mk3(0, 0, 0);
+        const bool nee = active && !bsdf_is_delta(v.bsdf);
+        const float fn = rcp(p);   // 1 / pick probability, 3830
+        const f3 w = mk3(fn, fn, fn);
+        estimate_by_bsdf<true, true>(S, Lds, v, wo, li, r[11], r[12], nee, Lb, w, nullptr, f3{0, 0, 0}, 0.f, 0, nullptr, Lp);   // (wave-uniform call)
+        if (nee) estimate_by_emitter<true, true>(S, Lds, v, wo, li, r[13], r[14], Ll, w, Lp);
+        if (active) {
+            float* o = out6 + 6 * (size_t)i;
+            o[0] = Lb.x; o[1] = Lb.y; o[2] = Lb.z; o[3] = Ll.x; o[4] = Ll.y; o[5] = Ll.z;
+        }
+    }
+}
+
+static int kat_light_pick_check(const ky_scene* scene, int rule, const float* in16, int n, const float* out) {
+    if (!scene || !in16 || !out || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (rule < KY_PICK_UNIFORM || rule > KY_PICK_SPATIAL) return fail(KY_ERR_INVALID_VALUE, "rule %d: 0 picks uniformly, 1 by power, 2 by position", rule);
+    if (scene->light_count <= 0) return fail(KY_ERR_INVALID_VALUE, "sample_single_light picks among the scene's lights: the scene has none");
+    for (int i = 0; i < n; ++i) {
+        const float sf = in16[16 * (size_t)i + 9], u = in16[16 * (size_t)i + 15];
+        if (!(sf >= 0 && sf < scene->surface_count)) return fail(KY_ERR_INVALID_VALUE, "row %d: surface out of range", i);
+        if (!(u >= 0.f && u < 1.f)) return fail(KY_ERR_INVALID_VALUE, "row %d: pick_u outside [0, 1)", i);
+    }
+    return KY_OK;
+}
+
+extern "C" {
+
+int kyhip_kat_light_pick(int device, const ky_scene* scene, int rule, const float* in16, int n, float* out18) {
+    KY_TRY(kat_light_pick_check(scene, rule, in16, n, out18));
+    return kat_run(device, in16, (size_t)n * 16 * 4, out18, (size_t)n * 18 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
+        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
+        if (r != KY_OK) return r;
+        hipLaunchKernelGGL(kat_light_pick_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, rule, d_in, n, d_out, (float*)nullptr);
+        return (int)KY_OK;
+    });
+}
+
+int kyhip_kat_single_light_rule(int device, const ky_scene* scene, int rule, const float* in16, int n, float* out6) {
+    KY_TRY(kat_light_pick_check(scene, rule, in16, n, out6));
+    if (rule == KY_PICK_UNIFORM) return kyhip_kat_single_light(device, scene, in16, n, out6);
+    return kat_run(device, in16, (size_t)n * 16 * 4, out6, (size_t)n * 6 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
+        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
+        if (r != KY_OK) return r;
+        hipLaunchKernelGGL(kat_light_pick_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, rule, d_in, n, (float*)nullptr, d_out);
+        return (int)KY_OK;
+    });
 }
 
 }  // extern "C"

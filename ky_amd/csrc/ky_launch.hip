@@ -351,6 +351,15 @@ static const Variant g_variants[] = {
     KY_VARIANT(false, KY_DIRECT_SINGLE_BOTH_MIS, false, false, KY_FEAT_VEACH, IT),             // ... inline shadow rays
     KY_VARIANT(false, KY_DIRECT_SINGLE_BOTH_MIS, true, false, 0, IT),                          // any lights: one nearest-hit scan and "does the hit carry my light"
     KY_VARIANT(false, KY_DIRECT_SINGLE_BOTH_MIS, false, false, 0, IT),
+    // ... its light picked by power (113) and by position at the vertex (177): the four rows of 49 for each rule (pick_light, ky_device.hpp)
+    KY_VARIANT(false, KY_DIRECT_SINGLE_POWER, true, false, KY_FEAT_VEACH, IT),
+    KY_VARIANT(false, KY_DIRECT_SINGLE_POWER, false, false, KY_FEAT_VEACH, IT),
+    KY_VARIANT(false, KY_DIRECT_SINGLE_POWER, true, false, 0, IT),
+    KY_VARIANT(false, KY_DIRECT_SINGLE_POWER, false, false, 0, IT),
+    KY_VARIANT(false, KY_DIRECT_SINGLE_SPATIAL, true, false, KY_FEAT_VEACH, IT),
+    KY_VARIANT(false, KY_DIRECT_SINGLE_SPATIAL, false, false, KY_FEAT_VEACH, IT),
+    KY_VARIANT(false, KY_DIRECT_SINGLE_SPATIAL, true, false, 0, IT),
+    KY_VARIANT(false, KY_DIRECT_SINGLE_SPATIAL, false, false, 0, IT),
     // direct_lighting_t and the three recursive integrators with both_mis (render_multiple_integrator 4740-4777)
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_CORNELL, KY_INTEGRATOR_PATH_TRACING_RECURSION),
     KY_VARIANT(false, KY_DIRECT_BOTH_MIS, false, false, KY_FEAT_SINGLE_ENV, KY_INTEGRATOR_PATH_TRACING_RECURSION),
@@ -531,8 +540,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     st->ws_clean = false;   // until this frame's resolve_kernel is enqueued (a pass: until its counter reset is)
 
     // the queue engine implements path_tracing_iteration_t; every other integrator runs on the lane engine
-    // (... and the queue engine has no sample_single_light: a strategy-49 launch runs on the lane engine, and kyhip_last_kernel says so)
-    const bool single = p->direct_sample == KY_DIRECT_SINGLE_BOTH_MIS;
+    // (... and the queue engine has no sample_single_light: a launch of a single-light strategy runs on the lane engine, and kyhip_last_kernel says so)
+    const bool single = ky_direct_is_single(p->direct_sample);
     // (... nor a masked form: a lighting launch runs on the lane engine too)
     // (... nor passes: a frame's pass runs on the lane engine)
     // (... nor the stratified sampler)
@@ -663,9 +672,10 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         if (single) {   // which form of sample_single_light this launch's kernel runs
             const int kfeat = jk ? ((p->sampler == KY_SAMPLER_DEBUG || sc->h->general != 0) ? 0 : sc->h->feat) : v->feat;   // the facts the kernel was compiled with
             const bool one = (kfeat & KY_FEAT_SINGLE_LIGHT) != 0;
-            c->last_note += one ? " [sample_single_light: one light, its wave-uniform estimators]"
-                                : ((kfeat & KY_FEAT_SPHERE_LIGHTS) && !jk ? " [sample_single_light: per-lane lights, each lane tests its own lamp's carriers]"
-                                                                          : " [sample_single_light: per-lane lights]");
+            const int rule = ky_direct_pick_rule(p->direct_sample);   // ... and the rule that picks the light, named when it is not the uniform one
+            const std::string head = rule == KY_PICK_POWER ? " [sample_single_light, power pick: " : (rule == KY_PICK_SPATIAL ? " [sample_single_light, spatial pick: " : " [sample_single_light: ");
+            c->last_note += head + (one ? "one light, its wave-uniform estimators]"
+                                        : ((kfeat & KY_FEAT_SPHERE_LIGHTS) && !jk ? "per-lane lights, each lane tests its own lamp's carriers]" : "per-lane lights]"));
             if (current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no sample_single_light]";
         }
         if (drop != 0 && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no masked form]";

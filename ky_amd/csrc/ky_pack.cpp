@@ -60,6 +60,7 @@ bool valid_params(const ky_render_params* p) {
     case KY_DIRECT_IDLE: case KY_DIRECT_BSDF: case KY_DIRECT_LIGHT: case KY_DIRECT_BSDF_MIS:
     case KY_DIRECT_LIGHT_MIS: case KY_DIRECT_BOTH_MIS: break;
     case KY_DIRECT_SINGLE_BOTH_MIS: break;   // sample_single_light (3813-3832), which is fixed to both_mis: flag 1 alone or on another strategy stays refused
+    case KY_DIRECT_SINGLE_POWER: case KY_DIRECT_SINGLE_SPATIAL: break;   // ... its light picked by power or by position: the pick flags alone, together or on another strategy stay refused
     default: return false;   // empty std::function -> bad_function_call (ky.cpp:3860)
     }
     if (p->sampler != KY_SAMPLER_DEBUG && p->sampler != KY_SAMPLER_RANDOM && p->sampler != KY_SAMPLER_STRATIFIED) return false;
@@ -108,11 +109,12 @@ ShardConst make_shard(const ky_render_params* p) {
 long long film_term_count(const ky_render_params* p, int n_lights, bool queue_engine, bool deferred) {
     const long long spp = p->samples_per_pixel;
     const bool iteration = p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION;
-    if (queue_engine && iteration && p->direct_sample != KY_DIRECT_SINGLE_BOTH_MIS) return spp;   // (strategy 49 runs on the lane engine whichever engine is chosen)
+    const bool single = ky_direct_is_single(p->direct_sample);
+    if (queue_engine && iteration && !single) return spp;   // (the single-light strategies run on the lane engine whichever engine is chosen)
     long long n = chunk_count(chunk_plan(p->samples_per_pixel));
     // (sample_single_light pushes for ONE light per vertex -- its estimate times the light count, ky.cpp:3830 -- so both_mis's count over all lights bounds it; terms
-    // beyond the limit that count leaves saturate like any other)
-    const bool both = p->direct_sample == KY_DIRECT_BOTH_MIS || p->direct_sample == KY_DIRECT_SINGLE_BOTH_MIS;
+    // beyond the limit that count leaves saturate like any other; under the power and spatial picks a term is up to n / a times one estimate, the count is the same)
+    const bool both = p->direct_sample == KY_DIRECT_BOTH_MIS || single;
     const int per_light = both ? 2 : (p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) ? 1 : 0;
     if (deferred && iteration) n += spp * p->max_path_depth * (n_lights > 0 ? n_lights : 0) * per_light;
     return n;
@@ -985,7 +987,102 @@ int pack_scene(const ky_scene* in, DScene* out) {
             if (in->lights[i].kind == KY_LIGHT_AREA) { any_area = true; own = own && out->light[i].pdf_from_carrier != 0; }
         if (carriers && any_area && own) out->feat |= KY_FEAT_OWN_CARRIER;
     }
+    pack_light_pick(in, &out->pick);
     return KY_OK;
+}
+
+// What sample_single_light's power and spatial picks read (DLightPick; DESIGN.md section 3, "One light per vertex"): the emitter proxies and the power rule's
+// probabilities.  The caller's scene has passed pack_scene's checks.  Everything is computed in double from the caller's floats and rounded once.
+static double pick_luminance(const float* c) {   // color_t::luminance (249); a colour that is not positive, or NaN, weighs nothing
+    const double e = (double)0.212671f * c[0] + (double)0.715160f * c[1] + (double)0.072169f * c[2];
+    return e > 0.0 ? std::min(e, 1e30) : 0.0;
+}
+static DProxy shape_proxy(const ky_shape& sh, int light, double e) {
+    DProxy q{};
+    q.light = light; q.e = (float)e;
+    if (sh.kind == KY_SHAPE_SPHERE || sh.kind == KY_SHAPE_DISK) {
+        cp3(q.c, sh.p[0]);
+        q.r = sh.radius;
+    } else {
+        // the points the shape samples: a triangle's three corners; a rectangle's p1 + (p0 - p1) u + (p2 - p1) v (1310), whose fourth corner is p0 + p2 - p1
+        double corner[4][3], c[3] = {0, 0, 0};
+        const int np = sh.kind == KY_SHAPE_TRIANGLE ? 3 : 4;
+        for (int k = 0; k < 3; ++k) {
+            corner[0][k] = sh.p[0][k]; corner[1][k] = sh.p[1][k]; corner[2][k] = sh.p[2][k];
+            corner[3][k] = (double)sh.p[0][k] + sh.p[2][k] - sh.p[1][k];
+            for (int j = 0; j < np; ++j) c[k] += corner[j][k];
+            c[k] /= np;
+            q.c[k] = (float)c[k];
+        }
+        double r2 = 0;
+        for (int j = 0; j < np; ++j) {
+            double d2 = 0;
+            for (int k = 0; k < 3; ++k) d2 += (corner[j][k] - c[k]) * (corner[j][k] - c[k]);
+            r2 = std::max(r2, d2);
+        }
+        q.r = (float)std::sqrt(r2);
+    }
+    if (sh.kind == KY_SHAPE_SPHERE) {
+        q.kind = KY_PROXY_SPHERE;
+    } else {
+        q.kind = KY_PROXY_PLANAR;
+        cp3(q.n, sh.normal);
+        q.area = host_shape_area(sh);
+    }
+    return q;
+}
+void pack_light_pick(const ky_scene* in, DLightPick* out) {
+    std::memset(out, 0, sizeof *out);
+    const int nl = in->light_count;
+    if (nl <= 0) return;
+    const double pi = 3.14159265358979323846;
+    // the carrier surfaces whose shape is not the sampled one, in the caller's surface order, at most KY_MAX_CARRIERS per light
+    std::vector<std::vector<int>> carriers(nl);
+    int total = nl;
+    for (int i = 0; i < nl; ++i) {
+        if (in->lights[i].kind != KY_LIGHT_AREA) continue;
+        for (int j = 0; j < in->surface_count && (int)carriers[i].size() < KY_MAX_CARRIERS; ++j)
+            if (in->surfaces[j].area_light == i && in->surfaces[j].shape != in->lights[i].shape) carriers[i].push_back(in->surfaces[j].shape);
+        total += (int)carriers[i].size();
+    }
+    for (int i = nl - 1; i >= 0 && total > KY_MAX_PROXIES; --i) {   // the table is full: carrier proxies go, from the last light backwards (the defensive share covers them)
+        const int drop = std::min((int)carriers[i].size(), total - KY_MAX_PROXIES);
+        carriers[i].resize(carriers[i].size() - drop);
+        total -= drop;
+    }
+    double w[KYHIP_MAX_LIGHTS], W = 0;
+    int n = 0;
+    for (int i = 0; i < nl; ++i) {
+        const ky_light& l = in->lights[i];
+        const double e = pick_luminance(l.color), R = l.world_radius;
+        out->first[i] = n;
+        DProxy q{};
+        q.light = i; q.e = (float)e;
+        if (l.kind == KY_LIGHT_AREA) {
+            q = shape_proxy(in->shapes[l.shape], i, e);
+            w[i] = pi * e * (double)host_shape_area(in->shapes[l.shape]);
+        } else if (l.kind == KY_LIGHT_POINT) {
+            q.kind = KY_PROXY_POINT;
+            cp3(q.c, l.position);
+            w[i] = 4 * pi * e;
+        } else if (l.kind == KY_LIGHT_DIRECTION) {
+            q.kind = KY_PROXY_DIRECTION;
+            for (int k = 0; k < 3; ++k) q.c[k] = -l.direction[k];   // towards the light, as sample_Li returns wi (2891)
+            w[i] = pi * R * R * e;
+        } else {
+            q.kind = KY_PROXY_ENVIRONMENT;
+            w[i] = pi * pi * R * R * e;
+        }
+        out->proxy[n++] = q;
+        for (int s : carriers[i]) out->proxy[n++] = shape_proxy(in->shapes[s], i, e);
+        w[i] = w[i] > 0.0 ? std::min(w[i], 1e30) : 0.0;   // (a NaN weighs nothing)
+        W += w[i];
+    }
+    out->first[nl] = n;
+    for (int i = nl + 1; i <= KYHIP_MAX_LIGHTS; ++i) out->first[i] = n;
+    out->n_proxies = n;
+    const double a = (double)KY_PICK_UNIFORM_SHARE;
+    for (int i = 0; i < nl; ++i) out->power_p[i] = (float)(W > 0.0 ? a / nl + (1.0 - a) * (w[i] / W) : 1.0 / nl);
 }
 
 // Deferred shadow rays (render_kernel<.., QUEUE>): which scenes get them.  They pay where most light samples die BEFORE the occlusion traversal and the few
@@ -1280,6 +1377,24 @@ int kyhip_scene_facts(const ky_scene* scene) {
     std::vector<DScene> packed(1);
     const int rc = pack_scene(scene, &packed[0]);
     return rc != KY_OK ? rc : packed[0].feat;
+}
+
+// host only: the tables of sample_single_light's power and spatial picks as pack_scene leaves them to the device (pack_light_pick)
+int kyhip_scene_light_pick(const ky_scene* scene, int rule, float* power_p16, float* proxies, int max_proxies) {
+    if (!scene || max_proxies < 0 || (max_proxies > 0 && !proxies)) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    if (rule != KY_PICK_POWER && rule != KY_PICK_SPATIAL) return fail(KY_ERR_INVALID_VALUE, "rule %d: 1 picks by power, 2 by position", rule);
+    std::vector<DScene> packed(1);   // pack_scene validates the scene
+    const int rc = pack_scene(scene, &packed[0]);
+    if (rc != KY_OK) return rc;
+    const DLightPick& K = packed[0].pick;
+    if (power_p16) std::memcpy(power_p16, K.power_p, sizeof K.power_p);
+    for (int i = 0; i < K.n_proxies && i < max_proxies; ++i) {
+        const DProxy& q = K.proxy[i];
+        float* o = proxies + 11 * (size_t)i;
+        o[0] = (float)q.light; o[1] = (float)q.kind;
+        cp3(o + 2, q.c); o[5] = q.r; cp3(o + 6, q.n); o[9] = q.area; o[10] = q.e;
+    }
+    return K.n_proxies;
 }
 
 // host only: the boxes the nearest-hit traversal tests whole (find_boxes): box_face[i] = 8 box + face (face = 2 axis + side) for a surface that is a box's face, -1 otherwise

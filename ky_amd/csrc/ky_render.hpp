@@ -80,7 +80,7 @@ struct ItemSlot {  // one fetched work item, decoded once (wave-uniform) and rea
 // (a masked instantiation starts from its twin's: it is the twin with a term less; a listed one is compiled for its twin's: it is the twin with one load more per item)
 template <int SAMPLER, int STRATEGY, bool QUEUE, bool GENERAL, int FEAT, int INTEGRATOR, bool LARGE, int DROP = 0, bool LISTED = false>
 constexpr int ky_waves_per_eu() {
-    return STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS ? KY_WAVES_PER_EU_SINGLE :
+    return ky_direct_is_single(STRATEGY) ? KY_WAVES_PER_EU_SINGLE :
            STRATEGY >= 0 ? (QUEUE ? (FEAT ? KY_WAVES_PER_EU_QUEUE_FEAT : KY_WAVES_PER_EU_QUEUE)
                                   : ((FEAT == 0 && STRATEGY == KY_DIRECT_BOTH_MIS) ? ((GENERAL || INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_RECURSION) ? KY_WAVES_PER_EU_NO_FACTS_GENERAL : KY_WAVES_PER_EU_NO_FACTS)
                                      : ((FEAT != 0 && STRATEGY == KY_DIRECT_BOTH_MIS && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION) ? ((FEAT & KY_FEAT_SINGLE_ENV) ? KY_WAVES_PER_EU_ENV : KY_WAVES_PER_EU_HOT) : KY_WAVES_PER_EU)))
@@ -94,7 +94,7 @@ constexpr int ky_waves_per_eu() {
 template <int SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false>
 KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderConstFor<SAMPLER>::type rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
                                unsigned* __restrict__ flags, float4* __restrict__ queue_mem) {
-    static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
+    static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || ky_direct_is_single(STRATEGY) || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
                   "the deferred shadow rays belong to the iterative integrator's strategies with a light-sampling half");
     static_assert(FEAT == 0 || (STRATEGY >= 0 && !GENERAL && SAMPLER != KY_SMP_DEBUG), "scene facts are instantiated for kernels with a fixed strategy only");
     static_assert(STRATEGY >= 0 || INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION, "the run-time-dispatched kernel reads the integrator from rc");
@@ -112,13 +112,13 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderCon
     LdsScene lds_tables = stage_scene<LARGE, (FEAT & KY_FEAT_SMALL_TABLES) != 0>(S);
     if (STRATEGY >= 0) { rc.strategy = STRATEGY; rc.integrator = INTEGRATOR; }  // compile-time constants from here on
     // sample_single_light reads its lights per lane: the kernels that may run it for several lights stage the light records too (3.75 KB of LDS)
-    if constexpr ((STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY < 0) && (FEAT & KY_FEAT_SINGLE_LIGHT) == 0)
-        lds_tables = stage_lights(S, lds_tables, rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS);
+    if constexpr ((ky_direct_is_single(STRATEGY) || STRATEGY < 0) && (FEAT & KY_FEAT_SINGLE_LIGHT) == 0)
+        lds_tables = stage_lights(S, lds_tables, ky_direct_is_single(rc.strategy));
     const LdsScene Lds = lds_tables;
     int nee_weight = (rc.strategy == KY_DIRECT_IDLE || rc.integrator < KY_INTEGRATOR_DIRECT_LIGHTING ||
                             rc.integrator == KY_INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION) ? 0 : S->n_lights;
-    if constexpr (STRATEGY == KY_DIRECT_SINGLE_BOTH_MIS || STRATEGY < 0)   // one light's estimate per vertex, however many lights the scene has
-        if (rc.strategy == KY_DIRECT_SINGLE_BOTH_MIS) nee_weight = min(nee_weight, 1);
+    if constexpr (ky_direct_is_single(STRATEGY) || STRATEGY < 0)   // one light's estimate per vertex, however many lights the scene has
+        if (ky_direct_is_single(rc.strategy)) nee_weight = min(nee_weight, 1);
 
     const int lane = threadIdx.x & 63;
     ItemSlot* my_ring = ring[threadIdx.x >> 6];

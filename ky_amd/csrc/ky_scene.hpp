@@ -106,6 +106,47 @@ struct DLight {  // light_t + the shape an area light samples; wave-uniform inde
     DSurf isect;          // traversal record of the sampled shape (pdf_direction re-intersects it, 1057-1061)
 };
 constexpr int KY_MAX_CARRIERS = 4;
+
+// sample_single_light's pick ("One light per vertex"): the two facts about a direct_sample value that the code asks for -- is it one of the
+// single-light strategies (49, 113, 177), and which rule picks its light: 0 uniformly (3821), 1 by power (KY_DIRECT_PICK_POWER), 2 by position at the vertex
+// (KY_DIRECT_PICK_SPATIAL).  A compile-time constant wherever the strategy is one.
+enum : int { KY_PICK_UNIFORM = 0, KY_PICK_POWER = 1, KY_PICK_SPATIAL = 2 };
+KY_HD constexpr bool ky_direct_is_single(int strategy) {
+    return strategy == KY_DIRECT_SINGLE_BOTH_MIS || strategy == KY_DIRECT_SINGLE_POWER || strategy == KY_DIRECT_SINGLE_SPATIAL;
+}
+KY_HD constexpr int ky_direct_pick_rule(int strategy) { return (strategy >> 6) & 3; }
+// The defensive share `a`: p[i] = a / n + (1 - a) w[i] / W, so every light keeps p >= a / n and no term grows beyond 1 / a times what the uniform pick adds
+#ifndef KY_PICK_UNIFORM_SHARE
+#define KY_PICK_UNIFORM_SHARE 0.25f
+#endif
+// The least the spatial rule's cosine c = clamp(N.om + sin_t, floor, 1) comes to.  With a floor of 0 a vertex that has every lamp at or below its horizon -- a
+// point of a lamp's own surface sees that lamp so -- would weigh its lights by the rounding of a sum that cancels, and p would jump between "all on one light"
+// and the uniform pick with the last bit; with the floor the weights stay positive wherever a proxy subtends a solid angle, and an error of an ulp in the
+// cosine is 2^-17 of a weight at the most.  What it costs: a lamp below the horizon keeps 1 / 64 of the weight it would have overhead.
+#ifndef KY_PICK_COS_FLOOR
+#define KY_PICK_COS_FLOOR 0.015625f
+#endif
+// An emitter proxy: what the spatial rule knows of one emitting shape (host: pack_light_pick).  One per light for the shape it samples (the environment: a record
+// without geometry), one more per carrier surface whose shape is another (create_mis_scene's lights 1 and 2).  48 B, read with a wave-uniform index (scalar loads).
+enum : int { KY_PROXY_SPHERE = 0, KY_PROXY_PLANAR = 1, KY_PROXY_POINT = 2, KY_PROXY_DIRECTION = 3, KY_PROXY_ENVIRONMENT = 4 };
+struct DProxy {
+    float c[3];      // sphere: centre; planar: centroid; point: position; direction: the unit vector towards the light
+    float r;         // sphere: radius; planar: bounding radius about the centroid; otherwise 0
+    float n[3];      // planar: the stored normal (the emitting side, 2957-2960)
+    float area;      // planar: the shape's area
+    float e;         // luminance of the light's colour (color_t::luminance, 249)
+    int32_t kind;    // KY_PROXY_*
+    int32_t light;   // the light it belongs to
+    int32_t pad_p;
+};
+constexpr int KY_MAX_PROXIES = 32;
+struct DLightPick {
+    float power_p[KYHIP_MAX_LIGHTS];            // the power rule's probabilities, defensive share included
+    int32_t first[KYHIP_MAX_LIGHTS + 1];        // light i's proxies are proxy[first[i] .. first[i + 1])
+    int32_t n_proxies, pad_k[2];
+    DProxy proxy[KY_MAX_PROXIES];
+};
+static_assert(sizeof(DProxy) == 48 && sizeof(DLightPick) % 16 == 0 && __builtin_offsetof(DLightPick, proxy) % 16 == 0, "DLightPick");
 constexpr int KY_LIVE_MAX = 32768;   // beyond every pixel a launch can have (valid_params: width, height <= 32767)
 static_assert(sizeof(DLight) % 16 == 0 && __builtin_offsetof(DLight, p1) % 16 == 0 && __builtin_offsetof(DLight, n) % 16 == 0, "DLight is read in 16-byte groups (shape_sample_position)");
 
@@ -192,6 +233,7 @@ struct DScene {
     int32_t orig[KYHIP_MAX_SURFACES];
     DMat mat[KYHIP_MAX_MATERIALS];
     DLight light[KYHIP_MAX_LIGHTS];
+    DLightPick pick;                    // sample_single_light's power and spatial picks; behind everything older kernels read
 };
 static_assert(__builtin_offsetof(DScene, light) % 16 == 0 && __builtin_offsetof(DScene, trav) % 16 == 0 && __builtin_offsetof(DScene, boxtrav) % 16 == 0 &&
               __builtin_offsetof(DBoxTrav, box) % 16 == 0, "16-byte scalar loads of light, table and box records");

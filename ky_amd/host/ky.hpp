@@ -678,9 +678,11 @@ public:
 // ---------------------------------------------------------------------------------------------
 enum class direct_sample_enum_t {
     idle, sample_single_light = 1, sample_all_light = 2, bsdf = 4, light = 8, bsdf_mis = 16, light_mis = 32,
-    both_mis = bsdf_mis | light_mis, default_stragtgy = sample_all_light | both_mis
+    both_mis = bsdf_mis | light_mis, default_stragtgy = sample_all_light | both_mis,
+    pick_power = 64, pick_spatial = 128   // how sample_single_light picks its light (the reference's `// TODO: power based, spatial based`, 3805 / 3821): free bits of its enum
 };
-// sample_single_light | both_mis (= KY_DIRECT_SINGLE_BOTH_MIS) is the one combination with sample_single_light the library renders (ky.cpp:3813-3832)
+// sample_single_light | both_mis (= KY_DIRECT_SINGLE_BOTH_MIS) is the one combination with sample_single_light the library renders (ky.cpp:3813-3832), alone (a uniform
+// pick) or with one of pick_power (= KY_DIRECT_SINGLE_POWER) and pick_spatial (= KY_DIRECT_SINGLE_SPATIAL); create_integrator takes all three
 constexpr direct_sample_enum_t operator|(direct_sample_enum_t a, direct_sample_enum_t b) { return (direct_sample_enum_t)((int)a | (int)b); }
 enum class integrator_enum_t {
     position, normal, basecolor, delta_bsdf, delta_light, direct_lighting_point, direct_lighting, stochastic_raytracing,

@@ -68,3 +68,17 @@ if not ONLY or "materials" in ONLY:
         fig = [max(M.figures(a), M.figures(b)) for a, b in zip(M.skip_errors(g, c, waves), M.skip_errors(k, c, waves))]
         v = waves["vote"].start + 17
         print("skip     %-26s" % ("%g:" % exponent), fmt(fig), " the voting lane %.1e" % float(M.rel_err(g[v, 8:12], c[v, 8:12]).max()))
+# sample_single_light's pick by power and by position (tests/test_light_pick_gpu.py): per scene and rule the largest |p - restatement| over the sixteen
+# probabilities of 4096 rows, the rows that pick another light, and how many of those lie beyond P_TOL of an edge.  The test's P_TOL is 4 x the largest difference.
+if not ONLY or "light_pick" in ONLY:
+    import test_light_pick_gpu as P
+    for which in ("veach", "cornell_lamp_point", "sixteen_lights", "general_shapes"):
+        for rule in ("power", "spatial"):
+            rng = np.random.default_rng(20240229)
+            scene, _, rows = P.pick_rows(which, P.RULES[rule][0], A, api, O, rng)
+            nl = P._light_count(scene)
+            g, li, p, p16, margin = P.pick_agreement(P.RULES[rule][0], A, api, scene, rows)
+            d = np.abs(g[:, 2:2 + nl].astype(np.float64) - p16)
+            differ = g[:, 0].astype(np.int64) != li
+            print("light_pick %-18s %-7s rows %d  max |p - restatement| %.3e (0.999 quantile %.3e)  index differs on %d, beyond P_TOL of an edge %d, largest margin among them %.3e"
+                  % (which, rule, len(rows), d.max(), np.quantile(d.max(axis=1), 0.999), int(differ.sum()), int((differ & (margin > P.P_TOL)).sum()), float(margin[differ].max()) if differ.any() else 0.0))

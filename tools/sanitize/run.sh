@@ -17,6 +17,9 @@ tail -3 build/san/pytest_asan.log
 echo "== stress, address + undefined"
 KYHIP_CACHE_DIR=$PWD/build/san/cache_a KYHIP_HIPCC=$PWD/tools/sanitize/fake_hipcc.sh ASAN_OPTIONS=detect_leaks=1 build/san/stress_asan 3000 > build/san/stress_asan.log 2>&1; RC_A=$?
 tail -5 build/san/stress_asan.log
+echo "== light pick tables, address + undefined"
+ASAN_OPTIONS=detect_leaks=1 build/san/light_pick_asan > build/san/light_pick_asan.log 2>&1; RC_P=$?
+tail -3 build/san/light_pick_asan.log
 echo "== stress, thread"
 KYHIP_CACHE_DIR=$PWD/build/san/cache_t KYHIP_HIPCC=$PWD/tools/sanitize/fake_hipcc.sh TSAN_OPTIONS="halt_on_error=1 die_after_fork=0" build/san/stress_tsan 3000 > build/san/stress_tsan.log 2>&1; RC_T=$?
 tail -5 build/san/stress_tsan.log
@@ -28,9 +31,10 @@ tail -5 build/san/stress_tsan.log
   echo "stress_asan 3000 (seam lock order x 2 threads x 2 devices with a fork in between, HostPool, banded add, chunk schedules, code cache x 6 threads): exit $RC_A"
   sed 's/^/  /' build/san/stress_asan.log | tail -6
   echo "  AddressSanitizer reports: $(grep -c 'ERROR: AddressSanitizer' build/san/stress_asan.log)   LeakSanitizer: $(grep -c 'ERROR: LeakSanitizer' build/san/stress_asan.log)   UBSan: $(grep -c 'runtime error:' build/san/stress_asan.log)"
+  echo "light_pick_asan (kyhip_scene_light_pick: 0 .. 16 lights x 0 .. 6 carriers each, the proxy table up to and past its cap): exit $RC_P: $(tail -1 build/san/light_pick_asan.log)"
   echo "stress_tsan 3000: exit $RC_T"
   sed 's/^/  /' build/san/stress_tsan.log | tail -6
   echo "  ThreadSanitizer reports: $(grep -c 'WARNING: ThreadSanitizer' build/san/stress_tsan.log)"
 } > profiles/${ROUND}_sanitize_summary.txt
 cat profiles/${ROUND}_sanitize_summary.txt
-[ $RC_PY -eq 0 ] && [ $RC_A -eq 0 ] && [ $RC_T -eq 0 ]
+[ $RC_PY -eq 0 ] && [ $RC_A -eq 0 ] && [ $RC_T -eq 0 ] && [ $RC_P -eq 0 ]

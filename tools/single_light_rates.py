@@ -3,7 +3,7 @@
   tools/single_light_rates.py veach <strategy> [spp]     kernel time of three renders after a warm-up, bench.py --workload veach's geometry (1280 x 720, depth 5)
   tools/single_light_rates.py unspec <strategy> [spp]    the same for configs[1]'s scene with kyhip_set_specialisation(0): strategy 32 runs the run-time-dispatched kernel
   tools/single_light_rates.py equal-time <budget ms> [reference spp]
-      both_mis (48) at 4096 spp and sample_single_light (49) at the spp it reaches in <budget ms> of kernel time (its own full-frame rate, measured here),
+      both_mis (48) at 4096 spp and sample_single_light (49, and 113 / 177: its light picked by power / by position) at the spp each reaches in <budget ms> of kernel time (its own full-frame rate, measured here),
       each against the oracle's both_mis film at <reference spp> under another seed, on the six tiles tests/test_configs_gpu.py takes of this frame
   tools/single_light_rates.py reference <reference spp> <file.npz>     only that oracle film (no GPU), saved; equal-time takes the file as a fourth argument
 KYHIP_LIB selects another build of the library (tools/mkvariant.sh).  The file uses nothing that strategy 49 added to the Python package, so a copy of it in a
@@ -70,11 +70,14 @@ else:
     budget_ms = float(sys.argv[2])
     ref_spp = int(sys.argv[3]) if len(sys.argv) > 3 else 131072
     scene = api.mis_scene(W, H)
-    ms49, _ = timed(scene, api.make_params(W, H, 4096, direct_sample=49))
+    SINGLE = (49, 113, 177)   # sample_single_light with its light picked uniformly, by power, by position at the vertex
     ms48, _ = timed(scene, api.make_params(W, H, 4096, direct_sample=48))
-    spp = {48: 4096, 49: int(4096 * budget_ms / min(ms49))}
-    print("equal-time %s: budget %.1f ms of kernel time (both_mis at 4096 spp on the commit before); here 48 takes %.1f ms, 49 %.1f ms at 4096 spp -> 49 reaches %d spp" % (
-        build, budget_ms, min(ms48), min(ms49), spp[49]), flush=True)
+    spp, ms = {48: 4096}, {48: ms48}
+    for strategy in SINGLE:
+        ms[strategy], _ = timed(scene, api.make_params(W, H, 4096, direct_sample=strategy))
+        spp[strategy] = int(4096 * budget_ms / min(ms[strategy]))
+    print("equal-time %s: budget %.1f ms of kernel time (both_mis at 4096 spp on the commit before); here at 4096 spp 48 takes %.1f ms, %s" % (
+        build, budget_ms, min(ms48), ", ".join("%d %.1f ms -> %d spp" % (k, min(ms[k]), spp[k]) for k in SINGLE)), flush=True)
     t0 = time.time()
     if len(sys.argv) > 4:
         saved = np.load(sys.argv[4])
@@ -82,13 +85,14 @@ else:
         ref = {t: saved["%d_%d" % t] for t in TILES}
     else:
         ref = reference(scene, ref_spp)
-    print("reference: the oracle's both_mis at %d spp, seed 99, %d tiles of 16 x 16 in %.0f s (its own noise adds %.1f %% / %.1f %% to the squared errors below)" % (
-        ref_spp, len(TILES), time.time() - t0, 100.0 * spp[48] / ref_spp, 100.0 * spp[49] / ref_spp), flush=True)
+    print("reference: the oracle's both_mis at %d spp, seed 99, %d tiles of 16 x 16 in %.0f s (its own noise adds %s %% to the squared errors below)" % (
+        ref_spp, len(TILES), time.time() - t0, " / ".join("%.1f" % (100.0 * spp[k] / ref_spp) for k in (48,) + SINGLE)), flush=True)
     print("%-12s %8s  %s  %9s" % ("strategy", "spp", "  ".join("tile %-8s" % (t,) for t in TILES), "all tiles"))
     total = {}
-    for strategy in (48, 49):
+    for strategy in (48,) + SINGLE:
         p = api.make_params(W, H, spp[strategy], direct_sample=strategy)
         err = [cut(api.render(scene, one_tile(p, *t)), p, *t) - ref[t] for t in TILES]
         total[strategy] = float(np.sqrt(np.mean(np.concatenate([e.ravel() for e in err]) ** 2)))
-        print("%-12s %8d  %s  %9.3e" % ("both_mis 48" if strategy == 48 else "single 49", spp[strategy], "  ".join("%-13.3e" % np.sqrt(np.mean(e ** 2)) for e in err), total[strategy]))
-    print("lower error at equal kernel time: %s (RMSE ratio 49 / 48 = %.2f)" % ("49" if total[49] < total[48] else "48", total[49] / total[48]))
+        print("%-12s %8d  %s  %9.3e" % ("both_mis 48" if strategy == 48 else "single %d" % strategy, spp[strategy], "  ".join("%-13.3e" % np.sqrt(np.mean(e ** 2)) for e in err), total[strategy]))
+    best = min(total, key=total.get)
+    print("lowest error at equal kernel time: %d (RMSE ratios to 48: %s)" % (best, ", ".join("%d %.2f" % (k, total[k] / total[48]) for k in SINGLE)))
