@@ -34,6 +34,9 @@
  *   ky_drivers stratified [scene] [spp] [cell]  one scene (cornell, the default, or veach) under the random and the stratified sampler side by side at equal spp
  *                                (16; cells of 256, the Veach scene 256 x 144), path_tracing_iteration d5 both_mis into a film_grid_t(1, 2, ...); prints both
  *                                kernel times and writes stratified.bmp: random | stratified
+ *   ky_drivers filtered [spp] [cell]  the Cornell box at a preview's sample count (16; cells of 256) under the box, the tent (radius 2) and the default Gaussian pixel
+ *                                filter side by side (film_t::set_filter, kyhip_render_filtered), path_tracing_iteration d5 both_mis into a film_grid_t(1, 3, ...);
+ *                                prints the three kernel times and writes filtered.bmp: box | tent | gaussian
  *   ky_drivers pick [spp] [w] [h]    the Veach frame under sample_single_light with its light picked uniformly (49), by power (113) and by position at the vertex
  *                                (177) side by side at equal spp (16; cells of 512 x 288), path_tracing_iteration d5 into a film_grid_t(1, 3, ...); writes pick.bmp:
  *                                uniform | power | spatial
@@ -265,6 +268,28 @@ static void render_stratified(bool veach, int spp, int cell) {
     film.store_image("stratified");
 }
 
+// The Cornell box under three pixel filters (the reference's empty `#pragma region filter`, ky.cpp:1525-1527): what a reconstruction filter does to the edges of a
+// preview.  The film owns the filter; a filtered render runs on one device (the default list), so the cells do not take KY_DEVICES.
+static void render_filtered(int spp, int cell) {
+    film_grid_t film(1, 3, cell, cell);
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::default_scene, film.get_resolution());
+    const char* names[3] = {"box", "tent", "gaussian"};
+    float ms[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) {
+        if (k == 0) film.set_filter(std::make_unique<box_filter_t>());
+        else if (k == 1) film.set_filter(std::make_unique<triangle_filter_t>(2.f));
+        else film.set_filter(std::make_unique<gaussian_filter_t>());
+        random_sampler_t sampler(spp);
+        auto integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
+        integrator->render(&scene, &sampler, &film);
+        ms[k] = integrator->last_kernel_ms();
+        film.next_subfilm();
+    }
+    std::printf("filtered: cornell %dx%d, %d spp: kernel", cell, cell, spp);
+    for (int k = 0; k < 3; ++k) std::printf(" %.3f ms %s%s", ms[k], names[k], k < 2 ? "," : "\n");
+    film.store_image("filtered");
+}
+
 // The headline frame in passes: a picture after the first 64 samples, the reference's progress line (3703) after every pass, and a final image that is
 // render()'s bit for bit (include/kyhip.h, kyhip_frame_*).
 static void render_progressive(int spp, int width, int height) {
@@ -470,6 +495,10 @@ int main(int argc, char* argv[]) {
             const int spp = argc > 3 ? std::atoi(argv[3]) : 16, cell = argc > 4 ? std::atoi(argv[4]) : 256;
             if (spp < 1 || spp > (1 << 24) || cell < 16) { std::fprintf(stderr, "stratified: 1 .. 2^24 samples per pixel, cells of 16 or more\n"); return 2; }
             render_stratified(veach, spp, cell);
+        } else if (!std::strcmp(which, "filtered")) {
+            const int spp = argc > 2 ? std::atoi(argv[2]) : 16, cell = argc > 3 ? std::atoi(argv[3]) : 256;
+            if (spp < 1 || cell < 16) { std::fprintf(stderr, "filtered: at least one sample per pixel, cells of 16 or more\n"); return 2; }
+            render_filtered(spp, cell);
         } else if (!std::strcmp(which, "pick")) {
             const int spp = argc > 2 ? std::atoi(argv[2]) : 16, w = argc > 3 ? std::atoi(argv[3]) : 512, h = argc > 4 ? std::atoi(argv[4]) : 288;
             if (spp < 1 || w < 16 || h < 16) { std::fprintf(stderr, "pick: at least one sample per pixel, cells of 16 x 16 or more\n"); return 2; }

@@ -177,6 +177,26 @@ typedef enum ky_sampler_kind {
 } ky_sampler_kind;
 #define KYHIP_STRATIFIED_DIMS 16   /* the draws of a camera sample that KY_SAMPLER_STRATIFIED stratifies (the camera's two among them) */
 
+/* Pixel reconstruction filters (the reference's empty `#pragma region filter`, ky.cpp:1525-1527), by filter importance sampling: the camera
+   sample's offset from its pixel's corner is drawn from the filter's density, 0.5 + F^-1(u) per axis, and the sample still lands in its own pixel with weight 1.  All
+   kinds are separable, one 1-D law for x and y, with support [-radius, radius] in pixels around the pixel's centre.  The filter that is rendered is the TABLE's
+   (kyhip_filter_table): a piecewise-linear inverse CDF over KYHIP_FILTER_TABLE intervals of u, which strays from the analytic CDF by at most 1.8e-3 for the kinds
+   below (DESIGN.md section 11 has the figures); the tent's inverse is closed and reads no table.  A filter travels beside ky_render_params, never inside them. */
+typedef enum ky_filter_kind {
+    KY_FILTER_BOX             = 0,  /* today's camera sample: uniform over the pixel.  The radius is ignored */
+    KY_FILTER_TENT            = 1,  /* density proportional to radius - |x| */
+    KY_FILTER_GAUSSIAN        = 2,  /* param = sigma in pixels; density exp(-x^2 / 2 sigma^2) - exp(-radius^2 / 2 sigma^2) on |x| < radius, as in pbrt */
+    KY_FILTER_BLACKMAN_HARRIS = 3   /* the four-term window 0.35875 + 0.48829 cos(pi x / R) + 0.14128 cos(2 pi x / R) + 0.01168 cos(3 pi x / R) over [-R, R] */
+} ky_filter_kind;
+#define KYHIP_FILTER_MAX_RADIUS 4   /* 0.5 <= radius <= 4 */
+#define KYHIP_FILTER_TABLE 256      /* intervals of the inverse-CDF table: KYHIP_FILTER_TABLE + 1 floats */
+typedef struct ky_pixel_filter {
+    int32_t kind;       /* ky_filter_kind */
+    float   radius;     /* pixels */
+    float   param;      /* KY_FILTER_GAUSSIAN: sigma; ignored by the other kinds */
+    int32_t reserved;   /* 0 */
+} ky_pixel_filter;
+
 typedef struct ky_render_params {
     int32_t  integrator;         /* ky_integrator_kind */
     int32_t  max_path_depth;     /* path_integrator_t::max_path_depth_ (4182) */
@@ -599,6 +619,42 @@ int     kyhip_frame_coverage(const kyhip_frame* f, int* ranges2, int n, int own[
 int     kyhip_frame_merge(kyhip_frame* dst, const void* state, size_t bytes);
 int     kyhip_frame_merge_from(kyhip_frame* dst, kyhip_frame* src);
 int     kyhip_frame_merge_ms(const kyhip_frame* f, float* ms);
+
+/*
+ * Pixel filters (ky_pixel_filter above).
+ * Host only, no device needed:
+ *   kyhip_filter_check     KY_OK, or KY_ERR_INVALID_VALUE with the message: NULL, an unknown kind, a radius outside 0.5 .. KYHIP_FILTER_MAX_RADIUS or not finite
+ *                          (a box's radius is not looked at), a Gaussian sigma that is not > 0 and finite, reserved != 0.
+ *   kyhip_filter_defaults  box; tent radius 2; Gaussian radius 1.5, sigma 0.5; Blackman-Harris radius 2.
+ *   kyhip_filter_table     the inverse-CDF table the device reads: n must be KYHIP_FILTER_TABLE + 1; out[i] = F^-1(i / KYHIP_FILTER_TABLE) in pixels from the pixel's
+ *                          centre, computed in double and rounded once; out[0] = -radius and out[n - 1] = +radius exactly, out[i] = -out[n - 1 - i].  Every kind gets
+ *                          one (the box's is the uniform law over [-0.5, 0.5]), though the device reads it for the Gaussian and Blackman-Harris only.
+ *   kyhip_scene_screen_bound_filtered  kyhip_scene_screen_bound for a launch under `filter`: the scene's live rectangle grown by ceil(radius - 0.5) pixels on every
+ *                          side before it is cut to the frame -- a filter's offsets lie in [0.5 - radius, 0.5 + radius], not in [0, 1) -- and the blocks of the shard
+ *                          outside THAT rectangle, which are the ones a filtered launch skips.  A box filter (or NULL) gives kyhip_scene_screen_bound's answer.
+ * On the device:
+ *   kyhip_render_filtered  kyhip_render under a pixel filter.  A box filter (or NULL) IS kyhip_render: the same film bit for bit, the same kernel.  Any other filter
+ *                          runs a filtered run-time-dispatched kernel (kyhip_last_kernel names it and the filter): there are no specialised, masked or queue-engine
+ *                          filtered kernels and no run-time instantiation of one.  The debug sampler's 0.5 is the pixel's centre under every filter: it ignores the
+ *                          filter and runs kyhip_render's kernels.  The film equals that of a filtered frame rendered in any number of passes or slices.
+ *   kyhip_frame_set_filter the frame's filter, before its first sample is rendered, loaded or merged (KY_ERR_INVALID_VALUE afterwards).  The filter is part of what the
+ *                          frame IS: for any filter but the box its kind, radius and param are folded into the scene hash of the frame's header, so a state loads and
+ *                          merges only into a frame with the same filter; the checkpoint's layout and size do not change.  Denoise guides stay traced through pixel centres.
+ *   kyhip_frame_filter     reads it back (box until one is set).
+ *   kyhip_kat_filter       the warp alone: out[i] = the offset from the pixel's corner for u[i] in [0, 1).
+ *   kyhip_kat_li_filtered  kyhip_kat_li's samples under a filter: what the filtered kernels add per camera sample.
+ */
+int     kyhip_filter_check(const ky_pixel_filter* filter);
+int     kyhip_filter_defaults(int kind, ky_pixel_filter* out);
+int     kyhip_filter_table(const ky_pixel_filter* filter, float* out, int n);
+int     kyhip_scene_screen_bound_filtered(const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter, int rect[4], long long counts[2]);
+int     kyhip_render_filtered(int device, const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter,
+                              float* film_rgb, size_t film_row_stride_px);
+int     kyhip_frame_set_filter(kyhip_frame* f, const ky_pixel_filter* filter);
+int     kyhip_frame_filter(const kyhip_frame* f, ky_pixel_filter* out);
+int     kyhip_kat_filter(int device, const ky_pixel_filter* filter, const float* u, int n, float* out);
+int     kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter,
+                              int x, int y, int s0, int n, float* out3);
 
 /*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent

@@ -76,15 +76,51 @@ def _scene_ptr(scene):
     return scene.flat if hasattr(scene, "flat") else scene
 
 
-def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0), lighting=None):
-    """kyhip_render: integrator_t::render(scene, sampler, film) on the GPU; returns the (accumulated) host film.
-    lighting: a mask of LIGHTING_EMIT / _DIRECT / _INDIRECT -- kyhip_render_lighting, only those light classes are added."""
+def pixel_filter(kind, radius=None, param=None):
+    """A ky_pixel_filter (_abi.PixelFilter): kyhip_filter_defaults(kind) -- tent radius 2, Gaussian radius 1.5 sigma 0.5, Blackman-Harris radius 2 -- with `radius`
+    and `param` (the Gaussian's sigma) replaced where given, then kyhip_filter_check, which raises KyError for what it refuses."""
     lib = A.load_kyhip()
+    f = A.PixelFilter()
+    _check(lib.kyhip_filter_defaults(int(kind), C.byref(f)), lib)
+    if radius is not None:
+        f.radius = float(radius)
+    if param is not None:
+        f.param = float(param)
+    _check(lib.kyhip_filter_check(C.byref(f)), lib)
+    return f
+
+
+def filter_table(filter):
+    """kyhip_filter_table (host only): the FILTER_TABLE + 1 float32 of the filter's inverse CDF, entry i = F^-1(i / FILTER_TABLE) in pixels from the pixel's centre."""
+    lib = A.load_kyhip()
+    out = np.zeros(A.FILTER_TABLE + 1, np.float32)
+    _check(lib.kyhip_filter_table(C.byref(filter), _fptr(out), out.size), lib)
+    return out
+
+
+def kat_filter(filter, u, device=0):
+    """kyhip_kat_filter: the filter's warp of each u in [0, 1) -- the camera sample's offset from its pixel's corner along one axis."""
+    lib = A.load_kyhip()
+    u = np.ascontiguousarray(u, np.float32).ravel()
+    out = np.zeros(u.size, np.float32)
+    _check(lib.kyhip_kat_filter(device, C.byref(filter), _fptr(u), int(u.size), _fptr(out)))
+    return out
+
+
+def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0), lighting=None, filter=None):
+    """kyhip_render: integrator_t::render(scene, sampler, film) on the GPU; returns the (accumulated) host film.
+    lighting: a mask of LIGHTING_EMIT / _DIRECT / _INDIRECT -- kyhip_render_lighting, only those light classes are added.
+    filter: a pixel_filter(...) -- kyhip_render_filtered, the camera samples drawn from the filter's density (not together with lighting)."""
+    lib = A.load_kyhip()
+    if filter is not None and lighting is not None:
+        raise ValueError("a render under a pixel filter has no masked form: filter= or lighting=, not both")
     if film is None:
         film = np.zeros((params.height, params.width, 3), np.float32)
     stride = film.shape[1] if row_stride_px is None else row_stride_px
     base = film.ctypes.data + (origin_px[1] * stride + origin_px[0]) * 12
-    if lighting is None:
+    if filter is not None:
+        _check(lib.kyhip_render_filtered(device, _scene_ptr(scene), C.byref(params), C.byref(filter), C.c_void_p(base), stride))
+    elif lighting is None:
         _check(lib.kyhip_render(device, _scene_ptr(scene), C.byref(params), C.c_void_p(base), stride))
     else:
         _check(lib.kyhip_render_lighting(device, _scene_ptr(scene), C.byref(params), int(lighting), C.c_void_p(base), stride))
@@ -138,9 +174,11 @@ class Frame:
     samples and more and behind a large curved mirror (DESIGN.md "Denoise").
     slice=(first, end): the frame owns and renders samples [first, end) of every pixel only (kyhip_frame_begin_slice; both 0 or a pass boundary, see slice_bounds);
     first == end is a collector that renders nothing.  merge() adds what another frame of the same scene and params holds, bit for bit: `done` counts the samples
-    held, `coverage` lists them, and slices that cover 0 .. total merged into one of them resolve to render(scene, params)."""
+    held, `coverage` lists them, and slices that cover 0 .. total merged into one of them resolve to render(scene, params).
+    filter=pixel_filter(...): the frame's camera samples are drawn from the filter's density (kyhip_frame_set_filter); a complete frame's resolve() is then
+    render(scene, params, filter=filter) bit for bit, and its states load and merge only into frames with the same filter."""
 
-    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0):
+    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0, filter=None):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
@@ -163,6 +201,22 @@ class Frame:
             if rc != A.KY_OK:
                 self.close()
                 _check(rc, self._lib)
+        if filter is not None:
+            rc = self._lib.kyhip_frame_set_filter(self._f, C.byref(filter))
+            if rc != A.KY_OK:
+                self.close()
+                _check(rc, self._lib)
+
+    def set_filter(self, filter):
+        """kyhip_frame_set_filter: the frame's pixel filter; refused once the frame holds a sample."""
+        _check(self._lib.kyhip_frame_set_filter(self._f, C.byref(filter)), self._lib)
+
+    @property
+    def filter(self):
+        """kyhip_frame_filter: the frame's pixel filter (the box until one is set)."""
+        f = A.PixelFilter()
+        _check(self._lib.kyhip_frame_filter(self._f, C.byref(f)), self._lib)
+        return f
 
     def set_guide_bounces(self, bounces):
         """kyhip_frame_set_guide_bounces: 0 .. 4 specular vertices the denoiser's guides follow behind the first hit; refused once the guides are traced."""
@@ -364,20 +418,20 @@ class Frame:
         _check(self._lib.kyhip_frame_load(self._f, state, len(state)), self._lib)
 
 
-def render_sliced(scene, params, devices, min_samples_per_pass, on_pass=None, noise=False, film=None):
+def render_sliced(scene, params, devices, min_samples_per_pass, on_pass=None, noise=False, film=None, filter=None):
     """The frame in len(devices) slices of its samples (slice_bounds), slice k on devices[k] (a device may repeat); returns the (accumulated) host film, which is
     render(scene, params) bit for bit.  The slices render in rounds of one pass each, one call after the other (concurrency across devices: ky_amd.dist); after
     every round on_pass(done, total, preview) is called with the samples per pixel done over all slices, and preview(denoise=False) merges the slices as they stand
     into a collector and returns its picture: resolve(normalise=True), or with denoise=True (needs noise=True and two rounds) denoise().  At the end slice 0's
-    frame merges the others and resolves."""
+    frame merges the others and resolves.  filter: every slice's (and the collector's) pixel filter; the film is then render(scene, params, filter=filter)."""
     bounds = slice_bounds(params.samples_per_pixel, len(devices))
     frames = []
     try:
         for k, dev in enumerate(devices):
-            frames.append(Frame(scene, params, device=dev, noise=noise, slice=(bounds[k], bounds[k + 1])))
+            frames.append(Frame(scene, params, device=dev, noise=noise, slice=(bounds[k], bounds[k + 1]), filter=filter))
 
         def preview(denoise=False):
-            with Frame(scene, params, device=devices[0], noise=noise, slice=(0, 0)) as collector:
+            with Frame(scene, params, device=devices[0], noise=noise, slice=(0, 0), filter=filter) as collector:
                 for f in frames:
                     collector.merge(f)
                 return collector.denoise() if denoise else collector.resolve(normalise=True)
@@ -464,6 +518,22 @@ def render_passes_host_api(scene, integrator_enum, depth, direct_sample, sampler
         return None
     if rc != 0:
         raise KyError("kyhost_render_passes failed: " + host.kyhost_last_error().decode())
+    return film
+
+
+def render_filtered_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, filter, mode="render", min_samples_per_pass=4, seed=1234,
+                             film=None, device=0):
+    """film_t::set_filter(filter) then create_integrator(...)->render / render_passes / render_sliced (over the device twice) / render_until (with a threshold
+    nothing reaches) through the C++ host classes (ky.hpp, filter_t): mode "render", "passes", "sliced" or "until".  filter: a pixel_filter(...)."""
+    host = A.load_kyhost()
+    if film is None:
+        film = np.zeros((height, width, 3), np.float32)
+    rc = host.kyhost_render_filtered(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device, int(filter.kind),
+                                     float(filter.radius), float(filter.param), ("render", "passes", "sliced", "until").index(mode), int(min_samples_per_pass))
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise KyError("kyhost_render_filtered failed: " + host.kyhost_last_error().decode())
     return film
 
 
@@ -661,19 +731,26 @@ def scene_boxes(scene):
     return rc, out[:n].copy()
 
 
-def scene_screen_bound(scene, params):
+def scene_screen_bound(scene, params, filter=None):
     """kyhip_scene_screen_bound (host only): ((x0, y0, x1, y1), dead, total) -- the scene's live rectangle in the frame of `params` (no camera ray of a pixel outside it
-    reaches a surface), and the 8 x 8 blocks of the params' shard outside it / in all."""
+    reaches a surface), and the 8 x 8 blocks of the params' shard outside it / in all.  filter: kyhip_scene_screen_bound_filtered -- the rectangle a launch under
+    that pixel filter reads, grown by ceil(radius - 0.5) pixels on every side."""
     lib = A.load_kyhip()
     rect = (C.c_int * 4)()
     counts = (C.c_longlong * 2)()
-    _check(lib.kyhip_scene_screen_bound(_scene_ptr(scene), C.byref(params), rect, counts))
+    if filter is None:
+        _check(lib.kyhip_scene_screen_bound(_scene_ptr(scene), C.byref(params), rect, counts))
+    else:
+        _check(lib.kyhip_scene_screen_bound_filtered(_scene_ptr(scene), C.byref(params), C.byref(filter), rect, counts))
     return tuple(int(v) for v in rect), int(counts[0]), int(counts[1])
 
 
-def kat_li(scene, params, x, y, s0, n, device=0):
+def kat_li(scene, params, x, y, s0, n, device=0, filter=None):
     lib = A.load_kyhip()
     out = np.zeros((n, 3), np.float32)
+    if filter is not None:   # kyhip_kat_li_filtered: the samples of a render under that pixel filter
+        _check(lib.kyhip_kat_li_filtered(device, _scene_ptr(scene), C.byref(params), C.byref(filter), x, y, s0, n, _fptr(out)))
+        return out
     _check(lib.kyhip_kat_li(device, _scene_ptr(scene), C.byref(params), x, y, s0, n, _fptr(out)))
     return out
 

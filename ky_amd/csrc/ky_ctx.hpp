@@ -133,6 +133,11 @@ struct FramePass {
     int n_live = -1;   // >= 0: a listed pass (a block-tracking frame, ky_blocks.hpp) over this many live blocks, whose ascending indices lie in `ws` behind the flag words
                        // (blocks_list_offset); every pass of such a frame is listed, and the kernel its first pass took is a listed one
     std::string jit_expr, jit_desc;
+    // The frame's pixel filter when it is not the box: every pass then runs a filtered row of the table, never a run-time instantiation.
+    // filter.table is the frame's own device copy of kyhip_filter_table; filter_note is what kyhip_last_kernel says of it.
+    bool filtered = false;
+    kyd::FilterConst filter{};
+    std::string filter_note;
 };
 // resolve_frame_kernel (ky_launch.hip) on `stream`: the frame's accumulators and flags, read and left as they are -> clamp01(value * scale) in the compact tile buffer
 int resolve_frame_device(const void* ws, float* d_tiles, int n_pix, double scale, hipStream_t stream);

@@ -362,6 +362,21 @@ KY_DEV void sampler_camera(typename SamplerFor<SAMPLER>::type& s, float& u0, flo
         u0 = sampler_next<SAMPLER>(s); u1 = sampler_next<SAMPLER>(s);
     }
 }
+// A pixel filter's warp: a number u in [0, 1) -> the camera sample's offset from the pixel's corner along one axis, 0.5 + F^-1(u), where F is
+// the filter's 1-D distribution over [-R, R].  The tent's inverse is closed; every other kind reads the piecewise-linear inverse-CDF table the host computed
+// (kyhip_filter_table: T[i] = F^-1(i / 256), T[0] = -R, T[256] = +R), two loads per axis.  Both are monotone in u, so the stratified pair keeps its strata.  The two
+// fused multiply-adds are written out: the rounding of the result is the source's, not the contraction pass's (section 10, item 5).  The products 2 u and 256 u are exact.
+KY_DEV float filter_offset(const FilterConst& fc, float u) {
+    if (fc.kind == KY_FILTER_TENT) {
+        const float w = u < 0.5f ? sqrtf(2.f * u) - 1.f : 1.f - sqrtf(2.f - 2.f * u);
+        return __builtin_fmaf(fc.radius, w, 0.5f);
+    }
+    const float t = u * (float)KYHIP_FILTER_TABLE;
+    const int i = min((int)t, KYHIP_FILTER_TABLE - 1);
+    const float fr = t - (float)i;
+    const float a = fc.table[i], b = fc.table[i + 1];
+    return 0.5f + __builtin_fmaf(fr, b - a, a);
+}
 
 // ---------------------------------------------------------------------------------------------
 // camera_t::generate_ray, ky.cpp:1884-1892
@@ -2361,12 +2376,15 @@ KY_DEV void path_state_dead(PathStateT<SMP>& ps) {
 
 // KEEP_LO (render_kernel): ps.Lo is not the sample's radiance but the running sum of the lane's pixel chunk -- every contribution of every
 // path of the chunk is added to it, the kernel scales and flushes it once per chunk -- so a new path leaves it alone.
-template <int SAMPLER, bool KEEP_LO = false>
-KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key, int x, int y, int sample) {
+// FILTER (the filtered kernels): the camera sample's two numbers go through the pixel filter's warp, so the ray leaves through
+// (x + ox, y + oy) with ox, oy in [0.5 - R, 0.5 + R] drawn from the filter's density; the sample still belongs to pixel (x, y) with weight 1.
+template <int SAMPLER, bool KEEP_LO = false, bool FILTER = false>
+KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key, int x, int y, int sample, const FilterConst& fc = FilterConst{}) {
     sampler_start_kind<SAMPLER>(ps.smp, pixel_key, (uint32_t)sample);
     // get_camera_sample, 943-946 / 971-974
     float u0, u1;
     sampler_camera<SAMPLER>(ps.smp, u0, u1);
+    if constexpr (FILTER) { u0 = filter_offset(fc, u0); u1 = filter_offset(fc, u1); }
     generate_ray(S, (float)x + u0, (float)y + u1, ps.o, ps.d);
     ps.beta = mk3(1, 1, 1);
     if (!KEEP_LO) ps.Lo = mk3(0, 0, 0);

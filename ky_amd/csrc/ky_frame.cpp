@@ -72,6 +72,7 @@ struct kyhip_frame {
     NoiseTrack noise;
     BlockTrack blocks;
     DenoiseTrack denoise;
+    DevBuf filter_table;          // the inverse-CDF table of the frame's pixel filter (kyhip_frame_set_filter), which pass.filter points to
     DevBuf merge_ws, merge_state; // what a merge from a saved state or from another device reads: the other frame's accumulator block and noise pairs
     TimedSpan merge;              // the last merge kernel (kyhip_frame_merge_ms)
 };
@@ -189,6 +190,51 @@ int kyhip_frame_begin(int device, const ky_scene* scene, const ky_render_params*
 }
 int kyhip_frame_begin_slice(int device, const ky_scene* scene, const ky_render_params* p, int first_sample, int end_sample, kyhip_frame** out) {
     return frame_begin(device, scene, p, first_sample, end_sample, out);
+}
+
+// ---- the frame's pixel filter ----
+int kyhip_frame_set_filter(kyhip_frame* f, const ky_pixel_filter* filter) {
+    KY_TRY(filter_check(filter));   // (the filter first, then the frame: the host-only builds' stand-in refuses in the same order)
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!f->book.untouched()) return f->book.set_filter(filter);   // (the book's refusal)
+    FramePass& pass = f->pass;
+    if (filter->kind != KY_FILTER_BOX) {   // the table first: a failed copy leaves the frame's filter what it was
+        DeviceCtx* c;
+        KY_TRY(get_ctx(f->device, &c));
+        float table[KYHIP_FILTER_TABLE + 1];
+        filter_table(filter, table);
+        if (!f->filter_table.p) HIP_TRY(f->filter_table.alloc(sizeof table));
+        HIP_TRY(hipMemcpy(f->filter_table.p, table, sizeof table, hipMemcpyHostToDevice));
+    }
+    KY_TRY(f->book.set_filter(filter));
+    pass.filtered = filter->kind != KY_FILTER_BOX;
+    pass.filter = FilterConst{filter->kind, filter->radius, filter_grow(filter), pass.filtered ? f->filter_table.as<const float>() : nullptr};
+    pass.filter_note = filter_describe(filter);
+    return KY_OK;
+}
+int kyhip_frame_filter(const kyhip_frame* f, ky_pixel_filter* out) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    *out = f->book.filter;
+    return KY_OK;
+}
+// kyhip_render under a pixel filter: a frame of its own, rendered in one pass and resolved -- the accumulators of a frame in any number of passes or slices are the
+// same words (DESIGN.md "Passes"), and resolve_frame_kernel at scale 1 is resolve_kernel bit for bit.  A box filter is kyhip_render itself.
+int kyhip_render_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, float* film_rgb, size_t stride_px) {
+    if (filter_is_box(filter)) {
+        if (filter) KY_TRY(filter_check(filter));
+        return kyhip_render(device, scene, p, film_rgb, stride_px);
+    }
+    KY_TRY(filter_check(filter));
+    if (p && valid_params(p) && p->sampler == KY_SAMPLER_DEBUG) return kyhip_render(device, scene, p, film_rgb, stride_px);   // (0.5 is the centre under every filter)
+    if (!film_rgb || (p && valid_params(p) && stride_px < (size_t)p->width)) return fail(KY_ERR_INVALID_VALUE, "bad film arguments");
+    kyhip_frame* f = nullptr;
+    KY_TRY(kyhip_frame_begin(device, scene, p, &f));
+    int rcode = kyhip_frame_set_filter(f, filter);
+    if (rcode == KY_OK) rcode = kyhip_frame_render(f, p->samples_per_pixel, nullptr);
+    if (rcode == KY_OK) rcode = kyhip_frame_resolve(f, 1, film_rgb, stride_px);
+    kyhip_frame_end(f);
+    return rcode;
 }
 
 int kyhip_frame_coverage(const kyhip_frame* f, int* ranges2, int n, int own[2]) {

@@ -49,7 +49,11 @@ static int frame_header_check(const FrameHeader& own, const void* buf, size_t by
     FrameHeader same = theirs;
     same.samples_done = own.samples_done;
     same.magic = own.magic;
-    if (std::memcmp(&same, &own, sizeof own) != 0) return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its render params, scene or film size differ from this frame's)");
+    if (std::memcmp(&same, &own, sizeof own) != 0) {
+        same.scene_hash = own.scene_hash;   // (the header's scene hash carries the frame's pixel filter too: filter_fold, ky_pack.cpp)
+        if (std::memcmp(&same, &own, sizeof own) == 0) return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its scene or its pixel filter differs from this frame's; kyhip_frame_set_filter)");
+        return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its render params, scene or film size differ from this frame's)");
+    }
     if (bytes < state_end) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes, the frame's state has %zu", bytes, state_end);
     *out = theirs;
     return KY_OK;
@@ -299,7 +303,35 @@ void FrameBook::begin(const ky_render_params* p, uint64_t scene_hash, int first_
     own_c0 = chunks_at_sample(plan, first_sample); own_c1 = chunks_at_sample(plan, end_sample);
     chunks_done = own_c0;
     header = frame_header(p, scene_hash, 0);
+    base_hash = scene_hash;
     retrack();
+}
+int FrameBook::set_filter(const ky_pixel_filter* f) {
+    KY_TRY(filter_check(f));
+    if (!untouched()) return fail(KY_ERR_INVALID_VALUE, "the frame holds samples already: its pixel filter is set before the first one is rendered, loaded or merged");
+    filter = *f;
+    if (filter.kind == KY_FILTER_BOX) filter = ky_pixel_filter{};   // (one box: its radius names nothing)
+    header.scene_hash = filter_fold(base_hash, &filter);
+    return KY_OK;
+}
+// Where a saved state differs from this frame in nothing but the header's scene hash, the refusal names the filter when that can be told: KY_OK otherwise (the
+// readers' own checks follow and refuse whatever else is wrong).
+int FrameBook::filter_refusal(const void* buf, size_t bytes) const {
+    if (!buf || bytes < sizeof(FrameHeader)) return KY_OK;
+    FrameHeader theirs;
+    std::memcpy(&theirs, buf, sizeof theirs);
+    if (theirs.scene_hash == header.scene_hash) return KY_OK;
+    FrameHeader same = theirs;
+    same.scene_hash = header.scene_hash; same.samples_done = header.samples_done; same.magic = header.magic;
+    if (std::memcmp(&same, &header, sizeof header) != 0) return KY_OK;
+    if (filter_is_box(&filter)) return KY_OK;   // (another scene, or a filter this frame does not have: the header check says so)
+    if (theirs.scene_hash == base_hash)
+        return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame of this scene with the box filter, this frame has a %s (kyhip_frame_set_filter)", filter_describe(&filter).c_str());
+    return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame with another pixel filter (or scene), this frame has a %s (kyhip_frame_set_filter)", filter_describe(&filter).c_str());
+}
+int FrameBook::load_check(const void* buf, size_t bytes, CheckpointCounts* out) const {
+    KY_TRY(filter_refusal(buf, bytes));
+    return checkpoint_check(header, layout, buf, bytes, out);
 }
 int FrameBook::tracks(bool want_blocks, bool want_noise) const {
     if (want_blocks && !blocks.on) return fail(KY_ERR_INVALID_VALUE, "the frame does not track blocks (kyhip_frame_track_blocks)");
@@ -418,6 +450,7 @@ void FrameBook::commit_load(const CheckpointCounts& n) {
 
 int FrameBook::merge_state(const void* state, size_t bytes, MergeStep* out) const {
     MergeSource m;
+    KY_TRY(filter_refusal(state, bytes));
     KY_TRY(merge_source_check(header, state, bytes, &m));
     MergeStep s;
     KY_TRY(merge_accept(cov, own_first, own_end, params.samples_per_pixel, noise.on, blocks.on, m.cov, m.noise_pixels != 0, &s.merged));
@@ -428,8 +461,11 @@ int FrameBook::merge_state(const void* state, size_t bytes, MergeStep* out) cons
 }
 int FrameBook::merge_book(const FrameBook& src, MergeStep* out) const {
     if (this == &src) return fail(KY_ERR_INVALID_VALUE, "merge: a frame holds its own samples already");
-    if (std::memcmp(&header, &src.header, sizeof header) != 0)
+    if (std::memcmp(&header, &src.header, sizeof header) != 0) {
+        if (std::memcmp(&filter, &src.filter, sizeof filter) != 0)
+            return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their pixel filter (this one: %s, the other: %s)", filter_describe(&filter).c_str(), filter_describe(&src.filter).c_str());
         return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their render params, scene or film size");
+    }
     if (src.blocks.on) return fail(KY_ERR_INVALID_VALUE, "merge: the other frame retires pixel blocks: its pixels stand at sample counts of their own and merge with nothing");
     MergeStep s;
     KY_TRY(merge_accept(cov, own_first, own_end, params.samples_per_pixel, noise.on, blocks.on, src.cov, src.noise.on, &s.merged));

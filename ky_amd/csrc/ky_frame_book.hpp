@@ -51,8 +51,16 @@ struct FrameBook {
         std::vector<int> inside;             // per block, its pixels inside the film
     } blocks;
 
+    // The frame's pixel filter, the box until set_filter: part of what the frame IS.  header.scene_hash is filter_fold(base_hash, &filter):
+    // the packed scene's hash itself under the box, so every state of an unfiltered frame is what it was.
+    ky_pixel_filter filter{};
+    uint64_t base_hash = 0;
+
     // the book of the frame of p that owns [first_sample, end_sample): behind begin_check
     void begin(const ky_render_params* p, uint64_t scene_hash, int first_sample, int end_sample);
+    // kyhip_frame_set_filter behind its NULL frame: refuses an invalid filter, and any filter once the frame holds or has loaded a sample; then a commit of its own
+    // (no device work stands behind it)
+    int set_filter(const ky_pixel_filter* f);
 
     // ---- questions ----
     int front() const { return chunk_end(plan, chunks_done - 1); }
@@ -69,7 +77,8 @@ struct FrameBook {
     int resolve(int normalise, const float* film_rgb, size_t stride_px, ResolveStep* out) const;
     int denoise_check(bool needs_variance) const;
     int save_host(void* buf, size_t bytes) const;          // refuses a short buffer, then writes the parts of the checkpoint the host holds
-    int load_check(const void* buf, size_t bytes, CheckpointCounts* out) const { return checkpoint_check(header, layout, buf, bytes, out); }
+    int load_check(const void* buf, size_t bytes, CheckpointCounts* out) const;
+    int filter_refusal(const void* buf, size_t bytes) const;   // a saved state that differs from this frame in its pixel filter: the refusal that names it
     int merge_state(const void* state, size_t bytes, MergeStep* out) const;
     int merge_book(const FrameBook& src, MergeStep* out) const;
     void block_stats(ky_block_stats* out) const;

@@ -99,6 +99,16 @@ void find_boxes(const ky_scene* in, Boxes& B);
 void screen_bound(const ky_scene* in, int32_t live[4]);
 // ... and for a launch's tiling: the 8 x 8 blocks of the shard that lie outside it (the work items a render kernel skips per chunk), and all of them
 void screen_bound_counts(const int32_t live[4], const ky_render_params* p, long long* dead, long long* total);
+// ---- pixel filters (ky_pixel_filter; ky_pack.cpp) ----
+int filter_check(const ky_pixel_filter* f);                    // kyhip_filter_check
+inline bool filter_is_box(const ky_pixel_filter* f) { return !f || f->kind == KY_FILTER_BOX; }
+int filter_grow(const ky_pixel_filter* f);                     // the pixels a valid filter's offsets reach beyond the pixel, ceil(radius - 0.5); 0 for a box
+void filter_table(const ky_pixel_filter* f, float* out);       // kyhip_filter_table's KYHIP_FILTER_TABLE + 1 floats, of a valid filter
+std::string filter_describe(const ky_pixel_filter* f);         // "tent filter, radius 2", "Gaussian filter, radius 1.5, sigma 0.5", "box filter"
+// the scene hash a frame's header carries under `f`: `hash` itself for a box, else `hash` with the filter's kind, radius bits and param bits folded in
+uint64_t filter_fold(uint64_t hash, const ky_pixel_filter* f);
+// the live rectangle as a launch under `f` reads it: grown by filter_grow on every side (the kernels' work decoder does the same, ky_render.hpp)
+void screen_bound_widen(const int32_t live[4], const ky_pixel_filter* f, int32_t out[4]);
 int pack_scene(const ky_scene* in, DScene* out);
 void pack_light_pick(const ky_scene* in, DLightPick* out);   // sample_single_light's power and spatial picks: the emitter proxies and the power rule's probabilities (a scene pack_scene accepts)
 uint64_t scene_hash(const DScene& s);

@@ -615,6 +615,137 @@ int kyhostcheck_screen_bound(void) {
     return 0;
 }
 
+// Pixel filters (ky_pack.cpp), host side: check, defaults and table (monotone, ends exact, symmetric) for every kind at the ends of the radius
+// range; the header fold (the box leaves a frame's scene hash alone, two radii give two hashes, a filter is refused once the frame holds samples); the widened live
+// rectangle on kyhostcheck_screen_bound's two scenes.  Returns 0, or the number of the case that went wrong.
+int kyhostcheck_filter(void) {
+    const float q = std::numeric_limits<float>::quiet_NaN();
+    constexpr int T = KYHIP_FILTER_TABLE + 1;
+    {   // what the check refuses, one rule at a time, and what it accepts
+        const ky_pixel_filter ok[] = {{KY_FILTER_BOX, 0.f, 0.f, 0}, {KY_FILTER_BOX, 99.f, q, 0}, {KY_FILTER_TENT, 0.5f, 0.f, 0}, {KY_FILTER_TENT, 4.f, q, 0},
+                                      {KY_FILTER_GAUSSIAN, 1.5f, 0.5f, 0}, {KY_FILTER_BLACKMAN_HARRIS, 2.f, -1.f, 0}};
+        for (const ky_pixel_filter& f : ok) if (kyhip_filter_check(&f) != KY_OK) return 1;
+        const ky_pixel_filter bad[] = {{-1, 2.f, 0.f, 0}, {4, 2.f, 0.f, 0}, {KY_FILTER_TENT, 0.49f, 0.f, 0}, {KY_FILTER_TENT, 4.01f, 0.f, 0}, {KY_FILTER_TENT, q, 0.f, 0},
+                                       {KY_FILTER_TENT, std::numeric_limits<float>::infinity(), 0.f, 0}, {KY_FILTER_GAUSSIAN, 1.5f, 0.f, 0}, {KY_FILTER_GAUSSIAN, 1.5f, -0.5f, 0},
+                                       {KY_FILTER_GAUSSIAN, 1.5f, q, 0}, {KY_FILTER_TENT, 2.f, 0.f, 1}, {KY_FILTER_BOX, 0.f, 0.f, 7}};
+        for (const ky_pixel_filter& f : bad) if (kyhip_filter_check(&f) != KY_ERR_INVALID_VALUE) return 2;
+        if (kyhip_filter_check(nullptr) != KY_ERR_INVALID_VALUE) return 3;
+    }
+    {   // the defaults
+        ky_pixel_filter f;
+        if (kyhip_filter_defaults(KY_FILTER_TENT, &f) != KY_OK || f.kind != KY_FILTER_TENT || f.radius != 2.f || f.reserved != 0 || kyhip_filter_check(&f) != KY_OK) return 4;
+        if (kyhip_filter_defaults(KY_FILTER_GAUSSIAN, &f) != KY_OK || f.radius != 1.5f || f.param != 0.5f || kyhip_filter_check(&f) != KY_OK) return 5;
+        if (kyhip_filter_defaults(KY_FILTER_BLACKMAN_HARRIS, &f) != KY_OK || f.radius != 2.f || kyhip_filter_check(&f) != KY_OK) return 6;
+        if (kyhip_filter_defaults(KY_FILTER_BOX, &f) != KY_OK || f.kind != KY_FILTER_BOX) return 7;
+        if (kyhip_filter_defaults(9, &f) != KY_ERR_INVALID_VALUE || kyhip_filter_defaults(KY_FILTER_TENT, nullptr) != KY_ERR_INVALID_VALUE) return 8;
+    }
+    {   // the table
+        const ky_pixel_filter fs[] = {{KY_FILTER_BOX, 0.f, 0.f, 0}, {KY_FILTER_TENT, 0.5f, 0.f, 0}, {KY_FILTER_TENT, 4.f, 0.f, 0}, {KY_FILTER_GAUSSIAN, 0.5f, 0.5f, 0},
+                                      {KY_FILTER_GAUSSIAN, 1.5f, 0.5f, 0}, {KY_FILTER_GAUSSIAN, 4.f, 1.f, 0}, {KY_FILTER_GAUSSIAN, 4.f, 0.25f, 0},
+                                      {KY_FILTER_BLACKMAN_HARRIS, 0.5f, 0.f, 0}, {KY_FILTER_BLACKMAN_HARRIS, 2.f, 0.f, 0}, {KY_FILTER_BLACKMAN_HARRIS, 4.f, 0.f, 0}};
+        for (const ky_pixel_filter& f : fs) {
+            std::vector<float> t(T, q);
+            if (kyhip_filter_table(&f, t.data(), T) != KY_OK) return 9;
+            const float R = f.kind == KY_FILTER_BOX ? 0.5f : f.radius;
+            if (t[0] != -R || t[T - 1] != R || t[T / 2] != 0.f) return 10;
+            for (int i = 0; i + 1 < T; ++i) if (!(t[i] <= t[i + 1])) return 11;
+            for (int i = 0; i < T; ++i) if (t[i] != -t[T - 1 - i]) return 12;
+            if (f.kind == KY_FILTER_TENT && std::fabs((double)t[T / 4] - (double)R * (std::sqrt(0.5) - 1)) > 1e-6) return 13;   // F^-1(1/4) = R (sqrt(1/2) - 1)
+        }
+        std::vector<float> t(T);
+        if (kyhip_filter_table(&fs[1], t.data(), T - 1) != KY_ERR_INVALID_VALUE || kyhip_filter_table(&fs[1], nullptr, T) != KY_ERR_INVALID_VALUE) return 14;
+        const ky_pixel_filter bad = {KY_FILTER_TENT, 5.f, 0.f, 0};
+        if (kyhip_filter_table(&bad, t.data(), T) != KY_ERR_INVALID_VALUE) return 15;
+    }
+    {   // the header fold, and when a frame takes a filter
+        ky_render_params p{};
+        p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS; p.samples_per_pixel = 64; p.sampler = KY_SAMPLER_RANDOM;
+        p.width = 16; p.height = 16; p.tile_w = 16; p.tile_h = 16; p.tile_first = 0; p.tile_step = 1;
+        const ky_pixel_filter box = {KY_FILTER_BOX, 3.f, 0.f, 0}, t1 = {KY_FILTER_TENT, 1.f, 0.f, 0}, t2 = {KY_FILTER_TENT, 2.f, 7.f, 0}, t2b = {KY_FILTER_TENT, 2.f, 0.f, 0},
+                              g = {KY_FILTER_GAUSSIAN, 1.5f, 0.5f, 0}, g2 = {KY_FILTER_GAUSSIAN, 1.5f, 0.25f, 0};
+        FrameBook a, b;
+        a.begin(&p, 0x1234, 0, 64);
+        b.begin(&p, 0x1234, 0, 0);   // (a collector: it may merge what a holds)
+        if (a.set_filter(&box) != KY_OK || a.header.scene_hash != 0x1234 || std::memcmp(&a.header, &b.header, sizeof a.header) != 0) return 16;
+        if (a.set_filter(&t1) != KY_OK || b.set_filter(&t2) != KY_OK) return 17;
+        if (a.header.scene_hash == 0x1234 || b.header.scene_hash == 0x1234 || a.header.scene_hash == b.header.scene_hash) return 18;
+        const uint64_t h2 = b.header.scene_hash;
+        if (b.set_filter(&t2b) != KY_OK || b.header.scene_hash != h2) return 19;   // (a tent's param names nothing)
+        if (b.set_filter(&g) != KY_OK || b.header.scene_hash == h2) return 20;
+        const uint64_t hg = b.header.scene_hash;
+        if (b.set_filter(&g2) != KY_OK || b.header.scene_hash == hg) return 21;
+        if (b.set_filter(&box) != KY_OK || b.header.scene_hash != 0x1234 || b.filter.kind != KY_FILTER_BOX) return 22;
+        MergeStep ms;
+        if (b.merge_book(a, &ms) != KY_ERR_INVALID_VALUE || last_error().find("pixel filter") == std::string::npos) return 23;
+        if (b.set_filter(&t1) != KY_OK || b.merge_book(a, &ms) != KY_OK) return 24;
+        // a saved state of the tent frame: the box frame and the Gaussian frame refuse it, the tent frame loads it; then no filter is taken any more
+        std::vector<unsigned char> state(a.layout.total, 0);
+        if (a.save_host(state.data(), state.size()) != KY_OK) return 25;
+        FrameBook c;
+        c.begin(&p, 0x1234, 0, 64);
+        CheckpointCounts n;
+        if (c.load_check(state.data(), state.size(), &n) != KY_ERR_INVALID_VALUE || last_error().find("pixel filter") == std::string::npos) return 26;
+        if (c.set_filter(&g) != KY_OK || c.load_check(state.data(), state.size(), &n) != KY_ERR_INVALID_VALUE || last_error().find("Gaussian") == std::string::npos) return 27;
+        if (c.set_filter(&t1) != KY_OK || c.load_check(state.data(), state.size(), &n) != KY_OK) return 28;
+        c.commit_load(n);
+        if (c.set_filter(&t1) != KY_ERR_INVALID_VALUE || c.set_filter(&box) != KY_ERR_INVALID_VALUE) return 29;
+        const ky_pixel_filter bad = {KY_FILTER_TENT, 0.25f, 0.f, 0};
+        if (a.set_filter(&bad) != KY_ERR_INVALID_VALUE || a.set_filter(nullptr) != KY_ERR_INVALID_VALUE || a.filter.radius != 1.f) return 30;
+    }
+    {   // the widened rectangle: kyhostcheck_screen_bound's box from far in front, and its point
+        ky_shape sp{};
+        sp.kind = KY_SHAPE_SPHERE; sp.radius = 0.f;
+        ky_material matte{};
+        matte.kind = KY_MATERIAL_MATTE; matte.color0[0] = matte.color0[1] = matte.color0[2] = 0.5f;
+        ky_light lamp{};
+        lamp.kind = KY_LIGHT_POINT; lamp.color[0] = lamp.color[1] = lamp.color[2] = 1.f;
+        auto rect_shape = [](const float (&pts)[4][3], float nx, float ny, float nz) {
+            ky_shape r{};
+            r.kind = KY_SHAPE_RECTANGLE;
+            std::memcpy(r.p, pts, sizeof r.p);
+            r.normal[0] = nx; r.normal[1] = ny; r.normal[2] = nz;
+            return r;
+        };
+        const float back[4][3] = {{-1, -1, 1}, {1, -1, 1}, {1, 1, 1}, {-1, 1, 1}}, floor_[4][3] = {{-1, -1, -1}, {1, -1, -1}, {1, -1, 1}, {-1, -1, 1}},
+                    ceil_[4][3] = {{-1, 1, -1}, {1, 1, -1}, {1, 1, 1}, {-1, 1, 1}}, left[4][3] = {{-1, -1, -1}, {-1, -1, 1}, {-1, 1, 1}, {-1, 1, -1}},
+                    right[4][3] = {{1, -1, -1}, {1, -1, 1}, {1, 1, 1}, {1, 1, -1}};
+        const std::vector<ky_shape> box5 = {rect_shape(back, 0, 0, -1), rect_shape(floor_, 0, 1, 0), rect_shape(ceil_, 0, -1, 0), rect_shape(left, 1, 0, 0), rect_shape(right, -1, 0, 0)};
+        std::vector<ky_surface> surf;
+        for (int i = 0; i < 5; ++i) surf.push_back(ky_surface{i, 0, -1});
+        ky_render_params p{};
+        p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS; p.samples_per_pixel = 4; p.sampler = KY_SAMPLER_RANDOM;
+        p.width = 256; p.height = 64; p.tile_w = 32; p.tile_h = 32; p.tile_first = 0; p.tile_step = 1;
+        for (int which = 0; which < 2; ++which) {
+            ky_scene s{};
+            s.shapes = which ? &sp : box5.data(); s.shape_count = which ? 1 : 5;
+            s.materials = &matte; s.material_count = 1;
+            s.lights = &lamp; s.light_count = 1;
+            s.surfaces = surf.data(); s.surface_count = which ? 1 : 5;
+            s.environment_light = -1;
+            s.camera.position[2] = -5.f; s.camera.front[2] = 1.f; s.camera.right[0] = 2.f; s.camera.up[1] = 0.5f;
+            s.camera.resolution[0] = 256.f; s.camera.resolution[1] = 64.f;
+            int r0[4], r[4];
+            long long c0[2], c[2];
+            if (kyhip_scene_screen_bound(&s, &p, r0, c0) != KY_OK || !(c0[0] > 0)) return 31 + which;
+            const ky_pixel_filter box = {KY_FILTER_BOX, 0.f, 0.f, 0};
+            if (kyhip_scene_screen_bound_filtered(&s, &p, &box, r, c) != KY_OK || std::memcmp(r, r0, sizeof r) != 0 || c[0] != c0[0] || c[1] != c0[1]) return 33 + which;
+            if (kyhip_scene_screen_bound_filtered(&s, &p, nullptr, r, c) != KY_OK || std::memcmp(r, r0, sizeof r) != 0) return 35 + which;
+            const float radii[] = {0.5f, 0.75f, 1.5f, 2.f, 4.f};
+            const int grows[] = {0, 1, 1, 2, 4};
+            for (int k = 0; k < 5; ++k) {
+                const ky_pixel_filter f = {KY_FILTER_TENT, radii[k], 0.f, 0};
+                if (kyhip_scene_screen_bound_filtered(&s, &p, &f, r, c) != KY_OK) return 37 + which;
+                const int g = grows[k];
+                if (r[0] != std::max(r0[0] - g, 0) || r[1] != std::max(r0[1] - g, 0) || r[2] != std::min(r0[2] + g, p.width) || r[3] != std::min(r0[3] + g, p.height)) return 39 + which;
+                if (c[1] != c0[1] || c[0] > c0[0]) return 41 + which;   // a wider rectangle skips no more blocks
+            }
+            const ky_pixel_filter bad = {KY_FILTER_TENT, 9.f, 0.f, 0};
+            if (kyhip_scene_screen_bound_filtered(&s, &p, &bad, r, c) != KY_ERR_INVALID_VALUE) return 43 + which;
+        }
+    }
+    return 0;
+}
+
 // ---- the entry points that need a GPU: absent from this build.  They exist as symbols because the host mirror (ky.hpp) and ctypes resolve every
 // symbol when a library is loaded; each validates what the product validates before it touches a device where a CPU test looks at that, and then
 // reports that there is no device -- exactly what libkyhip.so reports on a machine without a gfx950 GPU.
@@ -712,6 +843,24 @@ int kyhip_frame_set_guide_bounces(kyhip_frame*, int bounces) {
 }
 int kyhip_frame_guide_bounces(const kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_guide_chains(kyhip_frame*, uint64_t*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+// (the filter entries refuse an invalid filter before they look for a device or a frame, like the real ones: filter_check is host code; a box filter is the unfiltered entry)
+int kyhip_render_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, float* film, size_t stride) {
+    if (filter) KY_TRY(filter_check(filter));
+    return kyhip_render(device, scene, p, film, stride);
+}
+int kyhip_frame_set_filter(kyhip_frame*, const ky_pixel_filter* filter) {
+    KY_TRY(filter_check(filter));
+    return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+}
+int kyhip_frame_filter(const kyhip_frame*, ky_pixel_filter*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_kat_filter(int, const ky_pixel_filter* filter, const float*, int, float*) {
+    KY_TRY(filter_check(filter));
+    return no_gpu();
+}
+int kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, int x, int y, int s0, int n, float* out3) {
+    if (filter) KY_TRY(filter_check(filter));
+    return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);
+}
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_light_pick(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }   // (kyhip_scene_light_pick is host code: ky_pack.cpp)
 int kyhip_kat_single_light_rule(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }

@@ -704,3 +704,77 @@ int kyhip_kat_single_light_rule(int device, const ky_scene* scene, int rule, con
 }
 
 }  // extern "C"
+
+// ---- pixel filters (behind the other entries, whose listings keep their text) ----
+// the warp alone, as path_begin applies it to each of a camera sample's two numbers; `table`: KYHIP_FILTER_TABLE + 1 floats
+__global__ void kat_filter_kernel(FilterConst fc, const float* __restrict__ u, int n, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = filter_offset(fc, u[i]);
+}
+// kat_li_kernel / kat_li_stratified_kernel under a pixel filter: the walk of the filtered render kernels, which assume no scene facts (no box traversal, no pair scan)
+template <int SAMPLER>
+__global__ void kat_li_filtered_kernel(const DScene* __restrict__ S_, RenderConstF rc_, int x, int y, int s0, int n, float* __restrict__ out3) {
+    const SceneRef S{S_, true, 0, true};
+    const typename RenderConstFor<SAMPLER>::type rc = rc_;
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    PathStateFor<SAMPLER> ps;
+    sampler_bind(ps.smp, rc);
+    bool alive = i < n;
+    if (alive) path_begin<SAMPLER, false, true>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i, rc_.filter);
+    while (__any(alive)) {  // path_shade is a wave-uniform call
+        Vertex v;
+        bool have_vertex = false;
+        if (alive) have_vertex = path_intersect<SAMPLER>(ps, v, S, Lds, rc);
+        const bool cont = path_shade<SAMPLER>(ps, v, S, Lds, rc, have_vertex);
+        alive = have_vertex && cont;
+    }
+    if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
+}
+
+extern "C" {
+
+int kyhip_kat_filter(int device, const ky_pixel_filter* filter, const float* u, int n, float* out) {
+    KY_TRY(filter_check(filter));
+    if (!u || !out || n <= 0 || n > (1 << 26)) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    for (int i = 0; i < n; ++i)
+        if (!(u[i] >= 0.f && u[i] < 1.f)) return fail(KY_ERR_INVALID_VALUE, "u[%d] = %g outside [0, 1)", i, (double)u[i]);
+    constexpr int T = KYHIP_FILTER_TABLE + 1;
+    std::vector<float> in((size_t)T + (size_t)n);   // the table, then the numbers
+    filter_table(filter, in.data());
+    std::memcpy(in.data() + T, u, (size_t)n * sizeof(float));
+    return kat_run(device, in.data(), in.size() * 4, out, (size_t)n * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        const FilterConst fc{filter->kind, filter->kind == KY_FILTER_BOX ? 0.5f : filter->radius, filter_grow(filter), d_in};
+        hipLaunchKernelGGL(kat_filter_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, fc, d_in + T, n, d_out);
+        return (int)KY_OK;
+    });
+}
+
+int kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, int x, int y, int s0, int n, float* out3) {
+    if (filter_is_box(filter)) {
+        if (filter) KY_TRY(filter_check(filter));
+        return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);
+    }
+    KY_TRY(filter_check(filter));
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    if (p->sampler == KY_SAMPLER_DEBUG) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);   // (0.5 is the pixel's centre under every filter)
+    if (!scene || !out3 || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    KY_TRY(strat_samples_check(p, s0, n));
+    float table[KYHIP_FILTER_TABLE + 1];
+    filter_table(filter, table);
+    RenderConstF rc{};
+    static_cast<RenderConstS&>(rc) = make_rc(p);
+    const bool strat = p->sampler == KY_SAMPLER_STRATIFIED;
+    return kat_run(device, table, sizeof table, out3, (size_t)n * 3 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
+        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
+        if (r != KY_OK) return r;
+        rc.filter = FilterConst{filter->kind, filter->radius, filter_grow(filter), d_in};
+        const size_t lds = lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
+        const dim3 grid((n + 255) / 256), block(256);
+        if (strat) hipLaunchKernelGGL((kat_li_filtered_kernel<KY_SMP_STRATIFIED>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out);
+        else hipLaunchKernelGGL((kat_li_filtered_kernel<KY_SMP_RANDOM>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out);
+        return (int)KY_OK;
+    });
+}
+
+}  // extern "C"

@@ -272,6 +272,7 @@ int kyhip_device_count(void) {
 //   feat      the KY_FEAT_* facts of the scene the instantiation assumes
 using RenderFn = void (*)(const DScene*, RenderConst, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);
 using RenderFnS = void (*)(const DScene*, RenderConstS, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a stratified row's kernel: the launch constants carry the strata
+using RenderFnF = void (*)(const DScene*, RenderConstF, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a filtered row's kernel: ... and the pixel filter
 struct Variant {
     bool dbg;
     int strategy;
@@ -282,6 +283,9 @@ struct Variant {
     int drop;   // light classes (kyhip_render_lighting): 0 the unmasked kernel, 1 / 2 / 3 these drop bits at compile time, -1 the launch's bits read at run time
     bool listed;   // passes of a block-tracking frame (kyhip_frame_track_blocks): the work decoder reads the block from the frame's live list (ky_render.hpp, LISTED)
     RenderFnS fn_s;   // KY_SAMPLER_STRATIFIED (dbg is false, fn is null): render_kernel_stratified, which takes RenderConstS; null in every other row
+    RenderFnF fn_f;   // a launch under a pixel filter (fn and fn_s are null): render_kernel_filtered, which takes RenderConstF; null in every other row ...
+    bool f_strat;     // ... and whether it draws with the stratified sampler (else the random one)
+    bool strat() const { return fn_s != nullptr || (fn_f != nullptr && f_strat); }
 };
 #define KY_VARIANT(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel<D, S, Q, G, F, I>, 0}
 #define KY_VARIANT_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel<D, S, Q, G, F, I, true>, 0}
@@ -291,6 +295,8 @@ struct Variant {
 #define KY_VARIANT_LISTED_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel_listed<D, S, Q, G, F, I, true>, 0, true}
 // a stratified row: the strategy, queue, general, feat, integrator of the others, then large, drop and listed as the kernel template takes them
 #define KY_VARIANT_STRAT(S, Q, G, F, I, L, DROP, LISTED) Variant{false, S, Q, G, F, I, L, nullptr, DROP, LISTED, render_kernel_stratified<S, Q, G, F, I, L, DROP, LISTED>}
+// a filtered row (a pixel filter other than the box; strategy -1, any integrator): the sampler kind, general, large, listed
+#define KY_VARIANT_FILT(SMP, G, L, LISTED) Variant{false, -1, false, G, 0, IT, L, nullptr, 0, LISTED, nullptr, render_kernel_filtered<SMP, G, L, LISTED>, SMP == KY_SMP_STRATIFIED}
 // a row's three masked twins: emission at the first vertex dropped (lighting 2, 6), the k = 1 terms (5), both (4)
 #define KY_VARIANT_MASKED3(D, S, Q, G, F, I) KY_VARIANT_MASKED(1, D, S, Q, G, F, I), KY_VARIANT_MASKED(2, D, S, Q, G, F, I), KY_VARIANT_MASKED(3, D, S, Q, G, F, I)
 constexpr int IT = KY_INTEGRATOR_PATH_TRACING_ITERATION;
@@ -418,6 +424,20 @@ static const Variant g_variants[] = {
     KY_VARIANT_STRAT(-1, false, false, 0, IT, false, 0, false),
     KY_VARIANT_STRAT(-1, false, true, 0, IT, false, 0, false),
     KY_VARIANT_STRAT(-1, false, true, 0, IT, true, 0, false),
+    // launches under a pixel filter (kyhip_render_filtered, kyhip_frame_set_filter): the run-time-dispatched kernels only -- {random, stratified} x
+    // {plain, listed} x {not general, general, general + scene-sized LDS block}; no specialised, masked or queue-engine form, and no run-time instantiation
+    KY_VARIANT_FILT(KY_SMP_RANDOM, false, false, false),
+    KY_VARIANT_FILT(KY_SMP_RANDOM, true, false, false),
+    KY_VARIANT_FILT(KY_SMP_RANDOM, true, true, false),
+    KY_VARIANT_FILT(KY_SMP_RANDOM, false, false, true),
+    KY_VARIANT_FILT(KY_SMP_RANDOM, true, false, true),
+    KY_VARIANT_FILT(KY_SMP_RANDOM, true, true, true),
+    KY_VARIANT_FILT(KY_SMP_STRATIFIED, false, false, false),
+    KY_VARIANT_FILT(KY_SMP_STRATIFIED, true, false, false),
+    KY_VARIANT_FILT(KY_SMP_STRATIFIED, true, true, false),
+    KY_VARIANT_FILT(KY_SMP_STRATIFIED, false, false, true),
+    KY_VARIANT_FILT(KY_SMP_STRATIFIED, true, false, true),
+    KY_VARIANT_FILT(KY_SMP_STRATIFIED, true, true, true),
     // everything else: strategy and integrator at run time; the debug sampler; scenes with general shapes
     KY_VARIANT(false, -1, false, false, 0, IT),
     KY_VARIANT(true, -1, false, false, 0, IT),
@@ -431,12 +451,12 @@ static const Variant g_variants[] = {
 constexpr int KY_N_VARIANTS = (int)(sizeof g_variants / sizeof g_variants[0]);
 static_assert(KY_N_VARIANTS <= KY_MAX_VARIANTS, "DeviceCtx::variant_blocks");
 
-static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0, bool listed = false) {
+static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0, bool listed = false, bool filtered = false) {
     const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
     const bool general = packed->general != 0;
     const bool large = packed->n_surfaces > KY_LDS_SURFACES || packed->n_materials > KY_LDS_MATERIALS;
     for (const Variant& v : g_variants) {
-        if (v.dbg != dbg || (v.fn_s != nullptr) != strat || v.large != large || v.listed != listed) continue;
+        if (v.dbg != dbg || v.strat() != strat || (v.fn_f != nullptr) != filtered || v.large != large || v.listed != listed) continue;
         if (v.drop != drop && !(v.drop < 0 && drop != 0)) continue;
         if (general && !v.general) continue;
         if (v.strategy >= 0) {
@@ -504,6 +524,9 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     }
     const RenderConstS rc = make_rc(p);   // (the stratified kernels read all of it, the others its RenderConst)
     const bool strat = p->sampler == KY_SAMPLER_STRATIFIED;
+    // a pass of a frame with a pixel filter; the debug sampler's 0.5 is the pixel's centre under every filter, so its launches are the unfiltered ones
+    const bool filt = pass && pass->filtered && p->sampler != KY_SAMPLER_DEBUG;
+    if (filt && drop != 0) return fail(KY_ERR_INVALID_VALUE, "a launch under a pixel filter has no masked form");
     StreamState* st;
     rcode = get_stream_state(c, stream, &st);
     if (rcode != KY_OK) return rcode;
@@ -545,6 +568,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     // (... nor a masked form: a lighting launch runs on the lane engine too)
     // (... nor passes: a frame's pass runs on the lane engine)
     // (... nor the stratified sampler)
+    // (... nor a pixel filter: a filtered launch is a frame's pass)
     if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single && drop == 0 && !pass && !strat) {
         const int variant = p->sampler == KY_SAMPLER_DEBUG ? 2 : (p->direct_sample == KY_DIRECT_BOTH_MIS ? 0 : 1);
         const int per_cu = c->q_blocks_per_cu[variant] > 0 ? c->q_blocks_per_cu[variant] : 1;
@@ -562,9 +586,10 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     } else {
         // (a frame keeps the kernel of its first pass: the table and run-time instantiations differ in the last bit)
         const bool pinned = pass && pass->kernel != -1;
-        const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop, listed);
+        const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop, listed, filt);
         if (!v) return fail(KY_ERR_DEVICE, "internal: no render kernel for these parameters");
         if (pinned && pass->kernel >= 0 && v->listed != listed) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the block list");
+        if ((v->fn_f != nullptr) != filt) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the pixel filter");
         const int vi = (int)(v - g_variants);
         // run-time instantiation (kyhip_set_jit(1)): this launch's own kernel -- its sampler, strategy and integrator as compile-time constants and ALL
         // of the scene's facts -- unless the table's pick is exactly that already
@@ -572,10 +597,11 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         bool queue = v->queue;
         const int jit_mode = kyjit::mode();
         c->last_note.clear();
-        if (v->strategy < 0 && jit_mode == 0) c->last_note = " [the run-time-dispatched kernel: no row of the table holds this launch's strategy / integrator / shapes; kyhip_set_jit(1 / 2) instantiates its own]";
+        if (filt) c->last_note = " [" + pass->filter_note + ": a filtered launch runs the run-time-dispatched kernel; it takes no specialised row and instantiates no kernel of its own]";
+        else if (v->strategy < 0 && jit_mode == 0) c->last_note = " [the run-time-dispatched kernel: no row of the table holds this launch's strategy / integrator / shapes; kyhip_set_jit(1 / 2) instantiates its own]";
         // (a mode nobody chose -- the default of round 6 -- instantiates only where the table's pick knows nothing of the scene: a launch served by a row of facts stays on it,
         // a scene outside the table of facts gets its own kernel; kyhip_set_jit(1 / 2) / KYHIP_JIT instantiate for every launch that is not exactly a row)
-        const bool jit_wanted = jit_mode != 0 && (!kyjit::mode_by_default() || v->feat == 0 || v->strategy < 0);
+        const bool jit_wanted = !filt && jit_mode != 0 && (!kyjit::mode_by_default() || v->feat == 0 || v->strategy < 0);
         if (pinned && pass->kernel == -3) {   // the frame's own instantiation: loaded on this device by the first pass, and modules stay loaded
             DeviceCtx::JitKernel& k = c->jit[pass->jit_expr];
             if (!k.fn) return fail(KY_ERR_DEVICE, "internal: the frame's kernel render_kernel<%s> is not loaded", pass->jit_expr.c_str());
@@ -599,7 +625,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
             if (!((feat & (KY_FEAT_SINGLE_AREA | KY_FEAT_SINGLE_DELTA)) || env_pair)) feat &= ~KY_FEAT_BOXES;
             const bool want_queue = (p->direct_sample == KY_DIRECT_BOTH_MIS || single || p->direct_sample == KY_DIRECT_LIGHT_MIS || p->direct_sample == KY_DIRECT_LIGHT) &&
                                     p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && sh.n_pix < (1 << 26) && !general && shadow_queue_wanted(scene);
-            const bool same = v->dbg == dbg && (v->fn_s != nullptr) == strat && v->strategy == p->direct_sample && v->queue == want_queue && v->general == general && v->feat == feat &&
+            const bool same = v->dbg == dbg && v->strat() == strat && v->strategy == p->direct_sample && v->queue == want_queue && v->general == general && v->feat == feat &&
                               v->integrator == p->integrator && v->large == large_scene && v->drop == drop && v->listed == listed;
             if (!same) {
                 char expr[192];   // (an unmasked launch's key is what it was: the drop bits are named only where there are some)
@@ -644,7 +670,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         }
         if (!jk && (c->variant_blocks[vi] == 0 || c->variant_lds[vi] != lds_bytes)) {   // resident workgroups per CU: depends on the scene's LDS block
             int per_cu = 0;
-            if (v->fn_s) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_s, 256, lds_bytes));
+            if (v->fn_f) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_f, 256, lds_bytes));
+            else if (v->fn_s) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_s, 256, lds_bytes));
             else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn, 256, lds_bytes));
             c->variant_blocks[vi] = per_cu > 0 ? per_cu : 1;
             c->variant_lds[vi] = lds_bytes;
@@ -681,6 +708,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         if (drop != 0 && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no masked form]";
         if (pass && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine renders no passes]";
         if (strat && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no stratified sampler]";
+        if (filt && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no pixel filter]";
         if (pass) { pass->kernel = jk ? -3 : vi; pass->queue = queue; }
         if (!jk && v->drop < 0 && st->counter_drop != drop) {   // the drop bits of a run-time-dispatched masked kernel: word 2 of the counter block, written when they change
             HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(st->d_counter + 2), drop, 1, stream));
@@ -699,7 +727,12 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
             HIP_TRY(hipModuleLaunchKernel(jk->fn, grid, 1, 1, 256, 1, 1, (unsigned)lds_bytes, stream, args, nullptr));
             c->last_variant = -3;
         } else {
-            if (v->fn_s) hipLaunchKernelGGL(v->fn_s, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc, sh, st->d_counter, accum, flags, queue_mem);
+            if (v->fn_f) {
+                RenderConstF rc_f;
+                static_cast<RenderConstS&>(rc_f) = rc;
+                rc_f.filter = pass->filter;
+                hipLaunchKernelGGL(v->fn_f, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc_f, sh, st->d_counter, accum, flags, queue_mem);
+            } else if (v->fn_s) hipLaunchKernelGGL(v->fn_s, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc, sh, st->d_counter, accum, flags, queue_mem);
             else hipLaunchKernelGGL(v->fn, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc_plain, sh, st->d_counter, accum, flags, queue_mem);
             c->last_variant = vi;
         }
@@ -774,10 +807,11 @@ const char* kyhip_last_kernel(int device) {
     else if (c->last_variant >= 0) {
         const Variant& v = g_variants[c->last_variant];
         char buf[160];
-        snprintf(buf, sizeof buf, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d>", v.dbg ? "debug sampler, " : (v.fn_s ? "stratified sampler, " : ""), v.strategy, v.queue ? ", deferred shadow rays" : "",
+        snprintf(buf, sizeof buf, "render_kernel<%sstrategy %d%s%s%s, feat %d, integrator %d>", v.dbg ? "debug sampler, " : (v.strat() ? "stratified sampler, " : ""), v.strategy, v.queue ? ", deferred shadow rays" : "",
                  v.general ? ", general shapes" : "", v.large ? ", scene-sized LDS block" : "", v.feat, v.integrator);
         name = buf;
         if (v.listed) name.insert(name.size() - 1, ", listed blocks");
+        if (v.fn_f) name.insert(name.size() - 1, ", pixel filter");
         if (v.drop > 0) name.insert(name.size() - 1, ", drop " + std::to_string(v.drop));
         else if (v.drop < 0) name.insert(name.size() - 1, ", drop bits per launch");
     }

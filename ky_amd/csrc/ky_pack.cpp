@@ -666,6 +666,11 @@ bool screen_cull_enabled() {
 // The pixel -> direction map uses the camera's own resolution (cam_inv_w, cam_inv_h), not the launch's: the rectangle is a fact of the scene, in the pixel units of
 // its camera, and clamped to the range of pixels a launch can have rather than to that resolution (a launch wider than its camera's resolution is legal, and its
 // outer pixels see what their rays see).
+// Under a pixel filter the offsets are not in [0, 1): a sample of pixel x leaves through px = x + o with o in [0.5 - R, 0.5 + R], which lies
+// in [x - g, x + 1 + g] for g = ceil(R - 0.5) whole pixels.  The argument above needs only that px lies outside the exact projection's pixels, and it holds for every
+// pixel outside the rectangle grown by g on every side: x + 1 <= x0 - g gives px <= x0, x >= x1 + g gives px >= x1, and the whole pixel of margin is still there.
+// The rectangle stored in the scene stays the box filter's -- a fact of the scene, and part of its hash; a filtered launch's work decoder grows it by g as it
+// reads it (ky_render.hpp), and screen_bound_widen below is the host's statement of the same.
 void screen_bound(const ky_scene* in, int32_t live[4]) {
     live[0] = live[1] = 0; live[2] = live[3] = KY_LIVE_MAX;
     if (!in || !screen_cull_enabled() || in->environment_light >= 0 || in->surface_count <= 0 || !in->surfaces || !in->shapes) return;
@@ -751,6 +756,86 @@ void screen_bound_counts(const int32_t live[4], const ky_render_params* p, long 
     }
     if (dead) *dead = n_dead;
     if (total) *total = sh.n_blocks;
+}
+
+// ---- pixel filters (include/kyhip.h, ky_pixel_filter) ----
+static const char* filter_kind_name(int kind) {
+    return kind == KY_FILTER_BOX ? "box" : kind == KY_FILTER_TENT ? "tent" : kind == KY_FILTER_GAUSSIAN ? "Gaussian" : kind == KY_FILTER_BLACKMAN_HARRIS ? "Blackman-Harris" : "unknown";
+}
+int filter_check(const ky_pixel_filter* f) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "pixel filter is NULL");
+    if (f->kind < KY_FILTER_BOX || f->kind > KY_FILTER_BLACKMAN_HARRIS) return fail(KY_ERR_INVALID_VALUE, "pixel filter: unknown kind %d", f->kind);
+    if (f->reserved != 0) return fail(KY_ERR_INVALID_VALUE, "pixel filter: reserved is %d, not 0", f->reserved);
+    if (f->kind == KY_FILTER_BOX) return KY_OK;
+    if (!std::isfinite(f->radius) || !(f->radius >= 0.5f && f->radius <= (float)KYHIP_FILTER_MAX_RADIUS))
+        return fail(KY_ERR_INVALID_VALUE, "pixel filter: %s radius %g (0.5 .. %d pixels)", filter_kind_name(f->kind), (double)f->radius, KYHIP_FILTER_MAX_RADIUS);
+    if (f->kind == KY_FILTER_GAUSSIAN && (!std::isfinite(f->param) || !(f->param > 0.f)))
+        return fail(KY_ERR_INVALID_VALUE, "pixel filter: Gaussian sigma %g (param: > 0 pixels)", (double)f->param);
+    return KY_OK;
+}
+int filter_grow(const ky_pixel_filter* f) { return filter_is_box(f) ? 0 : (int)std::ceil((double)f->radius - 0.5); }
+std::string filter_describe(const ky_pixel_filter* f) {
+    if (filter_is_box(f)) return "box filter";
+    char buf[96];
+    if (f->kind == KY_FILTER_GAUSSIAN) snprintf(buf, sizeof buf, "Gaussian filter, radius %g, sigma %g", (double)f->radius, (double)f->param);
+    else snprintf(buf, sizeof buf, "%s filter, radius %g", filter_kind_name(f->kind), (double)f->radius);
+    return buf;
+}
+uint64_t filter_fold(uint64_t hash, const ky_pixel_filter* f) {
+    if (filter_is_box(f)) return hash;
+    uint32_t w[3];
+    w[0] = (uint32_t)f->kind;
+    std::memcpy(&w[1], &f->radius, 4);
+    std::memcpy(&w[2], &f->param, 4);
+    if (f->kind != KY_FILTER_GAUSSIAN) w[2] = 0;   // (the other kinds ignore param: it names nothing)
+    for (uint32_t v : w) {   // FNV-1a over the three words, then a 64-bit finaliser: two radii differ in the result whatever the scene
+        hash = (hash ^ v) * 0x100000001b3ull;
+        hash ^= hash >> 29;
+    }
+    return hash * 0x9e3779b97f4a7c15ull + 0x4b59464c54ull;
+}
+// The 1-D distribution F over [-R, R] of a valid filter, analytic, in double.
+static double filter_cdf(const ky_pixel_filter* f, double x) {
+    const double R = f->kind == KY_FILTER_BOX ? 0.5 : (double)f->radius;
+    const double t = x / R;
+    switch (f->kind) {
+    case KY_FILTER_TENT:
+        return t < 0 ? 0.5 * (1 + t) * (1 + t) : 1 - 0.5 * (1 - t) * (1 - t);
+    case KY_FILTER_GAUSSIAN: {
+        // the integral of exp(-x^2 / 2 s^2) - c from -R to x, over the same to R
+        const double s = (double)f->param, k = s * std::sqrt(std::acos(-1.0) / 2), q = s * std::sqrt(2.0);
+        const double c = std::exp(-R * R / (2 * s * s)), eR = std::erf(R / q);
+        return (k * (std::erf(x / q) + eR) - c * (x + R)) / (2 * k * eR - 2 * c * R);
+    }
+    case KY_FILTER_BLACKMAN_HARRIS: {
+        const double pi = std::acos(-1.0), a0 = 0.35875, a1 = 0.48829, a2 = 0.14128, a3 = 0.01168;
+        return ((t + 1) * a0 + (a1 * std::sin(pi * t) + a2 / 2 * std::sin(2 * pi * t) + a3 / 3 * std::sin(3 * pi * t)) / pi) / (2 * a0);
+    }
+    default:
+        return 0.5 * (1 + t);
+    }
+}
+// T[i] = F^-1(i / n), n = KYHIP_FILTER_TABLE: by bisection on F in double for the lower half (F is increasing on [-R, R]), which ends when the bracket's two ends
+// are neighbouring doubles; the upper half is the lower one mirrored (every F here is symmetric), the ends and the middle are exact.  One rounding to float.
+void filter_table(const ky_pixel_filter* f, float* out) {
+    const int n = KYHIP_FILTER_TABLE;
+    const double R = f->kind == KY_FILTER_BOX ? 0.5 : (double)f->radius;
+    out[0] = (float)-R; out[n] = (float)R; out[n / 2] = 0.f;
+    for (int i = 1; i < n / 2; ++i) {
+        const double u = (double)i / n;
+        double lo = -R, hi = 0;
+        for (;;) {
+            const double mid = 0.5 * (lo + hi);
+            if (!(mid > lo && mid < hi)) break;
+            if (filter_cdf(f, mid) < u) lo = mid; else hi = mid;
+        }
+        out[i] = (float)(0.5 * (lo + hi));
+        out[n - i] = -out[i];
+    }
+}
+void screen_bound_widen(const int32_t live[4], const ky_pixel_filter* f, int32_t out[4]) {
+    const int g = filter_grow(f);
+    out[0] = live[0] - g; out[1] = live[1] - g; out[2] = live[2] + g; out[3] = live[3] + g;
 }
 
 int pack_scene(const ky_scene* in, DScene* out) {
@@ -1430,6 +1515,41 @@ int kyhip_scene_screen_bound(const ky_scene* scene, const ky_render_params* para
     rect[0] = std::min(live[0], params->width); rect[1] = std::min(live[1], params->height);
     rect[2] = std::min(live[2], params->width); rect[3] = std::min(live[3], params->height);
     if (counts) screen_bound_counts(live, params, &counts[0], &counts[1]);
+    return KY_OK;
+}
+
+// ... for a launch under a pixel filter: the rectangle its work decoder reads, grown by ceil(radius - 0.5) on every side (screen_bound, the last paragraph)
+int kyhip_scene_screen_bound_filtered(const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter, int rect[4], long long counts[2]) {
+    if (filter_is_box(filter)) return kyhip_scene_screen_bound(scene, params, rect, counts);
+    KY_TRY(filter_check(filter));
+    if (!scene || !rect) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    if (!valid_params(params)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    if (!shard_in_range(params)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices");
+    std::vector<DScene> packed(1);
+    KY_TRY(pack_scene(scene, &packed[0]));
+    int32_t live[4];
+    screen_bound_widen(packed[0].live, filter, live);
+    rect[0] = std::min(std::max(live[0], 0), params->width); rect[1] = std::min(std::max(live[1], 0), params->height);
+    rect[2] = std::min(live[2], params->width); rect[3] = std::min(live[3], params->height);
+    if (counts) screen_bound_counts(live, params, &counts[0], &counts[1]);
+    return KY_OK;
+}
+
+// ---- pixel filters: the host-only entries (filter_check ... above) ----
+int kyhip_filter_check(const ky_pixel_filter* filter) { return filter_check(filter); }
+int kyhip_filter_defaults(int kind, ky_pixel_filter* out) {
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    ky_pixel_filter f = {kind, 0.f, 0.f, 0};
+    if (kind == KY_FILTER_TENT || kind == KY_FILTER_BLACKMAN_HARRIS) f.radius = 2.f;
+    else if (kind == KY_FILTER_GAUSSIAN) { f.radius = 1.5f; f.param = 0.5f; }
+    else if (kind != KY_FILTER_BOX) return fail(KY_ERR_INVALID_VALUE, "pixel filter: unknown kind %d", kind);
+    *out = f;
+    return KY_OK;
+}
+int kyhip_filter_table(const ky_pixel_filter* filter, float* out, int n) {
+    KY_TRY(filter_check(filter));
+    if (!out || n != KYHIP_FILTER_TABLE + 1) return fail(KY_ERR_INVALID_VALUE, "the filter table has %d floats (KYHIP_FILTER_TABLE + 1)", KYHIP_FILTER_TABLE + 1);
+    filter_table(filter, out);
     return KY_OK;
 }
 

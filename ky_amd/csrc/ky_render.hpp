@@ -91,9 +91,13 @@ constexpr int ky_waves_per_eu() {
 // of instantiations) and the extern "C" kernel of a run-time instantiation (ky_jit.cpp).
 // SAMPLER: KY_SMP_RANDOM, KY_SMP_DEBUG (what the `bool DEBUG_SAMPLER` of the kernel templates below converts to) or KY_SMP_STRATIFIED, whose launch constants are the
 // wider RenderConstS.
-template <int SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false>
+// FILTER: the camera sample's offsets are drawn from a pixel filter's density (`fc`; path_begin, ky_device.hpp) and the live rectangle is read fc.grow pixels wider
+// on every side; false -- every instantiation that does not name it -- ignores fc.
+template <int SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false,
+          bool FILTER = false>
 KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderConstFor<SAMPLER>::type rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
-                               unsigned* __restrict__ flags, float4* __restrict__ queue_mem) {
+                               unsigned* __restrict__ flags, float4* __restrict__ queue_mem, FilterConst fc = FilterConst{}) {
+    static_assert(!FILTER || (STRATEGY < 0 && !QUEUE && DROP == 0 && SAMPLER != KY_SMP_DEBUG), "the filtered kernels are the run-time-dispatched ones, unmasked");
     static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || ky_direct_is_single(STRATEGY) || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
                   "the deferred shadow rays belong to the iterative integrator's strategies with a light-sampling half");
     static_assert(FEAT == 0 || (STRATEGY >= 0 && !GENERAL && SAMPLER != KY_SMP_DEBUG), "scene facts are instantiated for kernels with a fixed strategy only");
@@ -229,7 +233,8 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderCon
                     const int trow = tile / sh.tiles_x, tcol = (tile % sh.tiles_x + trow) % sh.tiles_x;   // rotated rows
                     it.x0 = tcol * sh.tile_w + bx * 8;
                     it.y0 = trow * sh.tile_h + by * 8;
-                    const int4 live = scene_at<int4>(S, opaque_off((unsigned)__builtin_offsetof(DScene, live)));
+                    int4 live = scene_at<int4>(S, opaque_off((unsigned)__builtin_offsetof(DScene, live)));
+                    if constexpr (FILTER) { live.x -= fc.grow; live.y -= fc.grow; live.z += fc.grow; live.w += fc.grow; }   // a filter's offsets reach fc.grow pixels beyond the pixel (screen_bound, ky_pack.cpp)
                     dead = (it.x0 + 8 <= live.x || it.x0 >= live.z || it.y0 + 8 <= live.y || it.y0 >= live.w) ? 1 : 0;
                     it.pix0 = (k * sh.tile_h + by * 8) * sh.tile_w + bx * 8;
                     chunk_range(chunk_plan(rc.spp), c, it.s_begin, it.s_end);
@@ -275,7 +280,8 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderCon
                 const int xy = c_xy[tid];
                 const unsigned se = c_se[tid];
                 const uint32_t key = QUEUE ? sampler_pixel_key(rc.seed, (uint32_t)((xy >> 16) * rc.width + (xy & 0xffff))) : c_key[tid];
-                path_begin<SAMPLER, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7));
+                if constexpr (FILTER) path_begin<SAMPLER, true, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
+                else path_begin<SAMPLER, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7));
                 c_se[tid] = se + 127;             // next sample + 1, samples left - 1
                 open = (se & 127) > 1;
                 alive = true;
@@ -351,4 +357,14 @@ __global__ __launch_bounds__(256, (ky_waves_per_eu<KY_SMP_STRATIFIED, STRATEGY, 
     const DScene* __restrict__ S_, RenderConstS rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
     float4* __restrict__ queue_mem) {
     render_kernel_body<KY_SMP_STRATIFIED, STRATEGY, QUEUE, GENERAL, FEAT, INTEGRATOR, LARGE, DROP, LISTED>(S_, rc, sh, counter, accum, flags, queue_mem);
+}
+
+// The filtered instantiations (a pixel filter other than the box: kyhip_render_filtered, kyhip_frame_set_filter), plain and listed, for the random and the stratified
+// sampler: a kernel template of their own once more, whose launch constants carry the filter (RenderConstF).  Run-time-dispatched kernels only (strategy -1).
+template <int SAMPLER, bool GENERAL = false, bool LARGE = false, bool LISTED = false>
+__global__ __launch_bounds__(256, (ky_waves_per_eu<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED>())) void render_kernel_filtered(
+    const DScene* __restrict__ S_, RenderConstF rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
+    float4* __restrict__ queue_mem) {
+    static_assert(SAMPLER == KY_SMP_RANDOM || SAMPLER == KY_SMP_STRATIFIED, "the debug sampler ignores the filter: its launches run the unfiltered kernels");
+    render_kernel_body<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED, true>(S_, rc, sh, counter, accum, flags, queue_mem, rc.filter);
 }

@@ -308,5 +308,17 @@ struct RenderConstS : RenderConst {
 enum : int { KY_SMP_RANDOM = 0, KY_SMP_DEBUG = 1, KY_SMP_STRATIFIED = 2 };
 template <int SAMPLER> struct RenderConstFor { typedef RenderConst type; };
 template <> struct RenderConstFor<KY_SMP_STRATIFIED> { typedef RenderConstS type; };
+// A pixel filter (ky_pixel_filter) as a launch carries it: the kind and radius, the pixels the live rectangle grows by on every side
+// (ceil(radius - 0.5): ky_pack.cpp, screen_bound) and the inverse-CDF table in device memory, KYHIP_FILTER_TABLE + 1 floats (the tent reads none).  Only the
+// filtered kernels take the wider block, whichever sampler they draw with: every other kernel's arguments stay where they were.
+struct FilterConst {
+    int kind;
+    float radius;
+    int grow;
+    const float* table;
+};
+struct RenderConstF : RenderConstS {
+    FilterConst filter;
+};
 
 }  // namespace kyd

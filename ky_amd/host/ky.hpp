@@ -99,8 +99,54 @@ struct bounds3_t {
 inline float clamp01(float x) { return x < 0 ? 0 : (x > 1 ? 1 : x); }
 inline uint8_t gamma_encoding(float x) { return (uint8_t)(std::pow((double)clamp01(x), 1 / 2.2) * 255 + .5); }  // 1548
 
+// Pixel reconstruction filters (the reference's empty `#pragma region filter`, ky.cpp:1525-1527; include/kyhip.h, ky_pixel_filter): owned by the film, where pbrt
+// keeps them.  Rendered by filter importance sampling: the camera sample's offset is drawn from the filter's density and lands in its own pixel with weight 1.
+class filter_t {
+public:
+    virtual ~filter_t() = default;
+    virtual ky_pixel_filter c() const = 0;   // what the C ABI takes
+    float radius() const { return c().radius; }
+};
+class box_filter_t : public filter_t {   // today's camera sample: uniform over the pixel
+public:
+    ky_pixel_filter c() const override { return ky_pixel_filter{KY_FILTER_BOX, 0.f, 0.f, 0}; }
+};
+class triangle_filter_t : public filter_t {
+public:
+    explicit triangle_filter_t(float radius = 2.f) : radius_(radius) {}
+    ky_pixel_filter c() const override { return ky_pixel_filter{KY_FILTER_TENT, radius_, 0.f, 0}; }
+private:
+    float radius_;
+};
+class gaussian_filter_t : public filter_t {   // exp(-x^2 / 2 sigma^2) - exp(-radius^2 / 2 sigma^2) on |x| < radius
+public:
+    explicit gaussian_filter_t(float radius = 1.5f, float sigma = 0.5f) : radius_(radius), sigma_(sigma) {}
+    ky_pixel_filter c() const override { return ky_pixel_filter{KY_FILTER_GAUSSIAN, radius_, sigma_, 0}; }
+private:
+    float radius_, sigma_;
+};
+class blackman_harris_filter_t : public filter_t {   // the four-term window over [-radius, radius]
+public:
+    explicit blackman_harris_filter_t(float radius = 2.f) : radius_(radius) {}
+    ky_pixel_filter c() const override { return ky_pixel_filter{KY_FILTER_BLACKMAN_HARRIS, radius_, 0.f, 0}; }
+private:
+    float radius_;
+};
+
 class film_t {
 public:
+    // The film's reconstruction filter: the box until set_filter.  Every render entry of integrator_t reads it from the film it renders into; an invalid filter
+    // (kyhip_filter_check) is refused here.
+    void set_filter(std::unique_ptr<filter_t> filter) {
+        if (filter) {
+            const ky_pixel_filter f = filter->c();
+            if (kyhip_filter_check(&f) != KY_OK) throw std::runtime_error(std::string("film_t::set_filter: ") + kyhip_last_error());
+        }
+        filter_ = std::move(filter);
+    }
+    const filter_t* filter() const { return filter_.get(); }
+    ky_pixel_filter pixel_filter() const { return filter_ ? filter_->c() : ky_pixel_filter{KY_FILTER_BOX, 0.f, 0.f, 0}; }
+
     // The reference's film owns its pixels (`new color_t[]`, 1559).  Here they come from kyhip_film_alloc -- pinned host memory the GPU adds to in place
     // (include/kyhip.h: no staging copy, no host pass at the end of render()) -- and from ordinary memory where that returns NULL (no device).
     film_t(int width, int height) : width_(width), height_(height), count_((size_t)width * height) {
@@ -196,6 +242,7 @@ protected:
     size_t count_;
     color_t* pixels_ = nullptr;
     bool pinned_ = false;
+    std::unique_ptr<filter_t> filter_;
 };
 
 // mosaic of sub-films (1802-1836): render() targets the current cell
@@ -697,6 +744,14 @@ public:
     // current target.  Errors of the C ABI surface as exceptions, like the reference's LOG_ERROR (75-82).
     void render(scene_t* scene, sampler_t* original_sampler, film_t* film) {
         const ky_render_params p = params_for(original_sampler, film);
+        const ky_pixel_filter flt = film->pixel_filter();
+        if (flt.kind != KY_FILTER_BOX) {   // the film's pixel filter (film_t::set_filter): kyhip_render_filtered, on ONE device -- no masked form, no kyhip_render_multi
+            if (masked()) throw std::runtime_error("integrator_t::render: light classes are rendered under the box filter only");
+            if (devices_.size() != 1) throw std::runtime_error("integrator_t::render: a film with a pixel filter renders on one device (render_sliced spreads a filtered frame over several)");
+            const int rc = kyhip_render_filtered(devices_[0], &scene->flatten(), &p, &flt, film->target_origin(), film->row_stride_px());
+            if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_filtered: ") + kyhip_last_error());
+            return;
+        }
         if (masked()) {   // light classes (set_lighting): kyhip_render_lighting, which renders on ONE device: devices_[0]; the rest of a list given to set_devices is not used
                           // (a masked kyhip_render_multi is out of scope; the image does not depend on the list)
             const int rc = kyhip_render_lighting(devices_[0], &scene->flatten(), &p, lighting_, film->target_origin(), film->row_stride_px());
@@ -707,6 +762,14 @@ public:
         const int rc = kyhip_render_multi(devices_.data(), (int)devices_.size(), &scene->flatten(), &p, film->target_origin(), film->row_stride_px());
         if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_multi: ") + kyhip_last_error());
     }
+    // the film's pixel filter into a frame that has just begun (the box: nothing to do); own: end the frame before throwing
+    static void frame_filter(kyhip_frame* frame, const film_t* film, bool own = true) {
+        const ky_pixel_filter flt = film->pixel_filter();
+        if (flt.kind == KY_FILTER_BOX || kyhip_frame_set_filter(frame, &flt) == KY_OK) return;
+        const std::string what = std::string("kyhip_frame_set_filter: ") + kyhip_last_error();
+        if (own) kyhip_frame_end(frame);
+        throw std::runtime_error(what);
+    }
     // render() in passes (kyhip_frame_*, include/kyhip.h): the frame's samples are rendered min_samples_per_pass (or a few more: whole chunks) at a time on
     // devices_[0], and after each pass on_pass(done, total) is called -- where the reference prints "rendering... N spp, x%" (3703).  When it returns false,
     // or the frame is complete, the picture is added to the film like render() adds it: the mean of the samples done if the frame was stopped early, and for
@@ -716,6 +779,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        frame_filter(frame, film);
         try {
             int done = 0;
             bool go_on = true;
@@ -753,6 +817,7 @@ public:
             for (int k = 0; k < n; ++k) {
                 if (kyhip_frame_begin_slice(devices[(size_t)k], &flat, &p, bounds[(size_t)k], bounds[(size_t)k + 1], &frames[(size_t)k]) != KY_OK)
                     throw std::runtime_error(std::string("kyhip_frame_begin_slice: ") + kyhip_last_error());
+                frame_filter(frames[(size_t)k], film, false);   // (end_all below ends every frame)
                 bool seen = false;
                 for (int d : distinct) seen = seen || d == devices[(size_t)k];
                 if (!seen) distinct.push_back(devices[(size_t)k]);
@@ -813,6 +878,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        frame_filter(frame, film);
         int done = 0;
         try {
             ky_noise_stats st;
@@ -839,6 +905,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        frame_filter(frame, film);
         int done = 0;
         try {
             if (kyhip_frame_track_noise(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_noise: ") + kyhip_last_error());
@@ -869,6 +936,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
+        frame_filter(frame, film);
         ky_block_stats st{};
         try {
             int done = 0;

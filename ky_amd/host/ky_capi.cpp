@@ -117,6 +117,41 @@ int kyhost_render_lighting(void* scene, int integrator_enum, int depth, int dire
     return render_impl(scene, integrator_enum, depth, direct_sample_enum, sampler_kind, spp, seed, width, height, grid_rows, grid_cols, cell, film, device, lighting);
 }
 
+// film_t::set_filter then one of the integrator's render entries on a film_t of width x height: the film's pixel filter (ky.hpp, filter_t) through the host mirror.
+// filter_kind: ky_filter_kind, with `radius` and `param` (the Gaussian's sigma).  mode 0: render(); 1: render_passes(min_samples_per_pass) to the end; 2:
+// render_sliced over {device, device}; 3: render_until with a threshold nothing reaches (it renders to the end and adds the mean of all samples).
+// `film` is read, added to and written back.  Returns 0, -1 on error, -2 when create_integrator returns nullptr.
+int kyhost_render_filtered(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
+                           float* film, int device, int filter_kind, float radius, float param, int mode, int min_samples_per_pass) {
+    int status = 0;
+    int rc = guarded([&] {
+        std::unique_ptr<ky::integrator_t> integrator;
+        const auto ie = (ky::integrator_enum_t)integrator_enum;
+        if (ie == ky::integrator_enum_t::position || ie == ky::integrator_enum_t::normal || ie == ky::integrator_enum_t::basecolor)
+            integrator = std::make_unique<ky::debug_integrator_t>(ie, device);
+        else
+            integrator = ky::create_integrator(ie, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
+        if (!integrator) { status = -2; return; }
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
+        ky::film_t f(width, height);
+        if (filter_kind == KY_FILTER_BOX) f.set_filter(std::make_unique<ky::box_filter_t>());
+        else if (filter_kind == KY_FILTER_TENT) f.set_filter(std::make_unique<ky::triangle_filter_t>(radius));
+        else if (filter_kind == KY_FILTER_GAUSSIAN) f.set_filter(std::make_unique<ky::gaussian_filter_t>(radius, param));
+        else if (filter_kind == KY_FILTER_BLACKMAN_HARRIS) f.set_filter(std::make_unique<ky::blackman_harris_filter_t>(radius));
+        else throw std::runtime_error("kyhost_render_filtered: unknown filter kind");
+        const size_t n = (size_t)f.get_pixel_num() * 3;
+        std::memcpy(f.data(), film, n * sizeof(float));
+        ky::scene_t* sc = &((scene_box*)scene)->scene;
+        if (mode == 0) integrator->render(sc, sampler.get(), &f);
+        else if (mode == 1) integrator->render_passes(sc, sampler.get(), &f, min_samples_per_pass, {});
+        else if (mode == 2) integrator->render_sliced(sc, sampler.get(), &f, std::vector<int>{device, device}, min_samples_per_pass);
+        else if (mode == 3) integrator->render_until(sc, sampler.get(), &f, 0.f, 0.f, 2, min_samples_per_pass);
+        else throw std::runtime_error("kyhost_render_filtered: mode 0 .. 3");
+        std::memcpy(film, f.data(), n * sizeof(float));
+    });
+    return rc != 0 ? rc : status;
+}
+
 // create_integrator(...)->render_passes(&scene, sampler, &film, min_samples_per_pass, on_pass) on a film_t of width x height; on_pass(done, total, user) returns
 // nonzero to go on (NULL: render to the end).  `film` is read, added to and written back.  Returns 0, -1 on error, -2 when create_integrator returns nullptr.
 int kyhost_render_passes(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,

@@ -82,3 +82,18 @@ if not ONLY or "light_pick" in ONLY:
             differ = g[:, 0].astype(np.int64) != li
             print("light_pick %-18s %-7s rows %d  max |p - restatement| %.3e (0.999 quantile %.3e)  index differs on %d, beyond P_TOL of an edge %d, largest margin among them %.3e"
                   % (which, rule, len(rows), d.max(), np.quantile(d.max(axis=1), 0.999), int(differ.sum()), int((differ & (margin > P.P_TOL)).sum()), float(margin[differ].max()) if differ.any() else 0.0))
+# pixel filters (tests/test_filter.py; no GPU): how far the library's 256-interval inverse-CDF table strays from the analytic CDF (the test's DEVIATION), and the
+# two quadratures of the centring test against each other -- the restatement's warp of a 16 x 16 grid of u through kyo_li_tape against the oracle's 16x-supersampled
+# base-colour picture weighted by the analytic filter (the test's CENTRING; its bound is 2 x these) -- with the same for a warp centred on the pixel's corner
+if not ONLY or "filter" in ONLY:
+    import filter_restatement as F
+    import test_filter as TF
+    for case, _ in TF.DEVIATION:
+        f, flt = TF.both(api, *case)
+        print("filter table deviation", flt, "%.4e" % F.table_deviation(flt, api.filter_table(f)))
+    O.load()
+    base = TF.basecolor.__wrapped__(O, A, api) if hasattr(TF.basecolor, "__wrapped__") else None
+    if base is not None:
+        for kind, radius, param, _ in TF.CENTRING:
+            flt = F.Filter(kind, radius, param)
+            print("filter centring", flt, "rmse %.4e" % TF.centring_rmse(O, base, flt), "corner-centred %.4e" % TF.centring_rmse(O, base, flt, shift=-0.5))
