@@ -4,6 +4,7 @@
  * radiance with or without a vertex trace, the random-number streams by key -- on caller-supplied inputs, for tests/test_parity_gpu.py to compare with the
  * oracle (the streams: tests/test_sampler_gpu.py, with a restatement that shares no code with either).  Test surface
  * of the library, not part of a render; the kernels are the product's device functions (ky_device.hpp) called directly.
+ * The kernels come first and the entry points after them, both in the same order, by subject.
  */
 #include <cstring>
 #include <vector>
@@ -55,6 +56,28 @@ __global__ void kat_bsdf_kernel(DMat M, const float* __restrict__ in12, int n, f
     float* q = out13 + 13 * (size_t)i;
     q[0] = bs.f.x; q[1] = bs.f.y; q[2] = bs.f.z; q[3] = bs.wi.x; q[4] = bs.wi.y; q[5] = bs.wi.z; q[6] = bs.pdf;
     q[7] = (float)bs.flags; q[8] = ev.x; q[9] = ev.y; q[10] = ev.z; q[11] = pd; q[12] = bsdf_is_delta(B) ? 1.f : 0.f;
+}
+
+// the same rows and the same vertex through what the render kernels execute: bsdf_continue (the iterative integrator's sample: direction, value |cos| / pdf in one
+// factor, whether the path goes on) and bsdf_eval_parts (the light-sampling estimators' evaluation as two factors).  256 rows per workgroup in order: a wave is 64
+// consecutive rows, which is what phong_pow_lobe's vote sees.  FLAT_PHONG: a compile-time fact here as in the render kernels (KY_FEAT_FLAT_PHONG).
+template <bool FLAT_PHONG>
+__global__ void kat_bsdf_continue_kernel(DMat M, const float* __restrict__ in12, int n, float* __restrict__ out12) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* r = in12 + 12 * (size_t)i;
+    const f3 normal = ld3(r), wo = ld3(r + 3), wi_eval = ld3(r + 8);
+    Vertex v;
+    v.normal = normal;
+    v.bsdf = make_bsdf(M, r[11]);
+    vertex_prepare(v, wo);
+    const BsdfContinue c = bsdf_continue(v, wo, r[6], r[7], FLAT_PHONG);
+    f3 col; float scale, pd, abs_cos_i;
+    bsdf_eval_parts(v, wo, wi_eval, col, scale, pd, abs_cos_i);
+    const f3 ev = col * scale;
+    float* q = out12 + 12 * (size_t)i;
+    q[0] = c.wi.x; q[1] = c.wi.y; q[2] = c.wi.z; q[3] = c.weight.x; q[4] = c.weight.y; q[5] = c.weight.z;
+    q[6] = c.ok ? 1.f : 0.f; q[7] = c.specular ? 1.f : 0.f; q[8] = ev.x; q[9] = ev.y; q[10] = ev.z; q[11] = pd;
 }
 
 __global__ void kat_light_kernel(const DScene* __restrict__ S, int li, const float* __restrict__ in11, int n, float* __restrict__ out11) {
@@ -113,67 +136,6 @@ __global__ void kat_any_pair_kernel(const DScene* __restrict__ S_, const float* 
     trace_any_pair(S, A, B, occ_a, occ_b);
     out2[2 * (size_t)i] = occ_a ? 1.f : 0.f;
     out2[2 * (size_t)i + 1] = occ_b ? 1.f : 0.f;
-}
-
-// BOXES: the launch these samples replay runs a kernel with the box traversal (render_uses_boxes): the replay takes the same one, so that "per sample what render() did" holds
-// to the last decision (a ray along a box's edge may take the other face in the other traversal)
-// single_env (a run-time flag: these kernels are not timed): ... whose both_mis estimate is estimate_env_both (KY_FEAT_SINGLE_ENV): the replay takes that too
-template <bool DEBUG_SAMPLER, bool BOXES>
-__global__ void kat_li_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env) {
-    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));   // KAT kernels: always the scene-sized dynamic block
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    PathState ps;
-    bool alive = i < n;
-    if (alive) path_begin<DEBUG_SAMPLER>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i);
-    while (__any(alive)) {  // path_shade is a wave-uniform call
-        Vertex v;
-        bool have_vertex = false;
-        if (alive) have_vertex = path_intersect<DEBUG_SAMPLER>(ps, v, S, Lds, rc);
-        const bool cont = path_shade<DEBUG_SAMPLER>(ps, v, S, Lds, rc, have_vertex);
-        alive = have_vertex && cont;
-    }
-    if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
-}
-
-// kat_li_kernel for a masked launch (kyhip_render_lighting): the same walk with the launch's drop bits (path_intersect, ky_device.hpp)
-template <bool DEBUG_SAMPLER, bool BOXES>
-__global__ void kat_li_lighting_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env, int drop) {
-    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    PathState ps;
-    bool alive = i < n;
-    if (alive) path_begin<DEBUG_SAMPLER>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i);
-    while (__any(alive)) {  // path_shade is a wave-uniform call
-        Vertex v;
-        bool have_vertex = false;
-        if (alive) have_vertex = path_intersect<DEBUG_SAMPLER, -1>(ps, v, S, Lds, rc, drop);
-        const bool cont = path_shade<DEBUG_SAMPLER, -1>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, nullptr, 0, false, false, drop);
-        alive = have_vertex && cont;
-    }
-    if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
-}
-
-// kat_li_kernel and kat_li_lighting_kernel under the stratified sampler (KY_SAMPLER_STRATIFIED), whose launch constants carry the strata (RenderConstS): the same walk,
-// the drop bits read at run time (0 for kyhip_kat_li)
-template <bool BOXES>
-__global__ void kat_li_stratified_kernel(const DScene* __restrict__ S_, RenderConstS rc, int x, int y, int s0, int n, float* __restrict__ out3, int single_env, int drop) {
-    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    PathStateFor<KY_SMP_STRATIFIED> ps;
-    sampler_bind(ps.smp, rc);
-    bool alive = i < n;
-    if (alive) path_begin<KY_SMP_STRATIFIED>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i);
-    while (__any(alive)) {  // path_shade is a wave-uniform call
-        Vertex v;
-        bool have_vertex = false;
-        if (alive) have_vertex = path_intersect<KY_SMP_STRATIFIED, -1>(ps, v, S, Lds, rc, drop);
-        const bool cont = path_shade<KY_SMP_STRATIFIED, -1>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, nullptr, 0, false, false, drop);
-        alive = have_vertex && cont;
-    }
-    if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
 }
 
 // one light's direct-lighting estimate at given vertices with given random numbers (estimate_direct_lighting_*, 3889-4088)
@@ -237,384 +199,8 @@ __global__ void kat_single_light_kernel(const DScene* __restrict__ S, const floa
     }
 }
 
-// one camera sample, traced vertex by vertex (lane 0 walks the path; the other lanes only keep the wave-uniform calls company)
-template <bool DEBUG_SAMPLER, bool BOXES>
-__global__ void kat_li_trace_kernel(const DScene* __restrict__ S_, RenderConst rc, int x, int y, int s, int max_rows, float* __restrict__ out, int single_env) {
-    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));   // KAT kernels: always the scene-sized dynamic block
-    PathState ps;
-    bool alive = threadIdx.x == 0;
-    VertexTrace tr{out + 4, max_rows, 0};
-    if (alive) path_begin<DEBUG_SAMPLER>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s);
-    while (__any(alive)) {
-        Vertex v;
-        bool have_vertex = false;
-        if (alive) have_vertex = path_intersect<DEBUG_SAMPLER>(ps, v, S, Lds, rc);
-        const bool cont = path_shade<DEBUG_SAMPLER>(ps, v, S, Lds, rc, have_vertex, -1, &tr);
-        alive = have_vertex && cont;
-    }
-    if (threadIdx.x == 0) { out[0] = (float)tr.n; out[1] = ps.Lo.x; out[2] = ps.Lo.y; out[3] = ps.Lo.z; }
-}
-
-// kat_li_trace_kernel under the stratified sampler
-template <bool BOXES>
-__global__ void kat_li_trace_stratified_kernel(const DScene* __restrict__ S_, RenderConstS rc, int x, int y, int s, int max_rows, float* __restrict__ out, int single_env) {
-    const SceneRef S{S_, true, (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
-    PathStateFor<KY_SMP_STRATIFIED> ps;
-    sampler_bind(ps.smp, rc);
-    bool alive = threadIdx.x == 0;
-    VertexTrace tr{out + 4, max_rows, 0};
-    if (alive) path_begin<KY_SMP_STRATIFIED>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s);
-    while (__any(alive)) {
-        Vertex v;
-        bool have_vertex = false;
-        if (alive) have_vertex = path_intersect<KY_SMP_STRATIFIED>(ps, v, S, Lds, rc);
-        const bool cont = path_shade<KY_SMP_STRATIFIED>(ps, v, S, Lds, rc, have_vertex, -1, &tr);
-        alive = have_vertex && cont;
-    }
-    if (threadIdx.x == 0) { out[0] = (float)tr.n; out[1] = ps.Lo.x; out[2] = ps.Lo.y; out[3] = ps.Lo.z; }
-}
-
-// the same rows and the same vertex through what the render kernels execute: bsdf_continue (the iterative integrator's sample: direction, value |cos| / pdf in one
-// factor, whether the path goes on) and bsdf_eval_parts (the light-sampling estimators' evaluation as two factors).  256 rows per workgroup in order: a wave is 64
-// consecutive rows, which is what phong_pow_lobe's vote sees.  FLAT_PHONG: a compile-time fact here as in the render kernels (KY_FEAT_FLAT_PHONG).
-template <bool FLAT_PHONG>
-__global__ void kat_bsdf_continue_kernel(DMat M, const float* __restrict__ in12, int n, float* __restrict__ out12) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* r = in12 + 12 * (size_t)i;
-    const f3 normal = ld3(r), wo = ld3(r + 3), wi_eval = ld3(r + 8);
-    Vertex v;
-    v.normal = normal;
-    v.bsdf = make_bsdf(M, r[11]);
-    vertex_prepare(v, wo);
-    const BsdfContinue c = bsdf_continue(v, wo, r[6], r[7], FLAT_PHONG);
-    f3 col; float scale, pd, abs_cos_i;
-    bsdf_eval_parts(v, wo, wi_eval, col, scale, pd, abs_cos_i);
-    const f3 ev = col * scale;
-    float* q = out12 + 12 * (size_t)i;
-    q[0] = c.wi.x; q[1] = c.wi.y; q[2] = c.wi.z; q[3] = c.weight.x; q[4] = c.weight.y; q[5] = c.weight.z;
-    q[6] = c.ok ? 1.f : 0.f; q[7] = c.specular ? 1.f : 0.f; q[8] = ev.x; q[9] = ev.y; q[10] = ev.z; q[11] = pd;
-}
-
-// the bit patterns of the first k numbers of the stream the render kernels give the key (seed, pixel_index, sample_index): sampler_pixel_key, sampler_start
-// and sampler_next as path_begin calls them.  One thread per key; its k words lie together.
-template <bool DEBUG_SAMPLER>
-__global__ void kat_sampler_kernel(uint32_t seed, const uint32_t* __restrict__ keys2, int n, int k, uint32_t* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Sampler smp;
-    sampler_start(smp, sampler_pixel_key(seed, keys2[2 * (size_t)i]), keys2[2 * (size_t)i + 1]);
-    uint32_t* q = out + (size_t)i * (size_t)k;
-    for (int j = 0; j < k; ++j) q[j] = __float_as_uint(sampler_next<DEBUG_SAMPLER>(smp));
-}
-// ... of the stratified sampler: sampler_start_kind and sampler_next as the render kernels' later draws call them, or -- camera != 0 -- the first two through
-// sampler_camera, which is how path_begin draws them
-__global__ void kat_sampler_stratified_kernel(uint32_t seed, RenderConstS rc, int camera, const uint32_t* __restrict__ keys2, int n, int k, uint32_t* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    StratSampler smp;
-    sampler_bind(smp, rc);
-    sampler_start_kind<KY_SMP_STRATIFIED>(smp, sampler_pixel_key(seed, keys2[2 * (size_t)i]), keys2[2 * (size_t)i + 1]);
-    uint32_t* q = out + (size_t)i * (size_t)k;
-    int j = 0;
-    if (camera && k >= 2) {
-        float u0, u1;
-        sampler_camera<KY_SMP_STRATIFIED>(smp, u0, u1);
-        q[0] = __float_as_uint(u0); q[1] = __float_as_uint(u1);
-        j = 2;
-    }
-    for (; j < k; ++j) q[j] = __float_as_uint(sampler_next<KY_SMP_STRATIFIED>(smp));
-}
-
-// shared driver of the KAT entry points
-template <typename F>
-static int kat_run(int device, const void* in, size_t in_bytes, void* out, size_t out_bytes, F launch) {
-    DeviceCtx* c;
-    int rcode = get_ctx(device, &c);
-    if (rcode != KY_OK) return rcode;
-    std::lock_guard<std::mutex> lock(c->m);
-    DevBuf d_in, d_out;
-    HIP_TRY(d_in.alloc(in_bytes));
-    HIP_TRY(d_out.alloc(out_bytes));
-    HIP_TRY(hipDeviceSynchronize());   // KAT entries use the default stream and may replace the device's scene copy
-    HIP_TRY(hipMemcpy(d_in.p, in, in_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_out.p, 0, out_bytes));
-    rcode = launch(c, d_in.as<const float>(), d_out.as<float>());
-    if (rcode != KY_OK) return rcode;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
-    return KY_OK;
-}
-
-extern "C" {
-
-// ---- KAT entry points ----
-int kyhip_kat_intersect(int device, const ky_shape* shape, const float* rays7, int n, float* out8) {
-    if (!shape || !rays7 || !out8 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    if (shape->kind < KY_SHAPE_DISK || shape->kind > KY_SHAPE_SPHERE) return fail(KY_ERR_INVALID_VALUE, "unknown shape kind");
-    if (!shape_normal_ok(*shape)) return fail(KY_ERR_INVALID_VALUE, "the stored normal must be unit length");
-    KatShape ks{};
-    pack_shape(*shape, 0, &ks.surf, &ks.full);
-    cp3(ks.hit.n, shape->kind == KY_SHAPE_SPHERE ? shape->p[0] : shape->normal);
-    ks.hit.kind = shape->kind;
-    return kat_run(device, rays7, (size_t)n * 7 * 4, out8, (size_t)n * 8 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
-        hipLaunchKernelGGL(kat_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, ks, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-int kyhip_kat_camera(int device, const ky_camera* camera, const float* p_film2, int n, float* out6) {
-    if (!camera || !p_film2 || !out6 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    ky_scene sc{};
-    sc.environment_light = -1;
-    sc.camera = *camera;
-    if (!(camera->resolution[0] > 0) || !(camera->resolution[1] > 0)) return fail(KY_ERR_INVALID_VALUE, "bad camera resolution");
-    return kat_run(device, p_film2, (size_t)n * 2 * 4, out6, (size_t)n * 6 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* slot; int r = upload_scene(c, &sc, 0, &slot);
-        if (r != KY_OK) return r;
-        hipLaunchKernelGGL(kat_camera_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, (const DScene*)slot->d, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-int kyhip_kat_bsdf(int device, const ky_material* m, const float* in12, int n, float* out13) {
-    if (!m || !in12 || !out13 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    if (m->kind < KY_MATERIAL_MATTE || m->kind > KY_MATERIAL_PLASTIC) return fail(KY_ERR_INVALID_VALUE, "unknown material kind");
-    DMat d{};
-    pack_material(*m, &d);
-    return kat_run(device, in12, (size_t)n * 12 * 4, out13, (size_t)n * 13 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
-        hipLaunchKernelGGL(kat_bsdf_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-int kyhip_kat_light(int device, const ky_scene* scene, int light, const float* in11, int n, float* out11) {
-    if (!scene || !in11 || !out11 || n <= 0 || light < 0 || light >= scene->light_count) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    return kat_run(device, in11, (size_t)n * 11 * 4, out11, (size_t)n * 11 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        hipLaunchKernelGGL(kat_light_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, (const DScene*)sc->d, light, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-int kyhip_kat_scene_intersect(int device, const ky_scene* scene, const float* rays7, int n, float* out9) {
-    if (!scene || !rays7 || !out9 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    return kat_run(device, rays7, (size_t)n * 7 * 4, out9, (size_t)n * 9 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        if (sc->h->feat & KY_FEAT_BOXES)
-            hipLaunchKernelGGL(kat_scene_intersect_kernel<true>, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, d_in, n, d_out);
-        else
-            hipLaunchKernelGGL(kat_scene_intersect_kernel<false>, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-static int kat_occluded_impl(int device, const ky_scene* scene, const float* in9, int n, float* out1, int table) {
-    if (!scene || !in9 || !out1 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    if (table >= scene->light_count) return fail(KY_ERR_INVALID_VALUE, "light %d out of range", table);
-    return kat_run(device, in9, (size_t)n * 9 * 4, out1, (size_t)n * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        hipLaunchKernelGGL(kat_occluded_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, (const DScene*)sc->d, d_in, n, d_out, table);
-        return (int)KY_OK;
-    });
-}
-int kyhip_kat_occluded(int device, const ky_scene* scene, const float* in9, int n, float* out1) { return kat_occluded_impl(device, scene, in9, n, out1, -2); }
-int kyhip_kat_any_pair(int device, const ky_scene* scene, const float* in13, int n, float* out2) {
-    if (!scene || !in13 || !out2 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    return kat_run(device, in13, (size_t)n * 13 * 4, out2, (size_t)n * 2 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        if (sc->h->feat & KY_FEAT_BOXES) hipLaunchKernelGGL(kat_any_pair_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, (const DScene*)sc->d, d_in, n, d_out);
-        else hipLaunchKernelGGL(kat_any_pair_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, (const DScene*)sc->d, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-int kyhip_kat_occluded_between(int device, const ky_scene* scene, int light, const float* in9, int n, float* out1) {
-    if (light < -1) return fail(KY_ERR_INVALID_VALUE, "light %d out of range", light);
-    return kat_occluded_impl(device, scene, in9, n, out1, light);
-}
-
-int kyhip_kat_li(int device, const ky_scene* scene, const ky_render_params* p, int x, int y, int s0, int n, float* out3) {
-    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
-    if (!scene || !out3 || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    KY_TRY(strat_samples_check(p, s0, n));
-    const RenderConstS rcs = make_rc(p);
-    const RenderConst rc = rcs;
-    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
-    float dummy = 0.f;
-    return kat_run(device, &dummy, 4, out3, (size_t)n * 3 * 4, [&](DeviceCtx* c, const float*, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        const size_t lds = lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
-        const dim3 grid((n + 255) / 256), block(256);
-        const int rf = render_replay_feat(scene, p, sc->h);
-        const bool boxes = (rf & KY_FEAT_BOXES) != 0;
-        const int env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
-        if (strat && boxes) hipLaunchKernelGGL((kat_li_stratified_kernel<true>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, 0);
-        else if (strat) hipLaunchKernelGGL((kat_li_stratified_kernel<false>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, 0);
-        else if (dbg && boxes) hipLaunchKernelGGL((kat_li_kernel<true, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
-        else if (dbg) hipLaunchKernelGGL((kat_li_kernel<true, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
-        else if (boxes) hipLaunchKernelGGL((kat_li_kernel<false, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
-        else hipLaunchKernelGGL((kat_li_kernel<false, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env);
-        return (int)KY_OK;
-    });
-}
-
-// kyhip_kat_li for the samples of a masked render: what kyhip_render_lighting(lighting) adds per camera sample, before the mean and its clamp
-int kyhip_kat_li_lighting(int device, const ky_scene* scene, const ky_render_params* p, int lighting, int x, int y, int s0, int n, float* out3) {
-    LightingPlan plan;
-    int rcode = lighting_plan(p, lighting, &plan);
-    if (rcode != KY_OK) return rcode;
-    if (plan.plain) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);
-    if (!scene || !out3 || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    KY_TRY(strat_samples_check(p, s0, n));
-    if (plan.nothing) { std::memset(out3, 0, (size_t)n * 3 * sizeof(float)); return KY_OK; }
-    ky_render_params q = *p;
-    q.max_path_depth = plan.effective_depth;
-    const RenderConstS rcs = make_rc(&q);
-    const RenderConst rc = rcs;
-    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
-    const int drop = plan.dropped;
-    float dummy = 0.f;
-    return kat_run(device, &dummy, 4, out3, (size_t)n * 3 * 4, [&](DeviceCtx* c, const float*, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        const size_t lds = lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
-        const dim3 grid((n + 255) / 256), block(256);
-        const int rf = render_replay_feat(scene, &q, sc->h, drop);
-        const bool boxes = (rf & KY_FEAT_BOXES) != 0;
-        const int env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
-        if (strat && boxes) hipLaunchKernelGGL((kat_li_stratified_kernel<true>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, drop);
-        else if (strat) hipLaunchKernelGGL((kat_li_stratified_kernel<false>), grid, block, lds, 0, (const DScene*)sc->d, rcs, x, y, s0, n, d_out, env, drop);
-        else if (dbg && boxes) hipLaunchKernelGGL((kat_li_lighting_kernel<true, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
-        else if (dbg) hipLaunchKernelGGL((kat_li_lighting_kernel<true, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
-        else if (boxes) hipLaunchKernelGGL((kat_li_lighting_kernel<false, true>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
-        else hipLaunchKernelGGL((kat_li_lighting_kernel<false, false>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out, env, drop);
-        return (int)KY_OK;
-    });
-}
-
-int kyhip_kat_nee(int device, const ky_scene* scene, int direct_sample, int light, const float* in15, int n, float* out6) {
-    if (!scene || !in15 || !out6 || n <= 0 || light < 0 || light >= scene->light_count) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    if (direct_sample != KY_DIRECT_BSDF && direct_sample != KY_DIRECT_LIGHT && direct_sample != KY_DIRECT_BSDF_MIS && direct_sample != KY_DIRECT_LIGHT_MIS &&
-        direct_sample != KY_DIRECT_BOTH_MIS)
-        return fail(KY_ERR_INVALID_VALUE, "direct_sample %d has no estimator to test", direct_sample);
-    for (int i = 0; i < n; ++i) {
-        const float sf = in15[15 * (size_t)i + 9];
-        if (!(sf >= 0 && sf < scene->surface_count)) return fail(KY_ERR_INVALID_VALUE, "row %d: surface out of range", i);
-    }
-    return kat_run(device, in15, (size_t)n * 15 * 4, out6, (size_t)n * 6 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        hipLaunchKernelGGL(kat_nee_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, direct_sample, light, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-int kyhip_kat_single_light(int device, const ky_scene* scene, const float* in16, int n, float* out6) {
-    if (!scene || !in16 || !out6 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    if (scene->light_count <= 0) return fail(KY_ERR_INVALID_VALUE, "sample_single_light picks among the scene's lights: the scene has none");
-    for (int i = 0; i < n; ++i) {
-        const float sf = in16[16 * (size_t)i + 9], u = in16[16 * (size_t)i + 15];
-        if (!(sf >= 0 && sf < scene->surface_count)) return fail(KY_ERR_INVALID_VALUE, "row %d: surface out of range", i);
-        if (!(u >= 0.f && u < 1.f)) return fail(KY_ERR_INVALID_VALUE, "row %d: pick_u outside [0, 1)", i);
-    }
-    return kat_run(device, in16, (size_t)n * 16 * 4, out6, (size_t)n * 6 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        hipLaunchKernelGGL(kat_single_light_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-int kyhip_kat_li_trace(int device, const ky_scene* scene, const ky_render_params* p, int x, int y, int s, float* rows26, int max_rows, float* li3) {
-    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
-    if (p->integrator != KY_INTEGRATOR_PATH_TRACING_ITERATION) return fail(KY_ERR_INVALID_VALUE, "the vertex trace follows path_tracing_iteration_t");
-    if (!scene || !rows26 || max_rows <= 0 || max_rows > 4096 || s < 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    KY_TRY(strat_samples_check(p, s, 1));
-    const RenderConstS rcs = make_rc(p);
-    const RenderConst rc = rcs;
-    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
-    std::vector<float> host((size_t)4 + (size_t)max_rows * 26, 0.f);
-    float dummy = 0.f;
-    const int rcode = kat_run(device, &dummy, 4, host.data(), host.size() * 4, [&](DeviceCtx* c, const float*, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        const size_t lds = lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
-        const int rf = render_replay_feat(scene, p, sc->h);
-        const bool boxes = (rf & KY_FEAT_BOXES) != 0;
-        const int env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
-        if (strat && boxes) hipLaunchKernelGGL((kat_li_trace_stratified_kernel<true>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rcs, x, y, s, max_rows, d_out, env);
-        else if (strat) hipLaunchKernelGGL((kat_li_trace_stratified_kernel<false>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rcs, x, y, s, max_rows, d_out, env);
-        else if (dbg && boxes) hipLaunchKernelGGL((kat_li_trace_kernel<true, true>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
-        else if (dbg) hipLaunchKernelGGL((kat_li_trace_kernel<true, false>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
-        else if (boxes) hipLaunchKernelGGL((kat_li_trace_kernel<false, true>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
-        else hipLaunchKernelGGL((kat_li_trace_kernel<false, false>), dim3(1), dim3(64), lds, 0, (const DScene*)sc->d, rc, x, y, s, max_rows, d_out, env);
-        return (int)KY_OK;
-    });
-    if (rcode != KY_OK) return rcode;
-    const int n = (int)host[0];
-    std::memcpy(rows26, host.data() + 4, (size_t)n * 26 * sizeof(float));
-    if (li3) { li3[0] = host[1]; li3[1] = host[2]; li3[2] = host[3]; }
-    return n;
-}
-
-// kyhip_kat_bsdf's rows through bsdf_continue and bsdf_eval_parts (the last entry: its kernels are instantiated behind the others, whose listings keep their text)
-int kyhip_kat_bsdf_continue(int device, const ky_material* m, const float* in12, int n, int flat_phong, float* out12) {
-    if (!m || !in12 || !out12 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    if (m->kind < KY_MATERIAL_MATTE || m->kind > KY_MATERIAL_PLASTIC) return fail(KY_ERR_INVALID_VALUE, "unknown material kind");
-    DMat d{};
-    pack_material(*m, &d);
-    return kat_run(device, in12, (size_t)n * 12 * 4, out12, (size_t)n * 12 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
-        if (flat_phong) hipLaunchKernelGGL(kat_bsdf_continue_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
-        else hipLaunchKernelGGL(kat_bsdf_continue_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
-        return (int)KY_OK;
-    });
-}
-
-// the render kernels' random-number streams by key (behind the other entries, like kyhip_kat_bsdf_continue)
-int kyhip_kat_sampler(int device, uint32_t seed, const uint32_t* keys2, int n, int k, int debug, uint32_t* out) {
-    if (!keys2 || !out || n <= 0 || k < 1 || k > 256 || (size_t)n * (size_t)k > ((size_t)1 << 28)) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    return kat_run(device, keys2, (size_t)n * 2 * 4, out, (size_t)n * (size_t)k * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
-        const dim3 grid((n + 255) / 256), block(256);
-        if (debug) hipLaunchKernelGGL(kat_sampler_kernel<true>, grid, block, 0, 0, seed, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
-        else hipLaunchKernelGGL(kat_sampler_kernel<false>, grid, block, 0, 0, seed, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
-        return (int)KY_OK;
-    });
-}
-
-// ... for any ky_sampler_kind.  The stratified sampler's first two numbers are drawn twice, draw by draw and as path_begin draws them (sampler_camera), and the entry
-// fails with KY_ERR_DEVICE if the two disagree: there is one stream per key, however it is read.
-int kyhip_kat_sampler_kind(int device, int kind, uint32_t seed, int spp, const uint32_t* keys2, int n, int k, uint32_t* out) {
-    KY_TRY(kat_sampler_kind_check(kind, spp, keys2, n, k, out));
-    if (kind != KY_SAMPLER_STRATIFIED) return kyhip_kat_sampler(device, seed, keys2, n, k, kind == KY_SAMPLER_DEBUG, out);
-    ky_render_params q{};
-    q.samples_per_pixel = spp;
-    const RenderConstS rc = make_rc(&q);
-    std::vector<uint32_t> first(k >= 2 ? (size_t)n * (size_t)k : 0);
-    for (int camera = k >= 2 ? 1 : 0; camera >= 0; --camera) {
-        const int rcode = kat_run(device, keys2, (size_t)n * 2 * 4, out, (size_t)n * (size_t)k * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
-            hipLaunchKernelGGL(kat_sampler_stratified_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, seed, rc, camera, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
-            return (int)KY_OK;
-        });
-        if (rcode != KY_OK) return rcode;
-        if (camera) std::memcpy(first.data(), out, first.size() * sizeof(uint32_t));
-    }
-    if (!first.empty() && std::memcmp(first.data(), out, first.size() * sizeof(uint32_t)) != 0) return fail(KY_ERR_DEVICE, "the stratified camera sample differs between sampler_camera and sampler_next");
-    return KY_OK;
-}
-
-}  // extern "C"
-
-// sample_single_light's pick by power and by position (behind the other entries, like kyhip_kat_bsdf_continue): kat_single_light_kernel's rows, the light picked by
-// pick_light as the render kernels call it.  `out18` (may be null): {li, p[li], every light's p from the same weight function one light at a time}; `out6` (may be
-// null): the picked light's two both_mis halves over p[li].
+// sample_single_light's pick by power and by position: kat_single_light_kernel's rows, the light picked by pick_light as the render kernels call it.  `out18` (may
+// be null): {li, p[li], every light's p from the same weight function one light at a time}; `out6` (may be null): the picked light's two both_mis halves over p[li].
 static __device__ Vertex kat_pick_vertex(const DScene* __restrict__ S, const LdsScene& Lds, const float* r) {
     Vertex v;
     v.position = ld3(r); v.normal = ld3(r + 3);
@@ -668,6 +254,265 @@ __global__ void kat_light_pick_kernel(const DScene* __restrict__ S, int rule, co
     }
 }
 
+// the bit patterns of the first k numbers of the stream the render kernels give the key (seed, pixel_index, sample_index): sampler_pixel_key, sampler_start
+// and sampler_next as path_begin calls them.  One thread per key; its k words lie together.
+template <bool DEBUG_SAMPLER>
+__global__ void kat_sampler_kernel(uint32_t seed, const uint32_t* __restrict__ keys2, int n, int k, uint32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Sampler smp;
+    sampler_start(smp, sampler_pixel_key(seed, keys2[2 * (size_t)i]), keys2[2 * (size_t)i + 1]);
+    uint32_t* q = out + (size_t)i * (size_t)k;
+    for (int j = 0; j < k; ++j) q[j] = __float_as_uint(sampler_next<DEBUG_SAMPLER>(smp));
+}
+// ... of the stratified sampler: sampler_start_kind and sampler_next as the render kernels' later draws call them, or -- camera != 0 -- the first two through
+// sampler_camera, which is how path_begin draws them
+__global__ void kat_sampler_stratified_kernel(uint32_t seed, RenderConstS rc, int camera, const uint32_t* __restrict__ keys2, int n, int k, uint32_t* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    StratSampler smp;
+    sampler_bind(smp, rc);
+    sampler_start_kind<KY_SMP_STRATIFIED>(smp, sampler_pixel_key(seed, keys2[2 * (size_t)i]), keys2[2 * (size_t)i + 1]);
+    uint32_t* q = out + (size_t)i * (size_t)k;
+    int j = 0;
+    if (camera && k >= 2) {
+        float u0, u1;
+        sampler_camera<KY_SMP_STRATIFIED>(smp, u0, u1);
+        q[0] = __float_as_uint(u0); q[1] = __float_as_uint(u1);
+        j = 2;
+    }
+    for (; j < k; ++j) q[j] = __float_as_uint(sampler_next<KY_SMP_STRATIFIED>(smp));
+}
+
+// a pixel filter's warp alone, as path_begin applies it to each of a camera sample's two numbers; `table`: KYHIP_FILTER_TABLE + 1 floats
+__global__ void kat_filter_kernel(FilterConst fc, const float* __restrict__ u, int n, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = filter_offset(fc, u[i]);
+}
+
+// ---- the per-sample replay: one camera sample's radiance by the walk of the render kernel that rendered it, written once ----
+// What a launch decides and its replay has to decide alike are the five template arguments:
+//   SAMPLER  the sampler kind; its launch constants are RenderConstFor<SAMPLER>, wider by the strata for KY_SMP_STRATIFIED.
+//   BOXES    the launch runs a kernel with the box traversal (render_uses_boxes): the replay takes the same one, to the last decision (a ray along a box's edge may
+//            take the other face in the other traversal).  single_env, a run-time flag since these kernels are not timed, likewise: the launch's both_mis estimate
+//            is estimate_env_both (KY_FEAT_SINGLE_ENV).
+//   DROP     0, or -1 for a masked launch (kyhip_render_lighting), whose drop bits `drop` are read at run time (path_intersect, ky_device.hpp); the stratified
+//            sampler's forms always read them.  Which products contract to an fma differs between the two, so an unmasked replay keeps the compile-time 0.
+//   FILTER   the launch runs under a pixel filter (rc_.filter): the filtered render kernels assume no scene facts (no box traversal, no pair scan), and so does this.
+//   TRACE    one sample, s0, traced vertex by vertex into out[4..] (`n` rows at most) behind {rows, Lo}: lane 0 walks the path, the other lanes only keep the
+//            wave-uniform calls company.  Otherwise lane i < n walks sample s0 + i and writes out[3 i ..].
+template <int SAMPLER, bool FILTER> struct ReplayConstFor { typedef typename RenderConstFor<SAMPLER>::type type; };
+template <int SAMPLER> struct ReplayConstFor<SAMPLER, true> { typedef RenderConstF type; };
+
+template <int SAMPLER, bool BOXES, int DROP, bool FILTER, bool TRACE>
+__global__ void kat_li_kernel(const DScene* __restrict__ S_, typename ReplayConstFor<SAMPLER, FILTER>::type rc_, int x, int y, int s0, int n, float* __restrict__ out, int single_env, int drop) {
+    const SceneRef S{S_, true, FILTER ? 0 : (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
+    const typename RenderConstFor<SAMPLER>::type& rc = rc_;
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));   // KAT kernels: always the scene-sized dynamic block
+    const int i = TRACE ? 0 : blockIdx.x * blockDim.x + threadIdx.x;
+    PathStateFor<SAMPLER> ps;
+    sampler_bind(ps.smp, rc);
+    const bool mine = TRACE ? threadIdx.x == 0 : i < n;
+    bool alive = mine;
+    VertexTrace tr{out + 4, n, 0};
+    if (alive) {
+        const uint32_t key = sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x));
+        if constexpr (FILTER) path_begin<SAMPLER, false, true>(ps, S, key, x, y, s0 + i, rc_.filter);
+        else path_begin<SAMPLER>(ps, S, key, x, y, s0 + i);
+    }
+    while (__any(alive)) {  // path_shade is a wave-uniform call
+        Vertex v;
+        bool have_vertex = false;
+        if (alive) have_vertex = path_intersect<SAMPLER, DROP>(ps, v, S, Lds, rc, drop);
+        const bool cont = path_shade<SAMPLER, DROP>(ps, v, S, Lds, rc, have_vertex, -1, TRACE ? &tr : nullptr, nullptr, 0, false, false, drop);
+        alive = have_vertex && cont;
+    }
+    if (!mine) return;
+    if (TRACE) { out[0] = (float)tr.n; out[1] = ps.Lo.x; out[2] = ps.Lo.y; out[3] = ps.Lo.z; }
+    else { out[3 * (size_t)i] = ps.Lo.x; out[3 * (size_t)i + 1] = ps.Lo.y; out[3 * (size_t)i + 2] = ps.Lo.z; }
+}
+
+// ---- shared drivers of the KAT entry points ----
+template <typename F>
+static int kat_run(int device, const void* in, size_t in_bytes, void* out, size_t out_bytes, F launch) {
+    DeviceCtx* c;
+    int rcode = get_ctx(device, &c);
+    if (rcode != KY_OK) return rcode;
+    std::lock_guard<std::mutex> lock(c->m);
+    DevBuf d_in, d_out;
+    HIP_TRY(d_in.alloc(in_bytes));
+    HIP_TRY(d_out.alloc(out_bytes));
+    HIP_TRY(hipDeviceSynchronize());   // KAT entries use the default stream and may replace the device's scene copy
+    HIP_TRY(hipMemcpy(d_in.p, in, in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_out.p, 0, out_bytes));
+    rcode = launch(c, d_in.as<const float>(), d_out.as<float>());
+    if (rcode != KY_OK) return rcode;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return KY_OK;
+}
+
+// kat_run for the kernels that read a scene: uploads it and hands `launch` the device's copy, the packed host copy (what it holds) and the bytes of the scene-sized
+// dynamic LDS block
+template <typename F>
+static int kat_run_scene(int device, const ky_scene* scene, const void* in, size_t in_bytes, void* out, size_t out_bytes, F launch) {
+    return kat_run(device, in, in_bytes, out, out_bytes, [&](DeviceCtx* c, const float* d_in, float* d_out) {
+        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
+        if (r != KY_OK) return r;
+        launch((const DScene*)sc->d, (const DScene*)sc->h, (size_t)lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), d_in, d_out);
+        return (int)KY_OK;
+    });
+}
+
+// ---- the replay's host side: one shared refusal, one launch ----
+// what the four replay entries refuse alike, each after its own checks: samples s0 .. s0 + n - 1 of pixel (x, y) of a launch of p (valid: the caller has checked)
+static int replay_check(const ky_scene* scene, const ky_render_params* p, int x, int y, int s0, int n, const float* out) {
+    if (!scene || !out || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    return strat_samples_check(p, s0, n);
+}
+
+struct ReplayLaunch {   // kat_li_kernel's grid and arguments
+    dim3 grid, block;
+    size_t lds;
+    const DScene* S;
+    RenderConstF rc;   // (a kernel without a filter or strata takes the base it declares)
+    int x, y, s0, n;
+    float* out;
+    int boxes, single_env, drop;
+};
+template <int SAMPLER, int DROP, bool TRACE, bool FILTER = false>
+static void replay_launch(const ReplayLaunch& a) {   // (FILTER: both lines name the one form without boxes)
+    if (!FILTER && a.boxes) hipLaunchKernelGGL((kat_li_kernel<SAMPLER, !FILTER, DROP, FILTER, TRACE>), a.grid, a.block, a.lds, 0, a.S, a.rc, a.x, a.y, a.s0, a.n, a.out, a.single_env, a.drop);
+    else hipLaunchKernelGGL((kat_li_kernel<SAMPLER, false, DROP, FILTER, TRACE>), a.grid, a.block, a.lds, 0, a.S, a.rc, a.x, a.y, a.s0, a.n, a.out, a.single_env, a.drop);
+}
+
+// Replays samples s0 .. s0 + n - 1 of pixel (x, y) of a launch of `p` into out[3 n] -- trace: sample s0 alone into out[4 + 26 n], n rows at most -- with the form of
+// kat_li_kernel that launch's kernel corresponds to; these are all the forms there are.  masked: the launch has a lighting plan with drop bits `drop` (0 otherwise);
+// filter: its pixel filter, null for none (the callers hand a box filter and the debug sampler on without one).
+static int replay_run(int device, const ky_scene* scene, const ky_render_params* p, bool masked, int drop, const ky_pixel_filter* filter, bool trace,
+                      int x, int y, int s0, int n, float* out, size_t out_bytes) {
+    float table[KYHIP_FILTER_TABLE + 1] = {0.f};
+    if (filter) filter_table(filter, table);
+    const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
+    return kat_run_scene(device, scene, table, filter ? sizeof table : 4, out, out_bytes, [&](const DScene* S, const DScene* packed, size_t lds, const float* d_in, float* d_out) {
+        ReplayLaunch a{dim3(trace ? 1 : (n + 255) / 256), dim3(trace ? 64 : 256), lds, S, RenderConstF{}, x, y, s0, n, d_out, 0, 0, drop};
+        static_cast<RenderConstS&>(a.rc) = make_rc(p);
+        if (filter) {
+            a.rc.filter = FilterConst{filter->kind, filter->radius, filter_grow(filter), d_in};
+            return strat ? replay_launch<KY_SMP_STRATIFIED, 0, false, true>(a) : replay_launch<KY_SMP_RANDOM, 0, false, true>(a);
+        }
+        const int rf = render_replay_feat(scene, p, packed, drop);
+        a.boxes = (rf & KY_FEAT_BOXES) != 0;
+        a.single_env = (rf & KY_FEAT_SINGLE_ENV) ? 1 : 0;
+        if (trace) return strat ? replay_launch<KY_SMP_STRATIFIED, 0, true>(a) : dbg ? replay_launch<KY_SMP_DEBUG, 0, true>(a) : replay_launch<KY_SMP_RANDOM, 0, true>(a);
+        if (strat) return replay_launch<KY_SMP_STRATIFIED, -1, false>(a);
+        if (masked) return dbg ? replay_launch<KY_SMP_DEBUG, -1, false>(a) : replay_launch<KY_SMP_RANDOM, -1, false>(a);
+        return dbg ? replay_launch<KY_SMP_DEBUG, 0, false>(a) : replay_launch<KY_SMP_RANDOM, 0, false>(a);
+    });
+}
+
+extern "C" {
+
+// ---- KAT entry points ----
+int kyhip_kat_intersect(int device, const ky_shape* shape, const float* rays7, int n, float* out8) {
+    if (!shape || !rays7 || !out8 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (shape->kind < KY_SHAPE_DISK || shape->kind > KY_SHAPE_SPHERE) return fail(KY_ERR_INVALID_VALUE, "unknown shape kind");
+    if (!shape_normal_ok(*shape)) return fail(KY_ERR_INVALID_VALUE, "the stored normal must be unit length");
+    KatShape ks{};
+    pack_shape(*shape, 0, &ks.surf, &ks.full);
+    cp3(ks.hit.n, shape->kind == KY_SHAPE_SPHERE ? shape->p[0] : shape->normal);
+    ks.hit.kind = shape->kind;
+    return kat_run(device, rays7, (size_t)n * 7 * 4, out8, (size_t)n * 8 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, ks, d_in, n, d_out);
+        return (int)KY_OK;
+    });
+}
+
+int kyhip_kat_camera(int device, const ky_camera* camera, const float* p_film2, int n, float* out6) {
+    if (!camera || !p_film2 || !out6 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    ky_scene sc{};
+    sc.environment_light = -1;
+    sc.camera = *camera;
+    if (!(camera->resolution[0] > 0) || !(camera->resolution[1] > 0)) return fail(KY_ERR_INVALID_VALUE, "bad camera resolution");
+    return kat_run_scene(device, &sc, p_film2, (size_t)n * 2 * 4, out6, (size_t)n * 6 * 4, [&](const DScene* S, const DScene*, size_t, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_camera_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, S, d_in, n, d_out);
+    });
+}
+
+int kyhip_kat_bsdf(int device, const ky_material* m, const float* in12, int n, float* out13) {
+    if (!m || !in12 || !out13 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (m->kind < KY_MATERIAL_MATTE || m->kind > KY_MATERIAL_PLASTIC) return fail(KY_ERR_INVALID_VALUE, "unknown material kind");
+    DMat d{};
+    pack_material(*m, &d);
+    return kat_run(device, in12, (size_t)n * 12 * 4, out13, (size_t)n * 13 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_bsdf_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
+        return (int)KY_OK;
+    });
+}
+
+// kyhip_kat_bsdf's rows through bsdf_continue and bsdf_eval_parts
+int kyhip_kat_bsdf_continue(int device, const ky_material* m, const float* in12, int n, int flat_phong, float* out12) {
+    if (!m || !in12 || !out12 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (m->kind < KY_MATERIAL_MATTE || m->kind > KY_MATERIAL_PLASTIC) return fail(KY_ERR_INVALID_VALUE, "unknown material kind");
+    DMat d{};
+    pack_material(*m, &d);
+    return kat_run(device, in12, (size_t)n * 12 * 4, out12, (size_t)n * 12 * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        if (flat_phong) hipLaunchKernelGGL(kat_bsdf_continue_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
+        else hipLaunchKernelGGL(kat_bsdf_continue_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, d, d_in, n, d_out);
+        return (int)KY_OK;
+    });
+}
+
+int kyhip_kat_light(int device, const ky_scene* scene, int light, const float* in11, int n, float* out11) {
+    if (!scene || !in11 || !out11 || n <= 0 || light < 0 || light >= scene->light_count) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    return kat_run_scene(device, scene, in11, (size_t)n * 11 * 4, out11, (size_t)n * 11 * 4, [&](const DScene* S, const DScene*, size_t, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_light_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, S, light, d_in, n, d_out);
+    });
+}
+
+int kyhip_kat_scene_intersect(int device, const ky_scene* scene, const float* rays7, int n, float* out9) {
+    if (!scene || !rays7 || !out9 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    return kat_run_scene(device, scene, rays7, (size_t)n * 7 * 4, out9, (size_t)n * 9 * 4, [&](const DScene* S, const DScene* packed, size_t lds, const float* d_in, float* d_out) {
+        if (packed->feat & KY_FEAT_BOXES) hipLaunchKernelGGL(kat_scene_intersect_kernel<true>, dim3((n + 255) / 256), dim3(256), lds, 0, S, d_in, n, d_out);
+        else hipLaunchKernelGGL(kat_scene_intersect_kernel<false>, dim3((n + 255) / 256), dim3(256), lds, 0, S, d_in, n, d_out);
+    });
+}
+
+static int kat_occluded_impl(int device, const ky_scene* scene, const float* in9, int n, float* out1, int table) {
+    if (!scene || !in9 || !out1 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (table >= scene->light_count) return fail(KY_ERR_INVALID_VALUE, "light %d out of range", table);
+    return kat_run_scene(device, scene, in9, (size_t)n * 9 * 4, out1, (size_t)n * 4, [&](const DScene* S, const DScene*, size_t, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_occluded_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, S, d_in, n, d_out, table);
+    });
+}
+int kyhip_kat_occluded(int device, const ky_scene* scene, const float* in9, int n, float* out1) { return kat_occluded_impl(device, scene, in9, n, out1, -2); }
+int kyhip_kat_occluded_between(int device, const ky_scene* scene, int light, const float* in9, int n, float* out1) {
+    if (light < -1) return fail(KY_ERR_INVALID_VALUE, "light %d out of range", light);
+    return kat_occluded_impl(device, scene, in9, n, out1, light);
+}
+int kyhip_kat_any_pair(int device, const ky_scene* scene, const float* in13, int n, float* out2) {
+    if (!scene || !in13 || !out2 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    return kat_run_scene(device, scene, in13, (size_t)n * 13 * 4, out2, (size_t)n * 2 * 4, [&](const DScene* S, const DScene* packed, size_t, const float* d_in, float* d_out) {
+        if (packed->feat & KY_FEAT_BOXES) hipLaunchKernelGGL(kat_any_pair_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, S, d_in, n, d_out);
+        else hipLaunchKernelGGL(kat_any_pair_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, S, d_in, n, d_out);
+    });
+}
+
+int kyhip_kat_nee(int device, const ky_scene* scene, int direct_sample, int light, const float* in15, int n, float* out6) {
+    if (!scene || !in15 || !out6 || n <= 0 || light < 0 || light >= scene->light_count) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (direct_sample != KY_DIRECT_BSDF && direct_sample != KY_DIRECT_LIGHT && direct_sample != KY_DIRECT_BSDF_MIS && direct_sample != KY_DIRECT_LIGHT_MIS &&
+        direct_sample != KY_DIRECT_BOTH_MIS)
+        return fail(KY_ERR_INVALID_VALUE, "direct_sample %d has no estimator to test", direct_sample);
+    for (int i = 0; i < n; ++i) {
+        const float sf = in15[15 * (size_t)i + 9];
+        if (!(sf >= 0 && sf < scene->surface_count)) return fail(KY_ERR_INVALID_VALUE, "row %d: surface out of range", i);
+    }
+    return kat_run_scene(device, scene, in15, (size_t)n * 15 * 4, out6, (size_t)n * 6 * 4, [&](const DScene* S, const DScene*, size_t lds, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_nee_kernel, dim3((n + 255) / 256), dim3(256), lds, 0, S, direct_sample, light, d_in, n, d_out);
+    });
+}
+
 static int kat_light_pick_check(const ky_scene* scene, int rule, const float* in16, int n, const float* out) {
     if (!scene || !in16 || !out || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
     if (rule < KY_PICK_UNIFORM || rule > KY_PICK_SPATIAL) return fail(KY_ERR_INVALID_VALUE, "rule %d: 0 picks uniformly, 1 by power, 2 by position", rule);
@@ -680,59 +525,65 @@ static int kat_light_pick_check(const ky_scene* scene, int rule, const float* in
     return KY_OK;
 }
 
-extern "C" {
+int kyhip_kat_single_light(int device, const ky_scene* scene, const float* in16, int n, float* out6) {
+    if (!scene || !in16 || !out6 || n <= 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (scene->light_count <= 0) return fail(KY_ERR_INVALID_VALUE, "sample_single_light picks among the scene's lights: the scene has none");
+    for (int i = 0; i < n; ++i) {
+        const float sf = in16[16 * (size_t)i + 9], u = in16[16 * (size_t)i + 15];
+        if (!(sf >= 0 && sf < scene->surface_count)) return fail(KY_ERR_INVALID_VALUE, "row %d: surface out of range", i);
+        if (!(u >= 0.f && u < 1.f)) return fail(KY_ERR_INVALID_VALUE, "row %d: pick_u outside [0, 1)", i);
+    }
+    return kat_run_scene(device, scene, in16, (size_t)n * 16 * 4, out6, (size_t)n * 6 * 4, [&](const DScene* S, const DScene*, size_t lds, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_single_light_kernel, dim3((n + 255) / 256), dim3(256), lds, 0, S, d_in, n, d_out);
+    });
+}
 
 int kyhip_kat_light_pick(int device, const ky_scene* scene, int rule, const float* in16, int n, float* out18) {
     KY_TRY(kat_light_pick_check(scene, rule, in16, n, out18));
-    return kat_run(device, in16, (size_t)n * 16 * 4, out18, (size_t)n * 18 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        hipLaunchKernelGGL(kat_light_pick_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, rule, d_in, n, d_out, (float*)nullptr);
-        return (int)KY_OK;
+    return kat_run_scene(device, scene, in16, (size_t)n * 16 * 4, out18, (size_t)n * 18 * 4, [&](const DScene* S, const DScene*, size_t lds, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_light_pick_kernel, dim3((n + 255) / 256), dim3(256), lds, 0, S, rule, d_in, n, d_out, (float*)nullptr);
     });
 }
 
 int kyhip_kat_single_light_rule(int device, const ky_scene* scene, int rule, const float* in16, int n, float* out6) {
     KY_TRY(kat_light_pick_check(scene, rule, in16, n, out6));
     if (rule == KY_PICK_UNIFORM) return kyhip_kat_single_light(device, scene, in16, n, out6);
-    return kat_run(device, in16, (size_t)n * 16 * 4, out6, (size_t)n * 6 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        hipLaunchKernelGGL(kat_light_pick_kernel, dim3((n + 255) / 256), dim3(256), lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count), 0, (const DScene*)sc->d, rule, d_in, n, (float*)nullptr, d_out);
+    return kat_run_scene(device, scene, in16, (size_t)n * 16 * 4, out6, (size_t)n * 6 * 4, [&](const DScene* S, const DScene*, size_t lds, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_light_pick_kernel, dim3((n + 255) / 256), dim3(256), lds, 0, S, rule, d_in, n, (float*)nullptr, d_out);
+    });
+}
+
+// the render kernels' random-number streams by key
+int kyhip_kat_sampler(int device, uint32_t seed, const uint32_t* keys2, int n, int k, int debug, uint32_t* out) {
+    if (!keys2 || !out || n <= 0 || k < 1 || k > 256 || (size_t)n * (size_t)k > ((size_t)1 << 28)) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    return kat_run(device, keys2, (size_t)n * 2 * 4, out, (size_t)n * (size_t)k * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        const dim3 grid((n + 255) / 256), block(256);
+        if (debug) hipLaunchKernelGGL(kat_sampler_kernel<true>, grid, block, 0, 0, seed, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
+        else hipLaunchKernelGGL(kat_sampler_kernel<false>, grid, block, 0, 0, seed, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
         return (int)KY_OK;
     });
 }
 
-}  // extern "C"
-
-// ---- pixel filters (behind the other entries, whose listings keep their text) ----
-// the warp alone, as path_begin applies it to each of a camera sample's two numbers; `table`: KYHIP_FILTER_TABLE + 1 floats
-__global__ void kat_filter_kernel(FilterConst fc, const float* __restrict__ u, int n, float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = filter_offset(fc, u[i]);
-}
-// kat_li_kernel / kat_li_stratified_kernel under a pixel filter: the walk of the filtered render kernels, which assume no scene facts (no box traversal, no pair scan)
-template <int SAMPLER>
-__global__ void kat_li_filtered_kernel(const DScene* __restrict__ S_, RenderConstF rc_, int x, int y, int s0, int n, float* __restrict__ out3) {
-    const SceneRef S{S_, true, 0, true};
-    const typename RenderConstFor<SAMPLER>::type rc = rc_;
-    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    PathStateFor<SAMPLER> ps;
-    sampler_bind(ps.smp, rc);
-    bool alive = i < n;
-    if (alive) path_begin<SAMPLER, false, true>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i, rc_.filter);
-    while (__any(alive)) {  // path_shade is a wave-uniform call
-        Vertex v;
-        bool have_vertex = false;
-        if (alive) have_vertex = path_intersect<SAMPLER>(ps, v, S, Lds, rc);
-        const bool cont = path_shade<SAMPLER>(ps, v, S, Lds, rc, have_vertex);
-        alive = have_vertex && cont;
+// ... for any ky_sampler_kind.  The stratified sampler's first two numbers are drawn twice, draw by draw and as path_begin draws them (sampler_camera), and the entry
+// fails with KY_ERR_DEVICE if the two disagree: there is one stream per key, however it is read.
+int kyhip_kat_sampler_kind(int device, int kind, uint32_t seed, int spp, const uint32_t* keys2, int n, int k, uint32_t* out) {
+    KY_TRY(kat_sampler_kind_check(kind, spp, keys2, n, k, out));
+    if (kind != KY_SAMPLER_STRATIFIED) return kyhip_kat_sampler(device, seed, keys2, n, k, kind == KY_SAMPLER_DEBUG, out);
+    ky_render_params q{};
+    q.samples_per_pixel = spp;
+    const RenderConstS rc = make_rc(&q);
+    std::vector<uint32_t> first(k >= 2 ? (size_t)n * (size_t)k : 0);
+    for (int camera = k >= 2 ? 1 : 0; camera >= 0; --camera) {
+        const int rcode = kat_run(device, keys2, (size_t)n * 2 * 4, out, (size_t)n * (size_t)k * 4, [&](DeviceCtx*, const float* d_in, float* d_out) {
+            hipLaunchKernelGGL(kat_sampler_stratified_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, seed, rc, camera, (const uint32_t*)d_in, n, k, (uint32_t*)d_out);
+            return (int)KY_OK;
+        });
+        if (rcode != KY_OK) return rcode;
+        if (camera) std::memcpy(first.data(), out, first.size() * sizeof(uint32_t));
     }
-    if (i < n) { out3[3 * (size_t)i] = ps.Lo.x; out3[3 * (size_t)i + 1] = ps.Lo.y; out3[3 * (size_t)i + 2] = ps.Lo.z; }
+    if (!first.empty() && std::memcmp(first.data(), out, first.size() * sizeof(uint32_t)) != 0) return fail(KY_ERR_DEVICE, "the stratified camera sample differs between sampler_camera and sampler_next");
+    return KY_OK;
 }
-
-extern "C" {
 
 int kyhip_kat_filter(int device, const ky_pixel_filter* filter, const float* u, int n, float* out) {
     KY_TRY(filter_check(filter));
@@ -750,6 +601,26 @@ int kyhip_kat_filter(int device, const ky_pixel_filter* filter, const float* u, 
     });
 }
 
+// ---- the per-sample replay (replay_run) ----
+int kyhip_kat_li(int device, const ky_scene* scene, const ky_render_params* p, int x, int y, int s0, int n, float* out3) {
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    KY_TRY(replay_check(scene, p, x, y, s0, n, out3));
+    return replay_run(device, scene, p, false, 0, nullptr, false, x, y, s0, n, out3, (size_t)n * 3 * 4);
+}
+
+// kyhip_kat_li for the samples of a masked render: what kyhip_render_lighting(lighting) adds per camera sample, before the mean and its clamp
+int kyhip_kat_li_lighting(int device, const ky_scene* scene, const ky_render_params* p, int lighting, int x, int y, int s0, int n, float* out3) {
+    LightingPlan plan;
+    KY_TRY(lighting_plan(p, lighting, &plan));
+    if (plan.plain) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);
+    KY_TRY(replay_check(scene, p, x, y, s0, n, out3));
+    if (plan.nothing) { std::memset(out3, 0, (size_t)n * 3 * sizeof(float)); return KY_OK; }
+    ky_render_params q = *p;
+    q.max_path_depth = plan.effective_depth;
+    return replay_run(device, scene, &q, true, plan.dropped, nullptr, false, x, y, s0, n, out3, (size_t)n * 3 * 4);
+}
+
+// kyhip_kat_li for the samples of a render under a pixel filter: the walk of the filtered render kernels
 int kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, int x, int y, int s0, int n, float* out3) {
     if (filter_is_box(filter)) {
         if (filter) KY_TRY(filter_check(filter));
@@ -758,23 +629,23 @@ int kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_par
     KY_TRY(filter_check(filter));
     if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
     if (p->sampler == KY_SAMPLER_DEBUG) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);   // (0.5 is the pixel's centre under every filter)
-    if (!scene || !out3 || n <= 0 || x < 0 || y < 0 || x >= p->width || y >= p->height) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
-    KY_TRY(strat_samples_check(p, s0, n));
-    float table[KYHIP_FILTER_TABLE + 1];
-    filter_table(filter, table);
-    RenderConstF rc{};
-    static_cast<RenderConstS&>(rc) = make_rc(p);
-    const bool strat = p->sampler == KY_SAMPLER_STRATIFIED;
-    return kat_run(device, table, sizeof table, out3, (size_t)n * 3 * 4, [&](DeviceCtx* c, const float* d_in, float* d_out) {
-        SceneSlot* sc; int r = upload_scene(c, scene, 0, &sc);
-        if (r != KY_OK) return r;
-        rc.filter = FilterConst{filter->kind, filter->radius, filter_grow(filter), d_in};
-        const size_t lds = lds_scene_bytes(scene->surface_count, scene->material_count, scene->light_count);
-        const dim3 grid((n + 255) / 256), block(256);
-        if (strat) hipLaunchKernelGGL((kat_li_filtered_kernel<KY_SMP_STRATIFIED>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out);
-        else hipLaunchKernelGGL((kat_li_filtered_kernel<KY_SMP_RANDOM>), grid, block, lds, 0, (const DScene*)sc->d, rc, x, y, s0, n, d_out);
-        return (int)KY_OK;
-    });
+    KY_TRY(replay_check(scene, p, x, y, s0, n, out3));
+    return replay_run(device, scene, p, false, 0, filter, false, x, y, s0, n, out3, (size_t)n * 3 * 4);
+}
+
+// one camera sample, traced vertex by vertex
+int kyhip_kat_li_trace(int device, const ky_scene* scene, const ky_render_params* p, int x, int y, int s, float* rows26, int max_rows, float* li3) {
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    if (p->integrator != KY_INTEGRATOR_PATH_TRACING_ITERATION) return fail(KY_ERR_INVALID_VALUE, "the vertex trace follows path_tracing_iteration_t");
+    if (max_rows <= 0 || max_rows > 4096 || s < 0) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    KY_TRY(replay_check(scene, p, x, y, s, 1, rows26));
+    std::vector<float> host((size_t)4 + (size_t)max_rows * 26, 0.f);
+    const int rcode = replay_run(device, scene, p, false, 0, nullptr, true, x, y, s, max_rows, host.data(), host.size() * 4);
+    if (rcode != KY_OK) return rcode;
+    const int n = (int)host[0];
+    std::memcpy(rows26, host.data() + 4, (size_t)n * 26 * sizeof(float));
+    if (li3) { li3[0] = host[1]; li3[1] = host[2]; li3[2] = host[3]; }
+    return n;
 }
 
 }  // extern "C"

@@ -270,27 +270,39 @@ def test_one_frame_per_table_row(O, A, api, table_kernels, which):
     assert g.max() > 0 and (~fin).sum() <= 2 and e < film_tolerance(n_spp)
 
 
-def test_masked_and_traced_samples_equal_the_oracle(O, A, api):
+_masked_cache = {}
+
+
+@pytest.mark.parametrize("boxes", (1, 0))
+def test_masked_and_traced_samples_equal_the_oracle(O, A, api, boxes):
     """kyhip_kat_li_lighting and kyhip_kat_li_trace under the stratified sampler, every sample of eight pixels of the 16 x 16 Cornell frame at N = 16: the direct
     class alone is the oracle at depth 1 minus the oracle at depth 0 on the restatement's numbers (tests/test_lighting_gpu.py), and a traced sample ends with
-    the radiance the oracle gives that sample; the comparison and bound are test_paths_equal_the_oracle_on_the_restatements_numbers' for this scene."""
+    the radiance the oracle gives that sample; the comparison and bound are test_paths_equal_the_oracle_on_the_restatements_numbers' for this scene.
+    boxes: kyhip_set_boxes -- with the box traversal the trace is the replay kernel's form with boxes, without it the one form no other test launches; the oracle's
+    numbers, computed once, are the same for both."""
     w = h = n_spp = 16
     scene, params = scene_of(A, api, "cornell", w, h), strat_params(api, A, w, h, n_spp)
     at = lambda depth: api.make_params(w, h, n_spp, max_path_depth=depth, direct_sample=A.DIRECT_BOTH_MIS, sampler=A.SAMPLER_STRATIFIED)
-    bad = tot = 0
-    for x, y in ((8, 8), (2, 13), (13, 2), (5, 5), (10, 4), (4, 10), (15, 15), (0, 7)):
-        tape = S.tape(params.seed, y * w + x, n_spp, 64)
-        full = O.li_tape(scene, params, x, y, tape)[0]
-        direct = O.li_tape(scene, at(1), x, y, tape)[0] - O.li_tape(scene, at(0), x, y, tape)[0]
-        traced = np.stack([api.kat_li_trace(scene, params, x, y, s)[1] for s in range(n_spp)])
-        rows, _ = api.kat_li_trace(scene, params, x, y, 0)
-        assert len(rows) >= 1 and rows[0][0] == 0
-        for g, c in ((api.kat_li_lighting(scene, params, 2, x, y, 0, n_spp), direct), (traced, full)):
-            fin = np.isfinite(c).all(1)
-            d = np.abs(g[fin] - c[fin]).max(axis=1)
-            bad += int((d / np.maximum(1e-3, np.abs(c[fin]).max(axis=1)) > 1e-3).sum())
-            tot += int(fin.sum())
-    print("%d of %d samples differ" % (bad, tot))
+    lib = A.load_kyhip()
+    prev = lib.kyhip_set_boxes(boxes)
+    try:
+        bad = tot = 0
+        for x, y in ((8, 8), (2, 13), (13, 2), (5, 5), (10, 4), (4, 10), (15, 15), (0, 7)):
+            if (x, y) not in _masked_cache:
+                tape = S.tape(params.seed, y * w + x, n_spp, 64)
+                _masked_cache[x, y] = (O.li_tape(scene, params, x, y, tape)[0], O.li_tape(scene, at(1), x, y, tape)[0] - O.li_tape(scene, at(0), x, y, tape)[0])
+            full, direct = _masked_cache[x, y]
+            traced = np.stack([api.kat_li_trace(scene, params, x, y, s)[1] for s in range(n_spp)])
+            rows, _ = api.kat_li_trace(scene, params, x, y, 0)
+            assert len(rows) >= 1 and rows[0][0] == 0
+            for g, c in ((api.kat_li_lighting(scene, params, 2, x, y, 0, n_spp), direct), (traced, full)):
+                fin = np.isfinite(c).all(1)
+                d = np.abs(g[fin] - c[fin]).max(axis=1)
+                bad += int((d / np.maximum(1e-3, np.abs(c[fin]).max(axis=1)) > 1e-3).sum())
+                tot += int(fin.sum())
+    finally:
+        lib.kyhip_set_boxes(prev)
+    print("boxes %d: %d of %d samples differ" % (boxes, bad, tot))
     assert tot >= 250 and bad <= 0.002 * tot, (bad, tot)
 
 
