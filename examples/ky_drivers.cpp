@@ -37,6 +37,10 @@
  *   ky_drivers filtered [spp] [cell]  the Cornell box at a preview's sample count (16; cells of 256) under the box, the tent (radius 2) and the default Gaussian pixel
  *                                filter side by side (film_t::set_filter, kyhip_render_filtered), path_tracing_iteration d5 both_mis into a film_grid_t(1, 3, ...);
  *                                prints the three kernel times and writes filtered.bmp: box | tent | gaussian
+ *   ky_drivers lens [spp] [cell]      the Cornell box at a preview's sample count (16; cells of 256) through the pinhole and through a thin lens (camera_t::set_lens,
+ *                                kyhip_render_lens) of radius 2 % and 4 % of the scene's diagonal focused on the front ball -- the nearest sphere a coarse grid of pinhole
+ *                                rays finds (kyhip_kat_camera, kyhip_kat_scene_intersect) --, path_tracing_iteration d5 both_mis into a film_grid_t(1, 3, ...); prints
+ *                                the focus distance and the three kernel times and writes lens.bmp: pinhole | lens | wider lens
  *   ky_drivers pick [spp] [w] [h]    the Veach frame under sample_single_light with its light picked uniformly (49), by power (113) and by position at the vertex
  *                                (177) side by side at equal spp (16; cells of 512 x 288), path_tracing_iteration d5 into a film_grid_t(1, 3, ...); writes pick.bmp:
  *                                uniform | power | spatial
@@ -290,6 +294,47 @@ static void render_filtered(int spp, int cell) {
     film.store_image("filtered");
 }
 
+// The Cornell box through a thin lens (the reference's commented-out `p_lens`, ky.cpp:870-874, and `// sample_ray(...)`, 1894): depth of field.  The camera owns
+// the lens; a scene holds its camera const, so each cell renders with a copy of the camera that has the cell's lens.  One device, like a filtered render.
+static void render_lens(int spp, int cell) {
+    film_grid_t film(1, 3, cell, cell);
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::default_scene, film.get_resolution());
+    // focus: the depth along front of the nearest sphere hit among the pinhole rays through a 32 x 32 grid of the cell's pixels
+    const ky_scene& flat = scene.flatten();
+    const int g = 32, n = g * g;
+    std::vector<float> film2((size_t)n * 2), rays6((size_t)n * 6), rays7((size_t)n * 7), hits9((size_t)n * 9);
+    for (int i = 0; i < n; ++i) { film2[2 * (size_t)i] = ((i % g) + 0.5f) * cell / g; film2[2 * (size_t)i + 1] = ((i / g) + 0.5f) * cell / g; }
+    if (kyhip_kat_camera(0, &flat.camera, film2.data(), n, rays6.data()) != KY_OK) throw std::runtime_error(std::string("kyhip_kat_camera: ") + kyhip_last_error());
+    for (int i = 0; i < n; ++i) { std::copy(&rays6[6 * (size_t)i], &rays6[6 * (size_t)i] + 6, &rays7[7 * (size_t)i]); rays7[7 * (size_t)i + 6] = INFINITY; }
+    if (kyhip_kat_scene_intersect(0, &flat, rays7.data(), n, hits9.data()) != KY_OK) throw std::runtime_error(std::string("kyhip_kat_scene_intersect: ") + kyhip_last_error());
+    float focus = 0.f, nearest = INFINITY;
+    for (int i = 0; i < n; ++i) {
+        const float* hit = &hits9[9 * (size_t)i];
+        if (hit[0] == 0.f || flat.shapes[flat.surfaces[(int)hit[8]].shape].kind != KY_SHAPE_SPHERE || !(hit[1] < nearest)) continue;
+        nearest = hit[1];
+        focus = 0.f;
+        for (int k = 0; k < 3; ++k) focus += (hit[2 + k] - flat.camera.position[k]) * flat.camera.front[k];
+    }
+    if (!(focus > 0.f)) throw std::runtime_error("lens: no pinhole ray of the grid meets a ball");
+    const bounds3_t bound = scene.world_bound();
+    const float diagonal = (bound.max_ - bound.min_).magnitude();
+    const float radii[3] = {0.f, 0.02f * diagonal, 0.04f * diagonal};
+    float ms[3] = {0, 0, 0};
+    const const_camera_sptr_t pinhole = std::make_shared<camera_t>(*scene.get_camera());
+    for (int k = 0; k < 3; ++k) {
+        auto camera = std::make_shared<camera_t>(*pinhole);
+        camera->set_lens(radii[k], focus);
+        scene.set_camera(camera);
+        random_sampler_t sampler(spp);
+        auto integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
+        integrator->render(&scene, &sampler, &film);
+        ms[k] = integrator->last_kernel_ms();
+        film.next_subfilm();
+    }
+    std::printf("lens: cornell %dx%d, %d spp, focus %.4g: kernel %.3f ms pinhole, %.3f ms radius %.4g, %.3f ms radius %.4g\n", cell, cell, spp, focus, ms[0], ms[1], radii[1], ms[2], radii[2]);
+    film.store_image("lens");
+}
+
 // The headline frame in passes: a picture after the first 64 samples, the reference's progress line (3703) after every pass, and a final image that is
 // render()'s bit for bit (include/kyhip.h, kyhip_frame_*).
 static void render_progressive(int spp, int width, int height) {
@@ -499,6 +544,10 @@ int main(int argc, char* argv[]) {
             const int spp = argc > 2 ? std::atoi(argv[2]) : 16, cell = argc > 3 ? std::atoi(argv[3]) : 256;
             if (spp < 1 || cell < 16) { std::fprintf(stderr, "filtered: at least one sample per pixel, cells of 16 or more\n"); return 2; }
             render_filtered(spp, cell);
+        } else if (!std::strcmp(which, "lens")) {
+            const int spp = argc > 2 ? std::atoi(argv[2]) : 16, cell = argc > 3 ? std::atoi(argv[3]) : 256;
+            if (spp < 1 || cell < 16) { std::fprintf(stderr, "lens: at least one sample per pixel, cells of 16 or more\n"); return 2; }
+            render_lens(spp, cell);
         } else if (!std::strcmp(which, "pick")) {
             const int spp = argc > 2 ? std::atoi(argv[2]) : 16, w = argc > 3 ? std::atoi(argv[3]) : 512, h = argc > 4 ? std::atoi(argv[4]) : 288;
             if (spp < 1 || w < 16 || h < 16) { std::fprintf(stderr, "pick: at least one sample per pixel, cells of 16 x 16 or more\n"); return 2; }

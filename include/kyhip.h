@@ -197,6 +197,17 @@ typedef struct ky_pixel_filter {
     int32_t reserved;   /* 0 */
 } ky_pixel_filter;
 
+/* A thin lens in front of the camera (the reference's commented-out `point2_t p_lens` of camera_sample_t, ky.cpp:870-874, and `// sample_ray(...)`, 1894; DESIGN.md
+   section 12): a camera sample leaves from a point of a disk of `radius` around the camera's position, in the plane of `right` and `up`, towards the point its
+   pinhole ray meets on the plane at depth `focus_distance` along `front`.  What lies on that plane is sharp; everything else is blurred by a disk that grows with
+   radius * |1 / focus_distance - 1 / depth|.  radius 0 is the pinhole camera.  A lens travels beside ky_render_params, like a pixel filter: never inside
+   ky_camera, ky_scene or the params. */
+typedef struct ky_lens {
+    float   radius;           /* aperture radius, world units; 0: the pinhole */
+    float   focus_distance;   /* depth of the focus plane along `front`, world units; looked at only when radius > 0 */
+    int32_t reserved[2];      /* 0 */
+} ky_lens;
+
 typedef struct ky_render_params {
     int32_t  integrator;         /* ky_integrator_kind */
     int32_t  max_path_depth;     /* path_integrator_t::max_path_depth_ (4182) */
@@ -655,6 +666,37 @@ int     kyhip_frame_filter(const kyhip_frame* f, ky_pixel_filter* out);
 int     kyhip_kat_filter(int device, const ky_pixel_filter* filter, const float* u, int n, float* out);
 int     kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter,
                               int x, int y, int s0, int n, float* out3);
+
+/*
+ * The thin lens (ky_lens above).
+ * Host only, no device needed:
+ *   kyhip_lens_check       KY_OK, or KY_ERR_INVALID_VALUE with the message: NULL, a radius that is negative or not finite, a focus distance that is not finite
+ *                          and > 0 when the radius is > 0 (a pinhole's focus distance is not looked at), reserved words != 0.
+ *   kyhip_scene_screen_bound_lens  kyhip_scene_screen_bound_filtered for a launch under `lens` as well: with radius > 0 the whole pixel range -- the live
+ *                          rectangle's proof is a projection from ONE point and does not hold from a disk, so a lens launch culls nothing (counts[0] = 0).
+ *                          radius 0 (or NULL) gives kyhip_scene_screen_bound_filtered's answer.
+ * On the device:
+ *   kyhip_render_lens      kyhip_render_filtered under a lens.  radius 0 (or NULL) IS kyhip_render_filtered: the same film bit for bit, the same kernel.  Any
+ *                          other lens runs a lens row of the run-time-dispatched kernels (kyhip_last_kernel names it, the lens and the filter): the lens point
+ *                          is Shirley's concentric map of the sample's third and fourth numbers.  No specialised, masked or queue-engine lens kernels, no
+ *                          run-time instantiation.  The debug sampler's (0.5, 0.5) is the centre of the lens: it ignores the lens and runs kyhip_render's kernels.
+ *   kyhip_frame_set_lens   the frame's lens, before its first sample is rendered, loaded or merged (KY_ERR_INVALID_VALUE afterwards).  For radius > 0 the bits of
+ *                          radius and focus_distance are folded into the scene hash of the frame's header: a state loads and merges only into a frame with the
+ *                          same lens; the checkpoint's layout and size do not change.  Denoise guides stay traced from the lens centre through pixel centres.
+ *   kyhip_frame_lens       reads it back (the pinhole, {0, 0}, until one is set).
+ *   kyhip_kat_lens         the disk map alone: out[2 i], out[2 i + 1] = the point of the unit disk for u[2 i], u[2 i + 1] in [0, 1).
+ *   kyhip_kat_li_lens      kyhip_kat_li_filtered's samples under a lens: what the lens rows add per camera sample.
+ */
+int     kyhip_lens_check(const ky_lens* lens);
+int     kyhip_scene_screen_bound_lens(const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter, const ky_lens* lens,
+                                      int rect[4], long long counts[2]);
+int     kyhip_render_lens(int device, const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter, const ky_lens* lens,
+                          float* film_rgb, size_t film_row_stride_px);
+int     kyhip_frame_set_lens(kyhip_frame* f, const ky_lens* lens);
+int     kyhip_frame_lens(const kyhip_frame* f, ky_lens* out);
+int     kyhip_kat_lens(int device, const float* u2, int n, float* out2);
+int     kyhip_kat_li_lens(int device, const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter, const ky_lens* lens,
+                          int x, int y, int s0, int n, float* out3);
 
 /*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent

@@ -96,6 +96,10 @@ class PixelFilter(C.Structure):   # ky_pixel_filter
     _fields_ = [("kind", C.c_int32), ("radius", C.c_float), ("param", C.c_float), ("reserved", C.c_int32)]
 
 
+class Lens(C.Structure):   # ky_lens
+    _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_BLACKMAN_HARRIS = 0, 1, 2, 3   # ky_filter_kind
 FILTER_MAX_RADIUS = 4   # KYHIP_FILTER_MAX_RADIUS
 FILTER_TABLE = 256      # KYHIP_FILTER_TABLE: the inverse-CDF table has FILTER_TABLE + 1 floats
@@ -103,6 +107,7 @@ FILTER_TABLE = 256      # KYHIP_FILTER_TABLE: the inverse-CDF table has FILTER_T
 FP = C.POINTER(C.c_float)
 SP = C.POINTER(Scene)
 FLP = C.POINTER(PixelFilter)
+LP = C.POINTER(Lens)
 PP = C.POINTER(RenderParams)
 
 # every symbol include/kyhip.h declares: name -> (restype, argtypes)
@@ -197,6 +202,13 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_filter": (C.c_int, [C.c_void_p, FLP]),
     "kyhip_kat_filter": (C.c_int, [C.c_int, FLP, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_li_filtered": (C.c_int, [C.c_int, SP, PP, FLP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "kyhip_lens_check": (C.c_int, [LP]),
+    "kyhip_scene_screen_bound_lens": (C.c_int, [SP, PP, FLP, LP, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "kyhip_render_lens": (C.c_int, [C.c_int, SP, PP, FLP, LP, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_set_lens": (C.c_int, [C.c_void_p, LP]),
+    "kyhip_frame_lens": (C.c_int, [C.c_void_p, LP]),
+    "kyhip_kat_lens": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "kyhip_kat_li_lens": (C.c_int, [C.c_int, SP, PP, FLP, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -242,6 +254,8 @@ KYHOST_SYMBOLS = {
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhost_render_filtered": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                          C.c_float, C.c_int, C.c_int]),
+    "kyhost_render_lens": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                     C.c_int, C.c_int]),
     "kyhost_render_passes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
     "kyhost_render_sliced": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int,
@@ -281,6 +295,7 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
     "kyhostcheck_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_slices": (C.c_int, [C.c_int, PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kyhostcheck_filter": (C.c_int, []),
+    "kyhostcheck_lens": (C.c_int, []),
     "kyhostcheck_add_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_seam_stress": (C.c_int, [C.c_int]),
     "kyhostcheck_jit_stress": (C.c_int, [C.c_int, C.c_int]),

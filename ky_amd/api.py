@@ -107,18 +107,51 @@ def kat_filter(filter, u, device=0):
     return out
 
 
-def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0), lighting=None, filter=None):
+def lens(radius, focus_distance=0.0):
+    """A ky_lens (_abi.Lens): the aperture radius and the depth of the focus plane along the camera's front, both in world units, through kyhip_lens_check, which
+    raises KyError for what it refuses.  radius 0 is the pinhole camera; focus_distance(scene, x, y) finds the depth of what a pixel shows."""
+    lib = A.load_kyhip()
+    l = A.Lens(float(radius), float(focus_distance), (0, 0))
+    _check(lib.kyhip_lens_check(C.byref(l)), lib)
+    return l
+
+
+def kat_lens(u2, device=0):
+    """kyhip_kat_lens: the lens's disk map -- Shirley's concentric map -- of each pair u2[i] in [0, 1)^2 -> float32 [n, 2], points of the unit disk."""
+    lib = A.load_kyhip()
+    u2 = np.ascontiguousarray(u2, np.float32).reshape(-1, 2)
+    out = np.zeros(u2.shape, np.float32)
+    _check(lib.kyhip_kat_lens(device, _fptr(u2), int(u2.shape[0]), _fptr(out)))
+    return out
+
+
+def focus_distance(scene, x, y, device=0):
+    """The depth along the camera's front of what the pinhole ray through the centre of pixel (x, y) hits (kyhip_kat_camera, kyhip_kat_scene_intersect): the
+    focus_distance of a lens focused on it.  Raises KyError if the ray hits nothing."""
+    cam = _scene_ptr(scene).contents.camera
+    ray = kat_camera(cam, np.array([[x + 0.5, y + 0.5]], np.float32), device=device)[0]
+    hit = kat_scene_intersect(scene, np.array([list(ray) + [np.inf]], np.float32), device=device)[0]
+    if hit[0] == 0:
+        raise KyError("focus_distance: the camera ray through pixel (%d, %d) hits nothing" % (x, y))
+    front = np.array(list(cam.front), np.float64)
+    return float(np.dot(hit[2:5].astype(np.float64) - np.array(list(cam.position), np.float64), front) / np.linalg.norm(front))
+
+
+def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0), lighting=None, filter=None, lens=None):
     """kyhip_render: integrator_t::render(scene, sampler, film) on the GPU; returns the (accumulated) host film.
     lighting: a mask of LIGHTING_EMIT / _DIRECT / _INDIRECT -- kyhip_render_lighting, only those light classes are added.
-    filter: a pixel_filter(...) -- kyhip_render_filtered, the camera samples drawn from the filter's density (not together with lighting)."""
+    filter: a pixel_filter(...) -- kyhip_render_filtered, the camera samples drawn from the filter's density (not together with lighting).
+    lens: a lens(...) -- kyhip_render_lens, the camera rays leave from a disk and meet on the focus plane (with or without filter, not together with lighting)."""
     lib = A.load_kyhip()
-    if filter is not None and lighting is not None:
-        raise ValueError("a render under a pixel filter has no masked form: filter= or lighting=, not both")
+    if (filter is not None or lens is not None) and lighting is not None:
+        raise ValueError("a render under a pixel filter or a lens has no masked form: filter= / lens= or lighting=, not both")
     if film is None:
         film = np.zeros((params.height, params.width, 3), np.float32)
     stride = film.shape[1] if row_stride_px is None else row_stride_px
     base = film.ctypes.data + (origin_px[1] * stride + origin_px[0]) * 12
-    if filter is not None:
+    if lens is not None:
+        _check(lib.kyhip_render_lens(device, _scene_ptr(scene), C.byref(params), C.byref(filter) if filter is not None else None, C.byref(lens), C.c_void_p(base), stride))
+    elif filter is not None:
         _check(lib.kyhip_render_filtered(device, _scene_ptr(scene), C.byref(params), C.byref(filter), C.c_void_p(base), stride))
     elif lighting is None:
         _check(lib.kyhip_render(device, _scene_ptr(scene), C.byref(params), C.c_void_p(base), stride))
@@ -176,9 +209,10 @@ class Frame:
     first == end is a collector that renders nothing.  merge() adds what another frame of the same scene and params holds, bit for bit: `done` counts the samples
     held, `coverage` lists them, and slices that cover 0 .. total merged into one of them resolve to render(scene, params).
     filter=pixel_filter(...): the frame's camera samples are drawn from the filter's density (kyhip_frame_set_filter); a complete frame's resolve() is then
-    render(scene, params, filter=filter) bit for bit, and its states load and merge only into frames with the same filter."""
+    render(scene, params, filter=filter) bit for bit, and its states load and merge only into frames with the same filter.
+    lens=lens(...): the frame's camera rays leave from that lens (kyhip_frame_set_lens), with the same two consequences."""
 
-    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0, filter=None):
+    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0, filter=None, lens=None):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
@@ -206,6 +240,23 @@ class Frame:
             if rc != A.KY_OK:
                 self.close()
                 _check(rc, self._lib)
+
+        if lens is not None:
+            rc = self._lib.kyhip_frame_set_lens(self._f, C.byref(lens))
+            if rc != A.KY_OK:
+                self.close()
+                _check(rc, self._lib)
+
+    def set_lens(self, lens):
+        """kyhip_frame_set_lens: the frame's lens; refused once the frame holds a sample."""
+        _check(self._lib.kyhip_frame_set_lens(self._f, C.byref(lens)), self._lib)
+
+    @property
+    def lens(self):
+        """kyhip_frame_lens: the frame's lens (the pinhole, radius 0, until one is set)."""
+        l = A.Lens()
+        _check(self._lib.kyhip_frame_lens(self._f, C.byref(l)), self._lib)
+        return l
 
     def set_filter(self, filter):
         """kyhip_frame_set_filter: the frame's pixel filter; refused once the frame holds a sample."""
@@ -418,20 +469,20 @@ class Frame:
         _check(self._lib.kyhip_frame_load(self._f, state, len(state)), self._lib)
 
 
-def render_sliced(scene, params, devices, min_samples_per_pass, on_pass=None, noise=False, film=None, filter=None):
+def render_sliced(scene, params, devices, min_samples_per_pass, on_pass=None, noise=False, film=None, filter=None, lens=None):
     """The frame in len(devices) slices of its samples (slice_bounds), slice k on devices[k] (a device may repeat); returns the (accumulated) host film, which is
     render(scene, params) bit for bit.  The slices render in rounds of one pass each, one call after the other (concurrency across devices: ky_amd.dist); after
     every round on_pass(done, total, preview) is called with the samples per pixel done over all slices, and preview(denoise=False) merges the slices as they stand
     into a collector and returns its picture: resolve(normalise=True), or with denoise=True (needs noise=True and two rounds) denoise().  At the end slice 0's
-    frame merges the others and resolves.  filter: every slice's (and the collector's) pixel filter; the film is then render(scene, params, filter=filter)."""
+    frame merges the others and resolves.  filter, lens: every slice's (and the collector's) pixel filter and lens; the film is then render(scene, params, filter=filter, lens=lens)."""
     bounds = slice_bounds(params.samples_per_pixel, len(devices))
     frames = []
     try:
         for k, dev in enumerate(devices):
-            frames.append(Frame(scene, params, device=dev, noise=noise, slice=(bounds[k], bounds[k + 1]), filter=filter))
+            frames.append(Frame(scene, params, device=dev, noise=noise, slice=(bounds[k], bounds[k + 1]), filter=filter, lens=lens))
 
         def preview(denoise=False):
-            with Frame(scene, params, device=devices[0], noise=noise, slice=(0, 0), filter=filter) as collector:
+            with Frame(scene, params, device=devices[0], noise=noise, slice=(0, 0), filter=filter, lens=lens) as collector:
                 for f in frames:
                     collector.merge(f)
                 return collector.denoise() if denoise else collector.resolve(normalise=True)
@@ -534,6 +585,22 @@ def render_filtered_host_api(scene, integrator_enum, depth, direct_sample, sampl
         return None
     if rc != 0:
         raise KyError("kyhost_render_filtered failed: " + host.kyhost_last_error().decode())
+    return film
+
+
+def render_lens_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, lens, mode="render", min_samples_per_pass=4, seed=1234, film=None,
+                         device=0):
+    """camera_t::set_lens(radius, focus_distance) on the scene's camera, then create_integrator(...)->render / render_passes / render_sliced (over the device twice)
+    through the C++ host classes (ky.hpp): mode "render", "passes" or "sliced".  The scene's camera is the pinhole again afterwards.  lens: a lens(...)."""
+    host = A.load_kyhost()
+    if film is None:
+        film = np.zeros((height, width, 3), np.float32)
+    rc = host.kyhost_render_lens(scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device, float(lens.radius),
+                                 float(lens.focus_distance), ("render", "passes", "sliced").index(mode), int(min_samples_per_pass))
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise KyError("kyhost_render_lens failed: " + host.kyhost_last_error().decode())
     return film
 
 
@@ -731,23 +798,28 @@ def scene_boxes(scene):
     return rc, out[:n].copy()
 
 
-def scene_screen_bound(scene, params, filter=None):
+def scene_screen_bound(scene, params, filter=None, lens=None):
     """kyhip_scene_screen_bound (host only): ((x0, y0, x1, y1), dead, total) -- the scene's live rectangle in the frame of `params` (no camera ray of a pixel outside it
     reaches a surface), and the 8 x 8 blocks of the params' shard outside it / in all.  filter: kyhip_scene_screen_bound_filtered -- the rectangle a launch under
-    that pixel filter reads, grown by ceil(radius - 0.5) pixels on every side."""
+    that pixel filter reads, grown by ceil(radius - 0.5) pixels on every side.  lens: kyhip_scene_screen_bound_lens -- with radius > 0 the whole frame, nothing dead."""
     lib = A.load_kyhip()
     rect = (C.c_int * 4)()
     counts = (C.c_longlong * 2)()
-    if filter is None:
+    if lens is not None:
+        _check(lib.kyhip_scene_screen_bound_lens(_scene_ptr(scene), C.byref(params), C.byref(filter) if filter is not None else None, C.byref(lens), rect, counts))
+    elif filter is None:
         _check(lib.kyhip_scene_screen_bound(_scene_ptr(scene), C.byref(params), rect, counts))
     else:
         _check(lib.kyhip_scene_screen_bound_filtered(_scene_ptr(scene), C.byref(params), C.byref(filter), rect, counts))
     return tuple(int(v) for v in rect), int(counts[0]), int(counts[1])
 
 
-def kat_li(scene, params, x, y, s0, n, device=0, filter=None):
+def kat_li(scene, params, x, y, s0, n, device=0, filter=None, lens=None):
     lib = A.load_kyhip()
     out = np.zeros((n, 3), np.float32)
+    if lens is not None:   # kyhip_kat_li_lens: the samples of a render under that lens (and pixel filter)
+        _check(lib.kyhip_kat_li_lens(device, _scene_ptr(scene), C.byref(params), C.byref(filter) if filter is not None else None, C.byref(lens), x, y, s0, n, _fptr(out)))
+        return out
     if filter is not None:   # kyhip_kat_li_filtered: the samples of a render under that pixel filter
         _check(lib.kyhip_kat_li_filtered(device, _scene_ptr(scene), C.byref(params), C.byref(filter), x, y, s0, n, _fptr(out)))
         return out

@@ -68,7 +68,7 @@ struct SceneSlot {
     hipStream_t upload_stream = nullptr;
     unsigned long long last_use = 0;
 };
-constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8, KY_MAX_VARIANTS = 128;
+constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8, KY_MAX_VARIANTS = 160;
 // what kyhip_render / kyhip_render_multi keep between calls (the host-film seam); `m` serialises such calls per device, it is never
 // taken while a context's enqueue mutex is held
 // (measured on configs[1]'s 9.4 MB film, tools/seam_trace.py: what a call costs beyond its kernel -- the film's pinned download alone is 0.18 ms -- is
@@ -138,6 +138,11 @@ struct FramePass {
     bool filtered = false;
     kyd::FilterConst filter{};
     std::string filter_note;
+    // The frame's lens when its radius is > 0: every pass then runs a lens row of the table, whose constants carry `filter` too -- the box's
+    // {KY_FILTER_BOX, 0, 0, nullptr} where the frame has no filter.  lens_note is what kyhip_last_kernel says of it.
+    bool lensed = false;
+    kyd::LensConst lens{};
+    std::string lens_note;
 };
 // resolve_frame_kernel (ky_launch.hip) on `stream`: the frame's accumulators and flags, read and left as they are -> clamp01(value * scale) in the compact tile buffer
 int resolve_frame_device(const void* ws, float* d_tiles, int n_pix, double scale, hipStream_t stream);

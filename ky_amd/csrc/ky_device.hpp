@@ -377,6 +377,21 @@ KY_DEV float filter_offset(const FilterConst& fc, float u) {
     const float a = fc.table[i], b = fc.table[i + 1];
     return 0.5f + __builtin_fmaf(fr, b - a, a);
 }
+// The lens point of a camera sample: Shirley's concentric map of two numbers in [0, 1)^2 onto the unit disk.  (a, b) = 2 u - 1 lies in one of
+// four wedges of the square; the wedge's long coordinate is the radius and the short one over the long one, times pi / 4, the angle from the wedge's axis.  Both
+// wedge pairs evaluate sine and cosine of ONE angle t = (pi / 4) q, |q| <= 1 -- cos(pi / 2 - t) = sin t -- so the argument never leaves [-pi / 4, pi / 4] and one
+// division serves both.  The map is continuous (on the diagonals q = +-1 and both forms agree), area-preserving, keeps strata, and sends (0.5, 0.5) to the centre.
+// 2 u - 1 rounds once whether or not it is contracted (2 u is exact).
+KY_DEV void lens_disk(float u0, float u1, float& dx, float& dy) {
+    const float a = 2.f * u0 - 1.f, b = 2.f * u1 - 1.f;
+    const bool wide = fabsf(a) > fabsf(b);
+    const float r = wide ? a : b, num = wide ? b : a;
+    const float q = r == 0.f ? 0.f : num / r;   // (r == 0 only at the centre, where a == b == 0)
+    const float t = 0.78539816339744830962f * q;
+    const float c = r * cosf(t), s = r * sinf(t);
+    dx = wide ? c : s;
+    dy = wide ? s : c;
+}
 
 // ---------------------------------------------------------------------------------------------
 // camera_t::generate_ray, ky.cpp:1884-1892
@@ -2378,14 +2393,32 @@ KY_DEV void path_state_dead(PathStateT<SMP>& ps) {
 // path of the chunk is added to it, the kernel scales and flushes it once per chunk -- so a new path leaves it alone.
 // FILTER (the filtered kernels): the camera sample's two numbers go through the pixel filter's warp, so the ray leaves through
 // (x + ox, y + oy) with ox, oy in [0.5 - R, 0.5 + R] drawn from the filter's density; the sample still belongs to pixel (x, y) with weight 1.
-template <int SAMPLER, bool KEEP_LO = false, bool FILTER = false>
-KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key, int x, int y, int sample, const FilterConst& fc = FilterConst{}) {
+// CAM == KY_CAM_LENS (the lens kernels): the filter's warp where the filter is not the box (a wave-uniform skip), then the sample's third and
+// fourth numbers become a point of the lens (lens_disk).  The ray is today's generate_ray on a film point shifted against the lens point -- so it passes through
+// the point the pinhole ray of (px, py) meets on the focus plane -- and its origin is shifted once, onto the lens point: the origin differs from lane to lane.
+// The fused multiply-adds are written out (section 10, item 5).
+template <int SAMPLER, bool KEEP_LO = false, int CAM = KY_CAM_PLAIN>
+KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key, int x, int y, int sample, const typename CamConstFor<CAM>::type& fc = typename CamConstFor<CAM>::type{}) {
     sampler_start_kind<SAMPLER>(ps.smp, pixel_key, (uint32_t)sample);
     // get_camera_sample, 943-946 / 971-974
     float u0, u1;
     sampler_camera<SAMPLER>(ps.smp, u0, u1);
-    if constexpr (FILTER) { u0 = filter_offset(fc, u0); u1 = filter_offset(fc, u1); }
-    generate_ray(S, (float)x + u0, (float)y + u1, ps.o, ps.d);
+    if constexpr (CAM == KY_CAM_FILTER) { u0 = filter_offset(fc, u0); u1 = filter_offset(fc, u1); }
+    if constexpr (CAM == KY_CAM_LENS) {
+        if (fc.kind != KY_FILTER_BOX) { u0 = filter_offset(fc, u0); u1 = filter_offset(fc, u1); }
+        const float l0 = sampler_next<SAMPLER>(ps.smp), l1 = sampler_next<SAMPLER>(ps.smp);
+        float dx, dy;
+        lens_disk(l0, l1, dx, dy);
+        const LensConst& lc = fc.lens;
+        const float a = strat_fmul(lc.ar, dx), b = strat_fmul(lc.bu, dy);
+        generate_ray(S, __builtin_fmaf(-a, lc.wf, (float)x + u0), __builtin_fmaf(b, lc.hf, (float)y + u1), ps.o, ps.d);
+        const f3 right = ld3(S->cam_right), up = ld3(S->cam_up);
+        ps.o.x = __builtin_fmaf(up.x, b, __builtin_fmaf(right.x, a, ps.o.x));
+        ps.o.y = __builtin_fmaf(up.y, b, __builtin_fmaf(right.y, a, ps.o.y));
+        ps.o.z = __builtin_fmaf(up.z, b, __builtin_fmaf(right.z, a, ps.o.z));
+    } else {
+        generate_ray(S, (float)x + u0, (float)y + u1, ps.o, ps.d);
+    }
     ps.beta = mk3(1, 1, 1);
     if (!KEEP_LO) ps.Lo = mk3(0, 0, 0);
     ps.bounces = 0;

@@ -237,6 +237,42 @@ int kyhip_render_filtered(int device, const ky_scene* scene, const ky_render_par
     return rcode;
 }
 
+// ---- the frame's lens ----
+int kyhip_frame_set_lens(kyhip_frame* f, const ky_lens* lens) {
+    KY_TRY(lens_check(lens));   // (the lens first, then the frame, as for the filter)
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    LensConst lc{};
+    if (!lens_is_pinhole(lens) && f->book.untouched()) KY_TRY(lens_const_checked(&f->scene.camera, lens, &lc));   // (first: a refusal leaves the frame's lens what it was)
+    KY_TRY(f->book.set_lens(lens));   // (refused once the frame holds a sample; no device work stands behind a lens)
+    FramePass& pass = f->pass;
+    pass.lensed = !lens_is_pinhole(lens);
+    pass.lens = lc;
+    pass.lens_note = lens_describe(lens);
+    return KY_OK;
+}
+int kyhip_frame_lens(const kyhip_frame* f, ky_lens* out) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    *out = f->book.lens;
+    return KY_OK;
+}
+// kyhip_render_filtered under a lens: once more a frame of its own, rendered in one pass and resolved.  The pinhole is kyhip_render_filtered itself.
+int kyhip_render_lens(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, const ky_lens* lens, float* film_rgb, size_t stride_px) {
+    if (lens) KY_TRY(lens_check(lens));
+    if (lens_is_pinhole(lens)) return kyhip_render_filtered(device, scene, p, filter, film_rgb, stride_px);
+    if (filter) KY_TRY(filter_check(filter));
+    if (p && valid_params(p) && p->sampler == KY_SAMPLER_DEBUG) return kyhip_render(device, scene, p, film_rgb, stride_px);   // ((0.5, 0.5) is the centre of every lens)
+    if (!film_rgb || (p && valid_params(p) && stride_px < (size_t)p->width)) return fail(KY_ERR_INVALID_VALUE, "bad film arguments");
+    kyhip_frame* f = nullptr;
+    KY_TRY(kyhip_frame_begin(device, scene, p, &f));
+    int rcode = filter_is_box(filter) ? (int)KY_OK : kyhip_frame_set_filter(f, filter);
+    if (rcode == KY_OK) rcode = kyhip_frame_set_lens(f, lens);
+    if (rcode == KY_OK) rcode = kyhip_frame_render(f, p->samples_per_pixel, nullptr);
+    if (rcode == KY_OK) rcode = kyhip_frame_resolve(f, 1, film_rgb, stride_px);
+    kyhip_frame_end(f);
+    return rcode;
+}
+
 int kyhip_frame_coverage(const kyhip_frame* f, int* ranges2, int n, int own[2]) {
     if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
     return f->book.coverage(ranges2, n, own);

@@ -51,7 +51,7 @@ static int frame_header_check(const FrameHeader& own, const void* buf, size_t by
     same.magic = own.magic;
     if (std::memcmp(&same, &own, sizeof own) != 0) {
         same.scene_hash = own.scene_hash;   // (the header's scene hash carries the frame's pixel filter too: filter_fold, ky_pack.cpp)
-        if (std::memcmp(&same, &own, sizeof own) == 0) return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its scene or its pixel filter differs from this frame's; kyhip_frame_set_filter)");
+        if (std::memcmp(&same, &own, sizeof own) == 0) return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its scene, its pixel filter or its lens differs from this frame's; kyhip_frame_set_filter, kyhip_frame_set_lens)");
         return fail(KY_ERR_INVALID_VALUE, "frame state: saved from another frame (its render params, scene or film size differ from this frame's)");
     }
     if (bytes < state_end) return fail(KY_ERR_INVALID_VALUE, "frame state: %zu bytes, the frame's state has %zu", bytes, state_end);
@@ -311,7 +311,15 @@ int FrameBook::set_filter(const ky_pixel_filter* f) {
     if (!untouched()) return fail(KY_ERR_INVALID_VALUE, "the frame holds samples already: its pixel filter is set before the first one is rendered, loaded or merged");
     filter = *f;
     if (filter.kind == KY_FILTER_BOX) filter = ky_pixel_filter{};   // (one box: its radius names nothing)
-    header.scene_hash = filter_fold(base_hash, &filter);
+    header.scene_hash = lens_fold(filter_fold(base_hash, &filter), &lens);
+    return KY_OK;
+}
+int FrameBook::set_lens(const ky_lens* l) {
+    KY_TRY(lens_check(l));
+    if (!untouched()) return fail(KY_ERR_INVALID_VALUE, "the frame holds samples already: its lens is set before the first one is rendered, loaded or merged");
+    lens = *l;
+    if (lens_is_pinhole(&lens)) lens = ky_lens{};   // (one pinhole: its focus distance names nothing)
+    header.scene_hash = lens_fold(filter_fold(base_hash, &filter), &lens);
     return KY_OK;
 }
 // Where a saved state differs from this frame in nothing but the header's scene hash, the refusal names the filter when that can be told: KY_OK otherwise (the
@@ -324,10 +332,16 @@ int FrameBook::filter_refusal(const void* buf, size_t bytes) const {
     FrameHeader same = theirs;
     same.scene_hash = header.scene_hash; same.samples_done = header.samples_done; same.magic = header.magic;
     if (std::memcmp(&same, &header, sizeof header) != 0) return KY_OK;
-    if (filter_is_box(&filter)) return KY_OK;   // (another scene, or a filter this frame does not have: the header check says so)
+    if (!lens_is_pinhole(&lens)) {   // ... and the lens
+        if (theirs.scene_hash == filter_fold(base_hash, &filter))
+            return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame of this scene without a lens, this frame has a %s (kyhip_frame_set_lens)", lens_describe(&lens).c_str());
+        return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame with another lens or pixel filter (or scene), this frame has a %s and a %s (kyhip_frame_set_lens, kyhip_frame_set_filter)",
+                    lens_describe(&lens).c_str(), filter_describe(&filter).c_str());
+    }
+    if (filter_is_box(&filter)) return KY_OK;   // (another scene, or a filter or lens this frame does not have: the header check says so)
     if (theirs.scene_hash == base_hash)
         return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame of this scene with the box filter, this frame has a %s (kyhip_frame_set_filter)", filter_describe(&filter).c_str());
-    return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame with another pixel filter (or scene), this frame has a %s (kyhip_frame_set_filter)", filter_describe(&filter).c_str());
+    return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame with another pixel filter, a lens (or another scene), this frame has a %s and no lens (kyhip_frame_set_filter, kyhip_frame_set_lens)", filter_describe(&filter).c_str());
 }
 int FrameBook::load_check(const void* buf, size_t bytes, CheckpointCounts* out) const {
     KY_TRY(filter_refusal(buf, bytes));
@@ -462,6 +476,8 @@ int FrameBook::merge_state(const void* state, size_t bytes, MergeStep* out) cons
 int FrameBook::merge_book(const FrameBook& src, MergeStep* out) const {
     if (this == &src) return fail(KY_ERR_INVALID_VALUE, "merge: a frame holds its own samples already");
     if (std::memcmp(&header, &src.header, sizeof header) != 0) {
+        if (std::memcmp(&lens, &src.lens, sizeof lens) != 0)
+            return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their lens (this one: %s, the other: %s)", lens_describe(&lens).c_str(), lens_describe(&src.lens).c_str());
         if (std::memcmp(&filter, &src.filter, sizeof filter) != 0)
             return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their pixel filter (this one: %s, the other: %s)", filter_describe(&filter).c_str(), filter_describe(&src.filter).c_str());
         return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their render params, scene or film size");

@@ -55,6 +55,9 @@ struct FrameBook {
     // the packed scene's hash itself under the box, so every state of an unfiltered frame is what it was.
     ky_pixel_filter filter{};
     uint64_t base_hash = 0;
+    // ... and its lens (section 12), the pinhole {0, 0} until set_lens: header.scene_hash is lens_fold(filter_fold(base_hash, &filter), &lens)
+    ky_lens lens{};
+    int set_lens(const ky_lens* l);   // kyhip_frame_set_lens behind its NULL frame, as set_filter
 
     // the book of the frame of p that owns [first_sample, end_sample): behind begin_check
     void begin(const ky_render_params* p, uint64_t scene_hash, int first_sample, int end_sample);

@@ -109,6 +109,16 @@ std::string filter_describe(const ky_pixel_filter* f);         // "tent filter, 
 uint64_t filter_fold(uint64_t hash, const ky_pixel_filter* f);
 // the live rectangle as a launch under `f` reads it: grown by filter_grow on every side (the kernels' work decoder does the same, ky_render.hpp)
 void screen_bound_widen(const int32_t live[4], const ky_pixel_filter* f, int32_t out[4]);
+// ---- the thin lens (ky_lens; ky_pack.cpp) ----
+int lens_check(const ky_lens* l);                              // kyhip_lens_check
+inline bool lens_is_pinhole(const ky_lens* l) { return !l || !(l->radius > 0.f); }
+std::string lens_describe(const ky_lens* l);                   // "lens radius 0.02, focus 1.45", "pinhole"
+// the scene hash a frame's header carries under `l`: `hash` itself for the pinhole, else `hash` with the bits of radius and focus_distance folded in
+uint64_t lens_fold(uint64_t hash, const ky_lens* l);
+// a valid lens of radius > 0 in the units of `cam`'s generate_ray, computed in double and rounded once (LensConst, ky_scene.hpp)
+kyd::LensConst lens_const(const ky_camera* cam, const ky_lens* l);
+// ... refused (KY_ERR_INVALID_VALUE) where they are not finite: a camera whose front, right or up has no length or is not finite
+int lens_const_checked(const ky_camera* cam, const ky_lens* l, kyd::LensConst* out);
 int pack_scene(const ky_scene* in, DScene* out);
 void pack_light_pick(const ky_scene* in, DLightPick* out);   // sample_single_light's power and spatial picks: the emitter proxies and the power rule's probabilities (a scene pack_scene accepts)
 uint64_t scene_hash(const DScene& s);

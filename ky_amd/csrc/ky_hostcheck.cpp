@@ -746,7 +746,63 @@ int kyhostcheck_filter(void) {
     return 0;
 }
 
-// ---- the entry points that need a GPU: absent from this build.  They exist as symbols because the host mirror (ky.hpp) and ctypes resolve every
+// The thin lens (ky_pack.cpp, ky_frame_book.cpp), host side: the launch constants of a camera whose vectors are not unit length; the header
+// fold (the pinhole leaves a frame's scene hash alone whatever its focus distance, two radii and two focus distances give different hashes, a lens and a filter
+// fold independently and in either order of setting); when a frame takes a lens; what a frame with another lens refuses, and that the refusal names the lens.
+// Returns 0, or the number of the case that went wrong.
+int kyhostcheck_lens(void) {
+    {   // the constants: radius / |right|, radius / |up|, w |front| / focus, h |front| / focus
+        ky_camera cam{};
+        cam.front[2] = 2.f; cam.right[0] = 4.f; cam.up[1] = 0.5f; cam.resolution[0] = 256.f; cam.resolution[1] = 64.f;
+        const ky_lens l = {0.25f, 8.f, {0, 0}};
+        const LensConst c = lens_const(&cam, &l);
+        if (c.ar != 0.0625f || c.bu != 0.5f || c.wf != 64.f || c.hf != 16.f) return 1;
+    }
+    ky_render_params p{};
+    p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS; p.samples_per_pixel = 64; p.sampler = KY_SAMPLER_RANDOM;
+    p.width = 16; p.height = 16; p.tile_w = 16; p.tile_h = 16; p.tile_first = 0; p.tile_step = 1;
+    const ky_lens pin = {0.f, 3.f, {0, 0}}, l1 = {0.05f, 2.f, {0, 0}}, l2 = {0.06f, 2.f, {0, 0}}, l3 = {0.05f, 1.5f, {0, 0}}, bad = {0.05f, 0.f, {0, 0}};
+    const ky_pixel_filter tent = {KY_FILTER_TENT, 2.f, 0.f, 0}, box = {KY_FILTER_BOX, 0.f, 0.f, 0};
+    FrameBook a, b;
+    a.begin(&p, 0x1234, 0, 64);
+    b.begin(&p, 0x1234, 0, 0);   // (a collector)
+    if (a.set_lens(&pin) != KY_OK || a.header.scene_hash != 0x1234 || a.lens.focus_distance != 0.f || std::memcmp(&a.header, &b.header, sizeof a.header) != 0) return 2;
+    if (a.set_lens(&l1) != KY_OK || b.set_lens(&l2) != KY_OK) return 3;
+    const uint64_t h1 = a.header.scene_hash, h2 = b.header.scene_hash;
+    if (h1 == 0x1234 || h2 == 0x1234 || h1 == h2) return 4;
+    if (b.set_lens(&l3) != KY_OK || b.header.scene_hash == h1 || b.header.scene_hash == h2) return 5;
+    if (b.set_lens(&bad) != KY_ERR_INVALID_VALUE || b.set_lens(nullptr) != KY_ERR_INVALID_VALUE || b.lens.focus_distance != 1.5f) return 6;
+    // the lens and the filter fold independently: set in either order they give one hash, which is neither's alone
+    if (a.set_filter(&tent) != KY_OK) return 7;
+    const uint64_t both = a.header.scene_hash;
+    if (b.set_filter(&tent) != KY_OK || b.set_lens(&l1) != KY_OK || b.header.scene_hash != both || both == h1 || both == filter_fold(0x1234, &tent)) return 8;
+    if (a.set_filter(&box) != KY_OK || a.header.scene_hash != h1) return 9;
+    MergeStep ms;
+    if (b.merge_book(a, &ms) != KY_ERR_INVALID_VALUE || last_error().find("filter") == std::string::npos) return 10;   // (same lens, another filter)
+    if (b.set_filter(&box) != KY_OK || b.set_lens(&l2) != KY_OK || b.merge_book(a, &ms) != KY_ERR_INVALID_VALUE || last_error().find("lens radius 0.06, focus 2") == std::string::npos) return 11;
+    if (b.set_lens(&l1) != KY_OK || b.merge_book(a, &ms) != KY_OK) return 12;
+    // a saved state of the lens frame: the pinhole frame and a frame with another lens refuse it, the same lens loads it; then no lens is taken any more
+    std::vector<unsigned char> state(a.layout.total, 0);
+    if (a.save_host(state.data(), state.size()) != KY_OK) return 13;
+    FrameBook c;
+    c.begin(&p, 0x1234, 0, 64);
+    CheckpointCounts n;
+    if (c.load_check(state.data(), state.size(), &n) != KY_ERR_INVALID_VALUE || last_error().find("lens") == std::string::npos) return 14;
+    if (c.set_lens(&l3) != KY_OK || c.load_check(state.data(), state.size(), &n) != KY_ERR_INVALID_VALUE || last_error().find("lens radius 0.05, focus 1.5") == std::string::npos) return 15;
+    if (c.set_lens(&l1) != KY_OK || c.load_check(state.data(), state.size(), &n) != KY_OK) return 16;
+    c.commit_load(n);
+    if (c.set_lens(&l1) != KY_ERR_INVALID_VALUE || c.set_lens(&pin) != KY_ERR_INVALID_VALUE || last_error().find("lens") == std::string::npos) return 17;
+    FrameBook d;   // a pinhole state into a lens frame: "without a lens"
+    d.begin(&p, 0x1234, 0, 64);
+    std::vector<unsigned char> plain(d.layout.total, 0);
+    if (d.save_host(plain.data(), plain.size()) != KY_OK) return 18;
+    FrameBook e;
+    e.begin(&p, 0x1234, 0, 64);
+    if (e.set_lens(&l1) != KY_OK || e.load_check(plain.data(), plain.size(), &n) != KY_ERR_INVALID_VALUE || last_error().find("without a lens") == std::string::npos) return 19;
+    return 0;
+}
+
+// ---- the entry points that need a GPU: absent from this build. They exist as symbols because the host mirror (ky.hpp) and ctypes resolve every
 // symbol when a library is loaded; each validates what the product validates before it touches a device where a CPU test looks at that, and then
 // reports that there is no device -- exactly what libkyhip.so reports on a machine without a gfx950 GPU.
 static int no_gpu() { return fail(KY_ERR_NO_DEVICE, "sanitizer build of the host-only code: no GPU entry points"); }
@@ -860,6 +916,21 @@ int kyhip_kat_filter(int, const ky_pixel_filter* filter, const float*, int, floa
 int kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, int x, int y, int s0, int n, float* out3) {
     if (filter) KY_TRY(filter_check(filter));
     return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);
+}
+// (... and the lens entries an invalid lens, then an invalid filter: lens_check is host code; the pinhole is the filtered entry)
+int kyhip_render_lens(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, const ky_lens* lens, float* film, size_t stride) {
+    if (lens) KY_TRY(lens_check(lens));
+    return kyhip_render_filtered(device, scene, p, filter, film, stride);
+}
+int kyhip_frame_set_lens(kyhip_frame*, const ky_lens* lens) {
+    KY_TRY(lens_check(lens));
+    return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+}
+int kyhip_frame_lens(const kyhip_frame*, ky_lens*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_kat_lens(int, const float*, int, float*) { return no_gpu(); }
+int kyhip_kat_li_lens(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, const ky_lens* lens, int x, int y, int s0, int n, float* out3) {
+    if (lens) KY_TRY(lens_check(lens));
+    return kyhip_kat_li_filtered(device, scene, p, filter, x, y, s0, n, out3);
 }
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_light_pick(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }   // (kyhip_scene_light_pick is host code: ky_pack.cpp)

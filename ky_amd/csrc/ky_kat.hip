@@ -284,6 +284,11 @@ __global__ void kat_sampler_stratified_kernel(uint32_t seed, RenderConstS rc, in
     for (; j < k; ++j) q[j] = __float_as_uint(sampler_next<KY_SMP_STRATIFIED>(smp));
 }
 
+// the lens's disk map alone, as path_begin applies it to a camera sample's third and fourth numbers
+__global__ void kat_lens_kernel(const float* __restrict__ u2, int n, float* __restrict__ out2) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) lens_disk(u2[2 * (size_t)i], u2[2 * (size_t)i + 1], out2[2 * (size_t)i], out2[2 * (size_t)i + 1]);
+}
 // a pixel filter's warp alone, as path_begin applies it to each of a camera sample's two numbers; `table`: KYHIP_FILTER_TABLE + 1 floats
 __global__ void kat_filter_kernel(FilterConst fc, const float* __restrict__ u, int n, float* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -298,15 +303,17 @@ __global__ void kat_filter_kernel(FilterConst fc, const float* __restrict__ u, i
 //            is estimate_env_both (KY_FEAT_SINGLE_ENV).
 //   DROP     0, or -1 for a masked launch (kyhip_render_lighting), whose drop bits `drop` are read at run time (path_intersect, ky_device.hpp); the stratified
 //            sampler's forms always read them.  Which products contract to an fma differs between the two, so an unmasked replay keeps the compile-time 0.
-//   FILTER   the launch runs under a pixel filter (rc_.filter): the filtered render kernels assume no scene facts (no box traversal, no pair scan), and so does this.
+//   CAM      KY_CAM_FILTER: the launch runs under a pixel filter (rc_.filter): the filtered render kernels assume no scene facts (no box traversal, no pair scan),
+//            and so does this.  KY_CAM_LENS: ... and under a lens (rc_.lens; the filter may then be the box).  KY_CAM_PLAIN otherwise.
 //   TRACE    one sample, s0, traced vertex by vertex into out[4..] (`n` rows at most) behind {rows, Lo}: lane 0 walks the path, the other lanes only keep the
 //            wave-uniform calls company.  Otherwise lane i < n walks sample s0 + i and writes out[3 i ..].
-template <int SAMPLER, bool FILTER> struct ReplayConstFor { typedef typename RenderConstFor<SAMPLER>::type type; };
-template <int SAMPLER> struct ReplayConstFor<SAMPLER, true> { typedef RenderConstF type; };
+template <int SAMPLER, int CAM> struct ReplayConstFor { typedef typename RenderConstFor<SAMPLER>::type type; };
+template <int SAMPLER> struct ReplayConstFor<SAMPLER, KY_CAM_FILTER> { typedef RenderConstF type; };
+template <int SAMPLER> struct ReplayConstFor<SAMPLER, KY_CAM_LENS> { typedef RenderConstL type; };
 
-template <int SAMPLER, bool BOXES, int DROP, bool FILTER, bool TRACE>
-__global__ void kat_li_kernel(const DScene* __restrict__ S_, typename ReplayConstFor<SAMPLER, FILTER>::type rc_, int x, int y, int s0, int n, float* __restrict__ out, int single_env, int drop) {
-    const SceneRef S{S_, true, FILTER ? 0 : (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
+template <int SAMPLER, bool BOXES, int DROP, int CAM, bool TRACE>
+__global__ void kat_li_kernel(const DScene* __restrict__ S_, typename ReplayConstFor<SAMPLER, CAM>::type rc_, int x, int y, int s0, int n, float* __restrict__ out, int single_env, int drop) {
+    const SceneRef S{S_, true, CAM != KY_CAM_PLAIN ? 0 : (BOXES ? KY_FEAT_BOXES : 0) | (single_env ? KY_FEAT_SINGLE_ENV : 0), true};
     const typename RenderConstFor<SAMPLER>::type& rc = rc_;
     const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));   // KAT kernels: always the scene-sized dynamic block
     const int i = TRACE ? 0 : blockIdx.x * blockDim.x + threadIdx.x;
@@ -317,7 +324,8 @@ __global__ void kat_li_kernel(const DScene* __restrict__ S_, typename ReplayCons
     VertexTrace tr{out + 4, n, 0};
     if (alive) {
         const uint32_t key = sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x));
-        if constexpr (FILTER) path_begin<SAMPLER, false, true>(ps, S, key, x, y, s0 + i, rc_.filter);
+        if constexpr (CAM == KY_CAM_LENS) path_begin<SAMPLER, false, KY_CAM_LENS>(ps, S, key, x, y, s0 + i, lens_cam(rc_));
+        else if constexpr (CAM == KY_CAM_FILTER) path_begin<SAMPLER, false, KY_CAM_FILTER>(ps, S, key, x, y, s0 + i, rc_.filter);
         else path_begin<SAMPLER>(ps, S, key, x, y, s0 + i);
     }
     while (__any(alive)) {  // path_shade is a wave-uniform call
@@ -376,31 +384,37 @@ struct ReplayLaunch {   // kat_li_kernel's grid and arguments
     dim3 grid, block;
     size_t lds;
     const DScene* S;
-    RenderConstF rc;   // (a kernel without a filter or strata takes the base it declares)
+    RenderConstL rc;   // (a kernel without a lens, a filter or strata takes the base it declares)
     int x, y, s0, n;
     float* out;
     int boxes, single_env, drop;
 };
-template <int SAMPLER, int DROP, bool TRACE, bool FILTER = false>
-static void replay_launch(const ReplayLaunch& a) {   // (FILTER: both lines name the one form without boxes)
-    if (!FILTER && a.boxes) hipLaunchKernelGGL((kat_li_kernel<SAMPLER, !FILTER, DROP, FILTER, TRACE>), a.grid, a.block, a.lds, 0, a.S, a.rc, a.x, a.y, a.s0, a.n, a.out, a.single_env, a.drop);
-    else hipLaunchKernelGGL((kat_li_kernel<SAMPLER, false, DROP, FILTER, TRACE>), a.grid, a.block, a.lds, 0, a.S, a.rc, a.x, a.y, a.s0, a.n, a.out, a.single_env, a.drop);
+template <int SAMPLER, int DROP, bool TRACE, int CAM = KY_CAM_PLAIN>
+static void replay_launch(const ReplayLaunch& a) {   // (under a filter or a lens both lines name the one form without boxes)
+    constexpr bool FILTER = CAM != KY_CAM_PLAIN;
+    if (!FILTER && a.boxes) hipLaunchKernelGGL((kat_li_kernel<SAMPLER, !FILTER, DROP, CAM, TRACE>), a.grid, a.block, a.lds, 0, a.S, a.rc, a.x, a.y, a.s0, a.n, a.out, a.single_env, a.drop);
+    else hipLaunchKernelGGL((kat_li_kernel<SAMPLER, false, DROP, CAM, TRACE>), a.grid, a.block, a.lds, 0, a.S, a.rc, a.x, a.y, a.s0, a.n, a.out, a.single_env, a.drop);
 }
 
 // Replays samples s0 .. s0 + n - 1 of pixel (x, y) of a launch of `p` into out[3 n] -- trace: sample s0 alone into out[4 + 26 n], n rows at most -- with the form of
 // kat_li_kernel that launch's kernel corresponds to; these are all the forms there are.  masked: the launch has a lighting plan with drop bits `drop` (0 otherwise);
-// filter: its pixel filter, null for none (the callers hand a box filter and the debug sampler on without one).
+// filter: its pixel filter, null for none (the callers hand a box filter and the debug sampler on without one); lens: its lens, null for the pinhole (likewise).
 static int replay_run(int device, const ky_scene* scene, const ky_render_params* p, bool masked, int drop, const ky_pixel_filter* filter, bool trace,
-                      int x, int y, int s0, int n, float* out, size_t out_bytes) {
+                      int x, int y, int s0, int n, float* out, size_t out_bytes, const ky_lens* lens = nullptr) {
     float table[KYHIP_FILTER_TABLE + 1] = {0.f};
     if (filter) filter_table(filter, table);
     const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
     return kat_run_scene(device, scene, table, filter ? sizeof table : 4, out, out_bytes, [&](const DScene* S, const DScene* packed, size_t lds, const float* d_in, float* d_out) {
-        ReplayLaunch a{dim3(trace ? 1 : (n + 255) / 256), dim3(trace ? 64 : 256), lds, S, RenderConstF{}, x, y, s0, n, d_out, 0, 0, drop};
+        ReplayLaunch a{dim3(trace ? 1 : (n + 255) / 256), dim3(trace ? 64 : 256), lds, S, RenderConstL{}, x, y, s0, n, d_out, 0, 0, drop};
         static_cast<RenderConstS&>(a.rc) = make_rc(p);
+        if (lens) {   // (the filter's constants beside the lens's, the box's where there is no filter)
+            if (filter) a.rc.filter = FilterConst{filter->kind, filter->radius, filter_grow(filter), d_in};
+            a.rc.lens = lens_const(&scene->camera, lens);
+            return strat ? replay_launch<KY_SMP_STRATIFIED, 0, false, KY_CAM_LENS>(a) : replay_launch<KY_SMP_RANDOM, 0, false, KY_CAM_LENS>(a);
+        }
         if (filter) {
             a.rc.filter = FilterConst{filter->kind, filter->radius, filter_grow(filter), d_in};
-            return strat ? replay_launch<KY_SMP_STRATIFIED, 0, false, true>(a) : replay_launch<KY_SMP_RANDOM, 0, false, true>(a);
+            return strat ? replay_launch<KY_SMP_STRATIFIED, 0, false, KY_CAM_FILTER>(a) : replay_launch<KY_SMP_RANDOM, 0, false, KY_CAM_FILTER>(a);
         }
         const int rf = render_replay_feat(scene, p, packed, drop);
         a.boxes = (rf & KY_FEAT_BOXES) != 0;
@@ -631,6 +645,29 @@ int kyhip_kat_li_filtered(int device, const ky_scene* scene, const ky_render_par
     if (p->sampler == KY_SAMPLER_DEBUG) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);   // (0.5 is the pixel's centre under every filter)
     KY_TRY(replay_check(scene, p, x, y, s0, n, out3));
     return replay_run(device, scene, p, false, 0, filter, false, x, y, s0, n, out3, (size_t)n * 3 * 4);
+}
+
+// ... under a lens (and a pixel filter): the walk of the lens render kernels
+int kyhip_kat_li_lens(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, const ky_lens* lens, int x, int y, int s0, int n, float* out3) {
+    if (lens) KY_TRY(lens_check(lens));
+    if (lens_is_pinhole(lens)) return kyhip_kat_li_filtered(device, scene, p, filter, x, y, s0, n, out3);
+    if (filter) KY_TRY(filter_check(filter));
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    if (p->sampler == KY_SAMPLER_DEBUG) return kyhip_kat_li(device, scene, p, x, y, s0, n, out3);   // ((0.5, 0.5) is the centre of every lens)
+    KY_TRY(replay_check(scene, p, x, y, s0, n, out3));
+    LensConst lc;
+    KY_TRY(lens_const_checked(&scene->camera, lens, &lc));
+    return replay_run(device, scene, p, false, 0, filter_is_box(filter) ? nullptr : filter, false, x, y, s0, n, out3, (size_t)n * 3 * 4, lens);
+}
+
+int kyhip_kat_lens(int device, const float* u2, int n, float* out2) {
+    if (!u2 || !out2 || n <= 0 || n > (1 << 25)) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    for (int i = 0; i < 2 * n; ++i)
+        if (!(u2[i] >= 0.f && u2[i] < 1.f)) return fail(KY_ERR_INVALID_VALUE, "u[%d] = %g outside [0, 1)", i, (double)u2[i]);
+    return kat_run(device, u2, (size_t)n * 8, out2, (size_t)n * 8, [&](DeviceCtx*, const float* d_in, float* d_out) {
+        hipLaunchKernelGGL(kat_lens_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_in, n, d_out);
+        return (int)KY_OK;
+    });
 }
 
 // one camera sample, traced vertex by vertex

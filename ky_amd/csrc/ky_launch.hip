@@ -273,6 +273,7 @@ int kyhip_device_count(void) {
 using RenderFn = void (*)(const DScene*, RenderConst, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);
 using RenderFnS = void (*)(const DScene*, RenderConstS, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a stratified row's kernel: the launch constants carry the strata
 using RenderFnF = void (*)(const DScene*, RenderConstF, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a filtered row's kernel: ... and the pixel filter
+using RenderFnL = void (*)(const DScene*, RenderConstL, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a lens row's kernel: ... and the lens
 struct Variant {
     bool dbg;
     int strategy;
@@ -285,7 +286,9 @@ struct Variant {
     RenderFnS fn_s;   // KY_SAMPLER_STRATIFIED (dbg is false, fn is null): render_kernel_stratified, which takes RenderConstS; null in every other row
     RenderFnF fn_f;   // a launch under a pixel filter (fn and fn_s are null): render_kernel_filtered, which takes RenderConstF; null in every other row ...
     bool f_strat;     // ... and whether it draws with the stratified sampler (else the random one)
-    bool strat() const { return fn_s != nullptr || (fn_f != nullptr && f_strat); }
+    RenderFnL fn_l;   // a launch under a lens (fn, fn_s and fn_f are null; f_strat as above): render_kernel_lens, which takes RenderConstL; null in every other row
+    bool strat() const { return fn_s != nullptr || ((fn_f != nullptr || fn_l != nullptr) && f_strat); }
+    int cam() const { return fn_l ? KY_CAM_LENS : fn_f ? KY_CAM_FILTER : KY_CAM_PLAIN; }
 };
 #define KY_VARIANT(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel<D, S, Q, G, F, I>, 0}
 #define KY_VARIANT_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel<D, S, Q, G, F, I, true>, 0}
@@ -297,6 +300,8 @@ struct Variant {
 #define KY_VARIANT_STRAT(S, Q, G, F, I, L, DROP, LISTED) Variant{false, S, Q, G, F, I, L, nullptr, DROP, LISTED, render_kernel_stratified<S, Q, G, F, I, L, DROP, LISTED>}
 // a filtered row (a pixel filter other than the box; strategy -1, any integrator): the sampler kind, general, large, listed
 #define KY_VARIANT_FILT(SMP, G, L, LISTED) Variant{false, -1, false, G, 0, IT, L, nullptr, 0, LISTED, nullptr, render_kernel_filtered<SMP, G, L, LISTED>, SMP == KY_SMP_STRATIFIED}
+// a lens row (a ky_lens of radius > 0, under any pixel filter), shaped like a filtered row
+#define KY_VARIANT_LENS(SMP, G, L, LISTED) Variant{false, -1, false, G, 0, IT, L, nullptr, 0, LISTED, nullptr, nullptr, SMP == KY_SMP_STRATIFIED, render_kernel_lens<SMP, G, L, LISTED>}
 // a row's three masked twins: emission at the first vertex dropped (lighting 2, 6), the k = 1 terms (5), both (4)
 #define KY_VARIANT_MASKED3(D, S, Q, G, F, I) KY_VARIANT_MASKED(1, D, S, Q, G, F, I), KY_VARIANT_MASKED(2, D, S, Q, G, F, I), KY_VARIANT_MASKED(3, D, S, Q, G, F, I)
 constexpr int IT = KY_INTEGRATOR_PATH_TRACING_ITERATION;
@@ -438,6 +443,20 @@ static const Variant g_variants[] = {
     KY_VARIANT_FILT(KY_SMP_STRATIFIED, false, false, true),
     KY_VARIANT_FILT(KY_SMP_STRATIFIED, true, false, true),
     KY_VARIANT_FILT(KY_SMP_STRATIFIED, true, true, true),
+    // launches under a lens (kyhip_render_lens, kyhip_frame_set_lens), alone or with any pixel filter: twelve rows shaped like the filtered
+    // twelve, with the same things left out
+    KY_VARIANT_LENS(KY_SMP_RANDOM, false, false, false),
+    KY_VARIANT_LENS(KY_SMP_RANDOM, true, false, false),
+    KY_VARIANT_LENS(KY_SMP_RANDOM, true, true, false),
+    KY_VARIANT_LENS(KY_SMP_RANDOM, false, false, true),
+    KY_VARIANT_LENS(KY_SMP_RANDOM, true, false, true),
+    KY_VARIANT_LENS(KY_SMP_RANDOM, true, true, true),
+    KY_VARIANT_LENS(KY_SMP_STRATIFIED, false, false, false),
+    KY_VARIANT_LENS(KY_SMP_STRATIFIED, true, false, false),
+    KY_VARIANT_LENS(KY_SMP_STRATIFIED, true, true, false),
+    KY_VARIANT_LENS(KY_SMP_STRATIFIED, false, false, true),
+    KY_VARIANT_LENS(KY_SMP_STRATIFIED, true, false, true),
+    KY_VARIANT_LENS(KY_SMP_STRATIFIED, true, true, true),
     // everything else: strategy and integrator at run time; the debug sampler; scenes with general shapes
     KY_VARIANT(false, -1, false, false, 0, IT),
     KY_VARIANT(true, -1, false, false, 0, IT),
@@ -451,12 +470,12 @@ static const Variant g_variants[] = {
 constexpr int KY_N_VARIANTS = (int)(sizeof g_variants / sizeof g_variants[0]);
 static_assert(KY_N_VARIANTS <= KY_MAX_VARIANTS, "DeviceCtx::variant_blocks");
 
-static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0, bool listed = false, bool filtered = false) {
+static const Variant* pick_variant(const ky_render_params* p, const DScene* packed, bool deferred_rays, int n_pix, int drop = 0, bool listed = false, int cam = KY_CAM_PLAIN) {
     const bool dbg = p->sampler == KY_SAMPLER_DEBUG, strat = p->sampler == KY_SAMPLER_STRATIFIED;
     const bool general = packed->general != 0;
     const bool large = packed->n_surfaces > KY_LDS_SURFACES || packed->n_materials > KY_LDS_MATERIALS;
     for (const Variant& v : g_variants) {
-        if (v.dbg != dbg || v.strat() != strat || (v.fn_f != nullptr) != filtered || v.large != large || v.listed != listed) continue;
+        if (v.dbg != dbg || v.strat() != strat || v.cam() != cam || v.large != large || v.listed != listed) continue;
         if (v.drop != drop && !(v.drop < 0 && drop != 0)) continue;
         if (general && !v.general) continue;
         if (v.strategy >= 0) {
@@ -525,8 +544,10 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     const RenderConstS rc = make_rc(p);   // (the stratified kernels read all of it, the others its RenderConst)
     const bool strat = p->sampler == KY_SAMPLER_STRATIFIED;
     // a pass of a frame with a pixel filter; the debug sampler's 0.5 is the pixel's centre under every filter, so its launches are the unfiltered ones
-    const bool filt = pass && pass->filtered && p->sampler != KY_SAMPLER_DEBUG;
-    if (filt && drop != 0) return fail(KY_ERR_INVALID_VALUE, "a launch under a pixel filter has no masked form");
+    // ... or a lens: the debug sampler's (0.5, 0.5) is the centre of the lens, the pinhole's ray
+    const int cam = !pass || p->sampler == KY_SAMPLER_DEBUG ? KY_CAM_PLAIN : pass->lensed ? KY_CAM_LENS : pass->filtered ? KY_CAM_FILTER : KY_CAM_PLAIN;
+    const bool filt = cam != KY_CAM_PLAIN, lensed = cam == KY_CAM_LENS;
+    if (filt && drop != 0) return fail(KY_ERR_INVALID_VALUE, "a launch under a pixel filter or a lens has no masked form");
     StreamState* st;
     rcode = get_stream_state(c, stream, &st);
     if (rcode != KY_OK) return rcode;
@@ -568,7 +589,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     // (... nor a masked form: a lighting launch runs on the lane engine too)
     // (... nor passes: a frame's pass runs on the lane engine)
     // (... nor the stratified sampler)
-    // (... nor a pixel filter: a filtered launch is a frame's pass)
+    // (... nor a pixel filter or a lens: such a launch is a frame's pass)
     if (current_engine() == KY_ENGINE_QUEUE && p->integrator == KY_INTEGRATOR_PATH_TRACING_ITERATION && !large_scene && !single && drop == 0 && !pass && !strat) {
         const int variant = p->sampler == KY_SAMPLER_DEBUG ? 2 : (p->direct_sample == KY_DIRECT_BOTH_MIS ? 0 : 1);
         const int per_cu = c->q_blocks_per_cu[variant] > 0 ? c->q_blocks_per_cu[variant] : 1;
@@ -586,10 +607,10 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     } else {
         // (a frame keeps the kernel of its first pass: the table and run-time instantiations differ in the last bit)
         const bool pinned = pass && pass->kernel != -1;
-        const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop, listed, filt);
+        const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop, listed, cam);
         if (!v) return fail(KY_ERR_DEVICE, "internal: no render kernel for these parameters");
         if (pinned && pass->kernel >= 0 && v->listed != listed) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the block list");
-        if ((v->fn_f != nullptr) != filt) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the pixel filter");
+        if (v->cam() != cam) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the pixel filter or the lens");
         const int vi = (int)(v - g_variants);
         // run-time instantiation (kyhip_set_jit(1)): this launch's own kernel -- its sampler, strategy and integrator as compile-time constants and ALL
         // of the scene's facts -- unless the table's pick is exactly that already
@@ -597,7 +618,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         bool queue = v->queue;
         const int jit_mode = kyjit::mode();
         c->last_note.clear();
-        if (filt) c->last_note = " [" + pass->filter_note + ": a filtered launch runs the run-time-dispatched kernel; it takes no specialised row and instantiates no kernel of its own]";
+        if (lensed) c->last_note = " [" + pass->lens_note + ", " + (pass->filtered ? pass->filter_note : std::string("box filter")) + ": a lens launch runs the run-time-dispatched kernel and culls no pixel block; it takes no specialised row and instantiates no kernel of its own]";
+        else if (filt) c->last_note = " [" + pass->filter_note + ": a filtered launch runs the run-time-dispatched kernel; it takes no specialised row and instantiates no kernel of its own]";
         else if (v->strategy < 0 && jit_mode == 0) c->last_note = " [the run-time-dispatched kernel: no row of the table holds this launch's strategy / integrator / shapes; kyhip_set_jit(1 / 2) instantiates its own]";
         // (a mode nobody chose -- the default of round 6 -- instantiates only where the table's pick knows nothing of the scene: a launch served by a row of facts stays on it,
         // a scene outside the table of facts gets its own kernel; kyhip_set_jit(1 / 2) / KYHIP_JIT instantiate for every launch that is not exactly a row)
@@ -670,7 +692,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         }
         if (!jk && (c->variant_blocks[vi] == 0 || c->variant_lds[vi] != lds_bytes)) {   // resident workgroups per CU: depends on the scene's LDS block
             int per_cu = 0;
-            if (v->fn_f) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_f, 256, lds_bytes));
+            if (v->fn_l) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_l, 256, lds_bytes));
+            else if (v->fn_f) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_f, 256, lds_bytes));
             else if (v->fn_s) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_s, 256, lds_bytes));
             else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn, 256, lds_bytes));
             c->variant_blocks[vi] = per_cu > 0 ? per_cu : 1;
@@ -708,7 +731,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         if (drop != 0 && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no masked form]";
         if (pass && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine renders no passes]";
         if (strat && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no stratified sampler]";
-        if (filt && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no pixel filter]";
+        if (lensed && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no lens]";
+        else if (filt && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no pixel filter]";
         if (pass) { pass->kernel = jk ? -3 : vi; pass->queue = queue; }
         if (!jk && v->drop < 0 && st->counter_drop != drop) {   // the drop bits of a run-time-dispatched masked kernel: word 2 of the counter block, written when they change
             HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(st->d_counter + 2), drop, 1, stream));
@@ -727,7 +751,14 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
             HIP_TRY(hipModuleLaunchKernel(jk->fn, grid, 1, 1, 256, 1, 1, (unsigned)lds_bytes, stream, args, nullptr));
             c->last_variant = -3;
         } else {
-            if (v->fn_f) {
+            if (v->fn_l) {   // (the filter is the frame's, the box where it has none; the live rectangle grows over the whole pixel range)
+                RenderConstL rc_l;
+                static_cast<RenderConstS&>(rc_l) = rc;
+                rc_l.filter = pass->filter;
+                rc_l.filter.grow = KY_LIVE_MAX;
+                rc_l.lens = pass->lens;
+                hipLaunchKernelGGL(v->fn_l, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc_l, sh, st->d_counter, accum, flags, queue_mem);
+            } else if (v->fn_f) {
                 RenderConstF rc_f;
                 static_cast<RenderConstS&>(rc_f) = rc;
                 rc_f.filter = pass->filter;
@@ -812,6 +843,7 @@ const char* kyhip_last_kernel(int device) {
         name = buf;
         if (v.listed) name.insert(name.size() - 1, ", listed blocks");
         if (v.fn_f) name.insert(name.size() - 1, ", pixel filter");
+        if (v.fn_l) name.insert(name.size() - 1, ", lens");
         if (v.drop > 0) name.insert(name.size() - 1, ", drop " + std::to_string(v.drop));
         else if (v.drop < 0) name.insert(name.size() - 1, ", drop bits per launch");
     }

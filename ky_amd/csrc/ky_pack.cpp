@@ -838,6 +838,56 @@ void screen_bound_widen(const int32_t live[4], const ky_pixel_filter* f, int32_t
     out[0] = live[0] - g; out[1] = live[1] - g; out[2] = live[2] + g; out[3] = live[3] + g;
 }
 
+// ---- the thin lens (include/kyhip.h, ky_lens) ----
+// Under a lens the live rectangle's proof (screen_bound above) does not hold: it projects the scene's bound from ONE point, and a scene point at depth z along
+// `front` is seen from the lens point l (in units of `right`) at the film position of the pinhole shifted by l (1 / focus - 1 / z) -- unbounded as z -> 0 and as far
+// as the aperture is wide.  A lens launch therefore reads the whole pixel range: its work decoder grows the rectangle by KY_LIVE_MAX (ky_render.hpp; the sums stay
+// far inside int32), the packed scene and its hash stay the pinhole's, and kyhip_scene_screen_bound_lens states the same.  A finite widening proven from the depth
+// range of the world bound is out of scope.
+int lens_check(const ky_lens* l) {
+    if (!l) return fail(KY_ERR_INVALID_VALUE, "lens is NULL");
+    if (l->reserved[0] != 0 || l->reserved[1] != 0) return fail(KY_ERR_INVALID_VALUE, "lens: reserved is {%d, %d}, not 0", l->reserved[0], l->reserved[1]);
+    if (!std::isfinite(l->radius) || l->radius < 0.f) return fail(KY_ERR_INVALID_VALUE, "lens: radius %g (>= 0 and finite, world units; 0 is the pinhole)", (double)l->radius);
+    if (l->radius > 0.f && (!std::isfinite(l->focus_distance) || !(l->focus_distance > 0.f)))
+        return fail(KY_ERR_INVALID_VALUE, "lens: focus distance %g (> 0 and finite, world units along the camera's front)", (double)l->focus_distance);
+    return KY_OK;
+}
+std::string lens_describe(const ky_lens* l) {
+    if (lens_is_pinhole(l)) return "pinhole";
+    char buf[96];
+    snprintf(buf, sizeof buf, "lens radius %g, focus %g", (double)l->radius, (double)l->focus_distance);
+    return buf;
+}
+uint64_t lens_fold(uint64_t hash, const ky_lens* l) {
+    if (lens_is_pinhole(l)) return hash;
+    uint32_t w[2];
+    std::memcpy(&w[0], &l->radius, 4);
+    std::memcpy(&w[1], &l->focus_distance, 4);
+    for (uint32_t v : w) {   // filter_fold's mix with another closing constant: a lens and a filter of the same bits give different hashes
+        hash = (hash ^ v) * 0x100000001b3ull;
+        hash ^= hash >> 29;
+    }
+    return hash * 0x9e3779b97f4a7c15ull + 0x4c454e53ull;
+}
+LensConst lens_const(const ky_camera* cam, const ky_lens* l) {
+    auto len = [](const float v[3]) { return std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]); };
+    const double r = (double)l->radius, t = len(cam->front) / (double)l->focus_distance;   // (the ray parameter of the focus plane is focus / |front|)
+    LensConst c;
+    c.ar = (float)(r / len(cam->right));
+    c.bu = (float)(r / len(cam->up));
+    // (the kernels divide by the resolution through the float reciprocals pack_scene stores; w and h here are what those stand for)
+    c.wf = (float)((double)cam->resolution[0] * t);
+    c.hf = (float)((double)cam->resolution[1] * t);
+    return c;
+}
+int lens_const_checked(const ky_camera* cam, const ky_lens* l, LensConst* out) {
+    const LensConst c = lens_const(cam, l);
+    if (!(std::isfinite(c.ar) && std::isfinite(c.bu) && std::isfinite(c.wf) && std::isfinite(c.hf) && c.wf > 0.f && c.hf > 0.f))
+        return fail(KY_ERR_INVALID_VALUE, "lens: the scene's camera has no finite basis or resolution to carry a lens (front, right and up need a length)");
+    *out = c;
+    return KY_OK;
+}
+
 int pack_scene(const ky_scene* in, DScene* out) {
     if (!in) return fail(KY_ERR_INVALID_VALUE, "scene is NULL");
     if (in->surface_count < 0 || in->shape_count < 0 || in->material_count < 0 || in->light_count < 0)
@@ -1534,6 +1584,24 @@ int kyhip_scene_screen_bound_filtered(const ky_scene* scene, const ky_render_par
     if (counts) screen_bound_counts(live, params, &counts[0], &counts[1]);
     return KY_OK;
 }
+
+// ... and under a lens: the whole pixel range, nothing culled (lens_check, the paragraph above it)
+int kyhip_scene_screen_bound_lens(const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter, const ky_lens* lens, int rect[4], long long counts[2]) {
+    if (lens) KY_TRY(lens_check(lens));
+    if (lens_is_pinhole(lens)) return kyhip_scene_screen_bound_filtered(scene, params, filter, rect, counts);
+    if (filter) KY_TRY(filter_check(filter));
+    if (!scene || !rect) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    if (!valid_params(params)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    if (!shard_in_range(params)) return fail(KY_ERR_LIMIT, "frame too large for the device's 32-bit work-item and pixel indices");
+    std::vector<DScene> packed(1);
+    KY_TRY(pack_scene(scene, &packed[0]));
+    const int32_t live[4] = {packed[0].live[0] - KY_LIVE_MAX, packed[0].live[1] - KY_LIVE_MAX, packed[0].live[2] + KY_LIVE_MAX, packed[0].live[3] + KY_LIVE_MAX};   // as the work decoder reads it
+    rect[0] = std::min(std::max(live[0], 0), params->width); rect[1] = std::min(std::max(live[1], 0), params->height);
+    rect[2] = std::min(live[2], params->width); rect[3] = std::min(live[3], params->height);
+    if (counts) screen_bound_counts(live, params, &counts[0], &counts[1]);
+    return KY_OK;
+}
+int kyhip_lens_check(const ky_lens* lens) { return lens_check(lens); }
 
 // ---- pixel filters: the host-only entries (filter_check ... above) ----
 int kyhip_filter_check(const ky_pixel_filter* filter) { return filter_check(filter); }

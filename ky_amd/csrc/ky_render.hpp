@@ -91,12 +91,15 @@ constexpr int ky_waves_per_eu() {
 // of instantiations) and the extern "C" kernel of a run-time instantiation (ky_jit.cpp).
 // SAMPLER: KY_SMP_RANDOM, KY_SMP_DEBUG (what the `bool DEBUG_SAMPLER` of the kernel templates below converts to) or KY_SMP_STRATIFIED, whose launch constants are the
 // wider RenderConstS.
-// FILTER: the camera sample's offsets are drawn from a pixel filter's density (`fc`; path_begin, ky_device.hpp) and the live rectangle is read fc.grow pixels wider
-// on every side; false -- every instantiation that does not name it -- ignores fc.
+// CAM: KY_CAM_FILTER -- the camera sample's offsets are drawn from a pixel filter's density (`fc`; path_begin, ky_device.hpp) and the live rectangle is read fc.grow
+// pixels wider on every side; KY_CAM_LENS -- ... and the ray leaves from a point of the lens fc.lens, with fc.grow = KY_LIVE_MAX: the whole pixel range is live, for
+// the rectangle's proof is a projection from one point (screen_bound, ky_pack.cpp); the sums stay within int32.  KY_CAM_PLAIN -- every instantiation that does not
+// name it -- ignores fc.
 template <int SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false,
-          bool FILTER = false>
+          int CAM = KY_CAM_PLAIN>
 KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderConstFor<SAMPLER>::type rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
-                               unsigned* __restrict__ flags, float4* __restrict__ queue_mem, FilterConst fc = FilterConst{}) {
+                               unsigned* __restrict__ flags, float4* __restrict__ queue_mem, typename CamConstFor<CAM>::type fc = typename CamConstFor<CAM>::type{}) {
+    constexpr bool FILTER = CAM != KY_CAM_PLAIN;   // what the filtered and the lens kernels share: run-time dispatch, a widened live rectangle
     static_assert(!FILTER || (STRATEGY < 0 && !QUEUE && DROP == 0 && SAMPLER != KY_SMP_DEBUG), "the filtered kernels are the run-time-dispatched ones, unmasked");
     static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || ky_direct_is_single(STRATEGY) || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
                   "the deferred shadow rays belong to the iterative integrator's strategies with a light-sampling half");
@@ -280,7 +283,8 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderCon
                 const int xy = c_xy[tid];
                 const unsigned se = c_se[tid];
                 const uint32_t key = QUEUE ? sampler_pixel_key(rc.seed, (uint32_t)((xy >> 16) * rc.width + (xy & 0xffff))) : c_key[tid];
-                if constexpr (FILTER) path_begin<SAMPLER, true, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
+                if constexpr (CAM == KY_CAM_LENS) path_begin<SAMPLER, true, KY_CAM_LENS>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
+                else if constexpr (FILTER) path_begin<SAMPLER, true, KY_CAM_FILTER>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
                 else path_begin<SAMPLER, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7));
                 c_se[tid] = se + 127;             // next sample + 1, samples left - 1
                 open = (se & 127) > 1;
@@ -366,5 +370,15 @@ __global__ __launch_bounds__(256, (ky_waves_per_eu<SAMPLER, -1, false, GENERAL, 
     const DScene* __restrict__ S_, RenderConstF rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
     float4* __restrict__ queue_mem) {
     static_assert(SAMPLER == KY_SMP_RANDOM || SAMPLER == KY_SMP_STRATIFIED, "the debug sampler ignores the filter: its launches run the unfiltered kernels");
-    render_kernel_body<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED, true>(S_, rc, sh, counter, accum, flags, queue_mem, rc.filter);
+    render_kernel_body<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED, KY_CAM_FILTER>(S_, rc, sh, counter, accum, flags, queue_mem, rc.filter);
+}
+
+// The lens instantiations (a ky_lens of radius > 0: kyhip_render_lens, kyhip_frame_set_lens), shaped like the filtered ones: their launch constants (RenderConstL)
+// carry the lens and the pixel filter, the box among them.
+template <int SAMPLER, bool GENERAL = false, bool LARGE = false, bool LISTED = false>
+__global__ __launch_bounds__(256, (ky_waves_per_eu<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED>())) void render_kernel_lens(
+    const DScene* __restrict__ S_, RenderConstL rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
+    float4* __restrict__ queue_mem) {
+    static_assert(SAMPLER == KY_SMP_RANDOM || SAMPLER == KY_SMP_STRATIFIED, "the debug sampler ignores the lens: its launches run the pinhole kernels");
+    render_kernel_body<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED, KY_CAM_LENS>(S_, rc, sh, counter, accum, flags, queue_mem, lens_cam(rc));
 }

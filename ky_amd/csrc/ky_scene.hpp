@@ -320,5 +320,31 @@ struct FilterConst {
 struct RenderConstF : RenderConstS {
     FilterConst filter;
 };
+// A thin lens (ky_lens) as a launch carries it, in the units generate_ray computes in: a point (dx, dy) of the unit disk is the lens point
+// position + right * (ar dx) + up * (bu dy), and the film point moves by (-(ar dx) wf, +(bu dy) hf) pixels.  The four are computed by the host in double from the
+// scene's camera and rounded once (lens_const, ky_pack.cpp): ar = radius / |right|, bu = radius / |up|, wf = w |front| / focus, hf = h |front| / focus, with w x h
+// the camera's own resolution (1 / cam_inv_w, 1 / cam_inv_h) and |front| = 1 for a ky_camera as documented.  Only the lens kernels take the wider block; its
+// `filter` is the launch's pixel filter (the box when there is none) with grow = KY_LIVE_MAX: a lens launch reads the whole pixel range (screen_bound, ky_pack.cpp).
+struct LensConst {
+    float ar, bu, wf, hf;
+};
+struct RenderConstL : RenderConstF {
+    LensConst lens;
+};
+// what path_begin does with a camera sample beyond today's: nothing, the pixel filter's warp, or the warp and the lens
+enum : int { KY_CAM_PLAIN = 0, KY_CAM_FILTER = 1, KY_CAM_LENS = 2 };
+// ... and the constants it takes for that: the filter's, or the filter's and the lens's.  The device functions shared with the kernels that have no lens declare
+// their parameter as CamConstFor<CAM>::type, so those kernels' instantiations are what they were before there was a lens, to the last argument.
+struct LensCam : FilterConst {
+    LensConst lens;
+};
+template <int CAM> struct CamConstFor { typedef FilterConst type; };
+template <> struct CamConstFor<KY_CAM_LENS> { typedef LensCam type; };
+KY_HD inline LensCam lens_cam(const RenderConstL& rc) {
+    LensCam c;
+    static_cast<FilterConst&>(c) = rc.filter;
+    c.lens = rc.lens;
+    return c;
+}
 
 }  // namespace kyd

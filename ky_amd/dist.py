@@ -229,16 +229,16 @@ def gather_states(state, rank, world, group=None):
     return [t.numpy().tobytes() for t in out]
 
 
-def render_sliced_distributed(scene, params, rank, world, device_index=0, min_samples_per_pass=64, film=None, group=None, noise=False, filter=None):
+def render_sliced_distributed(scene, params, rank, world, device_index=0, min_samples_per_pass=64, film=None, group=None, noise=False, filter=None, lens=None):
     """integrator_t::render over `world` ranks by sample range: rank r renders slice r of api.slice_bounds(samples_per_pixel, world) over the whole film in passes
     of at least min_samples_per_pass, with no communication while rendering and perfect load balance; ONE gather of the saved states (through host memory: the group
     may be gloo) at the end, then rank 0 merges them into its own frame and resolves.  Returns the host film (numpy, api.render's bit for bit) on rank 0, None
     elsewhere.  noise=True: every rank tracks noise and rank 0's merged frame carries the pooled estimate.  filter: every rank's pixel filter (api.pixel_filter);
-    the film is then api.render(..., filter=filter)'s."""
+    the film is then api.render(..., filter=filter)'s.  lens: every rank's lens (api.lens), likewise."""
     lib = A.load_kyhip()
     _same_kernel_on_every_rank(lib, world)
     bounds = api.slice_bounds(params.samples_per_pixel, world)
-    with api.Frame(scene, params, device=device_index, noise=noise, slice=(bounds[rank], bounds[rank + 1]), filter=filter) as f:
+    with api.Frame(scene, params, device=device_index, noise=noise, slice=(bounds[rank], bounds[rank + 1]), filter=filter, lens=lens) as f:
         while f.done < bounds[rank + 1] - bounds[rank]:
             f.render(min_samples_per_pass)
         states = gather_states(f.save(), rank, world, group)

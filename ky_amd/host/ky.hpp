@@ -278,9 +278,20 @@ public:
         c.resolution[0] = resolution_.x; c.resolution[1] = resolution_.y;
         return c;
     }
+    // The thin lens the reference leaves room for (`point2_t p_lens`, ky.cpp:870-874; `// sample_ray(...)`, 1894; include/kyhip.h, ky_lens): an aperture of
+    // `radius` and a focus plane at depth `focus_distance` along front, both in world units; radius 0 is the pinhole this camera is until set_lens.  Every render
+    // entry of integrator_t reads it from the camera of the scene it renders; what kyhip_lens_check refuses is refused here.  (A scene holds its camera const:
+    // copy get_camera(), set the lens on the copy and hand it to scene_t::set_camera.)
+    void set_lens(float radius, float focus_distance) {
+        const ky_lens l{radius, focus_distance, {0, 0}};
+        if (kyhip_lens_check(&l) != KY_OK) throw std::runtime_error(std::string("camera_t::set_lens: ") + kyhip_last_error());
+        lens_ = l;
+    }
+    ky_lens lens() const { return lens_; }
 private:
     vec3_t position_, front_, right_, up_;
     vec2_t resolution_;
+    ky_lens lens_{};
 };
 using const_camera_sptr_t = std::shared_ptr<const camera_t>;
 
@@ -514,6 +525,7 @@ public:
         return b;
     }
     const camera_t* get_camera() const { return camera_.get(); }
+    void set_camera(const_camera_sptr_t camera) { camera_ = std::move(camera); }   // (e.g. a copy of get_camera() with a lens: camera_t::set_lens)
     int light_count() const { return (int)light_list_.size(); }
     const light_list_t& light_list() const { return light_list_; }
     const environment_light_t* environment_light() const { return environment_light_; }
@@ -745,6 +757,14 @@ public:
     void render(scene_t* scene, sampler_t* original_sampler, film_t* film) {
         const ky_render_params p = params_for(original_sampler, film);
         const ky_pixel_filter flt = film->pixel_filter();
+        const ky_lens lens = scene->get_camera()->lens();
+        if (lens.radius > 0.f) {   // the camera's lens (camera_t::set_lens): kyhip_render_lens under the film's filter, on ONE device like a filtered render
+            if (masked()) throw std::runtime_error("integrator_t::render: light classes are rendered through the pinhole only");
+            if (devices_.size() != 1) throw std::runtime_error("integrator_t::render: a camera with a lens renders on one device (render_sliced spreads such a frame over several)");
+            const int rc = kyhip_render_lens(devices_[0], &scene->flatten(), &p, &flt, &lens, film->target_origin(), film->row_stride_px());
+            if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_lens: ") + kyhip_last_error());
+            return;
+        }
         if (flt.kind != KY_FILTER_BOX) {   // the film's pixel filter (film_t::set_filter): kyhip_render_filtered, on ONE device -- no masked form, no kyhip_render_multi
             if (masked()) throw std::runtime_error("integrator_t::render: light classes are rendered under the box filter only");
             if (devices_.size() != 1) throw std::runtime_error("integrator_t::render: a film with a pixel filter renders on one device (render_sliced spreads a filtered frame over several)");
@@ -763,10 +783,14 @@ public:
         if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_multi: ") + kyhip_last_error());
     }
     // the film's pixel filter into a frame that has just begun (the box: nothing to do); own: end the frame before throwing
-    static void frame_filter(kyhip_frame* frame, const film_t* film, bool own = true) {
+    // ... and the lens of the scene's camera (the pinhole: nothing to do)
+    static void frame_filter(kyhip_frame* frame, const film_t* film, bool own = true, const scene_t* scene = nullptr) {
         const ky_pixel_filter flt = film->pixel_filter();
-        if (flt.kind == KY_FILTER_BOX || kyhip_frame_set_filter(frame, &flt) == KY_OK) return;
-        const std::string what = std::string("kyhip_frame_set_filter: ") + kyhip_last_error();
+        const ky_lens lens = scene ? scene->get_camera()->lens() : ky_lens{};
+        std::string what;
+        if (flt.kind != KY_FILTER_BOX && kyhip_frame_set_filter(frame, &flt) != KY_OK) what = std::string("kyhip_frame_set_filter: ") + kyhip_last_error();
+        else if (lens.radius > 0.f && kyhip_frame_set_lens(frame, &lens) != KY_OK) what = std::string("kyhip_frame_set_lens: ") + kyhip_last_error();
+        if (what.empty()) return;
         if (own) kyhip_frame_end(frame);
         throw std::runtime_error(what);
     }
@@ -779,7 +803,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
-        frame_filter(frame, film);
+        frame_filter(frame, film, true, scene);
         try {
             int done = 0;
             bool go_on = true;
@@ -817,7 +841,7 @@ public:
             for (int k = 0; k < n; ++k) {
                 if (kyhip_frame_begin_slice(devices[(size_t)k], &flat, &p, bounds[(size_t)k], bounds[(size_t)k + 1], &frames[(size_t)k]) != KY_OK)
                     throw std::runtime_error(std::string("kyhip_frame_begin_slice: ") + kyhip_last_error());
-                frame_filter(frames[(size_t)k], film, false);   // (end_all below ends every frame)
+                frame_filter(frames[(size_t)k], film, false, scene);   // (end_all below ends every frame)
                 bool seen = false;
                 for (int d : distinct) seen = seen || d == devices[(size_t)k];
                 if (!seen) distinct.push_back(devices[(size_t)k]);
@@ -878,7 +902,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
-        frame_filter(frame, film);
+        frame_filter(frame, film, true, scene);
         int done = 0;
         try {
             ky_noise_stats st;
@@ -905,7 +929,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
-        frame_filter(frame, film);
+        frame_filter(frame, film, true, scene);
         int done = 0;
         try {
             if (kyhip_frame_track_noise(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_noise: ") + kyhip_last_error());
@@ -936,7 +960,7 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
         if (kyhip_frame_begin(devices_[0], &scene->flatten(), &p, &frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_begin: ") + kyhip_last_error());
-        frame_filter(frame, film);
+        frame_filter(frame, film, true, scene);
         ky_block_stats st{};
         try {
             int done = 0;

@@ -152,6 +152,38 @@ int kyhost_render_filtered(void* scene, int integrator_enum, int depth, int dire
     return rc != 0 ? rc : status;
 }
 
+// camera_t::set_lens(radius, focus_distance) on a copy of the scene's camera (scene_t::set_camera), then one of the integrator's render entries on a film_t of
+// width x height: the camera's lens through the host mirror.  mode 0: render(); 1: render_passes(min_samples_per_pass) to the end; 2: render_sliced over
+// {device, device}.  The scene gets its own camera back whatever happens.  `film` is read, added to and written back.  Returns 0, -1 on error, -2 when
+// create_integrator returns nullptr.
+int kyhost_render_lens(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
+                       float* film, int device, float radius, float focus_distance, int mode, int min_samples_per_pass) {
+    int status = 0;
+    int rc = guarded([&] {
+        std::unique_ptr<ky::integrator_t> integrator = ky::create_integrator((ky::integrator_enum_t)integrator_enum, depth, (ky::direct_sample_enum_t)direct_sample_enum, device);
+        if (!integrator) { status = -2; return; }
+        std::unique_ptr<ky::sampler_t> sampler = make_sampler(sampler_kind, spp, seed);
+        ky::film_t f(width, height);
+        const size_t n = (size_t)f.get_pixel_num() * 3;
+        std::memcpy(f.data(), film, n * sizeof(float));
+        ky::scene_t* sc = &((scene_box*)scene)->scene;
+        struct restore_camera {
+            ky::scene_t* sc;
+            ky::const_camera_sptr_t pinhole;
+            ~restore_camera() { sc->set_camera(pinhole); }
+        } restore{sc, std::make_shared<ky::camera_t>(*sc->get_camera())};
+        auto with_lens = std::make_shared<ky::camera_t>(*sc->get_camera());
+        with_lens->set_lens(radius, focus_distance);
+        sc->set_camera(with_lens);
+        if (mode == 0) integrator->render(sc, sampler.get(), &f);
+        else if (mode == 1) integrator->render_passes(sc, sampler.get(), &f, min_samples_per_pass, {});
+        else if (mode == 2) integrator->render_sliced(sc, sampler.get(), &f, std::vector<int>{device, device}, min_samples_per_pass);
+        else throw std::runtime_error("kyhost_render_lens: mode 0 .. 2");
+        std::memcpy(film, f.data(), n * sizeof(float));
+    });
+    return rc != 0 ? rc : status;
+}
+
 // create_integrator(...)->render_passes(&scene, sampler, &film, min_samples_per_pass, on_pass) on a film_t of width x height; on_pass(done, total, user) returns
 // nonzero to go on (NULL: render to the end).  `film` is read, added to and written back.  Returns 0, -1 on error, -2 when create_integrator returns nullptr.
 int kyhost_render_passes(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,

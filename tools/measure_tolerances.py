@@ -97,3 +97,12 @@ if not ONLY or "filter" in ONLY:
         for kind, radius, param, _ in TF.CENTRING:
             flt = F.Filter(kind, radius, param)
             print("filter centring", flt, "rmse %.4e" % TF.centring_rmse(O, base, flt), "corner-centred %.4e" % TF.centring_rmse(O, base, flt, shift=-0.5))
+# the lens's disk map (tests/test_lens_gpu.py; one GPU): the largest deviation of the device's lens_disk from the double restatement over the test's 2^16 pairs --
+# the test's DISK_MEASURED, of which it allows four times and never more than 1e-5 -- and from the float32 restatement, whose quotient is correctly rounded
+if not ONLY or "lens" in ONLY:
+    import lens_restatement as L
+    import test_lens_gpu as TL
+    u = TL.disk_inputs()
+    got = api.kat_lens(u).astype(np.float64)
+    print("lens disk map: %d pairs, max |device - double restatement| %.4e, max |device - float32 restatement| %.4e, largest |point| - 1 %.3e"
+          % (u.shape[0], np.abs(got - L.disk(u, np.float64)).max(), np.abs(got - L.disk(u, np.float32)).max(), float(np.hypot(got[:, 0], got[:, 1]).max() - 1)))

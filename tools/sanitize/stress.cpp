@@ -15,6 +15,7 @@ int kyhostcheck_add_rows(int width, int height, int stride_px, int n_threads, in
 int kyhostcheck_chunks(int spp);
 int kyhostcheck_screen_bound(void);
 int kyhostcheck_filter(void);
+int kyhostcheck_lens(void);
 int kyhostcheck_jit_stress(int n_threads, int rounds);
 int kyhostcheck_checkpoint(const ky_render_params* p, int noise, int blocks, int check_blocks, const int* counts_in, const int32_t* states, size_t check_bytes,
                            size_t* offsets, int* counts_out, void* state_out, size_t state_capacity);
@@ -107,6 +108,9 @@ int main(int argc, char** argv) {
     rc = kyhostcheck_filter();   // pixel filters: check, defaults, table, the header fold, the widened live rectangle
     std::printf("filter -> %d\n", rc);
     if (rc) return 9;
+    rc = kyhostcheck_lens();   // the lens: launch constants, the header fold beside the filter's, refusals that name the lens
+    std::printf("lens -> %d\n", rc);
+    if (rc) return 10;
     {   // a checkpoint of a 40 x 24 frame (ragged tiles) for what it can track: accepted whole, refused one byte short of every part's end and by the other `blocks`
         ky_render_params p = {};
         p.integrator = KY_INTEGRATOR_PATH_TRACING_ITERATION; p.max_path_depth = 5; p.direct_sample = KY_DIRECT_BOTH_MIS; p.samples_per_pixel = 500; p.sampler = KY_SAMPLER_RANDOM;
