@@ -41,6 +41,9 @@
  *                                kyhip_render_lens) of radius 2 % and 4 % of the scene's diagonal focused on the front ball -- the nearest sphere a coarse grid of pinhole
  *                                rays finds (kyhip_kat_camera, kyhip_kat_scene_intersect) --, path_tracing_iteration d5 both_mis into a film_grid_t(1, 3, ...); prints
  *                                the focus distance and the three kernel times and writes lens.bmp: pinhole | lens | wider lens
+ *   ky_drivers textured [spp] [size] the Cornell box (16 spp; 256 x 256) with a 4 x 4 checker on its floor and a small image, generated here, on the wall the camera
+ *                                faces (checker_texture_t, image_texture_t on plastic_material_t / matte_material_t; kyhip_render_textured), path_tracing_iteration d5
+ *                                both_mis; prints the kernel's name and time and writes textured.bmp
  *   ky_drivers pick [spp] [w] [h]    the Veach frame under sample_single_light with its light picked uniformly (49), by power (113) and by position at the vertex
  *                                (177) side by side at equal spp (16; cells of 512 x 288), path_tracing_iteration d5 into a film_grid_t(1, 3, ...); writes pick.bmp:
  *                                uniform | power | spatial
@@ -292,6 +295,32 @@ static void render_filtered(int spp, int cell) {
     std::printf("filtered: cornell %dx%d, %d spp: kernel", cell, cell, spp);
     for (int k = 0; k < 3; ++k) std::printf(" %.3f ms %s%s", ms[k], names[k], k < 2 ? "," : "\n");
     film.store_image("filtered");
+}
+
+// The Cornell box with textures (the reference's `// TODO class texture_t`, ky.cpp:2559-2564): a 4 x 4 checker on the floor -- the plane the balls stand on, whose material
+// is the plastic one -- and an 8 x 8 image on the wall the camera faces, nearest and repeating twice each way.  The image is made here: red rises with x, green with
+// y, in sixteenths.  The materials own their textures; the scene's flattening collects the set and the integrator hands it to kyhip_render_textured.
+static void render_textured(int spp, int size) {
+    film_t film(size, size);
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::default_scene, film.get_resolution());
+    const ky_scene& flat = scene.flatten();
+    const int floor = flat.surfaces[3].material, wall = flat.surfaces[4].material;   // (surface_list_ order: 3 is the plane z = -1.28, 4 the plane y = -1.305)
+    const ky_material fm = flat.materials[floor];
+    std::vector<float> texels((size_t)8 * 8 * 3);
+    for (int y = 0; y < 8; ++y)
+        for (int x = 0; x < 8; ++x) {
+            float* t = &texels[((size_t)y * 8 + x) * 3];
+            t[0] = (2 * x + 1) / 16.f; t[1] = (2 * y + 1) / 16.f; t[2] = 0.25f;
+        }
+    scene.replace_material(floor, std::make_shared<plastic_material_t>(std::make_shared<checker_texture_t>(color_t{0.25f, 0.25f, 0.0625f}, color_t{0.03125f, 0.0625f, 0.25f}, vec2_t{4, 4}),
+                                                                       color_t{fm.color1[0], fm.color1[1], fm.color1[2]}, fm.exponent));
+    scene.replace_material(wall, std::make_shared<matte_material_t>(std::make_shared<image_texture_t>(8, 8, texels, false, false, vec2_t{2, 2})));
+    random_sampler_t sampler(spp);
+    auto integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
+    integrator->render(&scene, &sampler, &film);
+    std::string kernel = kyhip_last_kernel(0);
+    std::printf("textured: cornell %dx%d, %d spp: kernel %.3f ms  %s\n", size, size, spp, integrator->last_kernel_ms(), kernel.substr(0, kernel.find(" [")).c_str());
+    film.store_image("textured");
 }
 
 // The Cornell box through a thin lens (the reference's commented-out `p_lens`, ky.cpp:870-874, and `// sample_ray(...)`, 1894): depth of field.  The camera owns
@@ -548,6 +577,10 @@ int main(int argc, char* argv[]) {
             const int spp = argc > 2 ? std::atoi(argv[2]) : 16, cell = argc > 3 ? std::atoi(argv[3]) : 256;
             if (spp < 1 || cell < 16) { std::fprintf(stderr, "lens: at least one sample per pixel, cells of 16 or more\n"); return 2; }
             render_lens(spp, cell);
+        } else if (!std::strcmp(which, "textured")) {
+            const int spp = argc > 2 ? std::atoi(argv[2]) : 16, size = argc > 3 ? std::atoi(argv[3]) : 256;
+            if (spp < 1 || size < 16) { std::fprintf(stderr, "textured: at least one sample per pixel, a film of 16 or more\n"); return 2; }
+            render_textured(spp, size);
         } else if (!std::strcmp(which, "pick")) {
             const int spp = argc > 2 ? std::atoi(argv[2]) : 16, w = argc > 3 ? std::atoi(argv[3]) : 512, h = argc > 4 ? std::atoi(argv[4]) : 288;
             if (spp < 1 || w < 16 || h < 16) { std::fprintf(stderr, "pick: at least one sample per pixel, cells of 16 x 16 or more\n"); return 2; }

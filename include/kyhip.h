@@ -208,6 +208,30 @@ typedef struct ky_lens {
     int32_t reserved[2];      /* 0 */
 } ky_lens;
 
+/* Textures (the reference's empty `#pragma region texture` / `// TODO class texture_t`, ky.cpp:2559-2564): a texture replaces the colour
+   color0 of one material of the scene -- a matte material's diffuse_color_, a mirror's specular_color_, a plastic material's diffuse_color_ (its lobe probabilities
+   stay the struct's) -- by a function of the hit point's surface coordinates (u, v).  Glass is refused.  A texture set travels beside ky_scene, as a filter and a
+   lens travel beside the params: never inside ky_material or ky_scene.
+   (u, v) of a hit point p: rectangle u = (p - p0).(p1 - p0) / |p1 - p0|^2, v = (p - p0).(p3 - p0) / |p3 - p0|^2 (for a quad that is no parallelogram simply the
+   definition); triangle: the barycentric pair of p = p0 + u (p1 - p0) + v (p2 - p0); disk u = 0.5 + (p - c).s / 2r, v = 0.5 + (p - c).t / 2r with (s, t) of
+   frame_t(normal); sphere d = (p - c) / r, u = 0.5 + atan2(d.z, d.x) / 2 pi, v = acos(clamp(d.y, -1, 1)) / pi.
+   Checker: colour a where floor(u') + floor(v') is even, b where it is odd.  Image: u', v' are wrapped first -- repeat x - floor(x), clamp to [0, 1) --; nearest
+   reads texel (min(int(u' W), W - 1), min(int(v' H), H - 1)); bilinear is pbrt's, sampled at u' W - 0.5, its four neighbours wrapped or clamped by the same rule. */
+#define KYHIP_MAX_TEXTURES 16
+#define KYHIP_MAX_TEXTURE_SIZE 4096          /* an image dimension */
+#define KYHIP_MAX_TEXELS (1 << 24)           /* over the set's images */
+#define KYHIP_MAX_TEXTURE_SCALE (1 << 20)    /* |scale| and |offset|, each component */
+typedef enum ky_texture_kind { KY_TEXTURE_CHECKER = 0, KY_TEXTURE_IMAGE = 1 } ky_texture_kind;
+typedef enum ky_texture_flags { KY_TEXTURE_BILINEAR = 1 /* else nearest */, KY_TEXTURE_CLAMP = 2 /* else repeat */ } ky_texture_flags;
+typedef struct ky_texture {
+    int32_t kind, material;      /* the ky_scene material whose color0 this texture replaces; at most one texture per material */
+    int32_t flags, reserved;     /* image only; reserved 0 */
+    float   scale[2], offset[2]; /* (u', v') = (scale[0] u + offset[0], scale[1] v + offset[1]) */
+    float   a[3], b[3];          /* checker: colour where floor(u') + floor(v') is even / odd */
+    int32_t width, height;       /* image: 1 .. 4096 each */
+    const float* texels;         /* image: height rows of width RGB triples, row 0 at v' = 0; finite, >= 0 */
+} ky_texture;
+
 typedef struct ky_render_params {
     int32_t  integrator;         /* ky_integrator_kind */
     int32_t  max_path_depth;     /* path_integrator_t::max_path_depth_ (4182) */
@@ -697,6 +721,40 @@ int     kyhip_frame_lens(const kyhip_frame* f, ky_lens* out);
 int     kyhip_kat_lens(int device, const float* u2, int n, float* out2);
 int     kyhip_kat_li_lens(int device, const ky_scene* scene, const ky_render_params* params, const ky_pixel_filter* filter, const ky_lens* lens,
                           int x, int y, int s0, int n, float* out3);
+
+/*
+ * Textures (ky_texture above).
+ * Host only, no device needed:
+ *   kyhip_texture_check    KY_OK, or the refusal every entry below makes first.  KY_ERR_INVALID_VALUE: a NULL set with n_textures > 0, n_textures < 0, an unknown
+ *                          kind, a material index out of range, a glass material, a second texture on one material, a non-finite or negative a / b / texel, a scale
+ *                          that is 0, not finite or beyond KYHIP_MAX_TEXTURE_SCALE in size, an offset that is not finite or beyond it, flags beyond KY_TEXTURE_BILINEAR | KY_TEXTURE_CLAMP, reserved != 0, an image
+ *                          without texels or with a dimension < 1.  KY_ERR_LIMIT: more than KYHIP_MAX_TEXTURES textures, an image dimension over
+ *                          KYHIP_MAX_TEXTURE_SIZE, more than KYHIP_MAX_TEXELS texels over the set.
+ * On the device:
+ *   kyhip_render_textured  kyhip_render_lens under a texture set; filter and lens may be NULL.  n_textures == 0 IS kyhip_render_lens: the same film bit for bit, the
+ *                          same kernels.  Otherwise a textured row of the run-time-dispatched kernels runs (kyhip_last_kernel: "..., textured>" and a note that
+ *                          names the camera form): ONE camera form serves plain, filtered and lens launches -- it warps unless the filter is the box, and moves
+ *                          the ray onto the lens unless that is the pinhole -- and reads the live rectangle as the filtered kernels do (grown by the filter's
+ *                          reach; with a lens of radius > 0 the whole pixel range).  No specialised, masked or queue-engine textured kernels, no run-time
+ *                          instantiation, and no textured row for the debug sampler (KY_ERR_INVALID_VALUE).  A texture draws no random number and does not
+ *                          touch the film: a textured frame in any number of passes, slices or merges is the one-shot film bit for bit.
+ *                          sample_single_light's spatial pick (177) weighs a plastic vertex by the colour the vertex has, the textured one (it reads the
+ *                          vertex's material record, which is the lane's textured copy); the estimate is unbiased under any positive weights.
+ *   kyhip_frame_set_textures  the frame's texture set, before its first sample is rendered, loaded or merged (KY_ERR_INVALID_VALUE afterwards).  Descriptors and texels
+ *                          are copied and uploaded once; a digest of both is folded into the scene hash of the frame's header, so a state loads and merges only into
+ *                          a frame with the same textures.  n_textures == 0 removes the set.  Denoise guides know nothing of textures.
+ *   kyhip_kat_li_textured  kyhip_kat_li_lens's samples under a texture set: what the textured rows add per camera sample.
+ *   kyhip_kat_texture      a known-answer probe through the device functions the render kernels call: for n_points world points on surface `surface` (the caller's
+ *                          index; its material must carry a texture of the set) out5 = (u', v', r, g, b), the colour as the vertex's material takes it (on a
+ *                          plastic material: texel / diffuse_probability).
+ */
+int     kyhip_texture_check(const ky_scene* scene, const ky_texture* textures, int n_textures);
+int     kyhip_render_textured(int device, const ky_scene* scene, const ky_texture* textures, int n_textures, const ky_render_params* params,
+                              const ky_pixel_filter* filter, const ky_lens* lens, float* film_rgb, size_t film_row_stride_px);
+int     kyhip_frame_set_textures(kyhip_frame* f, const ky_texture* textures, int n_textures);
+int     kyhip_kat_li_textured(int device, const ky_scene* scene, const ky_texture* textures, int n_textures, const ky_render_params* params,
+                              const ky_pixel_filter* filter, const ky_lens* lens, int x, int y, int s0, int n, float* out3);
+int     kyhip_kat_texture(int device, const ky_scene* scene, const ky_texture* textures, int n_textures, int surface, const float* points3, int n_points, float* out5);
 
 /*
  * Duration in milliseconds of the integrator kernel (render_kernel) of the most recent

@@ -100,6 +100,15 @@ class Lens(C.Structure):   # ky_lens
     _fields_ = [("radius", C.c_float), ("focus_distance", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
+class Texture(C.Structure):   # ky_texture
+    _fields_ = [("kind", C.c_int32), ("material", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_float * 2), ("offset", C.c_float * 2),
+                ("a", C.c_float * 3), ("b", C.c_float * 3), ("width", C.c_int32), ("height", C.c_int32), ("texels", C.POINTER(C.c_float))]
+
+
+TEXTURE_CHECKER, TEXTURE_IMAGE = 0, 1        # ky_texture_kind
+TEXTURE_BILINEAR, TEXTURE_CLAMP = 1, 2       # ky_texture_flags
+MAX_TEXTURES, MAX_TEXTURE_SIZE, MAX_TEXELS = 16, 4096, 1 << 24   # KYHIP_MAX_TEXTURES, KYHIP_MAX_TEXTURE_SIZE, KYHIP_MAX_TEXELS
+
 FILTER_BOX, FILTER_TENT, FILTER_GAUSSIAN, FILTER_BLACKMAN_HARRIS = 0, 1, 2, 3   # ky_filter_kind
 FILTER_MAX_RADIUS = 4   # KYHIP_FILTER_MAX_RADIUS
 FILTER_TABLE = 256      # KYHIP_FILTER_TABLE: the inverse-CDF table has FILTER_TABLE + 1 floats
@@ -108,6 +117,7 @@ FP = C.POINTER(C.c_float)
 SP = C.POINTER(Scene)
 FLP = C.POINTER(PixelFilter)
 LP = C.POINTER(Lens)
+TP = C.POINTER(Texture)
 PP = C.POINTER(RenderParams)
 
 # every symbol include/kyhip.h declares: name -> (restype, argtypes)
@@ -209,6 +219,11 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_lens": (C.c_int, [C.c_void_p, LP]),
     "kyhip_kat_lens": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kat_li_lens": (C.c_int, [C.c_int, SP, PP, FLP, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "kyhip_texture_check": (C.c_int, [SP, TP, C.c_int]),
+    "kyhip_render_textured": (C.c_int, [C.c_int, SP, TP, C.c_int, PP, FLP, LP, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_set_textures": (C.c_int, [C.c_void_p, TP, C.c_int]),
+    "kyhip_kat_li_textured": (C.c_int, [C.c_int, SP, TP, C.c_int, PP, FLP, LP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "kyhip_kat_texture": (C.c_int, [C.c_int, SP, TP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "kyhip_kernel_ms": (C.c_float, [C.c_int]),
     "kyhip_last_kernel": (C.c_char_p, [C.c_int]),
     "kyhip_kat_nee": (C.c_int, [C.c_int, SP, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -254,6 +269,9 @@ KYHOST_SYMBOLS = {
                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhost_render_filtered": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
                                          C.c_float, C.c_int, C.c_int]),
+    "kyhost_scene_texture_checker": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kyhost_scene_texture_image": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "kyhost_scene_textures": (C.c_int, [C.c_void_p, TP, C.c_int]),
     "kyhost_render_lens": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float,
                                      C.c_int, C.c_int]),
     "kyhost_render_passes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,

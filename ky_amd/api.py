@@ -49,6 +49,34 @@ class SceneHandle:
     def c(self):
         return self.flat.contents
 
+    def _retextured(self, rc):
+        if rc != 0:
+            raise KyError("texture: " + self._host.kyhost_last_error().decode())
+        self.flat = self._host.kyhost_scene_flatten(self._ptr)   # (the material's struct colour is now the texture's base colour)
+
+    def texture_checker(self, material, a, b, scale=(1, 1), offset=(0, 0)):
+        """Material `material` rebuilt from a checker_texture_t (ky.hpp: the texture overloads of matte_material_t, mirror_material_t, plastic_material_t): the host
+        mirror's render entries then render the scene textured, and textures() is the set they hand to the C ABI."""
+        f = lambda v: np.ascontiguousarray(v, np.float32)
+        a, b, scale, offset = f(a), f(b), f(scale), f(offset)
+        self._retextured(self._host.kyhost_scene_texture_checker(self._ptr, int(material), _fptr(a), _fptr(b), _fptr(scale), _fptr(offset)))
+
+    def texture_image(self, material, array, bilinear=False, clamp=False, scale=(1, 1), offset=(0, 0)):
+        """Material `material` rebuilt from an image_texture_t of array[h, w, 3] (copied)."""
+        texels = np.ascontiguousarray(array, np.float32)
+        scale, offset = np.ascontiguousarray(scale, np.float32), np.ascontiguousarray(offset, np.float32)
+        self._retextured(self._host.kyhost_scene_texture_image(self._ptr, int(material), int(texels.shape[1]), int(texels.shape[0]), _fptr(texels), int(bilinear), int(clamp),
+                                                               _fptr(scale), _fptr(offset)))
+
+    def textures(self):
+        """scene_t::flatten_textures(): the ky_texture set of the scene's textured materials (valid while the scene lives and is not retextured)."""
+        n = self._host.kyhost_scene_textures(self._ptr, None, 0)
+        if n < 0:
+            raise KyError("textures: " + self._host.kyhost_last_error().decode())
+        arr = (A.Texture * max(n, 1))()
+        self._host.kyhost_scene_textures(self._ptr, arr, n)
+        return [arr[i] for i in range(n)]
+
     @property
     def ptr(self):
         return self._ptr
@@ -137,19 +165,72 @@ def focus_distance(scene, x, y, device=0):
     return float(np.dot(hit[2:5].astype(np.float64) - np.array(list(cam.position), np.float64), front) / np.linalg.norm(front))
 
 
-def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0), lighting=None, filter=None, lens=None):
+def texture_checker(material, a, b, scale=(1, 1), offset=(0, 0)):
+    """A checker ky_texture (_abi.Texture) on ky_scene material `material`, whose color0 it replaces: colour a where floor(u') + floor(v') is even, b where it is
+    odd, (u', v') = scale * (u, v) + offset.  A texture is checked against its scene where it is used (texture_check)."""
+    t = A.Texture(A.TEXTURE_CHECKER, int(material), 0, 0, tuple(float(v) for v in scale), tuple(float(v) for v in offset), tuple(float(v) for v in a),
+                  tuple(float(v) for v in b), 0, 0, None)
+    return t
+
+
+def texture_image(material, array, bilinear=False, clamp=False, scale=(1, 1), offset=(0, 0)):
+    """An image ky_texture on material `material`: array[h, w, 3], row 0 at v' = 0; nearest or bilinear (pbrt's), repeating or clamped.  The texture keeps the
+    float32 copy of the array it points to alive."""
+    texels = np.ascontiguousarray(array, np.float32)
+    if texels.ndim != 3 or texels.shape[2] != 3:
+        raise ValueError("texture_image: array[h, w, 3]")
+    t = A.Texture(A.TEXTURE_IMAGE, int(material), (A.TEXTURE_BILINEAR if bilinear else 0) | (A.TEXTURE_CLAMP if clamp else 0), 0, tuple(float(v) for v in scale),
+                  tuple(float(v) for v in offset), (0, 0, 0), (0, 0, 0), int(texels.shape[1]), int(texels.shape[0]), texels.ctypes.data_as(C.POINTER(C.c_float)))
+    t._texels = texels
+    return t
+
+
+def _texture_array(textures):
+    """(a contiguous ky_texture array or None, n) of a sequence of textures; the sequence keeps the texels alive"""
+    textures = list(textures) if textures is not None else []
+    if not textures:
+        return None, 0
+    arr = (A.Texture * len(textures))()
+    for i, t in enumerate(textures):
+        C.memmove(C.byref(arr, i * C.sizeof(A.Texture)), C.byref(t), C.sizeof(A.Texture))
+    return arr, len(textures)
+
+
+def texture_check(scene, textures):
+    """kyhip_texture_check (host only): raises KyError for a set that `scene` refuses -- a glass or out-of-range material, two textures on one material, a negative or
+    non-finite colour or texel, a scale of 0, an image without texels, or a set beyond the limits."""
+    lib = A.load_kyhip()
+    arr, n = _texture_array(textures)
+    _check(lib.kyhip_texture_check(_scene_ptr(scene), arr, n), lib)
+
+
+def kat_texture(scene, textures, surface, points, device=0):
+    """kyhip_kat_texture: (u', v', r, g, b) float32 [n, 5] of world points [n, 3] on surface `surface`, through the device functions the textured kernels call."""
+    lib = A.load_kyhip()
+    arr, n = _texture_array(textures)
+    points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    out = np.zeros((points.shape[0], 5), np.float32)
+    _check(lib.kyhip_kat_texture(device, _scene_ptr(scene), arr, n, int(surface), _fptr(points), int(points.shape[0]), _fptr(out)), lib)
+    return out
+
+
+def render(scene, params, film=None, device=0, row_stride_px=None, origin_px=(0, 0), lighting=None, filter=None, lens=None, textures=None):
     """kyhip_render: integrator_t::render(scene, sampler, film) on the GPU; returns the (accumulated) host film.
     lighting: a mask of LIGHTING_EMIT / _DIRECT / _INDIRECT -- kyhip_render_lighting, only those light classes are added.
     filter: a pixel_filter(...) -- kyhip_render_filtered, the camera samples drawn from the filter's density (not together with lighting).
     lens: a lens(...) -- kyhip_render_lens, the camera rays leave from a disk and meet on the focus plane (with or without filter, not together with lighting)."""
     lib = A.load_kyhip()
-    if (filter is not None or lens is not None) and lighting is not None:
-        raise ValueError("a render under a pixel filter or a lens has no masked form: filter= / lens= or lighting=, not both")
+    if (filter is not None or lens is not None or textures) and lighting is not None:
+        raise ValueError("a render under a pixel filter, a lens or textures has no masked form: filter= / lens= / textures= or lighting=, not both")
     if film is None:
         film = np.zeros((params.height, params.width, 3), np.float32)
     stride = film.shape[1] if row_stride_px is None else row_stride_px
     base = film.ctypes.data + (origin_px[1] * stride + origin_px[0]) * 12
-    if lens is not None:
+    if textures:   # kyhip_render_textured: the materials' colours from a texture set (texture_checker, texture_image), with or without filter and lens
+        arr, n = _texture_array(textures)
+        _check(lib.kyhip_render_textured(device, _scene_ptr(scene), arr, n, C.byref(params), C.byref(filter) if filter is not None else None,
+                                         C.byref(lens) if lens is not None else None, C.c_void_p(base), stride))
+    elif lens is not None:
         _check(lib.kyhip_render_lens(device, _scene_ptr(scene), C.byref(params), C.byref(filter) if filter is not None else None, C.byref(lens), C.c_void_p(base), stride))
     elif filter is not None:
         _check(lib.kyhip_render_filtered(device, _scene_ptr(scene), C.byref(params), C.byref(filter), C.c_void_p(base), stride))
@@ -212,7 +293,7 @@ class Frame:
     render(scene, params, filter=filter) bit for bit, and its states load and merge only into frames with the same filter.
     lens=lens(...): the frame's camera rays leave from that lens (kyhip_frame_set_lens), with the same two consequences."""
 
-    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0, filter=None, lens=None):
+    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0, filter=None, lens=None, textures=None):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
@@ -246,6 +327,18 @@ class Frame:
             if rc != A.KY_OK:
                 self.close()
                 _check(rc, self._lib)
+
+        if textures:   # textures=[texture_checker(...), texture_image(...)]: kyhip_frame_set_textures, part of what the frame is, like its filter and lens
+            try:
+                self.set_textures(textures)
+            except KyError:
+                self.close()
+                raise
+
+    def set_textures(self, textures):
+        """kyhip_frame_set_textures: the frame's texture set, copied and uploaded once; refused once the frame holds a sample."""
+        arr, n = _texture_array(textures)
+        _check(self._lib.kyhip_frame_set_textures(self._f, arr, n), self._lib)
 
     def set_lens(self, lens):
         """kyhip_frame_set_lens: the frame's lens; refused once the frame holds a sample."""
@@ -469,20 +562,21 @@ class Frame:
         _check(self._lib.kyhip_frame_load(self._f, state, len(state)), self._lib)
 
 
-def render_sliced(scene, params, devices, min_samples_per_pass, on_pass=None, noise=False, film=None, filter=None, lens=None):
+def render_sliced(scene, params, devices, min_samples_per_pass, on_pass=None, noise=False, film=None, filter=None, lens=None, textures=None):
     """The frame in len(devices) slices of its samples (slice_bounds), slice k on devices[k] (a device may repeat); returns the (accumulated) host film, which is
     render(scene, params) bit for bit.  The slices render in rounds of one pass each, one call after the other (concurrency across devices: ky_amd.dist); after
     every round on_pass(done, total, preview) is called with the samples per pixel done over all slices, and preview(denoise=False) merges the slices as they stand
     into a collector and returns its picture: resolve(normalise=True), or with denoise=True (needs noise=True and two rounds) denoise().  At the end slice 0's
-    frame merges the others and resolves.  filter, lens: every slice's (and the collector's) pixel filter and lens; the film is then render(scene, params, filter=filter, lens=lens)."""
+    frame merges the others and resolves.  filter, lens: every slice's (and the collector's) pixel filter and lens; the film is then render(scene, params, filter=filter, lens=lens).
+    textures: likewise every slice's texture set."""
     bounds = slice_bounds(params.samples_per_pixel, len(devices))
     frames = []
     try:
         for k, dev in enumerate(devices):
-            frames.append(Frame(scene, params, device=dev, noise=noise, slice=(bounds[k], bounds[k + 1]), filter=filter, lens=lens))
+            frames.append(Frame(scene, params, device=dev, noise=noise, slice=(bounds[k], bounds[k + 1]), filter=filter, lens=lens, textures=textures))
 
         def preview(denoise=False):
-            with Frame(scene, params, device=devices[0], noise=noise, slice=(0, 0), filter=filter, lens=lens) as collector:
+            with Frame(scene, params, device=devices[0], noise=noise, slice=(0, 0), filter=filter, lens=lens, textures=textures) as collector:
                 for f in frames:
                     collector.merge(f)
                 return collector.denoise() if denoise else collector.resolve(normalise=True)
@@ -814,9 +908,14 @@ def scene_screen_bound(scene, params, filter=None, lens=None):
     return tuple(int(v) for v in rect), int(counts[0]), int(counts[1])
 
 
-def kat_li(scene, params, x, y, s0, n, device=0, filter=None, lens=None):
+def kat_li(scene, params, x, y, s0, n, device=0, filter=None, lens=None, textures=None):
     lib = A.load_kyhip()
     out = np.zeros((n, 3), np.float32)
+    if textures:   # kyhip_kat_li_textured: the samples of a render under that texture set (and pixel filter and lens)
+        arr, nt = _texture_array(textures)
+        _check(lib.kyhip_kat_li_textured(device, _scene_ptr(scene), arr, nt, C.byref(params), C.byref(filter) if filter is not None else None,
+                                         C.byref(lens) if lens is not None else None, x, y, s0, n, _fptr(out)))
+        return out
     if lens is not None:   # kyhip_kat_li_lens: the samples of a render under that lens (and pixel filter)
         _check(lib.kyhip_kat_li_lens(device, _scene_ptr(scene), C.byref(params), C.byref(filter) if filter is not None else None, C.byref(lens), x, y, s0, n, _fptr(out)))
         return out

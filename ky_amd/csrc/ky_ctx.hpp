@@ -68,7 +68,7 @@ struct SceneSlot {
     hipStream_t upload_stream = nullptr;
     unsigned long long last_use = 0;
 };
-constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8, KY_MAX_VARIANTS = 160;
+constexpr int KY_STREAM_STATES = 8, KY_SCENE_SLOTS = 8, KY_MAX_VARIANTS = 192;
 // what kyhip_render / kyhip_render_multi keep between calls (the host-film seam); `m` serialises such calls per device, it is never
 // taken while a context's enqueue mutex is held
 // (measured on configs[1]'s 9.4 MB film, tools/seam_trace.py: what a call costs beyond its kernel -- the film's pinned download alone is 0.18 ms -- is
@@ -143,6 +143,11 @@ struct FramePass {
     bool lensed = false;
     kyd::LensConst lens{};
     std::string lens_note;
+    // The frame's texture set when it has one: every pass then runs a textured row of the table, whose one camera form takes `filter` and
+    // `lens` as they stand, the box and the pinhole included.  tex_note is what kyhip_last_kernel says of it.
+    bool textured = false;
+    kyd::TexConst tex{};
+    std::string tex_note;
 };
 // resolve_frame_kernel (ky_launch.hip) on `stream`: the frame's accumulators and flags, read and left as they are -> clamp01(value * scale) in the compact tile buffer
 int resolve_frame_device(const void* ws, float* d_tiles, int n_pix, double scale, hipStream_t stream);

@@ -2404,8 +2404,13 @@ KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key
     float u0, u1;
     sampler_camera<SAMPLER>(ps.smp, u0, u1);
     if constexpr (CAM == KY_CAM_FILTER) { u0 = filter_offset(fc, u0); u1 = filter_offset(fc, u1); }
-    if constexpr (CAM == KY_CAM_LENS) {
+    bool pinhole = false;   // KY_CAM_ANY (the textured kernels): the lens code under a wave-uniform skip of its own, the pinhole's ray otherwise
+    if constexpr (CAM == KY_CAM_ANY) pinhole = fc.lens.wf == 0.f;
+    if constexpr (CAM == KY_CAM_LENS || CAM == KY_CAM_ANY) {
         if (fc.kind != KY_FILTER_BOX) { u0 = filter_offset(fc, u0); u1 = filter_offset(fc, u1); }
+        if (pinhole) {
+            generate_ray(S, (float)x + u0, (float)y + u1, ps.o, ps.d);
+        } else {
         const float l0 = sampler_next<SAMPLER>(ps.smp), l1 = sampler_next<SAMPLER>(ps.smp);
         float dx, dy;
         lens_disk(l0, l1, dx, dy);
@@ -2416,6 +2421,7 @@ KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key
         ps.o.x = __builtin_fmaf(up.x, b, __builtin_fmaf(right.x, a, ps.o.x));
         ps.o.y = __builtin_fmaf(up.y, b, __builtin_fmaf(right.y, a, ps.o.y));
         ps.o.z = __builtin_fmaf(up.z, b, __builtin_fmaf(right.z, a, ps.o.z));
+        }
     } else {
         generate_ray(S, (float)x + u0, (float)y + u1, ps.o, ps.d);
     }
@@ -2484,6 +2490,112 @@ KY_DEV int path_pick_lobe(PathStateFor<SAMPLER>& ps, int surface, const LdsScene
     return pick_lobe(M, lobe_u);
 }
 
+// ---------------------------------------------------------------------------------------------
+// textures (ky_texture): a hit point's (u, v), the two look-ups, and the one place a vertex takes its material from
+// ---------------------------------------------------------------------------------------------
+// What the textured kernels hold of a set: its descriptors in LDS (a per-lane gather: the material differs from lane to lane), the surfaces' uv records and
+// the texels in global memory.
+struct TexLds {
+    const DTex* tex;
+    const DTexUV* uv;
+    const float4* texels;
+};
+// Cooperative, whole workgroup, behind stage_scene: the descriptors into LDS, and each textured material's link into the staged copy of its record -- bits 8-15 of
+// exp_flags = texture index + 1 (bits 0-3 and 16-31 are taken), and bit 2, "c0 is not black", whatever the struct's colour says.  Ends with a barrier.
+KY_DEV TexLds stage_textures(const TexConst& tc, const LdsScene& Lds) {
+    __shared__ __attribute__((aligned(16))) uint32_t tex[KYHIP_MAX_TEXTURES * sizeof(DTex) / 4];
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(tc.set->tex);
+    for (int i = threadIdx.x; i < (int)(KYHIP_MAX_TEXTURES * sizeof(DTex) / 4); i += blockDim.x) tex[i] = src[i];
+    const int n = tc.set->n_tex < KYHIP_MAX_TEXTURES ? tc.set->n_tex : KYHIP_MAX_TEXTURES;
+    if ((int)threadIdx.x < n) const_cast<DMat*>(Lds.mat)[tc.set->material[threadIdx.x]].exp_flags |= (((int)threadIdx.x + 1) << 8) | 4;
+    __syncthreads();
+    return TexLds{reinterpret_cast<const DTex*>(tex), tc.set->uv, tc.texels};
+}
+
+// (u, v) of the point p of the surface R describes, operation by operation as DESIGN.md section 13 states them: the fused multiply-adds are written out
+KY_DEV void tex_uv(const DTexUV& R, f3 p, float& u, float& v) {
+    const f3 d = p - ld3(R.o);
+    if (R.kind != 0) {   // sphere
+        const float nx = strat_fmul(d.x, R.k0), ny = strat_fmul(d.y, R.k0), nz = strat_fmul(d.z, R.k0);
+        u = __builtin_fmaf(atan2f(nz, nx), 0.15915494309189535f, 0.5f);
+        v = strat_fmul(acosf(fminf(fmaxf(ny, -1.f), 1.f)), 0.31830988618379067f);
+    } else {
+        const float a = __builtin_fmaf(d.z, R.e1[2], __builtin_fmaf(d.y, R.e1[1], strat_fmul(d.x, R.e1[0])));
+        const float b = __builtin_fmaf(d.z, R.e2[2], __builtin_fmaf(d.y, R.e2[1], strat_fmul(d.x, R.e2[0])));
+        u = __builtin_fmaf(R.k2, b, strat_fmul(R.k0, a)) + R.add;
+        v = __builtin_fmaf(R.k2, a, strat_fmul(R.k1, b)) + R.add;
+    }
+}
+// an image coordinate into [0, 1]: repeat x - floor(x) (which rounds to 1 for a tiny negative x: the texel index is capped), clamp to [0, 1)
+KY_DEV float tex_wrap(float x, bool clamp) { return clamp ? fminf(fmaxf(x, 0.f), 0.99999994f) : x - __builtin_floorf(x); }
+KY_DEV int tex_wrap_index(int i, int n, bool clamp) {   // a bilinear neighbour, -1 .. n
+    if (clamp) return min(max(i, 0), n - 1);
+    return i < 0 ? i + n : (i >= n ? i - n : i);
+}
+KY_DEV f3 tex_lerp(float t, float4 a, float4 b) {
+    return mk3(__builtin_fmaf(t, b.x - a.x, a.x), __builtin_fmaf(t, b.y - a.y, a.y), __builtin_fmaf(t, b.z - a.z, a.z));
+}
+// The colour of texture T at (u', v').  Two bodies: one texel -- a checker's parity picks texel 0 or 1 (a, b), a nearest look-up its texel --, or pbrt's bilinear
+// four.  Each texel is one 16-byte load.
+KY_DEV f3 tex_lookup(const DTex& T, const float4* __restrict__ texels, float u, float v) {
+    const int kind = T.kind_flags & 0xff, flags = T.kind_flags >> 8;
+    const bool clamp = (flags & KY_TEXTURE_CLAMP) != 0;
+    const float4* __restrict__ base = texels + T.first;
+    const int W = T.w, H = T.h;
+    if (kind == KY_TEXTURE_CHECKER || !(flags & KY_TEXTURE_BILINEAR)) {
+        int idx;
+        if (kind == KY_TEXTURE_CHECKER) {
+            idx = ((int)__builtin_floorf(u) + (int)__builtin_floorf(v)) & 1;
+        } else {
+            const int ix = min((int)strat_fmul(tex_wrap(u, clamp), (float)W), W - 1), iy = min((int)strat_fmul(tex_wrap(v, clamp), (float)H), H - 1);
+            idx = iy * W + ix;
+        }
+        const float4 t = base[idx];
+        return mk3(t.x, t.y, t.z);
+    }
+    const float s = __builtin_fmaf(tex_wrap(u, clamp), (float)W, -0.5f), t = __builtin_fmaf(tex_wrap(v, clamp), (float)H, -0.5f);
+    const float s0 = __builtin_floorf(s), t0 = __builtin_floorf(t);
+    const float ds = s - s0, dt = t - t0;
+    const int x0 = tex_wrap_index((int)s0, W, clamp), x1 = tex_wrap_index((int)s0 + 1, W, clamp);
+    const int y0 = tex_wrap_index((int)t0, H, clamp), y1 = tex_wrap_index((int)t0 + 1, H, clamp);
+    const float4 t00 = base[y0 * W + x0], t10 = base[y0 * W + x1], t01 = base[y1 * W + x0], t11 = base[y1 * W + x1];
+    const f3 top = tex_lerp(ds, t00, t10), bot = tex_lerp(ds, t01, t11);
+    return mk3(__builtin_fmaf(dt, bot.x - top.x, top.x), __builtin_fmaf(dt, bot.y - top.y, top.y), __builtin_fmaf(dt, bot.z - top.z, top.z));
+}
+// texture `ti` at the point p of (sorted) surface `surface`: (u', v') and the colour
+KY_DEV f3 tex_at(const TexLds& tx, int ti, int surface, f3 p, float& us, float& vs) {
+    const DTex& T = tx.tex[ti];
+    float u, v;
+    tex_uv(tx.uv[surface], p, u, v);
+    us = __builtin_fmaf(T.scale[0], u, T.offset[0]);
+    vs = __builtin_fmaf(T.scale[1], v, T.offset[1]);
+    return tex_lookup(T, tx.texels, us, vs);
+}
+// A lane's textured material, per lane in LDS: the scene's record with the look-up's colour as c0, so that everything behind make_bsdf -- which reads a vertex's
+// colours through Bsdf::m -- is what it is in every other kernel.  16 KB, allocated only in the kernels that name it.
+__shared__ DMat g_tex_mat[256];
+// The material record a vertex scatters by, at the one place a vertex reads it.  TEX (the textured kernels): where the staged record links a texture, the lane's
+// own copy of it with the look-up's colour as c0; lanes whose material has none skip the look-up under the exec mask.  Without TEX this is the read it has always been.
+template <bool TEX>
+KY_DEV const DMat& vertex_material(const LdsScene& Lds, const Vertex& v, const TexLds* tx) {
+    const DMat& M = Lds.mat[Lds.hit[v.surface].material];
+    if constexpr (TEX) {
+        const int ti = (M.exp_flags >> 8) & 0xff;
+        if (ti != 0) {
+            float us, vs;
+            const f3 col = tex_at(*tx, ti - 1, v.surface, v.position, us, vs);
+            DMat& D = g_tex_mat[threadIdx.x];
+            const uint32_t* s = reinterpret_cast<const uint32_t*>(&M);   // (word by word: the staged records are only known to be 4-byte aligned)
+            uint32_t* d = reinterpret_cast<uint32_t*>(&D);
+#pragma unroll
+            for (int k = 3; k < (int)(sizeof(DMat) / 4); ++k) d[k] = s[k];
+            D.c0[0] = col.x; D.c0[1] = col.y; D.c0[2] = col.z;
+            return D;
+        }
+    }
+    return M;
+}
+
 // Second half: material, direct lighting, continuation.  WAVE-UNIFORM call: every lane of the wave calls it, `active`
 // says whether this lane holds a vertex.  Returns true when the (active) lane's path continues.
 // per-vertex trace of one path (kyhip_kat_li_trace): rows of 26 floats, the format of the oracle's kyo_trace_li
@@ -2494,15 +2606,16 @@ struct VertexTrace {
 
 // `tr` is a null constant everywhere but in the trace KAT kernel, which removes the tracing code.
 // DROP / drop_rt: path_intersect's; bit 1 drops the light estimate of the vertex at bounces == 0, whose draws are still made (light_estimate_draws).
-template <int SAMPLER, int DROP = 0>
+// TEX / tx (the textured kernels): the vertex's material is vertex_material's -- the one place a texture is looked up.
+template <int SAMPLER, int DROP = 0, bool TEX = false>
 KY_DEV bool path_shade(PathStateFor<SAMPLER>& ps, Vertex& v, SceneRef S, const LdsScene& Lds, const RenderConst& rc, bool active,
                        int lobe = -1, VertexTrace* tr = nullptr, ShadowQueue* sq = nullptr, unsigned tag = 0, bool ride_along = false, bool free_state = false,
-                       int drop_rt = 0) {
+                       int drop_rt = 0, const TexLds* tx = nullptr) {
     const int drop = DROP >= 0 ? DROP : drop_rt;
     if (active) {
         // material->scattering(isect) for the nearest hit (3083); only plastic draws a lobe number (2663).
         // lobe >= 0: the caller has already made that draw (path_pick_lobe).
-        const DMat& M = Lds.mat[Lds.hit[v.surface].material];
+        const DMat& M = vertex_material<TEX>(Lds, v, tx);
         if (lobe < 0) {
             float lobe_u = 0.f;
             if (M.kind == KY_MATERIAL_PLASTIC) lobe_u = sampler_next<SAMPLER>(ps.smp);

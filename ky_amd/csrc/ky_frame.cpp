@@ -73,6 +73,7 @@ struct kyhip_frame {
     BlockTrack blocks;
     DenoiseTrack denoise;
     DevBuf filter_table;          // the inverse-CDF table of the frame's pixel filter (kyhip_frame_set_filter), which pass.filter points to
+    DevBuf tex_set, tex_texels;   // the frame's texture set (kyhip_frame_set_textures): the DTexSet block and the float4 texels pass.tex points to
     DevBuf merge_ws, merge_state; // what a merge from a saved state or from another device reads: the other frame's accumulator block and noise pairs
     TimedSpan merge;              // the last merge kernel (kyhip_frame_merge_ms)
 };
@@ -267,6 +268,58 @@ int kyhip_render_lens(int device, const ky_scene* scene, const ky_render_params*
     KY_TRY(kyhip_frame_begin(device, scene, p, &f));
     int rcode = filter_is_box(filter) ? (int)KY_OK : kyhip_frame_set_filter(f, filter);
     if (rcode == KY_OK) rcode = kyhip_frame_set_lens(f, lens);
+    if (rcode == KY_OK) rcode = kyhip_frame_render(f, p->samples_per_pixel, nullptr);
+    if (rcode == KY_OK) rcode = kyhip_frame_resolve(f, 1, film_rgb, stride_px);
+    kyhip_frame_end(f);
+    return rcode;
+}
+
+// ---- the frame's textures ----
+int kyhip_frame_set_textures(kyhip_frame* f, const ky_texture* textures, int n) {
+    if (!f) {   // (the set first, as far as it can be checked without a scene, then the frame -- as for the filter and the lens)
+        if (n < 0 || (n > 0 && !textures)) return fail(KY_ERR_INVALID_VALUE, "bad texture arguments");
+        if (n > KYHIP_MAX_TEXTURES) return fail(KY_ERR_LIMIT, "textures: %d, at most %d", n, KYHIP_MAX_TEXTURES);
+        return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    }
+    KY_TRY(texture_check(&f->scene, textures, n));
+    FramePass& pass = f->pass;
+    if (!f->book.untouched()) return f->book.set_textures(0);   // (the book's refusal)
+    DevBuf new_set, new_texels;   // the upload first, into buffers of its own: a failed allocation or copy leaves the frame's textures what they were
+    if (n > 0) {
+        static thread_local DScene packed;
+        KY_TRY(pack_scene(&f->scene, &packed));
+        std::unique_ptr<DTexSet> set(new DTexSet);
+        std::vector<float> texels4;
+        texture_pack(&f->scene, &packed, textures, n, set.get(), &texels4);
+        DeviceCtx* c;
+        KY_TRY(get_ctx(f->device, &c));
+        HIP_TRY(new_set.alloc(sizeof(DTexSet)));
+        HIP_TRY(new_texels.alloc(texels4.size() * sizeof(float)));
+        HIP_TRY(hipMemcpy(new_set.p, set.get(), sizeof(DTexSet), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(new_texels.p, texels4.data(), texels4.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    KY_TRY(f->book.set_textures(texture_digest(textures, n)));
+    std::swap(f->tex_set.p, new_set.p);         // (what the frame held before -- a set replaced before the first pass -- is released with new_set / new_texels)
+    std::swap(f->tex_texels.p, new_texels.p);
+    pass.textured = n > 0;
+    pass.tex = TexConst{n > 0 ? f->tex_set.as<const DTexSet>() : nullptr, n > 0 ? f->tex_texels.as<const float4>() : nullptr};
+    pass.tex_note = n > 0 ? texture_describe(textures, n) : std::string();
+    return KY_OK;
+}
+// kyhip_render_lens under a texture set: a frame of its own again.  No textures: kyhip_render_lens itself.
+int kyhip_render_textured(int device, const ky_scene* scene, const ky_texture* textures, int n, const ky_render_params* p, const ky_pixel_filter* filter, const ky_lens* lens,
+                          float* film_rgb, size_t stride_px) {
+    KY_TRY(texture_check(scene, textures, n));
+    if (n == 0) return kyhip_render_lens(device, scene, p, filter, lens, film_rgb, stride_px);
+    if (lens) KY_TRY(lens_check(lens));
+    if (filter) KY_TRY(filter_check(filter));
+    if (p && valid_params(p) && p->sampler == KY_SAMPLER_DEBUG) return fail(KY_ERR_INVALID_VALUE, "a render under a texture set has no row for the debug sampler");
+    if (!film_rgb || (p && valid_params(p) && stride_px < (size_t)p->width)) return fail(KY_ERR_INVALID_VALUE, "bad film arguments");
+    kyhip_frame* f = nullptr;
+    KY_TRY(kyhip_frame_begin(device, scene, p, &f));
+    int rcode = filter_is_box(filter) ? (int)KY_OK : kyhip_frame_set_filter(f, filter);
+    if (rcode == KY_OK && !lens_is_pinhole(lens)) rcode = kyhip_frame_set_lens(f, lens);
+    if (rcode == KY_OK) rcode = kyhip_frame_set_textures(f, textures, n);
     if (rcode == KY_OK) rcode = kyhip_frame_render(f, p->samples_per_pixel, nullptr);
     if (rcode == KY_OK) rcode = kyhip_frame_resolve(f, 1, film_rgb, stride_px);
     kyhip_frame_end(f);

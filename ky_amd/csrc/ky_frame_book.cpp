@@ -311,7 +311,7 @@ int FrameBook::set_filter(const ky_pixel_filter* f) {
     if (!untouched()) return fail(KY_ERR_INVALID_VALUE, "the frame holds samples already: its pixel filter is set before the first one is rendered, loaded or merged");
     filter = *f;
     if (filter.kind == KY_FILTER_BOX) filter = ky_pixel_filter{};   // (one box: its radius names nothing)
-    header.scene_hash = lens_fold(filter_fold(base_hash, &filter), &lens);
+    header.scene_hash = texture_fold(lens_fold(filter_fold(base_hash, &filter), &lens), tex_digest);
     return KY_OK;
 }
 int FrameBook::set_lens(const ky_lens* l) {
@@ -319,7 +319,13 @@ int FrameBook::set_lens(const ky_lens* l) {
     if (!untouched()) return fail(KY_ERR_INVALID_VALUE, "the frame holds samples already: its lens is set before the first one is rendered, loaded or merged");
     lens = *l;
     if (lens_is_pinhole(&lens)) lens = ky_lens{};   // (one pinhole: its focus distance names nothing)
-    header.scene_hash = lens_fold(filter_fold(base_hash, &filter), &lens);
+    header.scene_hash = texture_fold(lens_fold(filter_fold(base_hash, &filter), &lens), tex_digest);
+    return KY_OK;
+}
+int FrameBook::set_textures(uint64_t digest) {
+    if (!untouched()) return fail(KY_ERR_INVALID_VALUE, "the frame holds samples already: its textures are set before the first sample is rendered, loaded or merged");
+    tex_digest = digest;
+    header.scene_hash = texture_fold(lens_fold(filter_fold(base_hash, &filter), &lens), tex_digest);
     return KY_OK;
 }
 // Where a saved state differs from this frame in nothing but the header's scene hash, the refusal names the filter when that can be told: KY_OK otherwise (the
@@ -332,6 +338,8 @@ int FrameBook::filter_refusal(const void* buf, size_t bytes) const {
     FrameHeader same = theirs;
     same.scene_hash = header.scene_hash; same.samples_done = header.samples_done; same.magic = header.magic;
     if (std::memcmp(&same, &header, sizeof header) != 0) return KY_OK;
+    if (tex_digest != 0)   // ... and the textures
+        return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame with other textures or none, another lens or pixel filter (or scene); this frame has a texture set (kyhip_frame_set_textures)");
     if (!lens_is_pinhole(&lens)) {   // ... and the lens
         if (theirs.scene_hash == filter_fold(base_hash, &filter))
             return fail(KY_ERR_INVALID_VALUE, "frame state: saved by a frame of this scene without a lens, this frame has a %s (kyhip_frame_set_lens)", lens_describe(&lens).c_str());
@@ -476,6 +484,8 @@ int FrameBook::merge_state(const void* state, size_t bytes, MergeStep* out) cons
 int FrameBook::merge_book(const FrameBook& src, MergeStep* out) const {
     if (this == &src) return fail(KY_ERR_INVALID_VALUE, "merge: a frame holds its own samples already");
     if (std::memcmp(&header, &src.header, sizeof header) != 0) {
+        if (tex_digest != src.tex_digest)
+            return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their textures (kyhip_frame_set_textures)");
         if (std::memcmp(&lens, &src.lens, sizeof lens) != 0)
             return fail(KY_ERR_INVALID_VALUE, "merge: the frames differ in their lens (this one: %s, the other: %s)", lens_describe(&lens).c_str(), lens_describe(&src.lens).c_str());
         if (std::memcmp(&filter, &src.filter, sizeof filter) != 0)

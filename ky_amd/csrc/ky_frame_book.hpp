@@ -58,6 +58,9 @@ struct FrameBook {
     // ... and its lens (section 12), the pinhole {0, 0} until set_lens: header.scene_hash is lens_fold(filter_fold(base_hash, &filter), &lens)
     ky_lens lens{};
     int set_lens(const ky_lens* l);   // kyhip_frame_set_lens behind its NULL frame, as set_filter
+    // ... and the digest of its texture set (section 13; texture_digest, ky_pack.cpp), 0 while it has none: folded in last, texture_fold(lens_fold(...), digest)
+    uint64_t tex_digest = 0;
+    int set_textures(uint64_t digest);   // kyhip_frame_set_textures behind its checks; refused once the frame holds a sample
 
     // the book of the frame of p that owns [first_sample, end_sample): behind begin_check
     void begin(const ky_render_params* p, uint64_t scene_hash, int first_sample, int end_sample);

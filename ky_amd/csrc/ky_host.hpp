@@ -119,6 +119,14 @@ uint64_t lens_fold(uint64_t hash, const ky_lens* l);
 kyd::LensConst lens_const(const ky_camera* cam, const ky_lens* l);
 // ... refused (KY_ERR_INVALID_VALUE) where they are not finite: a camera whose front, right or up has no length or is not finite
 int lens_const_checked(const ky_camera* cam, const ky_lens* l, kyd::LensConst* out);
+// ---- textures (ky_texture; ky_pack.cpp) ----
+int texture_check(const ky_scene* scene, const ky_texture* textures, int n);   // kyhip_texture_check
+// a valid set as the device reads it: the block (descriptors, links, the uv record of every surface by `packed`'s sorted order) and the texels as float4, a plastic
+// material's divided by its diffuse_probability
+void texture_pack(const ky_scene* scene, const DScene* packed, const ky_texture* textures, int n, DTexSet* set, std::vector<float>* texels4);
+uint64_t texture_digest(const ky_texture* textures, int n);   // 64 bits over every descriptor field and every texel; never 0 for n > 0, 0 for n == 0
+uint64_t texture_fold(uint64_t hash, uint64_t digest);        // the scene hash a frame's header carries under a set of that digest: `hash` itself for 0
+std::string texture_describe(const ky_texture* textures, int n);   // "2 textures (checker on material 3, 4 x 4 nearest image on material 1)"
 int pack_scene(const ky_scene* in, DScene* out);
 void pack_light_pick(const ky_scene* in, DLightPick* out);   // sample_single_light's power and spatial picks: the emitter proxies and the power rule's probabilities (a scene pack_scene accepts)
 uint64_t scene_hash(const DScene& s);

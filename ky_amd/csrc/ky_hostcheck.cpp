@@ -932,6 +932,28 @@ int kyhip_kat_li_lens(int device, const ky_scene* scene, const ky_render_params*
     if (lens) KY_TRY(lens_check(lens));
     return kyhip_kat_li_filtered(device, scene, p, filter, x, y, s0, n, out3);
 }
+// (... and the texture entries an invalid set first: texture_check is host code; no textures is the lens entry)
+int kyhip_render_textured(int device, const ky_scene* scene, const ky_texture* textures, int n, const ky_render_params* p, const ky_pixel_filter* filter, const ky_lens* lens,
+                          float* film, size_t stride) {
+    KY_TRY(texture_check(scene, textures, n));
+    if (n == 0) return kyhip_render_lens(device, scene, p, filter, lens, film, stride);
+    return no_gpu();
+}
+int kyhip_frame_set_textures(kyhip_frame*, const ky_texture* textures, int n) {
+    if (n < 0 || (n > 0 && !textures)) return fail(KY_ERR_INVALID_VALUE, "bad texture arguments");
+    if (n > KYHIP_MAX_TEXTURES) return fail(KY_ERR_LIMIT, "textures: %d, at most %d", n, KYHIP_MAX_TEXTURES);
+    return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+}
+int kyhip_kat_li_textured(int device, const ky_scene* scene, const ky_texture* textures, int n_textures, const ky_render_params* p, const ky_pixel_filter* filter,
+                          const ky_lens* lens, int x, int y, int s0, int n, float* out3) {
+    KY_TRY(texture_check(scene, textures, n_textures));
+    if (n_textures == 0) return kyhip_kat_li_lens(device, scene, p, filter, lens, x, y, s0, n, out3);
+    return no_gpu();
+}
+int kyhip_kat_texture(int, const ky_scene* scene, const ky_texture* textures, int n_textures, int, const float*, int, float*) {
+    KY_TRY(texture_check(scene, textures, n_textures));
+    return no_gpu();
+}
 int kyhip_kat_nee(int, const ky_scene*, int, int, const float*, int, float*) { return no_gpu(); }
 int kyhip_kat_light_pick(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }   // (kyhip_scene_light_pick is host code: ky_pack.cpp)
 int kyhip_kat_single_light_rule(int, const ky_scene*, int, const float*, int, float*) { return no_gpu(); }

@@ -340,6 +340,44 @@ __global__ void kat_li_kernel(const DScene* __restrict__ S_, typename ReplayCons
     else { out[3 * (size_t)i] = ps.Lo.x; out[3 * (size_t)i + 1] = ps.Lo.y; out[3 * (size_t)i + 2] = ps.Lo.z; }
 }
 
+// ... and under a texture set: the walk of the textured render kernels -- no scene facts, the one camera form KY_CAM_ANY, the vertex's
+// material through vertex_material<true>.  A kernel of its own, so that every form of kat_li_kernel keeps its name and its code.
+template <int SAMPLER>
+__global__ void kat_li_textured_kernel(const DScene* __restrict__ S_, RenderConstT rc_, int x, int y, int s0, int n, float* __restrict__ out) {
+    const SceneRef S{S_, true, 0, true};
+    const typename RenderConstFor<SAMPLER>::type& rc = rc_;
+    const LdsScene Lds = stage_lights(S, stage_scene<true>(S), ky_direct_is_single(rc.strategy));
+    const TexLds tx = stage_textures(rc_.tex, Lds);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    PathStateFor<SAMPLER> ps;
+    sampler_bind(ps.smp, rc);
+    const bool mine = i < n;
+    bool alive = mine;
+    if (alive) path_begin<SAMPLER, false, KY_CAM_ANY>(ps, S, sampler_pixel_key(rc.seed, (uint32_t)(y * rc.width + x)), x, y, s0 + i, lens_cam(rc_));
+    while (__any(alive)) {  // path_shade is a wave-uniform call
+        Vertex v;
+        bool have_vertex = false;
+        if (alive) have_vertex = path_intersect<SAMPLER, 0>(ps, v, S, Lds, rc, 0);
+        const bool cont = path_shade<SAMPLER, 0, true>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, nullptr, 0, false, false, 0, &tx);
+        alive = have_vertex && cont;
+    }
+    if (!mine) return;
+    out[3 * (size_t)i] = ps.Lo.x; out[3 * (size_t)i + 1] = ps.Lo.y; out[3 * (size_t)i + 2] = ps.Lo.z;
+}
+// the known-answer probe of the texture code: (u', v', r, g, b) at world points of (sorted) surface `surface` under texture `ti`, through tex_at
+__global__ void kat_texture_kernel(TexConst tc, int ti, int surface, const float* __restrict__ points3, int n, float* __restrict__ out5) {
+    __shared__ __attribute__((aligned(16))) DTex tex[KYHIP_MAX_TEXTURES];
+    if (threadIdx.x < KYHIP_MAX_TEXTURES) tex[threadIdx.x] = tc.set->tex[threadIdx.x];
+    __syncthreads();
+    const TexLds tx{tex, tc.set->uv, tc.texels};
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float us, vs;
+    const f3 col = tex_at(tx, ti, surface, mk3(points3[3 * (size_t)i], points3[3 * (size_t)i + 1], points3[3 * (size_t)i + 2]), us, vs);
+    float* q = out5 + 5 * (size_t)i;
+    q[0] = us; q[1] = vs; q[2] = col.x; q[3] = col.y; q[4] = col.z;
+}
+
 // ---- shared drivers of the KAT entry points ----
 template <typename F>
 static int kat_run(int device, const void* in, size_t in_bytes, void* out, size_t out_bytes, F launch) {
@@ -668,6 +706,76 @@ int kyhip_kat_lens(int device, const float* u2, int n, float* out2) {
         hipLaunchKernelGGL(kat_lens_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_in, n, d_out);
         return (int)KY_OK;
     });
+}
+
+// ... under a texture set (and a pixel filter and a lens): the walk of the textured render kernels
+// the set on the device for the span of one KAT call
+struct KatTextures {
+    DevBuf set, texels;
+    TexConst tc{};
+    int upload(const ky_scene* scene, const DScene* packed, const ky_texture* textures, int n) {
+        std::unique_ptr<DTexSet> h(new DTexSet);
+        std::vector<float> texels4;
+        texture_pack(scene, packed, textures, n, h.get(), &texels4);
+        HIP_TRY(set.alloc(sizeof(DTexSet)));
+        HIP_TRY(texels.alloc(texels4.size() * sizeof(float)));
+        HIP_TRY(hipMemcpy(set.p, h.get(), sizeof(DTexSet), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(texels.p, texels4.data(), texels4.size() * sizeof(float), hipMemcpyHostToDevice));
+        tc = TexConst{set.as<const DTexSet>(), texels.as<const float4>()};
+        return KY_OK;
+    }
+};
+int kyhip_kat_li_textured(int device, const ky_scene* scene, const ky_texture* textures, int n_textures, const ky_render_params* p, const ky_pixel_filter* filter,
+                          const ky_lens* lens, int x, int y, int s0, int n, float* out3) {
+    KY_TRY(texture_check(scene, textures, n_textures));
+    if (n_textures == 0) return kyhip_kat_li_lens(device, scene, p, filter, lens, x, y, s0, n, out3);
+    if (lens) KY_TRY(lens_check(lens));
+    if (filter) KY_TRY(filter_check(filter));
+    if (!valid_params(p)) return fail(KY_ERR_INVALID_VALUE, "invalid render params");
+    if (p->sampler == KY_SAMPLER_DEBUG) return fail(KY_ERR_INVALID_VALUE, "a render under a texture set has no row for the debug sampler");
+    KY_TRY(replay_check(scene, p, x, y, s0, n, out3));
+    LensConst lc{0.f, 0.f, 0.f, 0.f};
+    if (!lens_is_pinhole(lens)) KY_TRY(lens_const_checked(&scene->camera, lens, &lc));
+    const bool filt = !filter_is_box(filter);
+    float table[KYHIP_FILTER_TABLE + 1] = {0.f};
+    if (filt) filter_table(filter, table);
+    KatTextures kt;
+    int up = KY_OK;
+    const int rcode = kat_run_scene(device, scene, table, filt ? sizeof table : 4, out3, (size_t)n * 3 * 4, [&](const DScene* S, const DScene* packed, size_t lds, const float* d_in, float* d_out) {
+        up = kt.upload(scene, packed, textures, n_textures);
+        if (up != KY_OK) return;
+        RenderConstT rc{};
+        static_cast<RenderConstS&>(rc) = make_rc(p);
+        if (filt) rc.filter = FilterConst{filter->kind, filter->radius, filter_grow(filter), d_in};
+        rc.lens = lc;
+        rc.tex = kt.tc;
+        const dim3 grid((n + 255) / 256), block(256);
+        if (p->sampler == KY_SAMPLER_STRATIFIED) hipLaunchKernelGGL((kat_li_textured_kernel<KY_SMP_STRATIFIED>), grid, block, lds, 0, S, rc, x, y, s0, n, d_out);
+        else hipLaunchKernelGGL((kat_li_textured_kernel<KY_SMP_RANDOM>), grid, block, lds, 0, S, rc, x, y, s0, n, d_out);
+    });
+    return up != KY_OK ? up : rcode;
+}
+
+int kyhip_kat_texture(int device, const ky_scene* scene, const ky_texture* textures, int n_textures, int surface, const float* points3, int n_points, float* out5) {
+    KY_TRY(texture_check(scene, textures, n_textures));
+    if (!scene || !points3 || !out5 || n_points <= 0 || n_points > (1 << 24) || n_textures < 1) return fail(KY_ERR_INVALID_VALUE, "bad KAT arguments");
+    if (surface < 0 || surface >= scene->surface_count) return fail(KY_ERR_INVALID_VALUE, "surface %d out of range", surface);
+    int ti = -1;
+    for (int i = 0; i < n_textures; ++i)
+        if (textures[i].material == scene->surfaces[surface].material) ti = i;
+    if (ti < 0) return fail(KY_ERR_INVALID_VALUE, "surface %d: its material %d carries no texture of the set", surface, scene->surfaces[surface].material);
+    KatTextures kt;
+    int up = KY_OK;
+    const int rcode = kat_run_scene(device, scene, points3, (size_t)n_points * 12, out5, (size_t)n_points * 20, [&](const DScene*, const DScene* packed, size_t, const float* d_in, float* d_out) {
+        up = kt.upload(scene, packed, textures, n_textures);
+        if (up != KY_OK) return;
+        int sorted = -1;
+        for (int j = 0; j < packed->n_surfaces; ++j)
+            if (packed->orig[j] == surface) sorted = j;
+        if (sorted < 0) { up = fail(KY_ERR_DEVICE, "internal: surface %d is not in the packed scene", surface); return; }
+        hipLaunchKernelGGL(kat_texture_kernel, dim3((n_points + 255) / 256), dim3(256), 0, 0, kt.tc, ti, sorted, d_in, n_points, d_out);
+    });
+    return up != KY_OK ? up : rcode;
 }
 
 // one camera sample, traced vertex by vertex

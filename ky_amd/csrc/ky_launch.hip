@@ -274,6 +274,7 @@ using RenderFn = void (*)(const DScene*, RenderConst, ShardConst, unsigned*, uns
 using RenderFnS = void (*)(const DScene*, RenderConstS, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a stratified row's kernel: the launch constants carry the strata
 using RenderFnF = void (*)(const DScene*, RenderConstF, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a filtered row's kernel: ... and the pixel filter
 using RenderFnL = void (*)(const DScene*, RenderConstL, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a lens row's kernel: ... and the lens
+using RenderFnT = void (*)(const DScene*, RenderConstT, ShardConst, unsigned*, unsigned long long*, unsigned*, float4*);   // a textured row's kernel: ... and the texture set
 struct Variant {
     bool dbg;
     int strategy;
@@ -287,8 +288,9 @@ struct Variant {
     RenderFnF fn_f;   // a launch under a pixel filter (fn and fn_s are null): render_kernel_filtered, which takes RenderConstF; null in every other row ...
     bool f_strat;     // ... and whether it draws with the stratified sampler (else the random one)
     RenderFnL fn_l;   // a launch under a lens (fn, fn_s and fn_f are null; f_strat as above): render_kernel_lens, which takes RenderConstL; null in every other row
-    bool strat() const { return fn_s != nullptr || ((fn_f != nullptr || fn_l != nullptr) && f_strat); }
-    int cam() const { return fn_l ? KY_CAM_LENS : fn_f ? KY_CAM_FILTER : KY_CAM_PLAIN; }
+    RenderFnT fn_t;   // a launch under a texture set (fn, fn_s, fn_f and fn_l are null; f_strat as above): render_kernel_textured, which takes RenderConstT; null in every other row
+    bool strat() const { return fn_s != nullptr || ((fn_f != nullptr || fn_l != nullptr || fn_t != nullptr) && f_strat); }
+    int cam() const { return fn_t ? KY_CAM_ANY : fn_l ? KY_CAM_LENS : fn_f ? KY_CAM_FILTER : KY_CAM_PLAIN; }
 };
 #define KY_VARIANT(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, false, render_kernel<D, S, Q, G, F, I>, 0}
 #define KY_VARIANT_LARGE(D, S, Q, G, F, I) Variant{D, S, Q, G, F, I, true, render_kernel<D, S, Q, G, F, I, true>, 0}
@@ -302,6 +304,8 @@ struct Variant {
 #define KY_VARIANT_FILT(SMP, G, L, LISTED) Variant{false, -1, false, G, 0, IT, L, nullptr, 0, LISTED, nullptr, render_kernel_filtered<SMP, G, L, LISTED>, SMP == KY_SMP_STRATIFIED}
 // a lens row (a ky_lens of radius > 0, under any pixel filter), shaped like a filtered row
 #define KY_VARIANT_LENS(SMP, G, L, LISTED) Variant{false, -1, false, G, 0, IT, L, nullptr, 0, LISTED, nullptr, nullptr, SMP == KY_SMP_STRATIFIED, render_kernel_lens<SMP, G, L, LISTED>}
+// a textured row (a texture set, under any pixel filter and lens or none), shaped like a lens row
+#define KY_VARIANT_TEX(SMP, G, L, LISTED) Variant{false, -1, false, G, 0, IT, L, nullptr, 0, LISTED, nullptr, nullptr, SMP == KY_SMP_STRATIFIED, nullptr, render_kernel_textured<SMP, G, L, LISTED>}
 // a row's three masked twins: emission at the first vertex dropped (lighting 2, 6), the k = 1 terms (5), both (4)
 #define KY_VARIANT_MASKED3(D, S, Q, G, F, I) KY_VARIANT_MASKED(1, D, S, Q, G, F, I), KY_VARIANT_MASKED(2, D, S, Q, G, F, I), KY_VARIANT_MASKED(3, D, S, Q, G, F, I)
 constexpr int IT = KY_INTEGRATOR_PATH_TRACING_ITERATION;
@@ -457,6 +461,20 @@ static const Variant g_variants[] = {
     KY_VARIANT_LENS(KY_SMP_STRATIFIED, false, false, true),
     KY_VARIANT_LENS(KY_SMP_STRATIFIED, true, false, true),
     KY_VARIANT_LENS(KY_SMP_STRATIFIED, true, true, true),
+    // launches under a texture set (kyhip_render_textured, kyhip_frame_set_textures), with or without a pixel filter and a lens: twelve rows
+    // shaped like the lens twelve, with the same things left out
+    KY_VARIANT_TEX(KY_SMP_RANDOM, false, false, false),
+    KY_VARIANT_TEX(KY_SMP_RANDOM, true, false, false),
+    KY_VARIANT_TEX(KY_SMP_RANDOM, true, true, false),
+    KY_VARIANT_TEX(KY_SMP_RANDOM, false, false, true),
+    KY_VARIANT_TEX(KY_SMP_RANDOM, true, false, true),
+    KY_VARIANT_TEX(KY_SMP_RANDOM, true, true, true),
+    KY_VARIANT_TEX(KY_SMP_STRATIFIED, false, false, false),
+    KY_VARIANT_TEX(KY_SMP_STRATIFIED, true, false, false),
+    KY_VARIANT_TEX(KY_SMP_STRATIFIED, true, true, false),
+    KY_VARIANT_TEX(KY_SMP_STRATIFIED, false, false, true),
+    KY_VARIANT_TEX(KY_SMP_STRATIFIED, true, false, true),
+    KY_VARIANT_TEX(KY_SMP_STRATIFIED, true, true, true),
     // everything else: strategy and integrator at run time; the debug sampler; scenes with general shapes
     KY_VARIANT(false, -1, false, false, 0, IT),
     KY_VARIANT(true, -1, false, false, 0, IT),
@@ -545,9 +563,11 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
     const bool strat = p->sampler == KY_SAMPLER_STRATIFIED;
     // a pass of a frame with a pixel filter; the debug sampler's 0.5 is the pixel's centre under every filter, so its launches are the unfiltered ones
     // ... or a lens: the debug sampler's (0.5, 0.5) is the centre of the lens, the pinhole's ray
-    const int cam = !pass || p->sampler == KY_SAMPLER_DEBUG ? KY_CAM_PLAIN : pass->lensed ? KY_CAM_LENS : pass->filtered ? KY_CAM_FILTER : KY_CAM_PLAIN;
-    const bool filt = cam != KY_CAM_PLAIN, lensed = cam == KY_CAM_LENS;
-    if (filt && drop != 0) return fail(KY_ERR_INVALID_VALUE, "a launch under a pixel filter or a lens has no masked form");
+    // ... or a texture set, which the debug sampler cannot ignore: there is no textured row for it
+    if (pass && pass->textured && p->sampler == KY_SAMPLER_DEBUG) return fail(KY_ERR_INVALID_VALUE, "a launch under a texture set has no row for the debug sampler");
+    const int cam = !pass || p->sampler == KY_SAMPLER_DEBUG ? KY_CAM_PLAIN : pass->textured ? KY_CAM_ANY : pass->lensed ? KY_CAM_LENS : pass->filtered ? KY_CAM_FILTER : KY_CAM_PLAIN;
+    const bool filt = cam != KY_CAM_PLAIN, textured = cam == KY_CAM_ANY, lensed = cam == KY_CAM_LENS || (textured && pass->lensed);
+    if (filt && drop != 0) return fail(KY_ERR_INVALID_VALUE, "a launch under a pixel filter, a lens or a texture set has no masked form");
     StreamState* st;
     rcode = get_stream_state(c, stream, &st);
     if (rcode != KY_OK) return rcode;
@@ -610,7 +630,7 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         const Variant* v = pass && pass->kernel >= 0 ? &g_variants[pass->kernel] : pick_variant(p, sc->h, shadow_queue_wanted(scene), sh.n_pix, drop, listed, cam);
         if (!v) return fail(KY_ERR_DEVICE, "internal: no render kernel for these parameters");
         if (pinned && pass->kernel >= 0 && v->listed != listed) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the block list");
-        if (v->cam() != cam) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the pixel filter or the lens");
+        if (v->cam() != cam) return fail(KY_ERR_DEVICE, "internal: the frame's kernel and its passes disagree about the pixel filter, the lens or the texture set");
         const int vi = (int)(v - g_variants);
         // run-time instantiation (kyhip_set_jit(1)): this launch's own kernel -- its sampler, strategy and integrator as compile-time constants and ALL
         // of the scene's facts -- unless the table's pick is exactly that already
@@ -618,7 +638,11 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         bool queue = v->queue;
         const int jit_mode = kyjit::mode();
         c->last_note.clear();
-        if (lensed) c->last_note = " [" + pass->lens_note + ", " + (pass->filtered ? pass->filter_note : std::string("box filter")) + ": a lens launch runs the run-time-dispatched kernel and culls no pixel block; it takes no specialised row and instantiates no kernel of its own]";
+        if (textured) c->last_note = " [" + pass->tex_note + ", " + (pass->lensed ? pass->lens_note : std::string("pinhole")) + ", " + (pass->filtered ? pass->filter_note : std::string("box filter")) +
+                                     ": a textured launch runs the run-time-dispatched kernel with one camera form for plain, filtered and lens launches; it culls the pixel blocks " +
+                                     (pass->lensed ? "of no part of the frame (a lens)" : "outside the live rectangle grown by the filter's reach, as a filtered launch does") +
+                                     "; it takes no specialised row and instantiates no kernel of its own]";
+        else if (lensed) c->last_note = " [" + pass->lens_note + ", " + (pass->filtered ? pass->filter_note : std::string("box filter")) + ": a lens launch runs the run-time-dispatched kernel and culls no pixel block; it takes no specialised row and instantiates no kernel of its own]";
         else if (filt) c->last_note = " [" + pass->filter_note + ": a filtered launch runs the run-time-dispatched kernel; it takes no specialised row and instantiates no kernel of its own]";
         else if (v->strategy < 0 && jit_mode == 0) c->last_note = " [the run-time-dispatched kernel: no row of the table holds this launch's strategy / integrator / shapes; kyhip_set_jit(1 / 2) instantiates its own]";
         // (a mode nobody chose -- the default of round 6 -- instantiates only where the table's pick knows nothing of the scene: a launch served by a row of facts stays on it,
@@ -692,7 +716,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         }
         if (!jk && (c->variant_blocks[vi] == 0 || c->variant_lds[vi] != lds_bytes)) {   // resident workgroups per CU: depends on the scene's LDS block
             int per_cu = 0;
-            if (v->fn_l) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_l, 256, lds_bytes));
+            if (v->fn_t) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_t, 256, lds_bytes));
+            else if (v->fn_l) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_l, 256, lds_bytes));
             else if (v->fn_f) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_f, 256, lds_bytes));
             else if (v->fn_s) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn_s, 256, lds_bytes));
             else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v->fn, 256, lds_bytes));
@@ -731,7 +756,8 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
         if (drop != 0 && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no masked form]";
         if (pass && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine renders no passes]";
         if (strat && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no stratified sampler]";
-        if (lensed && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no lens]";
+        if (textured && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no textures]";
+        else if (lensed && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no lens]";
         else if (filt && current_engine() == KY_ENGINE_QUEUE) c->last_note += " [lane engine: the queue engine has no pixel filter]";
         if (pass) { pass->kernel = jk ? -3 : vi; pass->queue = queue; }
         if (!jk && v->drop < 0 && st->counter_drop != drop) {   // the drop bits of a run-time-dispatched masked kernel: word 2 of the counter block, written when they change
@@ -751,7 +777,15 @@ int kyh::render_tiles_device(int device, const ky_scene* scene, const ky_render_
             HIP_TRY(hipModuleLaunchKernel(jk->fn, grid, 1, 1, 256, 1, 1, (unsigned)lds_bytes, stream, args, nullptr));
             c->last_variant = -3;
         } else {
-            if (v->fn_l) {   // (the filter is the frame's, the box where it has none; the live rectangle grows over the whole pixel range)
+            if (v->fn_t) {   // (the filter and the lens are the frame's, the box and the pinhole -- all zeros -- where it has none)
+                RenderConstT rc_t;
+                static_cast<RenderConstS&>(rc_t) = rc;
+                rc_t.filter = pass->filter;
+                rc_t.lens = pass->lensed ? pass->lens : LensConst{0.f, 0.f, 0.f, 0.f};
+                if (pass->lensed) rc_t.filter.grow = KY_LIVE_MAX;
+                rc_t.tex = pass->tex;
+                hipLaunchKernelGGL(v->fn_t, dim3(grid), dim3(256), lds_bytes, stream, (const DScene*)sc->d, rc_t, sh, st->d_counter, accum, flags, queue_mem);
+            } else if (v->fn_l) {   // (the filter is the frame's, the box where it has none; the live rectangle grows over the whole pixel range)
                 RenderConstL rc_l;
                 static_cast<RenderConstS&>(rc_l) = rc;
                 rc_l.filter = pass->filter;
@@ -846,6 +880,7 @@ const char* kyhip_last_kernel(int device) {
         if (v.fn_l) name.insert(name.size() - 1, ", lens");
         if (v.drop > 0) name.insert(name.size() - 1, ", drop " + std::to_string(v.drop));
         else if (v.drop < 0) name.insert(name.size() - 1, ", drop bits per launch");
+        if (v.fn_t) name.insert(name.size() - 1, ", textured");
     }
     name += c->last_note;
     return name.c_str();

@@ -888,6 +888,145 @@ int lens_const_checked(const ky_camera* cam, const ky_lens* l, LensConst* out) {
     return KY_OK;
 }
 
+// ---- textures (include/kyhip.h, ky_texture) ----
+int texture_check(const ky_scene* scene, const ky_texture* t, int n) {
+    if (n < 0) return fail(KY_ERR_INVALID_VALUE, "textures: n_textures %d", n);
+    if (n == 0) return KY_OK;
+    if (!t) return fail(KY_ERR_INVALID_VALUE, "textures is NULL");
+    if (!scene || !scene->materials) return fail(KY_ERR_INVALID_VALUE, "scene is NULL");
+    if (n > KYHIP_MAX_TEXTURES) return fail(KY_ERR_LIMIT, "textures: %d, at most %d", n, KYHIP_MAX_TEXTURES);
+    auto colour_ok = [](const float* c) { return std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) && c[0] >= 0.f && c[1] >= 0.f && c[2] >= 0.f; };
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        const ky_texture& x = t[i];
+        if (x.kind != KY_TEXTURE_CHECKER && x.kind != KY_TEXTURE_IMAGE) return fail(KY_ERR_INVALID_VALUE, "texture %d: unknown kind %d", i, x.kind);
+        if (x.reserved != 0) return fail(KY_ERR_INVALID_VALUE, "texture %d: reserved is %d, not 0", i, x.reserved);
+        if (x.flags & ~(KY_TEXTURE_BILINEAR | KY_TEXTURE_CLAMP)) return fail(KY_ERR_INVALID_VALUE, "texture %d: unknown flags %d", i, x.flags);
+        if (x.material < 0 || x.material >= scene->material_count) return fail(KY_ERR_INVALID_VALUE, "texture %d: material %d out of range (%d materials)", i, x.material, scene->material_count);
+        const int mk = scene->materials[x.material].kind;
+        if (mk == KY_MATERIAL_GLASS) return fail(KY_ERR_INVALID_VALUE, "texture %d: material %d is glass, whose colours take no texture", i, x.material);
+        if (mk != KY_MATERIAL_MATTE && mk != KY_MATERIAL_MIRROR && mk != KY_MATERIAL_PLASTIC) return fail(KY_ERR_INVALID_VALUE, "texture %d: material %d has unknown kind %d", i, x.material, mk);
+        for (int k = 0; k < i; ++k)
+            if (t[k].material == x.material) return fail(KY_ERR_INVALID_VALUE, "texture %d: material %d has texture %d already (at most one per material)", i, x.material, k);
+        for (int k = 0; k < 2; ++k) {
+            // (both within +-KYHIP_MAX_TEXTURE_SCALE: (u, v) of a point of its surface lie in [0, 1] -- a little beyond on a quad that is no parallelogram --, so u' and v'
+            // stay far inside the range where floor(u') + floor(v') is an exact int)
+            if (!std::isfinite(x.scale[k]) || x.scale[k] == 0.f || std::fabs(x.scale[k]) > (float)KYHIP_MAX_TEXTURE_SCALE)
+                return fail(KY_ERR_INVALID_VALUE, "texture %d: scale[%d] = %g (finite, not 0, at most %d in size)", i, k, (double)x.scale[k], (int)KYHIP_MAX_TEXTURE_SCALE);
+            if (!std::isfinite(x.offset[k]) || std::fabs(x.offset[k]) > (float)KYHIP_MAX_TEXTURE_SCALE)
+                return fail(KY_ERR_INVALID_VALUE, "texture %d: offset[%d] = %g (finite, at most %d in size)", i, k, (double)x.offset[k], (int)KYHIP_MAX_TEXTURE_SCALE);
+        }
+        if (x.kind == KY_TEXTURE_CHECKER) {
+            if (!colour_ok(x.a) || !colour_ok(x.b)) return fail(KY_ERR_INVALID_VALUE, "texture %d: a checker's colours are finite and >= 0", i);
+            continue;   // (a checker's two colours are no texels of the caller's: the limit counts images)
+        }
+        if (x.width > KYHIP_MAX_TEXTURE_SIZE || x.height > KYHIP_MAX_TEXTURE_SIZE)
+            return fail(KY_ERR_LIMIT, "texture %d: %d x %d texels, at most %d each way", i, x.width, x.height, KYHIP_MAX_TEXTURE_SIZE);
+        if (x.width < 1 || x.height < 1) return fail(KY_ERR_INVALID_VALUE, "texture %d: %d x %d texels", i, x.width, x.height);
+        if (!x.texels) return fail(KY_ERR_INVALID_VALUE, "texture %d: an image without texels", i);
+        total += (long long)x.width * x.height;
+        if (total > (long long)KYHIP_MAX_TEXELS) return fail(KY_ERR_LIMIT, "textures: more than %d texels over the set", (int)KYHIP_MAX_TEXELS);
+        const size_t nf = (size_t)x.width * x.height * 3;
+        for (size_t k = 0; k < nf; ++k)
+            if (!(std::isfinite(x.texels[k]) && x.texels[k] >= 0.f)) return fail(KY_ERR_INVALID_VALUE, "texture %d: texel value %zu is %g (finite, >= 0)", i, k, (double)x.texels[k]);
+    }
+    return KY_OK;
+}
+uint64_t texture_digest(const ky_texture* t, int n) {
+    if (n <= 0) return 0;
+    uint64_t h = 0xcbf29ce484222325ull ^ (uint64_t)n;
+    auto word = [&h](uint32_t v) { h = (h ^ v) * 0x100000001b3ull; h ^= h >> 29; };
+    auto fl = [&word](float f) { uint32_t v; std::memcpy(&v, &f, 4); word(v); };
+    for (int i = 0; i < n; ++i) {
+        const ky_texture& x = t[i];
+        word((uint32_t)x.kind); word((uint32_t)x.material); word((uint32_t)x.flags);
+        for (int k = 0; k < 2; ++k) { fl(x.scale[k]); fl(x.offset[k]); }
+        if (x.kind == KY_TEXTURE_CHECKER) {
+            for (int k = 0; k < 3; ++k) { fl(x.a[k]); fl(x.b[k]); }
+        } else {
+            word((uint32_t)x.width); word((uint32_t)x.height);
+            const size_t nf = (size_t)x.width * x.height * 3;
+            for (size_t k = 0; k < nf; ++k) fl(x.texels[k]);
+        }
+    }
+    h = h * 0x9e3779b97f4a7c15ull + 0x54455854ull;
+    return h ? h : 1;
+}
+uint64_t texture_fold(uint64_t hash, uint64_t digest) {
+    if (digest == 0) return hash;
+    uint64_t h = (hash ^ digest) * 0x100000001b3ull;
+    h ^= h >> 29;
+    return h * 0x9e3779b97f4a7c15ull + 0x54455846ull;
+}
+std::string texture_describe(const ky_texture* t, int n) {
+    std::string s = std::to_string(n) + (n == 1 ? " texture (" : " textures (");
+    for (int i = 0; i < n; ++i) {
+        char buf[96];
+        if (t[i].kind == KY_TEXTURE_CHECKER) snprintf(buf, sizeof buf, "%schecker on material %d", i ? ", " : "", t[i].material);
+        else snprintf(buf, sizeof buf, "%s%d x %d %s %s image on material %d", i ? ", " : "", t[i].width, t[i].height, (t[i].flags & KY_TEXTURE_BILINEAR) ? "bilinear" : "nearest",
+                      (t[i].flags & KY_TEXTURE_CLAMP) ? "clamped" : "repeating", t[i].material);
+        s += buf;
+    }
+    return s + ")";
+}
+// The uv record of one surface (DTexUV, ky_scene.hpp): every constant computed in double from the caller's floats and rounded once.
+static void texture_uv_record(const ky_shape& sh, const DHit& hit, DTexUV* r) {
+    std::memset(r, 0, sizeof *r);
+    auto sub = [](const float a[3], const float b[3], double o[3]) { for (int k = 0; k < 3; ++k) o[k] = (double)a[k] - (double)b[k]; };
+    auto dotd = [](const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    cp3(r->o, sh.p[0]);
+    if (sh.kind == KY_SHAPE_SPHERE) {
+        r->kind = 1;
+        r->k0 = (float)(1.0 / (double)sh.radius);
+        return;
+    }
+    if (sh.kind == KY_SHAPE_DISK) {
+        cp3(r->e1, hit.fs); cp3(r->e2, hit.ft);
+        r->k0 = r->k1 = (float)(1.0 / (2.0 * (double)sh.radius));
+        r->add = 0.5f;
+        return;
+    }
+    double e1[3], e2[3];
+    sub(sh.p[1], sh.p[0], e1);
+    sub(sh.kind == KY_SHAPE_RECTANGLE ? sh.p[3] : sh.p[2], sh.p[0], e2);
+    for (int k = 0; k < 3; ++k) { r->e1[k] = (float)e1[k]; r->e2[k] = (float)e2[k]; }
+    const double g11 = dotd(e1, e1), g22 = dotd(e2, e2), g12 = dotd(e1, e2);
+    if (sh.kind == KY_SHAPE_RECTANGLE) {
+        r->k0 = (float)(1.0 / g11); r->k1 = (float)(1.0 / g22);
+    } else {   // the inverse of the Gram matrix (g11 g12; g12 g22)
+        const double det = g11 * g22 - g12 * g12;
+        r->k0 = (float)(g22 / det); r->k1 = (float)(g11 / det); r->k2 = (float)(-g12 / det);
+    }
+}
+void texture_pack(const ky_scene* scene, const DScene* packed, const ky_texture* t, int n, DTexSet* set, std::vector<float>* texels4) {
+    std::memset(set, 0, sizeof *set);
+    texels4->clear();
+    set->n_tex = n;
+    for (int i = 0; i < n; ++i) {
+        const ky_texture& x = t[i];
+        const ky_material& m = scene->materials[x.material];
+        // a plastic material's Lambert albedo is Kd / P_diff (pack_material): the same float division, once per texel
+        const bool plastic = m.kind == KY_MATERIAL_PLASTIC;
+        auto push = [&](const float* c) {
+            for (int k = 0; k < 3; ++k) texels4->push_back(plastic ? c[k] / m.diffuse_probability : c[k]);
+            texels4->push_back(0.f);
+        };
+        DTex& d = set->tex[i];
+        d.kind_flags = x.kind | ((x.kind == KY_TEXTURE_IMAGE ? x.flags : 0) << 8);
+        d.first = (int32_t)(texels4->size() / 4);
+        d.scale[0] = x.scale[0]; d.scale[1] = x.scale[1]; d.offset[0] = x.offset[0]; d.offset[1] = x.offset[1];
+        set->material[i] = x.material;
+        if (x.kind == KY_TEXTURE_CHECKER) {
+            d.w = 2; d.h = 1;
+            push(x.a); push(x.b);
+        } else {
+            d.w = x.width; d.h = x.height;
+            for (size_t k = 0; k < (size_t)x.width * x.height; ++k) push(x.texels + 3 * k);
+        }
+    }
+    for (int j = 0; j < packed->n_surfaces; ++j) texture_uv_record(scene->shapes[scene->surfaces[packed->orig[j]].shape], packed->hit[j], &set->uv[j]);
+}
+
 int pack_scene(const ky_scene* in, DScene* out) {
     if (!in) return fail(KY_ERR_INVALID_VALUE, "scene is NULL");
     if (in->surface_count < 0 || in->shape_count < 0 || in->material_count < 0 || in->light_count < 0)
@@ -1602,6 +1741,7 @@ int kyhip_scene_screen_bound_lens(const ky_scene* scene, const ky_render_params*
     return KY_OK;
 }
 int kyhip_lens_check(const ky_lens* lens) { return lens_check(lens); }
+int kyhip_texture_check(const ky_scene* scene, const ky_texture* textures, int n_textures) { return texture_check(scene, textures, n_textures); }
 
 // ---- pixel filters: the host-only entries (filter_check ... above) ----
 int kyhip_filter_check(const ky_pixel_filter* filter) { return filter_check(filter); }

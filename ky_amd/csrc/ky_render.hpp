@@ -96,9 +96,11 @@ constexpr int ky_waves_per_eu() {
 // the rectangle's proof is a projection from one point (screen_bound, ky_pack.cpp); the sums stay within int32.  KY_CAM_PLAIN -- every instantiation that does not
 // name it -- ignores fc.
 template <int SAMPLER, int STRATEGY, bool QUEUE = false, bool GENERAL = false, int FEAT = 0, int INTEGRATOR = KY_INTEGRATOR_PATH_TRACING_ITERATION, bool LARGE = false, int DROP = 0, bool LISTED = false,
-          int CAM = KY_CAM_PLAIN>
+          int CAM = KY_CAM_PLAIN, bool TEX = false>
 KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderConstFor<SAMPLER>::type rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum,
-                               unsigned* __restrict__ flags, float4* __restrict__ queue_mem, typename CamConstFor<CAM>::type fc = typename CamConstFor<CAM>::type{}) {
+                               unsigned* __restrict__ flags, float4* __restrict__ queue_mem, typename CamConstFor<CAM>::type fc = typename CamConstFor<CAM>::type{},
+                               TexConst tc = TexConst{}) {
+    static_assert(!TEX || CAM == KY_CAM_ANY, "the textured kernels have one camera form");
     constexpr bool FILTER = CAM != KY_CAM_PLAIN;   // what the filtered and the lens kernels share: run-time dispatch, a widened live rectangle
     static_assert(!FILTER || (STRATEGY < 0 && !QUEUE && DROP == 0 && SAMPLER != KY_SMP_DEBUG), "the filtered kernels are the run-time-dispatched ones, unmasked");
     static_assert(!QUEUE || ((STRATEGY == KY_DIRECT_BOTH_MIS || ky_direct_is_single(STRATEGY) || STRATEGY == KY_DIRECT_LIGHT_MIS || STRATEGY == KY_DIRECT_LIGHT) && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_ITERATION),
@@ -122,6 +124,8 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderCon
     if constexpr ((ky_direct_is_single(STRATEGY) || STRATEGY < 0) && (FEAT & KY_FEAT_SINGLE_LIGHT) == 0)
         lds_tables = stage_lights(S, lds_tables, ky_direct_is_single(rc.strategy));
     const LdsScene Lds = lds_tables;
+    TexLds tex_lds{};   // TEX: the set's descriptors in LDS and the textured materials' links in the staged records (stage_textures, ky_device.hpp)
+    if constexpr (TEX) tex_lds = stage_textures(tc, Lds);
     int nee_weight = (rc.strategy == KY_DIRECT_IDLE || rc.integrator < KY_INTEGRATOR_DIRECT_LIGHTING ||
                             rc.integrator == KY_INTEGRATOR_SIMPLE_PATH_TRACING_RECURSION) ? 0 : S->n_lights;
     if constexpr (ky_direct_is_single(STRATEGY) || STRATEGY < 0)   // one light's estimate per vertex, however many lights the scene has
@@ -283,7 +287,8 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderCon
                 const int xy = c_xy[tid];
                 const unsigned se = c_se[tid];
                 const uint32_t key = QUEUE ? sampler_pixel_key(rc.seed, (uint32_t)((xy >> 16) * rc.width + (xy & 0xffff))) : c_key[tid];
-                if constexpr (CAM == KY_CAM_LENS) path_begin<SAMPLER, true, KY_CAM_LENS>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
+                if constexpr (CAM == KY_CAM_ANY) path_begin<SAMPLER, true, KY_CAM_ANY>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
+                else if constexpr (CAM == KY_CAM_LENS) path_begin<SAMPLER, true, KY_CAM_LENS>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
                 else if constexpr (FILTER) path_begin<SAMPLER, true, KY_CAM_FILTER>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7), fc);
                 else path_begin<SAMPLER, true>(ps, S, key, xy & 0xffff, xy >> 16, (int)(se >> 7));
                 c_se[tid] = se + 127;             // next sample + 1, samples left - 1
@@ -317,8 +322,8 @@ KY_DEV void render_kernel_body(const DScene* __restrict__ S_, typename RenderCon
         if (QUEUE) tag = ((unsigned)c_pix[tid] << 6) | (unsigned)lane;
         // ---- (3) shade the vertex: direct lighting, continuation ----
         {
-            const bool cont = path_shade<SAMPLER, DROP>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, QUEUE ? &sq : nullptr, tag,
-                                                              STRATEGY >= 0 && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_RECURSION, true, drop_rt);  // wave-uniform call
+            const bool cont = path_shade<SAMPLER, DROP, TEX>(ps, v, S, Lds, rc, have_vertex, -1, nullptr, QUEUE ? &sq : nullptr, tag,
+                                                              STRATEGY >= 0 && INTEGRATOR == KY_INTEGRATOR_PATH_TRACING_RECURSION, true, drop_rt, TEX ? &tex_lds : nullptr);  // wave-uniform call
             if (have_vertex && !cont) {
                 alive = false;
             }
@@ -381,4 +386,15 @@ __global__ __launch_bounds__(256, (ky_waves_per_eu<SAMPLER, -1, false, GENERAL, 
     float4* __restrict__ queue_mem) {
     static_assert(SAMPLER == KY_SMP_RANDOM || SAMPLER == KY_SMP_STRATIFIED, "the debug sampler ignores the lens: its launches run the pinhole kernels");
     render_kernel_body<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED, KY_CAM_LENS>(S_, rc, sh, counter, accum, flags, queue_mem, lens_cam(rc));
+}
+
+// The textured instantiations (a texture set: kyhip_render_textured, kyhip_frame_set_textures), shaped like the lens ones: their launch
+// constants (RenderConstT) carry the set beside the lens and the pixel filter.  ONE camera form, KY_CAM_ANY, serves plain, filtered and lens launches: the box and
+// the pinhole are wave-uniform skips.
+template <int SAMPLER, bool GENERAL = false, bool LARGE = false, bool LISTED = false>
+__global__ __launch_bounds__(256, (ky_waves_per_eu<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED>())) void render_kernel_textured(
+    const DScene* __restrict__ S_, RenderConstT rc, ShardConst sh, unsigned* __restrict__ counter, unsigned long long* __restrict__ accum, unsigned* __restrict__ flags,
+    float4* __restrict__ queue_mem) {
+    static_assert(SAMPLER == KY_SMP_RANDOM || SAMPLER == KY_SMP_STRATIFIED, "no textured row for the debug sampler");
+    render_kernel_body<SAMPLER, -1, false, GENERAL, 0, KY_INTEGRATOR_PATH_TRACING_ITERATION, LARGE, 0, LISTED, KY_CAM_ANY, true>(S_, rc, sh, counter, accum, flags, queue_mem, lens_cam(rc), rc.tex);
 }

@@ -347,4 +347,50 @@ KY_HD inline LensCam lens_cam(const RenderConstL& rc) {
     return c;
 }
 
+// ---- textures (ky_texture): a device block of its own beside the scene, which stays what it is ----
+// One texture as the kernels read it, 32 B, gathered per lane from LDS (the material, and with it the texture, differs from lane to lane).  The colours live with
+// the texels: a checker is the 2 x 1 image {a, b}, so a checker and a nearest look-up are ONE body that differs in how it finds its index.
+struct DTex {
+    int32_t kind_flags;        // ky_texture_kind | ky_texture_flags << 8
+    int32_t first;             // its first texel in the set's float4 array
+    int32_t w, h;              // image: the texel counts; checker: 2, 1
+    float scale[2], offset[2];
+};
+static_assert(sizeof(DTex) == 32, "DTex");
+// What turns a hit point p of one surface into (u, v), 64 B, read per lane from global memory with the (sorted) surface index.  With d = p - o,
+// a = d . e1 and b = d . e2:
+//   planar (kind 0)  u = k2 b + k0 a + add, v = k2 a + k1 b + add
+//                    rectangle: o = p0, e1 = p1 - p0, e2 = p3 - p0, k0 = 1 / |e1|^2, k1 = 1 / |e2|^2, k2 = 0, add = 0
+//                    triangle:  o = p0, e1 = p1 - p0, e2 = p2 - p0, (k0 k2; k2 k1) the inverse of the edges' Gram matrix, add = 0
+//                    disk:      o = centre, e1 = s, e2 = t of frame_t(normal) (DHit::fs / ft), k0 = k1 = 1 / 2r, k2 = 0, add = 0.5
+//   sphere (kind 1)  o = centre, k0 = 1 / r: n = d k0, u = 0.5 + atan2(n.z, n.x) / 2 pi, v = acos(clamp(n.y, -1, 1)) / pi
+struct DTexUV {
+    float o[3];
+    int32_t kind;
+    float e1[3], k0;
+    float e2[3], k1;
+    float k2, add, pad_u[2];
+};
+static_assert(sizeof(DTexUV) == 64, "DTexUV");
+struct DTexSet {
+    DTex tex[KYHIP_MAX_TEXTURES];
+    int32_t material[KYHIP_MAX_TEXTURES];   // the material each texture colours (in range: texture_check)
+    int32_t n_tex, pad_s[3];
+    DTexUV uv[KYHIP_MAX_SURFACES];          // by the device's sorted surface index
+};
+static_assert(sizeof(DTexSet) % 16 == 0 && __builtin_offsetof(DTexSet, uv) % 16 == 0, "DTexSet");
+// ... as a launch carries it: the block and the set's texels, one float4 (r, g, b, 0) each -- one 16-byte load per texel.  A texture on a plastic material holds
+// texel / diffuse_probability, the Lambert lobe's albedo as DMat::c0 holds it (pack_material's division, made once per texel by the host).
+struct TexConst {
+    const DTexSet* set;
+    const float4* texels;
+};
+struct RenderConstT : RenderConstL {
+    TexConst tex;
+};
+// the camera-sample mode of the textured kernels: the filter's warp unless the filter is the box, the lens unless it is the pinhole (LensConst::wf == 0), both
+// wave-uniform skips -- one form for plain, filtered and lens launches
+enum : int { KY_CAM_ANY = 3 };
+template <> struct CamConstFor<KY_CAM_ANY> { typedef LensCam type; };
+
 }  // namespace kyd

@@ -373,10 +373,65 @@ private:
 // ---------------------------------------------------------------------------------------------
 // materials (ky.cpp:2568-2682)
 // ---------------------------------------------------------------------------------------------
+// Textures (the reference's empty `#pragma region texture` / `// TODO class texture_t`, ky.cpp:2559-2564; include/kyhip.h ky_texture): a colour as a
+// function of a hit point's surface coordinates.  A matte, mirror or plastic material built from a texture takes the texture's value where it took its diffuse /
+// specular / diffuse colour; scene_t::flatten_textures collects the set the C entries take, and every render entry of integrator_t hands it on.
+class texture_t {
+public:
+    virtual ~texture_t() = default;
+    // the constant that stands in the material's struct (ky_material::color0): what a plastic material's lobe probabilities are made of, and what a renderer
+    // without textures would show
+    virtual color_t base_color() const = 0;
+    // the ky_texture of this texture on ky_scene material `material`; false: a constant, which is the material's own colour and needs none
+    virtual bool flatten(int material, ky_texture* out) const = 0;
+};
+using texture_sptr_t = std::shared_ptr<texture_t>;
+class constant_texture_t : public texture_t {
+public:
+    explicit constant_texture_t(color_t color) : color_(color) {}
+    color_t base_color() const override { return color_; }
+    bool flatten(int, ky_texture*) const override { return false; }
+private:
+    color_t color_;
+};
+class checker_texture_t : public texture_t {   // a where floor(u') + floor(v') is even, b where it is odd; (u', v') = scale (u, v) + offset
+public:
+    checker_texture_t(color_t a, color_t b, vec2_t scale = {1, 1}, vec2_t offset = {0, 0}) : a_(a), b_(b), scale_(scale), offset_(offset) {}
+    color_t base_color() const override { return a_; }
+    bool flatten(int material, ky_texture* out) const override {
+        ky_texture t{}; t.kind = KY_TEXTURE_CHECKER; t.material = material;
+        t.scale[0] = scale_.x; t.scale[1] = scale_.y; t.offset[0] = offset_.x; t.offset[1] = offset_.y;
+        store3(t.a, a_); store3(t.b, b_);
+        *out = t;
+        return true;
+    }
+private:
+    color_t a_, b_; vec2_t scale_, offset_;
+};
+class image_texture_t : public texture_t {   // height rows of width RGB triples, row 0 at v' = 0; nearest or bilinear, repeating or clamped
+public:
+    image_texture_t(int width, int height, std::vector<float> texels, bool bilinear = false, bool clamp = false, vec2_t scale = {1, 1}, vec2_t offset = {0, 0})
+        : width_(width), height_(height), texels_(std::move(texels)), bilinear_(bilinear), clamp_(clamp), scale_(scale), offset_(offset) {
+        if (width < 1 || height < 1 || texels_.size() != (size_t)width * (size_t)height * 3) throw std::runtime_error("image_texture_t: width x height RGB triples");
+    }
+    color_t base_color() const override { return {texels_[0], texels_[1], texels_[2]}; }
+    bool flatten(int material, ky_texture* out) const override {
+        ky_texture t{}; t.kind = KY_TEXTURE_IMAGE; t.material = material;
+        t.flags = (bilinear_ ? KY_TEXTURE_BILINEAR : 0) | (clamp_ ? KY_TEXTURE_CLAMP : 0);
+        t.scale[0] = scale_.x; t.scale[1] = scale_.y; t.offset[0] = offset_.x; t.offset[1] = offset_.y;
+        t.width = width_; t.height = height_; t.texels = texels_.data();   // (valid while this texture lives)
+        *out = t;
+        return true;
+    }
+private:
+    int width_, height_; std::vector<float> texels_; bool bilinear_, clamp_; vec2_t scale_, offset_;
+};
+
 class material_t {
 public:
     virtual ~material_t() = default;
     virtual ky_material flatten() const = 0;
+    virtual const texture_t* texture() const { return nullptr; }   // the texture a material was built from, if any
 };
 using material_sptr_t = std::shared_ptr<material_t>;
 using material_list_t = std::vector<material_sptr_t>;
@@ -384,16 +439,22 @@ using material_list_t = std::vector<material_sptr_t>;
 class matte_material_t : public material_t {
 public:
     explicit matte_material_t(color_t diffuse_color) : diffuse_color_(diffuse_color) {}
+    explicit matte_material_t(texture_sptr_t diffuse) : diffuse_color_(diffuse->base_color()), texture_(std::move(diffuse)) {}
     ky_material flatten() const override { ky_material m{}; m.kind = KY_MATERIAL_MATTE; store3(m.color0, diffuse_color_); return m; }
+    const texture_t* texture() const override { return texture_.get(); }
 private:
     color_t diffuse_color_;
+    texture_sptr_t texture_;
 };
 class mirror_material_t : public material_t {
 public:
     explicit mirror_material_t(color_t specular_color) : specular_color_(specular_color) {}
+    explicit mirror_material_t(texture_sptr_t specular) : specular_color_(specular->base_color()), texture_(std::move(specular)) {}
     ky_material flatten() const override { ky_material m{}; m.kind = KY_MATERIAL_MIRROR; store3(m.color0, specular_color_); return m; }
+    const texture_t* texture() const override { return texture_.get(); }
 private:
     color_t specular_color_;
+    texture_sptr_t texture_;
 };
 class glass_material_t : public material_t {
 public:
@@ -414,6 +475,11 @@ public:
         diffuse_probility_  = diffuse / luminance;
         specular_probility_ = specular / luminance;
     }
+    // the diffuse colour from a texture: the lobe probabilities are those of its base colour and stay what they are at every hit
+    plastic_material_t(texture_sptr_t diffuse, color_t specular_color, float shininess) : plastic_material_t(diffuse->base_color(), specular_color, shininess) {
+        texture_ = std::move(diffuse);
+    }
+    const texture_t* texture() const override { return texture_.get(); }
     ky_material flatten() const override {
         ky_material m{}; m.kind = KY_MATERIAL_PLASTIC; store3(m.color0, diffuse_color_); store3(m.color1, specular_color_);
         m.exponent = exponent_; m.diffuse_probability = diffuse_probility_; m.specular_probability = specular_probility_;
@@ -421,6 +487,7 @@ public:
     }
 private:
     color_t diffuse_color_, specular_color_; float exponent_, diffuse_probility_{}, specular_probility_{};
+    texture_sptr_t texture_;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -562,6 +629,25 @@ public:
         return flat_;
     }
 
+    // The texture set of the scene's materials for the C ABI (kyhip_render_textured, kyhip_frame_set_textures): one ky_texture per material that was built from a
+    // checker or an image, in material order, naming the material by its index in flatten()'s list.  Pointers inside stay valid while this scene_t lives.
+    const std::vector<ky_texture>& flatten_textures() const {
+        flat_textures_.clear();
+        for (size_t i = 0; i < material_list_.size(); ++i) {
+            ky_texture t;
+            if (const texture_t* tex = material_list_[i]->texture()) if (tex->flatten((int)i, &t)) flat_textures_.push_back(t);
+        }
+        return flat_textures_;
+    }
+    // material `index` of the list replaced (e.g. by a textured one); the surfaces that carried the old one carry the new one
+    void replace_material(int index, material_sptr_t material) {
+        if (index < 0 || index >= (int)material_list_.size() || !material) throw std::runtime_error("ky::scene_t::replace_material: no such material");
+        for (surface_t& s : surface_list_) if (s.material == material_list_[(size_t)index].get()) s.material = material.get();
+        material_list_[(size_t)index] = std::move(material);
+    }
+    int material_count() const { return (int)material_list_.size(); }
+    const material_t* material(int index) const { return material_list_.at((size_t)index).get(); }
+
     static scene_t create_cornell_box_scene(cornell_box_enum_t scene_enum, point2_t film_resolution);  // 3240-3432
     static scene_t create_mis_scene(point2_t film_resolution);                                         // 3434-3533
 
@@ -576,6 +662,7 @@ private:
     mutable std::vector<ky_material> flat_materials_;
     mutable std::vector<ky_light> flat_lights_;
     mutable std::vector<ky_surface> flat_surfaces_;
+    mutable std::vector<ky_texture> flat_textures_;
     mutable ky_scene flat_{};
 };
 
@@ -758,6 +845,14 @@ public:
         const ky_render_params p = params_for(original_sampler, film);
         const ky_pixel_filter flt = film->pixel_filter();
         const ky_lens lens = scene->get_camera()->lens();
+        const std::vector<ky_texture>& textures = scene->flatten_textures();
+        if (!textures.empty()) {   // textured materials (texture_t): kyhip_render_textured under the film's filter and the camera's lens, on ONE device like a lens render
+            if (masked()) throw std::runtime_error("integrator_t::render: light classes are rendered without textures only");
+            if (devices_.size() != 1) throw std::runtime_error("integrator_t::render: a scene with textures renders on one device (render_sliced spreads such a frame over several)");
+            const int rc = kyhip_render_textured(devices_[0], &scene->flatten(), textures.data(), (int)textures.size(), &p, &flt, &lens, film->target_origin(), film->row_stride_px());
+            if (rc != KY_OK) throw std::runtime_error(std::string("kyhip_render_textured: ") + kyhip_last_error());
+            return;
+        }
         if (lens.radius > 0.f) {   // the camera's lens (camera_t::set_lens): kyhip_render_lens under the film's filter, on ONE device like a filtered render
             if (masked()) throw std::runtime_error("integrator_t::render: light classes are rendered through the pinhole only");
             if (devices_.size() != 1) throw std::runtime_error("integrator_t::render: a camera with a lens renders on one device (render_sliced spreads such a frame over several)");
@@ -790,6 +885,10 @@ public:
         std::string what;
         if (flt.kind != KY_FILTER_BOX && kyhip_frame_set_filter(frame, &flt) != KY_OK) what = std::string("kyhip_frame_set_filter: ") + kyhip_last_error();
         else if (lens.radius > 0.f && kyhip_frame_set_lens(frame, &lens) != KY_OK) what = std::string("kyhip_frame_set_lens: ") + kyhip_last_error();
+        else if (scene) {   // ... and the texture set of the scene's materials (none: nothing to do)
+            const std::vector<ky_texture>& textures = scene->flatten_textures();
+            if (!textures.empty() && kyhip_frame_set_textures(frame, textures.data(), (int)textures.size()) != KY_OK) what = std::string("kyhip_frame_set_textures: ") + kyhip_last_error();
+        }
         if (what.empty()) return;
         if (own) kyhip_frame_end(frame);
         throw std::runtime_error(what);

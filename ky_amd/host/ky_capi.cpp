@@ -54,6 +54,46 @@ const ky_scene* kyhost_scene_flatten(void* scene) {
     return flat;
 }
 
+// Material `material` of the scene rebuilt from a texture (ky.hpp: the texture_sptr_t overloads of matte_material_t, mirror_material_t and plastic_material_t): the
+// material keeps its kind and, for plastic, its specular colour and exponent; glass takes no texture.  Every render entry below then renders the scene textured.
+static void retexture(ky::scene_t& scene, int material, ky::texture_sptr_t texture) {
+    if (material < 0 || material >= scene.material_count()) throw std::runtime_error("texture: material index out of range");
+    const ky_material m = scene.material(material)->flatten();
+    ky::material_sptr_t made;
+    if (m.kind == KY_MATERIAL_MATTE) made = std::make_shared<ky::matte_material_t>(texture);
+    else if (m.kind == KY_MATERIAL_MIRROR) made = std::make_shared<ky::mirror_material_t>(texture);
+    else if (m.kind == KY_MATERIAL_PLASTIC) made = std::make_shared<ky::plastic_material_t>(texture, ky::color_t{m.color1[0], m.color1[1], m.color1[2]}, m.exponent);
+    else throw std::runtime_error("texture: a glass material takes no texture");
+    scene.replace_material(material, made);
+}
+// checker_texture_t(a, b, scale, offset) on material `material`
+int kyhost_scene_texture_checker(void* scene, int material, const float* a3, const float* b3, const float* scale2, const float* offset2) {
+    return guarded([&] {
+        retexture(((scene_box*)scene)->scene, material, std::make_shared<ky::checker_texture_t>(ky::color_t{a3[0], a3[1], a3[2]}, ky::color_t{b3[0], b3[1], b3[2]},
+                                                                                                 ky::vec2_t{scale2[0], scale2[1]}, ky::vec2_t{offset2[0], offset2[1]}));
+    });
+}
+// image_texture_t(width, height, texels, bilinear, clamp, scale, offset) on material `material`; the texels are copied
+int kyhost_scene_texture_image(void* scene, int material, int width, int height, const float* texels, int bilinear, int clamp, const float* scale2, const float* offset2) {
+    return guarded([&] {
+        if (width < 1 || height < 1 || !texels) throw std::runtime_error("texture: an image of width x height RGB triples");
+        std::vector<float> copy(texels, texels + (size_t)width * (size_t)height * 3);
+        retexture(((scene_box*)scene)->scene, material, std::make_shared<ky::image_texture_t>(width, height, std::move(copy), bilinear != 0, clamp != 0,
+                                                                                               ky::vec2_t{scale2[0], scale2[1]}, ky::vec2_t{offset2[0], offset2[1]}));
+    });
+}
+// scene_t::flatten_textures(): writes min(count, max) ky_texture to `out` (may be NULL with max 0) and returns the count, or -1 on error.  Pointers inside are valid
+// until the scene is destroyed or retextured.
+int kyhost_scene_textures(void* scene, ky_texture* out, int max) {
+    int n = -1;
+    guarded([&] {
+        const std::vector<ky_texture>& set = ((scene_box*)scene)->scene.flatten_textures();
+        for (int i = 0; i < (int)set.size() && i < max; ++i) out[i] = set[(size_t)i];
+        n = (int)set.size();
+    });
+    return n;
+}
+
 // the sampler_t of a ky_sampler_kind (every other value: the random sampler, as before the stratified one existed)
 static std::unique_ptr<ky::sampler_t> make_sampler(int kind, int spp, unsigned seed) {
     std::unique_ptr<ky::sampler_t> sampler;
