@@ -302,3 +302,154 @@ def test_the_host_mirrors_flattening_yields_the_set_the_c_call_takes(A, api):
     d, s = lum(after.color0), lum(after.color1)
     assert abs(after.diffuse_probability - d / (d + s)) < 1e-6 and abs(after.diffuse_probability + after.specular_probability - 1) < 1e-6
     assert [sf.material for sf in (scene.c.surfaces[i] for i in range(scene.c.surface_count))].count(plastic) >= 1   # the surfaces carry the new material
+
+
+# ---- tiled() refuses what it would cut wrongly ----
+
+def test_tiled_refuses_a_parallelogram_whose_edges_are_not_orthogonal(A, api):
+    """tex_uv's rectangle body is u = d . e1 / |e1|^2; on a sheared parallelogram that is not the coordinate tiled() cuts along, so it refuses one"""
+    from helpers import make_material, make_shape
+    box = api.cornell_box_scene(A.CB_DEFAULT_SCENE, 16, 16)
+    for shear, refused in ((0.0, False), (1e-3, True), (0.3, True)):
+        scene, _ = X.copy_scene(A, box.c)
+        shapes, mats, lights, surfaces = scene._keep
+        shapes.append(make_shape(A, A.SHAPE_RECTANGLE, [(-0.5, 0.0, -0.5), (0.5, 0.0, -0.5), (0.5 + shear, 0.0, 0.5), (-0.5 + shear, 0.0, 0.5)]))
+        mats.append(make_material(A, A.MATERIAL_MATTE, (0.5, 0.5, 0.5)))
+        surfaces.append(A.Surface(len(shapes) - 1, len(mats) - 1, -1))
+        from helpers import CustomScene
+        scene = CustomScene(A, A.Camera.from_buffer_copy(box.c.camera), shapes, mats, lights, surfaces)
+        tex = [X.Tex(X.CHECKER, len(mats) - 1, scale=(2, 2), a=(1, 1, 1), b=(0, 0, 0))]
+        if refused:
+            with pytest.raises(AssertionError, match="orthogonal"):
+                X.tiled(A, scene.scene, tex)
+        else:
+            assert X.tiled(A, scene.scene, tex).scene.surface_count == scene.scene.surface_count + 3
+    for case in (X.cornell_case, X.veach_case):   # every shipped case is still cut
+        scene, textures = case(A, api, 16, 16)
+        assert X.tiled(A, scene.scene, textures).scene.surface_count > scene.scene.surface_count
+
+
+# ---- the texel layout: three more named defects ----
+
+def layout_set():
+    """a checker, the 3 x 5 image and a 5 x 3 image behind it: the image's first texel is 2, and every defective index stays inside the array"""
+    return [X.Tex(X.CHECKER, 0, a=(1, 1, 1), b=(0, 0, 0)), X.Tex(X.IMAGE, 1, texels=X.texels_of(0, 3, 5)), X.Tex(X.IMAGE, 2, texels=X.texels_of(1, 5, 3))]
+
+
+def test_defects_of_the_texel_layout():
+    """the check: at the centre of texel (x, y) of the 3 x 5 image -- image 0 -- a nearest look-up reads ((x + 1) / 8, (y + 1) / 8, 1 / 16)"""
+    textures = layout_set()
+    flat, first = X.pack(textures)
+    assert first == [0, 2, 17] and len(flat) == 32
+    y, x = np.meshgrid(np.arange(5), np.arange(3), indexing="ij")
+    us, vs = ((x.ravel() + 0.5) / 3).astype(f32), ((y.ravel() + 0.5) / 5).astype(f32)
+    want = np.stack([(x.ravel() + 1) / 8, (y.ravel() + 1) / 8, np.full(15, 1 / 16)], axis=1).astype(f32)
+
+    def check(**kw):
+        return np.array_equal(X.nearest_packed(textures, 1, us, vs, f32, **kw), want)
+    assert check() and np.array_equal(X.nearest(textures[1], us, vs), want)
+    for defect in ("transposed", "stride_h", "no_first"):
+        assert not check(defect=defect), defect
+    gen = np.random.default_rng(5)   # the packed look-up is the structured one
+    us, vs = (gen.random(2048) * 6 - 3).astype(f32), (gen.random(2048) * 6 - 3).astype(f32)
+    for i in (1, 2):
+        assert np.array_equal(X.nearest_packed(textures, i, us, vs), X.nearest(textures[i], us, vs))
+
+
+# What the float32 restatement must read at X.edge_cases()'s points, written by hand: texel (ix, iy) of a nearest look-up, 0 / 1 = colour a / b of a checker.
+EDGE_PINS = {
+    "on k / W": [(0, 0), (1, 0), (2, 0), (3, 0), (0, 0), (2, 1), (1, 0), (0, 0), (0, 0), (0, 0), (0, 0)],   # u' = 1 wraps to 0; so does every corner
+    "-2^-30": [(3, 0), (1, 0), (2, 1)],            # -2^-30 - floor = 1.0f: index 4, capped at 3; 0.25 - 2^-30 is 0.25f (the float64 path reads texel 0 there)
+    "beyond 1000": [(0, 0), (0, 0), (1, 0), (2, 0), (1, 1)],   # -2048, 2048, 0.25, -2047.5 (fraction 0.5), 2047.25
+    "clamped": [(0, 1), (3, 0), (2, 1), (3, 0), (0, 1), (3, 1), (3, 0), (0, 0)],   # u' = 3 u - 1, v' = 1.5 - 2 v, both clamped to [0, 1 - 2^-24]
+    "on k / 5": [(1, 1), (2, 2), (3, 1), (4, 0), (0, 1)],   # float(k / 5) 5 rounds to k; the float below 1 / 3 times 3 is 1 - 2^-24
+    "checker on integers": [0, 1, 0, 1, 0, 0, 0, 0, 0, 0],
+    "checker beyond 1000": [0, 0, 1, 0, 1],        # floor(-2047.5) = -2048
+    "checker -2^-30": [1, 0, 0],                   # floor(-2^-30) = -1
+}
+
+
+def test_the_float32_restatement_at_edge_coordinates_reads_the_pinned_texels():
+    rect = X.Shape(X.RECTANGLE, X.EDGE_RECT, (0, -1, 0))
+    cases = X.edge_cases()
+    assert set(cases) == set(EDGE_PINS)
+    for name, (tex, uvs) in cases.items():
+        pts = X.edge_points(uvs)
+        u, v = X.uv(rect, pts, f32)
+        assert np.array_equal(u, np.asarray(uvs, f32)[:, 0]) and np.array_equal(v, np.asarray(uvs, f32)[:, 1]), name   # (u, v) of these points is exact
+        got = X.probe(rect, tex, pts, f32)
+        assert np.abs(got[:, :2]).max() < 2.0 ** 24
+        if tex.kind == X.CHECKER:
+            want = np.where(np.array(EDGE_PINS[name])[:, None] == 0, tex.a[None, :], tex.b[None, :])
+        else:
+            want = np.array([tex.texels[iy, ix] for ix, iy in EDGE_PINS[name]])
+        assert np.array_equal(got[:, 2:], want.astype(f32)), (name, got[:, 2:], want)
+    # the float64 path does sit on the other side of an edge at one of them, which is why the device is held to the float32 path there
+    tex, uvs = cases["-2^-30"]
+    assert not np.array_equal(X.probe(rect, tex, X.edge_points(uvs), f64)[:, 2:].astype(f32), X.probe(rect, tex, X.edge_points(uvs), f32)[:, 2:])
+
+
+# ---- the scene that textures every shape kind: properties of the inputs, and that the expected samples notice wrong plumbing ----
+
+_expected_cache = {}
+
+
+def shapes_expected(O, A, api, which, n_spp, sampler, with_k=True):
+    """(scene, textures, names, params, X.expected_samples(...)) of X.shapes_case / _shipped / _large at 32 x 32, computed once per case and shared"""
+    key = (which, n_spp, sampler, with_k)
+    if key not in _expected_cache:
+        case = {"general": X.shapes_case, "shipped": X.shapes_case_shipped, "large": X.shapes_case_large}[which]
+        scene, textures, names = case(A, api, 32, 32)
+        kind = F.SAMPLER_STRATIFIED if sampler == "stratified" else F.SAMPLER_RANDOM
+        params = api.make_params(32, 32, n_spp, integrator=A.INTEGRATOR_BASECOLOR, sampler=kind)
+        _expected_cache[key] = (scene, textures, names, params, X.expected_samples(O, A, scene, textures, params, with_k=with_k))
+    return _expected_cache[key]
+
+
+@pytest.mark.parametrize("sampler", ("random", "stratified"))
+@pytest.mark.parametrize("n_spp", (5, 16))
+@pytest.mark.parametrize("which", ("general", "shipped", "large"))
+def test_the_shapes_cases_inputs(O, A, api, which, n_spp, sampler):
+    """At most 2 % of the samples that land on textured surfaces lie within 1e-4 of a cell or texel edge or on a sphere's seam; every textured surface is seen;
+    the set is one the library accepts."""
+    scene, textures, names, params, E = shapes_expected(O, A, api, which, n_spp, sampler, with_k=False)
+    api.texture_check(scene, [t.to_api(api) for t in textures])
+    on = E.textured
+    print("%s N = %d, %s: %d of %d samples on textured surfaces, %d of them unclean (allowed %.1f)" % (which, n_spp, sampler, on.sum(), on.size, (on & ~E.clean).sum(), 0.02 * on.sum()))
+    assert on.sum() >= (0.02 if which == "large" else 0.25) * on.size   # (the large scene's balls are small)
+    assert (on & ~E.clean).sum() <= 0.02 * on.sum()
+    seen = [s for s in (names["balls"] if which == "large" else names.values()) if (E.surface == s).sum() >= (1 if which == "large" else 5)]
+    if which == "large":
+        assert len(seen) >= 16, len(seen)   # (of 33 records behind the one texture)
+    else:
+        assert len(seen) == len(names), (seen, names)
+
+
+def test_the_first_hit_is_the_first_row_of_the_oracles_trace(O, A, api):
+    """expected_samples takes the first hit from kyo_kat_camera and kyo_kat_scene_intersect on the tape's camera sample; under the random sampler, whose generator
+    the oracle has, that is the first row of kyo_trace_li -- surface and position, bit for bit, every sample"""
+    scene, textures, names, params, E = shapes_expected(O, A, api, "general", 5, "random", with_k=False)
+    pt = api.make_params(32, 32, 5)
+    surface, position = E.surface.reshape(32, 32, 5), E.position.reshape(32, 32, 5, 3)
+    for y in range(32):
+        for x in range(32):
+            for s in range(5):
+                rows = O.trace_li(scene, pt, x, y, s, max_rows=2)
+                if surface[y, x, s] < 0:
+                    assert len(rows) == 0
+                else:
+                    assert int(rows[0, 1]) == surface[y, x, s] and np.array_equal(rows[0, 3:6], position[y, x, s]), (x, y, s)
+
+
+@pytest.mark.parametrize("sampler", ("random", "stratified"))
+def test_the_expected_samples_move_when_the_plumbing_is_wrong(O, A, api, sampler):
+    """Recomputed with the uv records rotated among the textured surfaces (a record read at the sorted index where the caller's was meant) and with the shared
+    material's second surface -- the second ball -- given the triangle's record: each changes at least 25 % of the samples on the surfaces whose record moved."""
+    scene, textures, names, params, E = shapes_expected(O, A, api, "general", 16, sampler, with_k=False)
+    order = [names[n] for n in ("tri", "disk", "ball2", "quad", "wall", "ball")]
+    for what, record_of in (("rotated", {s: order[(i + 1) % len(order)] for i, s in enumerate(order)}), ("shared", {names["ball2"]: names["tri"]})):
+        wrong = X.expected_samples(O, A, scene, textures, params, with_k=False, record_of=record_of)
+        rows = np.isin(E.surface, list(record_of))
+        moved = (np.abs(wrong.expected[rows] - E.expected[rows]).max(axis=1) > 1e-3).sum()
+        print("%s, %s: %d of %d samples move" % (sampler, what, moved, rows.sum()))
+        assert rows.sum() >= 100 and moved >= 0.25 * rows.sum()

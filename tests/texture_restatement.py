@@ -274,6 +274,8 @@ def tiled(A, c, textures, subdivide=1):
         P = sh.p.astype(f64)
         e1, e3 = P[1] - P[0], P[3] - P[0]
         assert np.abs(P[0] + e1 + e3 - P[2]).max() < 1e-6, "only parallelograms are cut"
+        # tex_uv's u is d . e1 / |e1|^2: on a sheared parallelogram that is not the coordinate the cuts below run along
+        assert abs(e1 @ e3) <= 1e-6 * np.sqrt((e1 @ e1) * (e3 @ e3)), "only parallelograms whose edges are orthogonal are cut"
         us, vs = [0.0] + cuts(tex, 0, subdivide) + [1.0], [0.0] + cuts(tex, 1, subdivide) + [1.0]
         for b in range(len(vs) - 1):
             for a in range(len(us) - 1):
@@ -295,3 +297,217 @@ def tiled(A, c, textures, subdivide=1):
                 shapes.append(s)
                 surfaces.append(A.Surface(len(shapes) - 1, colour_material[key], sf.area_light))
     return CustomScene(A, A.Camera.from_buffer_copy(c.camera), shapes, materials, lights, surfaces, c.environment_light)
+
+
+# ---- the texel layout of a set (texture_pack), and the defects it can have ----
+
+def texels_of(k, w, h):
+    """Image k, [h, w, 3]: texel (x, y) is ((x + 1) / 8, (y + 1) / 8, (k + 1) / 16), exact in float32 -- a nearest look-up's colour names the texel it read"""
+    x, y = np.meshgrid(np.arange(w), np.arange(h))
+    return np.stack([(x + 1) / 8.0, (y + 1) / 8.0, np.full((h, w), (k + 1) / 16.0)], axis=2).astype(f32)
+
+
+def pack(textures):
+    """texture_pack's texel array restated: every texture's texels one behind the other in set order, an image row by row from row 0, a checker as the 2 x 1
+    image {a, b} -> (flat [n, 3] float32, [first texel of each texture])"""
+    flat, first = [], []
+    for t in textures:
+        first.append(sum(len(f) for f in flat))
+        flat.append(np.stack([t.a, t.b]) if t.kind == CHECKER else t.texels.reshape(-1, 3))
+    return np.concatenate(flat).astype(f32), first
+
+
+def nearest_packed(textures, i, us, vs, dtype=f32, defect=None):
+    """nearest() of image i of a set through the packed array: texel first + iy W + ix.  The named defects: "transposed" reads first + ix H + iy, "stride_h"
+    first + iy H + ix, "no_first" iy W + ix."""
+    tex = textures[i]
+    flat, first = pack(textures)
+    H, W = tex.texels.shape[:2]
+    ix = np.minimum(mul(wrap(tex, us, dtype), dtype(W), dtype).astype(np.int64), W - 1)
+    iy = np.minimum(mul(wrap(tex, vs, dtype), dtype(H), dtype).astype(np.int64), H - 1)
+    idx = {None: first[i] + iy * W + ix, "transposed": first[i] + ix * H + iy, "stride_h": first[i] + iy * H + ix, "no_first": iy * W + ix}[defect]
+    return flat[idx]
+
+
+# ---- a scene that textures every shape kind ----
+
+SKEW = [(0.0, 0.0, 0.0), (3.0, 0.0, 0.0), (4.0, 2.5, 0.0), (-0.5, 2.0, 0.0)]   # the probe's quad that is no parallelogram
+
+
+def interleaved(A, base, new_shapes, new_materials, new_surfaces, at):
+    """The ky_scene `base` with shapes and materials appended and new_surfaces[k] = (shape offset, material) put at place at[k] of the caller's surface list"""
+    scene, _ = copy_scene(A, base)
+    shapes, mats, lights, surfaces = scene._keep
+    n_shapes = len(shapes)
+    shapes += list(new_shapes)
+    mats += list(new_materials)
+    for (sh, m), where in sorted(zip(new_surfaces, at), key=lambda e: e[1]):
+        surfaces.insert(where, A.Surface(n_shapes + sh, m, -1))
+    return CustomScene(A, A.Camera.from_buffer_copy(base.camera), shapes, mats, lights, surfaces, base.environment_light)
+
+
+def _matte(A, c):
+    from helpers import make_material
+    return make_material(A, A.MATERIAL_MATTE, c)
+
+
+def shapes_case(A, api, w, h, shipped=False):
+    """The Cornell box with a texture on every shape kind -> (scene, [Tex], {name: caller's surface index}).  Added: a free triangle, a tilted disk, the probe's
+    skew quad (a quarter its size, facing the camera) and a second ball that SHARES the triangle's material; the small mirror ball turns matte.  The caller's list
+    interleaves the kinds -- rectangle, triangle, rectangle, disk, rectangle, sphere, rectangle, quad, rectangle, sphere ... -- so a sort by kind permutes it.
+    Textures, all on matte materials: a 3 x 5 nearest image on the back wall (a face of the room's box), a 7 x 2 nearest clamped image with negative scale[1] on the
+    ball, one checker with non-integer scale and an offset on the triangle's material (triangle and second ball), a 5 x 3 bilinear repeating image on the disk, a
+    second checker on the quad.  The bilinear image sits on a planar shape on purpose: its colour is continuous in the hit point, the expected colour is taken at the
+    ORACLE's hit point, and a sphere's hit distance -b - sqrt(b^2 - c) cancels (b^2 is about 17 here), so the two sides' float32 hit points on a ball lie several 1e-6
+    apart whichever is nearer the truth -- more than the bilinear tolerance; a planar hit distance is one quotient.  (Bilinear look-ups on a sphere are held to the
+    restatement at GIVEN points by the probe tests.)  shipped: without triangle, disk and quad, so that the launch keeps the row of the shipped shapes -- whose
+    surfaces are balls and faces of boxes, so this set has no bilinear image; the second ball keeps its checker and the second checker goes to the wall x = -1.27."""
+    from helpers import make_shape
+    handle = api.cornell_box_scene(A.CB_DEFAULT_SCENE, w, h)
+    base = handle.c
+    assert base.surface_count == 12 and base.shapes[base.surfaces[5].shape].kind == SPHERE and base.materials[base.surfaces[5].material].kind == A.MATERIAL_MIRROR
+    m0 = base.material_count
+    mats = [_matte(A, (0.2, 0.3, 0.7)), _matte(A, (0.7, 0.6, 0.5)), _matte(A, (0.6, 0.7, 0.3)), _matte(A, (0.5, 0.5, 0.6)), _matte(A, (0.7, 0.4, 0.4))]
+    wall_m, ball_m, tri_m, disk_m, quad_m = range(m0, m0 + 5)
+    ball2 = make_shape(A, A.SHAPE_SPHERE, [(0.05, -0.3, 0.7)], radius=0.3)
+    if shipped:
+        scene = interleaved(A, base, [ball2], mats, [(0, tri_m)], [1])
+        names = {"left": 0, "ball2": 1, "wall": 5, "ball": 6}
+    else:
+        tri = make_shape(A, A.SHAPE_TRIANGLE, [(-1.0, -0.6, 0.1), (-0.6, -0.5, 1.0), (-0.1, -0.9, 0.3)])
+        disk = make_shape(A, A.SHAPE_DISK, [(0.75, -0.5, 0.45)], normal=(-0.36, 0.8, 0.48), radius=0.4)
+        quad = make_shape(A, A.SHAPE_RECTANGLE, [(0.45 - 0.25 * x, -0.9, -0.35 + 0.25 * y) for x, y, _ in SKEW])
+        # base: left 0, right 1, top 2, floor 3, wall 4, ball 5, glass ball 6, lamp 7 .. 11
+        scene = interleaved(A, base, [tri, disk, ball2, quad], mats, [(0, tri_m), (1, disk_m), (2, tri_m), (3, quad_m)], [1, 3, 5, 7])
+        names = {"left": 0, "tri": 1, "disk": 3, "ball2": 5, "quad": 7, "wall": 8, "ball": 9}
+    c = scene.scene
+    c.surfaces[names["wall"]].material, c.surfaces[names["ball"]].material = wall_m, ball_m
+    if shipped:
+        c.surfaces[names["left"]].material = disk_m
+    for name, kind in (("wall", RECTANGLE), ("ball", SPHERE), ("ball2", SPHERE), ("tri", TRIANGLE), ("disk", DISK), ("quad", RECTANGLE), ("left", RECTANGLE)):
+        assert name not in names or c.shapes[c.surfaces[names[name]].shape].kind == kind, name
+    textures = [Tex(IMAGE, ball_m, CLAMP, scale=(1.5, -1.5), offset=(-0.2, 1.2), texels=texels_of(2, 7, 2)),
+                Tex(CHECKER, tri_m, scale=(3.5, 2.5), offset=(0.3, -0.2), a=(0.9, 0.8, 0.1), b=(0.1, 0.2, 0.7)),
+                Tex(IMAGE, wall_m, 0, scale=(2.3, 1.7), offset=(0.15, 0.4), texels=texels_of(0, 3, 5)),
+                Tex(CHECKER, quad_m if not shipped else disk_m, scale=(2.5, 3.5), offset=(0.25, 0.6), a=(0.8, 0.3, 0.2), b=(0.2, 0.7, 0.6))]
+    if not shipped:
+        textures.append(Tex(IMAGE, disk_m, BILINEAR, scale=(2.0, 1.0), offset=(0.1, 0.05), texels=texels_of(1, 5, 3)))
+    scene._keep_handle = handle
+    return scene, textures, names
+
+
+def shapes_case_shipped(A, api, w, h):
+    return shapes_case(A, api, w, h, shipped=True)
+
+
+def shapes_case_large(A, api, w, h):
+    """tests/test_stratified_gpu.py's large_scene -- the Cornell box and 65 small balls -- with a checker on the balls' matte material: more than 64 surfaces, and
+    33 uv records behind one texture"""
+    import test_stratified_gpu as T
+    scene = T.large_scene(A, api, w, h)
+    c = scene.scene
+    m = c.surfaces[12].material
+    balls = [i for i in range(c.surface_count) if c.surfaces[i].material == m]
+    assert c.surface_count == 77 and len(balls) == 33 and c.materials[m].kind == A.MATERIAL_MATTE and all(c.shapes[c.surfaces[i].shape].kind == SPHERE for i in balls)
+    return scene, [Tex(CHECKER, m, scale=(4.0, 2.0), offset=(0.3, 0.1), a=(0.9, 0.8, 0.1), b=(0.1, 0.2, 0.7))], {"balls": balls}
+
+
+def flat_textures(textures):
+    """the control set: every texture replaced by a checker with a == b, a colour of its own each (a silhouette between two textured surfaces shows)"""
+    return [Tex(CHECKER, t.material, scale=(3.0, 2.0), offset=(0.5, 0.25), a=(0.25 + 0.125 * i, 0.875 - 0.125 * i, 0.5), b=(0.25 + 0.125 * i, 0.875 - 0.125 * i, 0.5))
+            for i, t in enumerate(textures)]
+
+
+class FirstHits:
+    """what expected_samples returns"""
+
+
+def expected_samples(O, A, scene, textures, params, stride=64, record_of=None, with_k=True):
+    """Every sample [h, w, N] of the frame `params` as the oracle and the restatement give it under INTEGRATOR_BASECOLOR:
+      surface, position  the oracle's first hit of the tape's camera ray (kyo_kat_camera, kyo_kat_scene_intersect: what kyo_trace_li's first row holds), caller's index;
+      k                  kyo_li_tape under basecolor on the scene with every textured material's color0 = (1, 1, 1);
+      expected           k x probe(shape, texture, position, float64)'s colour on a textured surface, k elsewhere (float64);
+      textured, bilinear, clean (>= 1e-4 from a cell or texel edge and, on a sphere, from the seam u = 0 = 1; every untextured sample is clean), e_ref (the float32
+      restatement's largest distance from the float64 one over the bilinear samples).
+    record_of {surface: surface}: the named plumbing defects -- a surface's (u, v) taken from ANOTHER surface's shape.  with_k=False: k = 1 (no oracle replay)."""
+    import filter_restatement as F
+    c = scene.scene
+    w, h, n = params.width, params.height, params.samples_per_pixel
+    tapes = np.stack([np.stack([F.tape(params.seed, y * w + x, n, stride, params.sampler, None) for x in range(w)]) for y in range(h)]).astype(f32)
+    px = (np.arange(w, dtype=f32)[None, :, None] + tapes[..., 0]).astype(f32)
+    py = (np.arange(h, dtype=f32)[:, None, None] + tapes[..., 1]).astype(f32)
+    rays = O.kat_camera(c.camera, np.stack([px, py], axis=-1).reshape(-1, 2))
+    hit = O.kat_scene_intersect(scene, np.concatenate([rays, np.full((len(rays), 1), np.inf, f32)], axis=1))
+    out = FirstHits()
+    out.tapes = tapes
+    out.surface = np.where(hit[:, 0] > 0, hit[:, 8].astype(np.int64), -1)
+    out.position = hit[:, 2:5].copy()
+    by_material = {t.material: t for t in textures}
+    white = copy_scene(A, c)[0]
+    for m in by_material:
+        assert c.materials[m].kind == A.MATERIAL_MATTE   # (basecolor is linear in a matte colour)
+        for j in range(3):
+            white.materials[m].color0[j] = 1.0
+    bp = A.RenderParams.from_buffer_copy(params)
+    bp.integrator = A.INTEGRATOR_BASECOLOR
+    k = np.ones((h, w, n, 3), f32)
+    for y in range(h if with_k else 0):
+        for x in range(w):
+            k[y, x] = O.li_tape(white, bp, x, y, tapes[y, x])[0]
+    out.k = k.reshape(-1, 3)
+    colour = np.ones((len(hit), 3), f64)
+    out.textured, out.bilinear, out.clean = np.zeros(len(hit), bool), np.zeros(len(hit), bool), np.ones(len(hit), bool)
+    out.e_ref = 0.0
+    for s in range(c.surface_count):
+        tex = by_material.get(c.surfaces[s].material)
+        rows = out.surface == s
+        if tex is None or not rows.any():
+            continue
+        shape = Shape.of(c.shapes[c.surfaces[(record_of or {}).get(s, s)].shape])
+        r64 = probe(shape, tex, out.position[rows], f64)
+        colour[rows] = r64[:, 2:]
+        out.textured[rows] = True
+        clean = edge_distance(tex, r64[:, 0], r64[:, 1]) >= 1e-4
+        if shape.kind == SPHERE:
+            u = uv(shape, out.position[rows], f64)[0]
+            clean &= np.minimum(u, 1 - u) >= 1e-4
+        out.clean[rows] = clean
+        if tex.kind == IMAGE and tex.flags & BILINEAR:
+            out.bilinear[rows] = True
+            out.e_ref = max(out.e_ref, float(np.abs(probe(shape, tex, out.position[rows], f32)[:, 2:].astype(f64) - r64[:, 2:]).max()))
+    out.expected = out.k.astype(f64) * colour
+    out.shape = (h, w, n)
+    for a in (out.surface, out.position, out.k, out.expected, out.textured, out.bilinear, out.clean):
+        a.setflags(write=False)
+    return out
+
+
+# ---- edge coordinates ----
+
+EDGE_RECT = [(0.0, 0.0, 0.0), (2.0, 0.0, 0.0), (2.0, 0.0, 4.0), (0.0, 0.0, 4.0)]   # |e1|^2 = 4, |e2|^2 = 16: (u, v) of (2 u, 0, 4 v) is exact
+
+
+def edge_points(uvs):
+    uvs = np.asarray(uvs, f32)
+    return np.stack([f32(2) * uvs[:, 0], np.zeros(len(uvs), f32), f32(4) * uvs[:, 1]], axis=1).astype(f32)
+
+
+def edge_cases(material=0):
+    """name -> (Tex, (u, v) [n, 2] float32 of points of EDGE_RECT): coordinates u' that sit exactly on integers and on k / W, at -2^-30 (where the repeat wrap rounds
+    to 1 and the index is capped), beyond +-1000, beyond [0, 1] under clamp, and at the rectangle's corners.  |u'| < 2^24 throughout.  tests/test_texture.py pins
+    the float32 restatement at these points to hand-written texel indices."""
+    below = lambda x: np.nextafter(f32(x), f32(0))
+    corners = [(0, 0), (1, 0), (1, 1), (0, 1)]
+    img, img5 = texels_of(0, 4, 2), texels_of(1, 5, 3)
+    a, b = (0.9, 0.8, 0.1), (0.1, 0.2, 0.7)
+    return {
+        "on k / W": (Tex(IMAGE, material, texels=img), [(0, 0.25), (0.25, 0.25), (0.5, 0.25), (0.75, 0.25), (1, 0.25), (0.5, 0.5), (below(0.5), below(0.5))] + corners),
+        "-2^-30": (Tex(IMAGE, material, offset=(-2.0 ** -30, 0), texels=img), [(0, 0.25), (0.25, 0.25), (0.5, 0.75)]),
+        "beyond 1000": (Tex(IMAGE, material, scale=(4096, 1), offset=(-2048, 0), texels=img), [(0, 0.25), (1, 0.25), (0.5 + 2.0 ** -14, 0.25), (2.0 ** -13, 0.25),
+                                                                                              (1 - 3 * 2.0 ** -14, 0.75)]),
+        "clamped": (Tex(IMAGE, material, CLAMP, scale=(3, -2), offset=(-1, 1.5), texels=img), [(0, 0), (1, 1), (0.5, 0.5), (0.75, 0.625)] + corners),
+        "on k / 5": (Tex(IMAGE, material, texels=img5), [(f32(0.2), f32(1 / 3)), (f32(0.4), f32(2 / 3)), (f32(0.6), f32(1 / 3)), (f32(0.8), below(1 / 3)), (below(0.2), 0.5)]),
+        "checker on integers": (Tex(CHECKER, material, scale=(4, 2), a=a, b=b), [(0, 0.25), (0.25, 0.25), (0.5, 0.25), (0.75, 0.25), (1, 0.25), (0.25, 0.5)] + corners),
+        "checker beyond 1000": (Tex(CHECKER, material, scale=(4096, 1), offset=(-2048, 0), a=a, b=b), [(0, 0.25), (2.0 ** -13, 0.25), (2.0 ** -12, 0.25), (1, 0.25), (1, 1)]),
+        "checker -2^-30": (Tex(CHECKER, material, offset=(-2.0 ** -30, 0), a=a, b=b), [(0, 0.25), (0.5, 0.25), (0, 1)]),
+    }
