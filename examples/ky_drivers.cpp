@@ -27,7 +27,8 @@
  *                                the picture and, next to it, the sample-count map (white: the frame's total)
  *   ky_drivers denoise [low_spp] [spp] [w] [h]  the same frame after its first low_spp samples (64 of 1024, 1024 x 768), in two passes, as the plain mean and through
  *                                the edge-avoiding filter (integrator_t::render_denoised), next to the complete frame; writes denoise.bmp: raw | denoised | full
- *                                (a fifth argument, guide_bounces 1 .. 4, adds the filter with specular-chain guides: raw | first-hit | chains | full)
+ *                                (a fifth argument, guide_bounces 1 .. 4, adds the filter with specular-chain guides: raw | first-hit | chains | full;
+ *                                a sixth, albedo_grid 1 .. 8, one more cell before the full frame: the filter with those guide bounces and albedo demodulation)
  *   ky_drivers sliced [n] [spp] [w] [h]  the same frame by sample range (3 slices, 512 spp, 1024 x 768; kyhip_frame_begin_slice, kyhip_frame_merge_from): the n slices
  *                                render on device 0 one after the other, slice 0 merges the rest; prints per slice its samples and kernel time, the merge times, and
  *                                whether the film is render()'s bit for bit (it must be: exit status 1 otherwise); writes sliced.bmp
@@ -505,9 +506,10 @@ static void render_adaptive(float threshold, int spp, int width, int height) {
 
 // The headline frame early on, raw and denoised (integrator_t::render_denoised; include/kyhip.h, kyhip_frame_denoise), and complete: three cells side by side.  The
 // first two are the same samples: the frame's first passes, two of at least low_spp / 2 samples.  guide_bounces 1 .. 4 adds a cell, the same samples once more
-// denoised with guides that follow the balls' mirror and glass that far (kyhip_frame_set_guide_bounces): raw | first-hit | chains | full.
-static void render_denoise(int low_spp, int spp, int width, int height, int guide_bounces) {
-    film_grid_t film(1, guide_bounces > 0 ? 4 : 3, width, height);
+// denoised with guides that follow the balls' mirror and glass that far (kyhip_frame_set_guide_bounces): raw | first-hit | chains | full.  albedo_grid 1 .. 8 adds
+// another before the full frame: those guide bounces and albedo demodulation (kyhip_frame_set_albedo_grid).
+static void render_denoise(int low_spp, int spp, int width, int height, int guide_bounces, int albedo_grid) {
+    film_grid_t film(1, 3 + (guide_bounces > 0 ? 1 : 0) + (albedo_grid > 0 ? 1 : 0), width, height);
     scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, film.get_resolution());
     std::unique_ptr<sampler_t> sampler = std::make_unique<random_sampler_t>(spp);
     std::unique_ptr<integrator_t> integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
@@ -522,9 +524,13 @@ static void render_denoise(int low_spp, int spp, int width, int height, int guid
         integrator->render_denoised(&scene, sampler.get(), &film, per_pass, low_spp, nullptr, guide_bounces);
         film.next_subfilm();
     }
+    if (albedo_grid > 0) {
+        integrator->render_denoised(&scene, sampler.get(), &film, per_pass, low_spp, nullptr, guide_bounces, albedo_grid);
+        film.next_subfilm();
+    }
     integrator->render(&scene, sampler.get(), &film);
-    std::printf("denoise: %dx%d, raw at %d and denoised at %d of %d spp (%.3f seconds with its passes)%s, then the complete frame\n", width, height, raw_done, done, spp, seconds,
-                guide_bounces > 0 ? ", denoised once more with specular-chain guides" : "");
+    std::printf("denoise: %dx%d, raw at %d and denoised at %d of %d spp (%.3f seconds with its passes)%s%s, then the complete frame\n", width, height, raw_done, done, spp, seconds,
+                guide_bounces > 0 ? ", denoised once more with specular-chain guides" : "", albedo_grid > 0 ? ", and once more with albedo demodulation" : "");
     film.store_image("denoise");
 }
 
@@ -562,7 +568,7 @@ int main(int argc, char* argv[]) {
             render_adaptive(threshold, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768);
         } else if (!std::strcmp(which, "denoise")) {
             render_denoise(argc > 2 ? std::atoi(argv[2]) : 64, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768,
-                           argc > 6 ? std::atoi(argv[6]) : 0);
+                           argc > 6 ? std::atoi(argv[6]) : 0, argc > 7 ? std::atoi(argv[7]) : 0);
         } else if (!std::strcmp(which, "stratified")) {
             const bool veach = argc > 2 && !std::strcmp(argv[2], "veach");
             if (argc > 2 && !veach && std::strcmp(argv[2], "cornell")) { std::fprintf(stderr, "stratified: cornell or veach\n"); return 2; }

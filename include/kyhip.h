@@ -599,8 +599,29 @@ int     kyhip_frame_blocks_ms(const kyhip_frame* f, float* retire_ms, float* lis
  * kyhip_frame_guide_bounces: the value, or KY_ERR_INVALID_VALUE for a NULL frame.
  * kyhip_frame_guide_chains: WRITES width x height keys, y down, row_stride_px keys apart (all 0 at 0 bounces); the frame as for kyhip_frame_guides, which
  *   returns the chain-end guides.
+ *
+ * Albedo demodulation (opt-in per frame; the default, grid 0, is everything above to the byte and to the kernel).  With an albedo grid G = 1 .. KYHIP_ALBEDO_MAX_GRID
+ * one more kernel, traced once per frame when the guides are, gives every pixel an ALBEDO {r, g, b, w}: G x G camera rays per pixel through the frame's own camera
+ * form (its pixel filter's warp and its lens) -- sub-sample (i, j), j-major, has the film pair ((i + 0.5) g, (j + 0.5) g) and the lens pair ((j + 0.5) g,
+ * (G - 1 - i + 0.5) g) with g the float 1 / G -- each walked through mirrors and glass for up to the frame's guide bounces as the guide kernel walks the centre ray.
+ * A sub-sample's colour starts at (1, 1, 1); each specular vertex walked through multiplies by what its branch carries (a mirror's colour; glass: its reflection
+ * colour reflected, its transmission colour transmitted); the vertex the walk ends on multiplies by its colour0 as the integrator takes it -- the frame's texture
+ * there where the material has one, and for plastic colour0 / diffuse_probability -- if it is matte, plastic or a mirror, and by nothing if it is glass; a miss and
+ * a surface that carries an area light multiply by nothing.  The pixel's albedo is the float32 sum of the G^2 colours in visit order times the float 1 / G^2, and w
+ * the number of sub-samples that ended on a surface without a lamp.  kyhip_frame_denoise then DEMODULATES: with a' = max(albedo, 1/64) per channel, a class-0
+ * pixel's colour is divided by a' and its variance by luminance(a')^2 before the levels, and the filtered colour is multiplied by a' before the clamp (double
+ * arithmetic, one float32 rounding each; ky_amd/csrc/ky_denoise.hpp).  The levels filter what the light did, not what a checker or a texel edge did.  Pixels of
+ * class 1, 2 and 3 take neither step; levels == 0 stays kyhip_frame_resolve(f, 1, ...).
+ * kyhip_frame_set_albedo_grid: 0 .. KYHIP_ALBEDO_MAX_GRID (0: off), else KY_ERR_INVALID_VALUE; KY_ERR_INVALID_VALUE with the frame untouched once its guides have
+ *   been traced (the first kyhip_frame_denoise / _guides / _guide_chains / _albedo call that reaches the device), unless the value is the one it has.  The albedo is
+ *   traced with the guide bounces, filter, lens and textures the frame holds at that call.  No part of a checkpoint.
+ * kyhip_frame_albedo_grid: the value, or KY_ERR_INVALID_VALUE for a NULL frame.
+ * kyhip_frame_albedo: WRITES width x height float4 {r, g, b, w}, y down, row_stride_px float4 apart; the frame as for kyhip_frame_guides; KY_ERR_INVALID_VALUE
+ *   at grid 0.
+ * kyhip_frame_albedo_ms: the hipEvent span of the albedo trace (set once per frame), negative where there was none.
  */
 #define KYHIP_GUIDE_MAX_BOUNCES 4
+#define KYHIP_ALBEDO_MAX_GRID 8
 typedef struct ky_denoise_params { int32_t levels, normal_squarings; float sigma_luminance, sigma_plane; } ky_denoise_params;
 void    kyhip_denoise_defaults(ky_denoise_params* out);
 int     kyhip_frame_denoise(kyhip_frame* f, const ky_denoise_params* p, float* film_rgb, size_t film_row_stride_px);
@@ -609,6 +630,10 @@ int     kyhip_frame_denoise_ms(const kyhip_frame* f, float* guides_ms, float* fi
 int     kyhip_frame_set_guide_bounces(kyhip_frame* f, int bounces);
 int     kyhip_frame_guide_bounces(const kyhip_frame* f);
 int     kyhip_frame_guide_chains(kyhip_frame* f, uint64_t* keys, size_t row_stride_px);
+int     kyhip_frame_set_albedo_grid(kyhip_frame* f, int grid);
+int     kyhip_frame_albedo_grid(const kyhip_frame* f);
+int     kyhip_frame_albedo(kyhip_frame* f, float* albedo4, size_t row_stride_px);
+int     kyhip_frame_albedo_ms(const kyhip_frame* f, float* ms);
 
 /*
  * Slices: a frame's sample ranges rendered apart and merged, bit for bit (DESIGN.md section 3 "Slices").  A pixel's samples are keyed by their absolute index,
@@ -742,7 +767,7 @@ int     kyhip_kat_li_lens(int device, const ky_scene* scene, const ky_render_par
  *                          vertex's material record, which is the lane's textured copy); the estimate is unbiased under any positive weights.
  *   kyhip_frame_set_textures  the frame's texture set, before its first sample is rendered, loaded or merged (KY_ERR_INVALID_VALUE afterwards).  Descriptors and texels
  *                          are copied and uploaded once; a digest of both is folded into the scene hash of the frame's header, so a state loads and merges only into
- *                          a frame with the same textures.  n_textures == 0 removes the set.  Denoise guides know nothing of textures.
+ *                          a frame with the same textures.  n_textures == 0 removes the set.  The denoise guides hold geometry only; a frame's albedo (kyhip_frame_set_albedo_grid) reads the set.
  *   kyhip_kat_li_textured  kyhip_kat_li_lens's samples under a texture set: what the textured rows add per camera sample.
  *   kyhip_kat_texture      a known-answer probe through the device functions the render kernels call: for n_points world points on surface `surface` (the caller's
  *                          index; its material must carry a texture of the set) out5 = (u', v', r, g, b), the colour as the vertex's material takes it (on a

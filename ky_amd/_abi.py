@@ -137,6 +137,7 @@ SPP = C.POINTER(SmallptParams)
 SLICE_MAX_RANGES = 32   # KYHIP_SLICE_MAX_RANGES
 GUIDE_MAX_BOUNCES = 4   # KYHIP_GUIDE_MAX_BOUNCES
 GUIDE_KEY_UNRESOLVED = 1 << 62   # a chain key's bit for "more specular vertices than the frame's guide bounces"
+ALBEDO_MAX_GRID = 8     # KYHIP_ALBEDO_MAX_GRID
 
 KYHIP_SYMBOLS = {
     "kyhip_last_error": (C.c_char_p, []),
@@ -197,6 +198,10 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_set_guide_bounces": (C.c_int, [C.c_void_p, C.c_int]),
     "kyhip_frame_guide_bounces": (C.c_int, [C.c_void_p]),
     "kyhip_frame_guide_chains": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_set_albedo_grid": (C.c_int, [C.c_void_p, C.c_int]),
+    "kyhip_frame_albedo_grid": (C.c_int, [C.c_void_p]),
+    "kyhip_frame_albedo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_frame_albedo_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "kyhip_slice_bounds": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "kyhip_frame_begin_slice": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "kyhip_frame_coverage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
@@ -286,6 +291,8 @@ KYHOST_SYMBOLS = {
                                          C.c_int, C.POINTER(DenoiseParams)]),
     "kyhost_render_denoised_chains": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                                 C.c_int, C.POINTER(DenoiseParams), C.c_int]),
+    "kyhost_render_denoised_albedo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int]),
     "kyhost_store_image": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "kyhost_gamma_encoding": (C.c_int, [C.c_float]),
 }
@@ -310,6 +317,8 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
                                      C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int]),
     "kyhostcheck_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_double, C.c_void_p]),
     "kyhostcheck_denoise_keyed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_double, C.c_void_p]),
+    "kyhostcheck_denoise_albedo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_double,
+                                             C.c_void_p]),
     "kyhostcheck_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_slices": (C.c_int, [C.c_int, PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kyhostcheck_filter": (C.c_int, []),

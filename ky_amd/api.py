@@ -291,9 +291,12 @@ class Frame:
     held, `coverage` lists them, and slices that cover 0 .. total merged into one of them resolve to render(scene, params).
     filter=pixel_filter(...): the frame's camera samples are drawn from the filter's density (kyhip_frame_set_filter); a complete frame's resolve() is then
     render(scene, params, filter=filter) bit for bit, and its states load and merge only into frames with the same filter.
-    lens=lens(...): the frame's camera rays leave from that lens (kyhip_frame_set_lens), with the same two consequences."""
+    lens=lens(...): the frame's camera rays leave from that lens (kyhip_frame_set_lens), with the same two consequences.
+    albedo=G, 1 .. 8: denoise() divides every surface pixel by an albedo before its levels and multiplies it back behind them (kyhip_frame_set_albedo_grid): the
+    mean colour of what G x G camera rays per pixel end on, the frame's textures included, traced once per frame with the guides (albedo(), albedo_ms()); 0, the
+    default: off, and denoise() is what it is without."""
 
-    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0, filter=None, lens=None, textures=None):
+    def __init__(self, scene, params, device=0, noise=False, blocks=False, slice=None, guide_bounces=0, filter=None, lens=None, textures=None, albedo=0):
         self._lib = A.load_kyhip()
         self._f = C.c_void_p()
         self.height, self.width = params.height, params.width
@@ -313,6 +316,11 @@ class Frame:
                 _check(rc, self._lib)
         if guide_bounces:
             rc = self._lib.kyhip_frame_set_guide_bounces(self._f, int(guide_bounces))
+            if rc != A.KY_OK:
+                self.close()
+                _check(rc, self._lib)
+        if albedo:
+            rc = self._lib.kyhip_frame_set_albedo_grid(self._f, int(albedo))
             if rc != A.KY_OK:
                 self.close()
                 _check(rc, self._lib)
@@ -369,6 +377,17 @@ class Frame:
     @property
     def guide_bounces(self):
         n = self._lib.kyhip_frame_guide_bounces(self._f)
+        if n < 0:
+            _check(n, self._lib)
+        return n
+
+    def set_albedo_grid(self, grid):
+        """kyhip_frame_set_albedo_grid: 0 (off) .. 8 sub-samples per pixel edge of the albedo denoise() demodulates by; refused once the guides are traced."""
+        _check(self._lib.kyhip_frame_set_albedo_grid(self._f, int(grid)), self._lib)
+
+    @property
+    def albedo_grid(self):
+        n = self._lib.kyhip_frame_albedo_grid(self._f)
         if n < 0:
             _check(n, self._lib)
         return n
@@ -517,6 +536,19 @@ class Frame:
         keys = np.zeros((self.height, self.width), np.uint64)
         _check(self._lib.kyhip_frame_guide_chains(self._f, C.c_void_p(keys.ctypes.data), self.width), self._lib)
         return keys
+
+    def albedo(self):
+        """kyhip_frame_albedo: (H, W, 4) float32 {r, g, b, w}: the albedo a frame with an albedo grid demodulates by, and the number of the pixel's sub-samples
+        that ended on a surface without a lamp."""
+        a = np.zeros((self.height, self.width, 4), np.float32)
+        _check(self._lib.kyhip_frame_albedo(self._f, C.c_void_p(a.ctypes.data), self.width), self._lib)
+        return a
+
+    def albedo_ms(self):
+        """kyhip_frame_albedo_ms: the albedo trace in ms, negative where there was none."""
+        a = C.c_float(-1)
+        _check(self._lib.kyhip_frame_albedo_ms(self._f, C.byref(a)), self._lib)
+        return a.value
 
     def denoise_ms(self):
         """kyhip_frame_denoise_ms: (the guide trace, the last denoise()'s gather + levels + add) in ms, negative where there was none."""
@@ -750,16 +782,19 @@ def render_adaptive_host_api(scene, integrator_enum, depth, direct_sample, sampl
 
 
 def render_denoised_host_api(scene, integrator_enum, depth, direct_sample, sampler, spp, width, height, min_samples_per_pass, stop_after_samples, params=None,
-                             seed=1234, film=None, device=0, guide_bounces=None):
+                             seed=1234, film=None, device=0, guide_bounces=None, albedo=None):
     """create_integrator(...)->render_denoised(&scene, sampler, &film, min_samples_per_pass, stop_after_samples, params) through the C++ host classes: (the film
     with the denoised picture so far added, the samples done per pixel).  params: an _abi.DenoiseParams, None for the library's defaults.  guide_bounces: None,
-    or render_denoised's last argument (kyhost_render_denoised_chains)."""
+    or render_denoised's guide_bounces (kyhost_render_denoised_chains).  albedo: None, or render_denoised's albedo_grid (kyhost_render_denoised_albedo)."""
     host = A.load_kyhost()
     if film is None:
         film = np.zeros((height, width, 3), np.float32)
     args = (scene.ptr, integrator_enum, depth, direct_sample, sampler, spp, seed, width, height, _fptr(film), device, int(min_samples_per_pass),
             int(stop_after_samples), None if params is None else C.byref(params))
-    rc = host.kyhost_render_denoised(*args) if guide_bounces is None else host.kyhost_render_denoised_chains(*args, int(guide_bounces))
+    if albedo is not None:
+        rc = host.kyhost_render_denoised_albedo(*args, int(guide_bounces or 0), int(albedo))
+    else:
+        rc = host.kyhost_render_denoised(*args) if guide_bounces is None else host.kyhost_render_denoised_chains(*args, int(guide_bounces))
     if rc == -2:
         return None
     if rc < 0:

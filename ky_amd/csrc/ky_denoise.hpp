@@ -65,6 +65,31 @@ KY_NOFMA_FN KY_HD inline Px4 gather_pixel(long long r, long long g, long long b,
 
 KY_HD inline bool is_surface(const Px4& gb) { return gb.w == (float)KY_DN_SURFACE; }
 
+// ---- albedo demodulation (DESIGN.md "Denoise", "Albedo"; kyhip_frame_set_albedo_grid) ----
+// A frame with an albedo grid divides a class-0 pixel's colour by the pixel's albedo a = {r, g, b} before the levels and multiplies it back behind them, so the
+// levels filter what the light did and not what the surface's colour did.  Both steps use a' = max(a, 1/64) per channel: the floor keeps a black albedo from
+// dividing by zero, and the round trip is the identity up to two float32 roundings whatever a is.  (a NaN channel takes the floor.)
+//   demodulate  c <- (float)(c / a'),  v <- (float)(v / Y(a')^2)   exact where the noise is in the irradiance and the albedo is known
+//   remodulate  c <- (float)(c * a'),  v stays (nothing reads it behind the levels)
+// Pixels of class 1, 2 and 3 take neither step.
+KY_HD inline double albedo_floor(float a) { return a > 0.015625f ? (double)a : 0.015625; }
+KY_NOFMA_FN KY_HD inline Px4 demodulate_pixel(const Px4& c, const Px4& a) {
+    KY_NOFMA_BODY
+    const double ax = albedo_floor(a.x), ay = albedo_floor(a.y), az = albedo_floor(a.z);
+    const double ya = 0.212671 * ax + 0.715160 * ay + 0.072169 * az;   // luminance's weights
+    Px4 o;
+    o.x = (float)((double)c.x / ax); o.y = (float)((double)c.y / ay); o.z = (float)((double)c.z / az);
+    o.w = (float)((double)c.w / (ya * ya));
+    return o;
+}
+KY_NOFMA_FN KY_HD inline Px4 remodulate_pixel(const Px4& c, const Px4& a) {
+    KY_NOFMA_BODY
+    Px4 o;
+    o.x = (float)((double)c.x * albedo_floor(a.x)); o.y = (float)((double)c.y * albedo_floor(a.y)); o.z = (float)((double)c.z * albedo_floor(a.z));
+    o.w = c.w;
+    return o;
+}
+
 // One level at pixel (x, y) with its taps `step` pixels apart: the pixel's new {r, g, b, v}.  cv, ga, gb: width x height, film order.
 //   v_bar  the (1 2 1)^T (1 2 1) / 16 average of v over the class-0 neighbours at distance 1 inside the film, renormalised by the weights used
 //   tap q = p + (i, j) step, i, j = -2 .. 2 in row-major (j, i) order, inside the film and class 0:
@@ -167,4 +192,16 @@ int denoise_level_device(const void* cv_in, void* cv_out, const void* ga, const 
 int denoise_level_keyed_device(const void* cv_in, void* cv_out, const void* ga, const void* gb, const void* key, int step, const LevelConst& k, void* stream);
 // clamp01 per channel and ADD into a film (device memory, or the device alias of a pinned host film): film_t::add_color
 int denoise_add_device(const void* cv, float* film, size_t stride_px, int width, int height, void* stream);
+// ---- of a frame with an albedo grid (kyhip_frame_set_albedo_grid) ----
+constexpr int KY_DN_ALBEDO_MAX_GRID = KYHIP_ALBEDO_MAX_GRID;
+// The albedo of the whole film, traced once per frame: `albedo` = width x height Px4 {r, g, b, w}, the mean over grid x grid camera rays per pixel of the colour
+// the ray's specular chain (bounces 0 .. KYHIP_GUIDE_MAX_BOUNCES) ends on, and the number of them that ended on a surface that carries no lamp.  cam: the frame's
+// camera form (the pixel filter and the lens as its passes carry them), tex: its texture set (set == NULL: none).  Uploads, enqueues and WAITS like the guides.
+int denoise_albedo_device(int device, const ky_scene* scene, int width, int height, int bounces, int grid, const kyd::LensCam& cam, const kyd::TexConst& tex, void* albedo,
+                          void* stream);
+// denoise_gather_device that demodulates the class-0 pixels by `albedo` (demodulate_pixel), and denoise_add_device that remodulates them before the clamp
+// (remodulate_pixel; gb: the classes the gather wrote)
+int denoise_gather_albedo_device(const void* ws, const void* noise_state, const void* blocks, const ShardConst& sh, int width, int height, int total_spp, int n_done,
+                                 int batches, const void* gb_traced, const void* albedo, void* cv, void* gb, void* stream);
+int denoise_add_albedo_device(const void* cv, const void* gb, const void* albedo, float* film, size_t stride_px, int width, int height, void* stream);
 }  // namespace kydn

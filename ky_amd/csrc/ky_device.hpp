@@ -2431,6 +2431,26 @@ KY_DEV void path_begin(PathStateFor<SAMPLER>& ps, SceneRef S, uint32_t pixel_key
     ps.prev_specular = false;
 }
 
+// path_begin<..., KY_CAM_ANY>'s ray for GIVEN numbers, operation by operation: (u0, u1) the camera sample's film pair, (l0, l1) its lens pair -- the filter's
+// warp unless the filter is the box, the lens code unless the lens is the pinhole.  For the callers that lay their own points over a pixel instead of drawing
+// them (denoise_albedo_kernel, ky_denoise.hip); path_begin itself stays as it is, so every kernel that calls it keeps its listing.
+KY_DEV void camera_ray_any(SceneRef S, const LensCam& fc, int x, int y, float u0, float u1, float l0, float l1, f3& o, f3& d) {
+    if (fc.kind != KY_FILTER_BOX) { u0 = filter_offset(fc, u0); u1 = filter_offset(fc, u1); }
+    if (fc.lens.wf == 0.f) {
+        generate_ray(S, (float)x + u0, (float)y + u1, o, d);
+        return;
+    }
+    float dx, dy;
+    lens_disk(l0, l1, dx, dy);
+    const LensConst& lc = fc.lens;
+    const float a = strat_fmul(lc.ar, dx), b = strat_fmul(lc.bu, dy);
+    generate_ray(S, __builtin_fmaf(-a, lc.wf, (float)x + u0), __builtin_fmaf(b, lc.hf, (float)y + u1), o, d);
+    const f3 right = ld3(S->cam_right), up = ld3(S->cam_up);
+    o.x = __builtin_fmaf(up.x, b, __builtin_fmaf(right.x, a, o.x));
+    o.y = __builtin_fmaf(up.y, b, __builtin_fmaf(right.y, a, o.y));
+    o.z = __builtin_fmaf(up.z, b, __builtin_fmaf(right.z, a, o.z));
+}
+
 // First half of a path vertex: trace the current ray and account for what the hit (or miss) itself contributes.
 // Returns false when the path has ended (radiance complete in ps.Lo); true when `v` holds a vertex to shade.
 // DROP (light classes, lighting_enum_t 3591-3603): bit 0 -- nothing the camera ray's own hit or miss emits is added (class k = 0); bit 1 -- no

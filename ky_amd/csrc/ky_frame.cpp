@@ -56,6 +56,10 @@ struct DenoiseTrack {
     std::vector<float> hga, hgb;       // host copies of the guides (kyhip_frame_guides)
     std::vector<uint64_t> hkey;        // ... and of the keys (kyhip_frame_guide_chains)
     TimedSpan guides, filter;          // the guide trace; the last call's gather, levels and add (kyhip_frame_denoise_ms)
+    int albedo_grid = 0;               // kyhip_frame_set_albedo_grid: 0 is off; fixed once the guides are traced
+    DevBuf albedo;                     // width x height Px4 {r, g, b, count} of a frame with an albedo grid, traced when the guides are
+    std::vector<float> halbedo;        // ... and its host copy (kyhip_frame_albedo)
+    TimedSpan albedo_span;             // the albedo trace (kyhip_frame_albedo_ms)
 };
 struct kyhip_frame {
     int device = 0;
@@ -632,16 +636,31 @@ static int denoise_prepare(kyhip_frame* f, DeviceCtx* c, bool timed_filter) {
     for (DevBuf* b : {&d.ga, &d.gb_traced, &d.gb, &d.cv[0], &d.cv[1]})
         if (!b->p) HIP_TRY(b->alloc(bytes));
     if (d.guide_bounces > 0 && !d.key.p) HIP_TRY(d.key.alloc((size_t)p->width * (size_t)p->height * sizeof(uint64_t)));
+    if (d.albedo_grid > 0 && !d.albedo.p) HIP_TRY(d.albedo.alloc(bytes));
     KY_TRY(d.guides.create());
     KY_TRY(d.filter.create());
+    if (d.albedo_grid > 0) KY_TRY(d.albedo_span.create());
     if (!d.guides_done) {
         KY_TRY(timed(d.guides, c->stream, "denoise guides", "", [&] {
             if (d.guide_bounces > 0) return denoise_chain_guides_device(f->device, &f->scene, p->width, p->height, d.guide_bounces, d.ga.p, d.gb_traced.p, d.key.p, c->stream);
             return denoise_guides_device(f->device, &f->scene, p->width, p->height, d.ga.p, d.gb_traced.p, c->stream);
         }));
+        if (d.albedo_grid > 0) {   // the albedo with the guides: through the camera form, the textures and the guide bounces the frame holds now
+            const FramePass& pass = f->pass;
+            LensCam cam;
+            static_cast<FilterConst&>(cam) = pass.filter;
+            cam.lens = pass.lensed ? pass.lens : LensConst{0.f, 0.f, 0.f, 0.f};
+            const TexConst tex = pass.textured ? pass.tex : TexConst{nullptr, nullptr};
+            KY_TRY(timed(d.albedo_span, c->stream, "denoise albedo", "", [&] {
+                return denoise_albedo_device(f->device, &f->scene, p->width, p->height, d.guide_bounces, d.albedo_grid, cam, tex, d.albedo.p, c->stream);
+            }));
+        }
         d.guides_done = true;
     }
     if (timed_filter) d.filter.begin(c->stream);   // (kyhip_frame_denoise: its span begins with the gather and ends behind the delivery's add)
+    if (d.albedo_grid > 0)
+        return denoise_gather_albedo_device(f->ws.p, f->noise.state.p, block_state_or_null(f), book.sh, p->width, p->height, p->samples_per_pixel, book.held(),
+                                            book.noise.batches, d.gb_traced.p, d.albedo.p, d.cv[0].p, d.gb.p, c->stream);
     return denoise_gather_device(f->ws.p, f->noise.state.p, block_state_or_null(f), book.sh, p->width, p->height, p->samples_per_pixel, book.held(), book.noise.batches,
                                  d.gb_traced.p, d.cv[0].p, d.gb.p, c->stream);
 }
@@ -672,6 +691,7 @@ int kyhip_frame_denoise(kyhip_frame* f, const ky_denoise_params* params, float* 
                                     : denoise_level_device(d.cv[l & 1].p, d.cv[(l + 1) & 1].p, d.ga.p, d.gb.p, 1 << l, k, c->stream);
     const void* result = d.cv[q.levels & 1].p;
     return deliver(f, c->stream, rcode, "denoise", &d.filter, film_rgb, stride_px, [&](float* dst, size_t dst_stride) {
+        if (d.albedo_grid > 0) return denoise_add_albedo_device(result, d.gb.p, d.albedo.p, dst, dst_stride, p->width, p->height, c->stream);
         return denoise_add_device(result, dst, dst_stride, p->width, p->height, c->stream);   // film order already
     });
 }
@@ -729,6 +749,47 @@ int kyhip_frame_guide_chains(kyhip_frame* f, uint64_t* keys, size_t stride_px) {
     d.hkey.assign(n, 0);
     if (d.guide_bounces > 0) HIP_TRY(hipMemcpy(d.hkey.data(), d.key.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     for (int y = 0; y < p->height; ++y) std::memcpy(keys + (size_t)y * stride_px, d.hkey.data() + (size_t)y * p->width, (size_t)p->width * sizeof(uint64_t));
+    return KY_OK;
+}
+
+// ---- the albedo of a frame that demodulates (DESIGN.md "Denoise", "Albedo") ----
+int kyhip_frame_set_albedo_grid(kyhip_frame* f, int grid) {
+    if (grid < 0 || grid > KY_DN_ALBEDO_MAX_GRID) return fail(KY_ERR_INVALID_VALUE, "albedo grid %d: 0 .. %d", grid, KY_DN_ALBEDO_MAX_GRID);
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    DenoiseTrack& d = f->denoise;
+    if (grid == d.albedo_grid) return KY_OK;
+    if (d.guides_done) return fail(KY_ERR_INVALID_VALUE, "albedo grid %d: the frame's guides are traced, with %d", grid, d.albedo_grid);
+    d.albedo_grid = grid;
+    return KY_OK;
+}
+
+int kyhip_frame_albedo_grid(const kyhip_frame* f) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    return f->denoise.albedo_grid;
+}
+
+int kyhip_frame_albedo(kyhip_frame* f, float* albedo4, size_t stride_px) {
+    KY_TRY(denoise_frame_check(f, false));
+    const ky_render_params* p = &f->book.params;
+    if (!albedo4) return fail(KY_ERR_INVALID_VALUE, "albedo4 is NULL");
+    if (stride_px < (size_t)p->width) return fail(KY_ERR_INVALID_VALUE, "row_stride_px %zu: the albedo's rows are %d pixels", stride_px, p->width);
+    DenoiseTrack& d = f->denoise;
+    if (d.albedo_grid == 0) return fail(KY_ERR_INVALID_VALUE, "the frame has no albedo: its albedo grid is 0");
+    if (f->book.sh.n_pix == 0) return KY_OK;
+    DeviceCtx* c;
+    KY_TRY(get_ctx(f->device, &c));
+    const int rcode = denoise_prepare(f, c, false);
+    KY_TRY(finish(c->stream, rcode, "denoise albedo"));
+    const size_t n = (size_t)p->width * (size_t)p->height * 4;
+    d.halbedo.resize(n);
+    HIP_TRY(hipMemcpy(d.halbedo.data(), d.albedo.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    for (int y = 0; y < p->height; ++y) std::memcpy(albedo4 + (size_t)y * stride_px * 4, d.halbedo.data() + (size_t)y * p->width * 4, (size_t)p->width * 4 * sizeof(float));
+    return KY_OK;
+}
+
+int kyhip_frame_albedo_ms(const kyhip_frame* f, float* ms) {
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (ms) *ms = f->denoise.albedo_span.ms();
     return KY_OK;
 }
 

@@ -534,6 +534,26 @@ int kyhostcheck_denoise_keyed(const float* cv, const float* ga, const float* gb,
     return denoise_on_host(cv, ga, gb, key, width, height, p, pix, out);
 }
 
+// ... of a frame with an albedo grid (DESIGN.md "Denoise", "Albedo"): `albedo` is width x height x 4 floats {r, g, b, w}; the class-0 pixels are demodulated
+// (demodulate_pixel), the levels run -- keyed where `key` is not NULL --, and the class-0 pixels are remodulated (remodulate_pixel).  Writes {r, g, b, v} like the others.
+int kyhostcheck_denoise_albedo(const float* cv, const float* ga, const float* gb, const uint64_t* key, const float* albedo, int width, int height, const ky_denoise_params* p,
+                               double pix, float* out) {
+    using namespace kydn;
+    if (!cv || !gb || !albedo || !out || width < 1 || height < 1) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<Px4> c(n), b(n), a(n);
+    std::memcpy(c.data(), cv, n * sizeof(Px4));
+    std::memcpy(b.data(), gb, n * sizeof(Px4));
+    std::memcpy(a.data(), albedo, n * sizeof(Px4));
+    for (size_t i = 0; i < n; ++i)
+        if (is_surface(b[i])) c[i] = demodulate_pixel(c[i], a[i]);
+    KY_TRY(denoise_on_host(&c[0].x, ga, gb, key, width, height, p, pix, &c[0].x));
+    for (size_t i = 0; i < n; ++i)
+        if (is_surface(b[i])) c[i] = remodulate_pixel(c[i], a[i]);
+    std::memcpy(out, c.data(), n * sizeof(Px4));
+    return KY_OK;
+}
+
 // The live rectangle (screen_bound, kyhip_scene_screen_bound) on degenerate inputs: a unit box of five matte rectangles (open towards -z) or one sphere, seen by a
 // camera that looks along +z.  Whatever the proof cannot cover must give the whole frame: the camera on the bound's face, inside the bound, a NaN vertex, no surfaces.
 // A sphere of radius zero is a bound that is a point: a rectangle of a few pixels.  Returns 0, or the number of the case that went wrong.
@@ -899,6 +919,13 @@ int kyhip_frame_set_guide_bounces(kyhip_frame*, int bounces) {
 }
 int kyhip_frame_guide_bounces(const kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_guide_chains(kyhip_frame*, uint64_t*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_set_albedo_grid(kyhip_frame*, int grid) {
+    if (grid < 0 || grid > KYHIP_ALBEDO_MAX_GRID) return fail(KY_ERR_INVALID_VALUE, "albedo grid %d: 0 .. %d", grid, KYHIP_ALBEDO_MAX_GRID);
+    return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+}
+int kyhip_frame_albedo_grid(const kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_albedo(kyhip_frame*, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+int kyhip_frame_albedo_ms(const kyhip_frame*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 // (the filter entries refuse an invalid filter before they look for a device or a frame, like the real ones: filter_check is host code; a box filter is the unfiltered entry)
 int kyhip_render_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, float* film, size_t stride) {
     if (filter) KY_TRY(filter_check(filter));

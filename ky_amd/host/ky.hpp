@@ -1021,9 +1021,11 @@ public:
     // samples per pixel are done or the frame is complete -- two passes at least, the filter needs a variance -- then ADDS the picture so far through the
     // edge-avoiding filter (params NULL: kyhip_denoise_defaults) where render_until adds the plain mean.  A frame that is complete behind its first pass (its total is
     // at most one pass long) has one batch only: it is added unfiltered, exactly as render() adds it.  guide_bounces 1 .. KYHIP_GUIDE_MAX_BOUNCES: the filter's
-    // guides follow mirrors and glass that far behind the first hit (kyhip_frame_set_guide_bounces); 0: first-hit guides.  Returns the samples done per pixel.
+    // guides follow mirrors and glass that far behind the first hit (kyhip_frame_set_guide_bounces); 0: first-hit guides.  albedo_grid 1 .. KYHIP_ALBEDO_MAX_GRID: the
+    // filter divides every surface pixel by an albedo of that many sub-samples per pixel edge before its levels and multiplies it back behind them
+    // (kyhip_frame_set_albedo_grid: the scene's textures stay sharp); 0: off.  Returns the samples done per pixel.
     int render_denoised(scene_t* scene, sampler_t* original_sampler, film_t* film, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params = nullptr,
-                        int guide_bounces = 0) {
+                        int guide_bounces = 0, int albedo_grid = 0) {
         if (masked()) throw std::runtime_error("integrator_t::render_denoised: light classes are rendered by render() only");
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
@@ -1033,6 +1035,7 @@ public:
         try {
             if (kyhip_frame_track_noise(frame) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_track_noise: ") + kyhip_last_error());
             if (kyhip_frame_set_guide_bounces(frame, guide_bounces) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_set_guide_bounces: ") + kyhip_last_error());
+            if (kyhip_frame_set_albedo_grid(frame, albedo_grid) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_set_albedo_grid: ") + kyhip_last_error());
             int passes = 0;
             for (; done < p.samples_per_pixel && (passes < 2 || done < stop_after_samples); ++passes)
                 if (kyhip_frame_render(frame, min_samples_per_pass, &done) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_render: ") + kyhip_last_error());

@@ -299,15 +299,23 @@ int kyhost_render_until(void* scene, int integrator_enum, int depth, int direct_
 // create_integrator(...)->render_denoised(&scene, sampler, &film, min_samples_per_pass, stop_after_samples, params) on a film_t of width x height; params may be
 // NULL (the library's defaults).  `film` is read, added to and written back.  Returns the samples done per pixel (>= 1), -1 on error, -2 when create_integrator
 // returns nullptr.  kyhost_render_denoised_chains: ... with render_denoised's guide_bounces (kyhip_frame_set_guide_bounces); the other is its 0.
+// kyhost_render_denoised_albedo: ... and its albedo_grid (kyhip_frame_set_albedo_grid); the other two are its 0.
+int kyhost_render_denoised_albedo(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
+                                  float* film, int device, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params, int guide_bounces,
+                                  int albedo_grid);
 int kyhost_render_denoised_chains(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
-                                  float* film, int device, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params, int guide_bounces);
+                                  float* film, int device, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params, int guide_bounces) {
+    return kyhost_render_denoised_albedo(scene, integrator_enum, depth, direct_sample_enum, sampler_kind, spp, seed, width, height, film, device, min_samples_per_pass,
+                                         stop_after_samples, params, guide_bounces, 0);
+}
 int kyhost_render_denoised(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
                            float* film, int device, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params) {
     return kyhost_render_denoised_chains(scene, integrator_enum, depth, direct_sample_enum, sampler_kind, spp, seed, width, height, film, device, min_samples_per_pass,
                                          stop_after_samples, params, 0);
 }
-int kyhost_render_denoised_chains(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
-                                  float* film, int device, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params, int guide_bounces) {
+int kyhost_render_denoised_albedo(void* scene, int integrator_enum, int depth, int direct_sample_enum, int sampler_kind, int spp, unsigned seed, int width, int height,
+                                  float* film, int device, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params, int guide_bounces,
+                                  int albedo_grid) {
     int status = 0;
     int rc = guarded([&] {
         std::unique_ptr<ky::integrator_t> integrator;
@@ -321,7 +329,7 @@ int kyhost_render_denoised_chains(void* scene, int integrator_enum, int depth, i
         ky::film_t f(width, height);
         const size_t n = (size_t)f.get_pixel_num() * 3;
         std::memcpy(f.data(), film, n * sizeof(float));
-        status = integrator->render_denoised(&((scene_box*)scene)->scene, sampler.get(), &f, min_samples_per_pass, stop_after_samples, params, guide_bounces);
+        status = integrator->render_denoised(&((scene_box*)scene)->scene, sampler.get(), &f, min_samples_per_pass, stop_after_samples, params, guide_bounces, albedo_grid);
         std::memcpy(film, f.data(), n * sizeof(float));
     });
     return rc != 0 ? rc : status;

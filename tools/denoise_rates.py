@@ -5,7 +5,10 @@
 hipEvent time (kyhip_frame_denoise_ms) of the guide trace and of the filter -- gather, levels and add in one span -- for 1 .. 6 levels into a pinned film, so
 that the span holds kernels only: the increment from L - 1 to L levels is the level with step 2^(L - 1), and what one level's span holds beyond an increment is
 the gather and the add.  Next to a 64-sample pass's render kernel (kyhip_kernel_ms) and the noise kernels (kyhip_frame_noise_ms).  Medians of five calls after
-a warm-up.  Then, per guide bounce count 1 .. 4 (kyhip_frame_set_guide_bounces), a frame of its own: the chain trace and the keyed filter the same way."""
+a warm-up.  Then, per guide bounce count 1 .. 4 (kyhip_frame_set_guide_bounces), a frame of its own: the chain trace and the keyed filter the same way.
+  tools/denoise_rates.py albedo cornell|veach [spp]   (profiles/denoise_albedo_rates.txt; DESIGN.md "Denoise", "Albedo") the same two geometries under
+tests/texture_restatement.py's texture sets: the albedo trace (kyhip_frame_albedo_ms) at grids 1, 2, 4 and 8 -- once per frame, so the median over five frames
+each -- next to the guide trace and a 64-sample pass, and the default five-level filter's span with and without demodulation, medians of five calls."""
 import ctypes as C
 import os
 import sys
@@ -13,6 +16,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from ky_amd import api, _abi as A
 
+ALBEDO = sys.argv[1:2] == ["albedo"]
+if ALBEDO:
+    del sys.argv[1]
 what = sys.argv[1] if len(sys.argv) > 1 else "cornell"
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 lib = A.load_kyhip()
@@ -21,6 +27,51 @@ W, H = (1024, 768) if what == "cornell" else (1280, 720)
 scene = api.cornell_box_scene(A.CB_DEFAULT_SCENE, W, H) if what == "cornell" else api.mis_scene(W, H)
 p = api.make_params(W, H, spp)
 film = api.PinnedFilm(H, W)
+
+
+def albedo_rates():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import texture_restatement as X
+    tscene, textures = (X.cornell_case if what == "cornell" else X.veach_case)(A, api, W, H)
+    tx = [t.to_api(api) for t in textures]
+
+    def filter_span(f):
+        f.denoise(film=film.array)   # warm-up; traces the guides and the albedo
+        runs = []
+        for _ in range(5):
+            f.denoise(film=film.array)
+            runs.append(f.denoise_ms()[1])
+        return float(np.median(runs)), runs
+
+    with api.Frame(tscene, p, noise=True, textures=tx) as f:
+        f.render(64)
+        first = api.kernel_ms()
+        f.render(64)
+        print("%s %d x %d under %d textures, %d spp; passes of 64: render kernel %.3f and %.3f ms  [%s]" % (
+            what, W, H, len(tx), spp, first, api.kernel_ms(), lib.kyhip_last_kernel(0).decode()), flush=True)
+        plain, runs = filter_span(f)
+        print("no albedo: guide trace %.4f ms; filter, 5 levels: %.4f ms (five calls: %s)" % (f.denoise_ms()[0], plain, " ".join("%.4f" % r for r in runs)), flush=True)
+    for bounces in (0, 2):
+        for grid in (1, 2, 4, 8):
+            traces, guides, spans = [], [], []
+            for _ in range(5):
+                with api.Frame(tscene, p, noise=True, textures=tx, guide_bounces=bounces, albedo=grid) as f:
+                    f.render(64)
+                    f.render(64)
+                    span, runs = filter_span(f)
+                    traces.append(f.albedo_ms())
+                    guides.append(f.denoise_ms()[0])
+                    spans.append(span)
+            t = float(np.median(traces))
+            print("%d guide bounces, albedo grid %d: albedo trace, once per frame: %.4f ms = %.3f ns per sub-sample = %.3f of a 64-sample pass (five frames: %s); guide "
+                  "trace %.4f ms; demodulated filter, 5 levels: %.4f ms (plain: %.4f ms; five frames: %s)" % (
+                      bounces, grid, t, t * 1e6 / (W * H * grid * grid), t / first, " ".join("%.4f" % r for r in traces), float(np.median(guides)),
+                      float(np.median(spans)), plain, " ".join("%.4f" % r for r in spans)), flush=True)
+
+
+if ALBEDO:
+    albedo_rates()
+    sys.exit(0)
 with api.Frame(scene, p, noise=True) as f:
     f.render(64)
     first = api.kernel_ms()

@@ -9,8 +9,15 @@ Prints the RMSE against a high-sample oracle frame, raw and denoised, at 112, 22
 with specular-chain guides (four guide bounces: the oracle's trace_li under the debug sampler fed to tests/denoise_chains_restatement.py, taps of the same key
 only), for the default scene and for the large mirror ball, at 48, 112, 224 and 500 samples: RMSE over the whole film and over the pixels whose key is not 0.
 
+`albedo` (profiles/denoise_albedo_replay.txt; DESIGN.md "Denoise", "Albedo"): tests/texture_restatement.py's cornell_case -- a checker on the plastic floor, a
+4 x 4 nearest image on the back wall, a checker on a mirror wall -- cut into constant-colour tiles (tiled()), which the unchanged oracle can trace; the same replay
+at the default sigmas with today's filter and with albedo demodulation (tests/denoise_albedo_restatement.py) at albedo grids 1, 2, 4 and 8 and under both variance
+rules (v / Y(a')^2, the one the library uses, and v Y(1 / a')^2).  The albedo is the oracle's camera and scene-intersect KATs at the sub-sample positions with the
+tiled material's colour.  RMSE over the whole film and over the pixels whose centre first hits a textured surface, at 48, 112, 224 and 500 samples.
+
 usage: tools/denoise_replay.py [truth_spp]
-       tools/denoise_replay.py chains [truth_spp]"""
+       tools/denoise_replay.py chains [truth_spp]
+       tools/denoise_replay.py albedo [truth_spp]"""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +34,8 @@ SEEDS = (1234, 101, 202, 303, 404)   # the first three are the GPU test's
 AT = (112, 224, 500)
 PAIRS = [(4.0, 1.0), (1.0, 1.0), (1.5, 1.0), (2.0, 1.0), (1.5, 0.25), (1.5, 0.1), (2.0, 0.25), (3.0, 0.25), (8.0, 1.0)]   # (4, 1): where the scan started; (1.5, 0.25): the defaults
 CHAINS = sys.argv[1:2] == ["chains"]
-if CHAINS:
+ALBEDO = sys.argv[1:2] == ["albedo"]
+if CHAINS or ALBEDO:
     del sys.argv[1]
 TRUTH_SPP = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 
@@ -77,8 +85,60 @@ def replay_chains():
                 d, r[:, 0].min(), r[:, 0].max(), int((r[:, 0] < 1).sum()), len(r), r[:, 1].min(), r[:, 1].max(), int((r[:, 1] < 1).sum()), len(r)))
 
 
+def replay_albedo():
+    import denoise_albedo_restatement as DA
+    import texture_restatement as X
+    at, grids, rules, seeds = (48, 112, 224, 500), (1, 2, 4, 8), ("y2", "inv"), SEEDS[:3]
+    scene, textures = X.cornell_case(A, api, W, H)
+    tiled = X.tiled(A, scene.scene, textures)
+    truth = O.render(tiled, api.make_params(W, H, TRUTH_SPP, seed=987654)).astype(np.float64)
+    ga, gb = D.guides_from_hits(tiled.scene, O.kat_scene_intersect(tiled, D.centre_rays(O.kat_camera, tiled.scene.camera, W, H)), W, H)
+    pix = D.pixel_width(tiled.scene.camera, W)
+    albedo = {g: DA.albedo(O, A, tiled, [], W, H, g, check_clean=False)[0] for g in grids}
+    first = DA.albedo(O, A, scene, textures, W, H, 1, check_clean=False)[2][..., 0]
+    materials = {t.material for t in textures}
+    tex = np.isin(first, [s for s in range(scene.scene.surface_count) if scene.scene.surfaces[s].material in materials])
+    everywhere = np.ones((H, W), bool)
+    print("cornell_case %d x %d tiled (%d surfaces), %d spp, one chunk per pass; truth: the oracle at %d spp; D.DEFAULTS; %d of %d pixels first-hit a textured surface" % (
+        W, H, tiled.scene.surface_count, SPP, TRUTH_SPP, int(tex.sum()), W * H))
+    print("RMSE of clamp01(picture) against the truth.  today = the filter without an albedo; gG = demodulated by a G x G albedo, rule v / Y(a')^2; gG' = rule v Y(1 / a')^2")
+    cols = ["g%d" % g for g in grids] + ["g%d'" % g for g in grids]
+    print(" seed samples where    |     raw    today | " + " ".join("%8s" % c for c in cols) + " | g4 / today  g4 / raw  g1 / today  g4' / g4")
+    table = {}
+    for seed in seeds:
+        frames = DA.replay(O, api, R, tiled, W, H, SPP, seed, at)
+        for d in at:
+            cv = frames[d]
+            today = D.denoise(cv, ga, gb, pix, **D.DEFAULTS)
+            out = {(g, r): DA.denoise(cv, ga, gb, albedo[g], pix, variance=r, **D.DEFAULTS) for g in grids for r in rules}
+            for where, sel in (("film", everywhere), ("textured", tex)):
+                e = {k: DA.rmse(v, truth, sel) for k, v in out.items()}
+                raw, td = DA.rmse(cv, truth, sel), DA.rmse(today, truth, sel)
+                table[(seed, d, where)] = (raw, td, e)
+                print("%5d %7d %-8s | %.5f  %.5f | " % (seed, d, where, raw, td) + " ".join("%8.5f" % e[(g, r)] for r in rules for g in grids) +
+                      " |      %.3f     %.3f       %.3f      %.3f" % (e[(4, "y2")] / td, e[(4, "y2")] / raw, e[(1, "y2")] / td, e[(4, "inv")] / e[(4, "y2")]))
+    for where in ("film", "textured"):
+        print("\n%s pixels, ranges over the %d seeds:" % (where, len(seeds)))
+        for d in at:
+            rows = [table[(s, d, where)] for s in seeds]
+            rng = lambda f: "%.2f - %.2f" % (min(f(*r) for r in rows), max(f(*r) for r in rows))
+            print("  at %3d samples: today / raw %s;  g4 / raw %s;  g4 / today %s;  g1 / raw %s;  g1 / today %s;  g8 / g4 %s;  g4' / g4 %s" % (
+                d, rng(lambda raw, td, e: td / raw), rng(lambda raw, td, e: e[(4, "y2")] / raw), rng(lambda raw, td, e: e[(4, "y2")] / td),
+                rng(lambda raw, td, e: e[(1, "y2")] / raw), rng(lambda raw, td, e: e[(1, "y2")] / td), rng(lambda raw, td, e: e[(8, "y2")] / e[(4, "y2")]),
+                rng(lambda raw, td, e: e[(4, "inv")] / e[(4, "y2")])))
+    n = len(seeds) * len(at)
+    print("\ng4 below today in %d of %d cases on the textured pixels and %d of %d over the film; g4 below g1 in %d of %d (textured) and %d of %d (film)" % (
+        sum(table[(s, d, "textured")][2][(4, "y2")] < table[(s, d, "textured")][1] for s in seeds for d in at), n,
+        sum(table[(s, d, "film")][2][(4, "y2")] < table[(s, d, "film")][1] for s in seeds for d in at), n,
+        sum(table[(s, d, "textured")][2][(4, "y2")] < table[(s, d, "textured")][2][(1, "y2")] for s in seeds for d in at), n,
+        sum(table[(s, d, "film")][2][(4, "y2")] < table[(s, d, "film")][2][(1, "y2")] for s in seeds for d in at), n))
+
+
 if CHAINS:
     replay_chains()
+    sys.exit(0)
+if ALBEDO:
+    replay_albedo()
     sys.exit(0)
 
 scene =api.cornell_box_scene(A.CB_DEFAULT_SCENE, W, H)
