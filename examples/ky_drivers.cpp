@@ -29,6 +29,8 @@
  *                                the edge-avoiding filter (integrator_t::render_denoised), next to the complete frame; writes denoise.bmp: raw | denoised | full
  *                                (a fifth argument, guide_bounces 1 .. 4, adds the filter with specular-chain guides: raw | first-hit | chains | full;
  *                                a sixth, albedo_grid 1 .. 8, one more cell before the full frame: the filter with those guide bounces and albedo demodulation)
+ *   ky_drivers flythrough [frames] [spp] [size]  the Cornell box with both balls along a fixed camera path (8 frames of 16 spp, 512 x 384: a dolly, a move to the right and a
+ *                                pan), guide bounces 1, every frame denoised across the frames before it (history_t; kyhip_frame_denoise_temporal); writes fly_NNN.bmp
  *   ky_drivers sliced [n] [spp] [w] [h]  the same frame by sample range (3 slices, 512 spp, 1024 x 768; kyhip_frame_begin_slice, kyhip_frame_merge_from): the n slices
  *                                render on device 0 one after the other, slice 0 merges the rest; prints per slice its samples and kernel time, the merge times, and
  *                                whether the film is render()'s bit for bit (it must be: exit status 1 otherwise); writes sliced.bmp
@@ -534,6 +536,35 @@ static void render_denoise(int low_spp, int spp, int width, int height, int guid
     film.store_image("denoise");
 }
 
+// A fly-through denoised across its frames (history_t, integrator_t::render_denoised(..., history_t*); include/kyhip.h, kyhip_frame_denoise_temporal): the Cornell
+// box with both balls, guide bounces 1, the camera dollying forwards, moving to its right and panning along a fixed path; every frame has `spp` samples in two
+// passes and a seed of its own, and takes what the frames before it saw of the surfaces it sees.  Writes fly_NNN.bmp per frame.
+static void render_flythrough(int frames, int spp, int size) {
+    const int width = size, height = size * 3 / 4;
+    film_t film(width, height);
+    scene_t scene = scene_t::create_cornell_box_scene(cornell_box_enum_t::both_small_spheres | cornell_box_enum_t::light_area, film.get_resolution());
+    const ky_camera start = scene.flatten().camera;
+    const vec3_t p0{start.position[0], start.position[1], start.position[2]}, f0{start.front[0], start.front[1], start.front[2]};
+    const vec3_t r0 = vec3_t{start.right[0], start.right[1], start.right[2]}.normalize(), up{start.up[0], start.up[1], start.up[2]};
+    const float fov_degree = 2.f * std::atan(up.magnitude()) * 180.f / 3.14159265358979f;
+    history_t history(width, height);
+    std::unique_ptr<integrator_t> integrator = create_integrator(integrator_enum_t::path_tracing_iteration, 5, direct_sample_enum_t::both_mis);
+    float kernel_ms = 0.f;
+    for (int k = 0; k < frames; ++k) {
+        const float s = frames > 1 ? (float)k / (float)(frames - 1) : 0.f;
+        scene.set_camera(std::make_shared<camera_t>(p0 + f0 * (0.6f * s) + r0 * (0.3f * s), f0 + r0 * (0.12f * s), up, fov_degree, film.get_resolution()));
+        film_t frame_film(width, height);
+        random_sampler_t sampler(spp);
+        sampler.set_seed(1234u + (unsigned)k);
+        integrator->render_denoised(&scene, &sampler, &frame_film, std::max(1, (spp + 1) / 2), spp, nullptr, 1, 0, &history);
+        kernel_ms += history.ms();
+        char name[32];
+        std::snprintf(name, sizeof name, "fly_%03d", k);
+        frame_film.store_image(name);
+    }
+    std::printf("flythrough: %d frames of %dx%d at %d spp, guide bounces 1; the temporal kernel took %.3f ms per frame\n", frames, width, height, spp, kernel_ms / (float)frames);
+}
+
 // BASELINE.json configs[4]: the stress frame
 static void render_stress(int spp, int res) {
     film_t film(res, res);
@@ -569,6 +600,10 @@ int main(int argc, char* argv[]) {
         } else if (!std::strcmp(which, "denoise")) {
             render_denoise(argc > 2 ? std::atoi(argv[2]) : 64, argc > 3 ? std::atoi(argv[3]) : 1024, argc > 4 ? std::atoi(argv[4]) : 1024, argc > 5 ? std::atoi(argv[5]) : 768,
                            argc > 6 ? std::atoi(argv[6]) : 0, argc > 7 ? std::atoi(argv[7]) : 0);
+        } else if (!std::strcmp(which, "flythrough")) {
+            const int frames = argc > 2 ? std::atoi(argv[2]) : 8, spp = argc > 3 ? std::atoi(argv[3]) : 16, size = argc > 4 ? std::atoi(argv[4]) : 512;
+            if (frames < 1 || frames > 999 || spp < 2 || size < 16) { std::fprintf(stderr, "flythrough: 1 .. 999 frames, two samples per pixel or more, a film of 16 or more\n"); return 2; }
+            render_flythrough(frames, spp, size);
         } else if (!std::strcmp(which, "stratified")) {
             const bool veach = argc > 2 && !std::strcmp(argv[2], "veach");
             if (argc > 2 && !veach && std::strcmp(argv[2], "cornell")) { std::fprintf(stderr, "stratified: cornell or veach\n"); return 2; }

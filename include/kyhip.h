@@ -636,6 +636,46 @@ int     kyhip_frame_albedo(kyhip_frame* f, float* albedo4, size_t row_stride_px)
 int     kyhip_frame_albedo_ms(const kyhip_frame* f, float* ms);
 
 /*
+ * Temporal reuse: denoise across frames under a moving camera (DESIGN.md section 3 "Denoise", "Temporal").  A kyhip_history is a device-resident object of its
+ * own, independent of any frame's lifetime: per pixel, in film order and double-buffered, the accumulated colour and variance {r, g, b, v}, the accumulated sample
+ * count m (float32; 0: the pixel is nobody's tap), the guides {n, t} and {P} as they stood at the call that wrote them, the camera of that frame, and whether its
+ * colours are albedo-demodulated.  It is no part of any checkpoint: kyhip_frame_state_bytes and saved states do not know of it.
+ * THE CALLER'S CONTRACT: every frame that uses one history renders the SAME scene -- shapes, materials, lights, textures -- and differs in its camera (and seed,
+ * sample counts, filter, lens) only.  Nothing checks this: there are no motion vectors, and moved geometry or lights show as ghosts.
+ *
+ * kyhip_frame_denoise_temporal is kyhip_frame_denoise with one kernel between the gather and the first level.  A class-0 pixel whose chain key is 0 projects its
+ * guide position through the history's camera, takes the up to four history pixels around the landing point (bilinear weights times the level's own normal and
+ * plane-distance weights, with t->normal_squarings and t->sigma_plane: they are the disocclusion test), and where their weight reaches t->min_weight blends their
+ * mean with its own by sample counts: alpha = n / (n + M), M = min(the taps' mean m, t->max_history x n), n the samples the frame holds; the variance follows as
+ * alpha^2 v + (1 - alpha)^2 v_h and the new count is n + M (ky_amd/csrc/ky_denoise.hpp, temporal_pixel_t: double arithmetic, two calls on equal inputs return
+ * identical bytes).  Elsewhere the pixel keeps its own bits with m = n.  Pixels of class 1, 2, 3 and pixels with a non-zero chain key pass through with m = 0: a
+ * virtual image behind a mirror does not reproject by this formula.  The result becomes the history's new side, the levels run on it (the history is not written
+ * by them), then remodulate, clamp and ADD as kyhip_frame_denoise does.  levels == 0 delivers the accumulated picture unfiltered.  With a history that holds no
+ * picture (fresh, or reset) the film is kyhip_frame_denoise's bit for bit at levels >= 1.
+ * A frame with 0 guide bounces is accepted: its mirror and glass pixels then reuse history like any surface, and what they show LAGS the camera.  Use guide
+ * bounces >= 1 where the scene has either.
+ * KY_ERR_INVALID_VALUE, before any device work and with film and history untouched: a NULL frame, history or film; everything kyhip_frame_denoise refuses (its
+ * parameters, a frame that tracks no noise, a shard, fewer than two noise batches); a frame that tracks blocks; a history of another device or size than the
+ * frame's; a frame whose albedo mode (grid 0, or grid > 0) differs from what the history holds; max_history outside (0, 1024], sigma_plane <= 0, min_weight
+ * outside [0, 1), normal_squarings outside 0 .. 10.  p and t may be NULL: the defaults.
+ * kyhip_temporal_defaults: host only.  kyhip_history_create: width, height >= 1.  kyhip_history_reset: the history holds no picture afterwards, and its frame count
+ * is 0.  kyhip_history_frames: the temporal calls since create / reset, or KY_ERR_INVALID_VALUE for a NULL history.  kyhip_history_read: WRITES width x height
+ * float4 {r, g, b, v} (row_stride_px float4 apart) and width x height float counts (row_stride_px floats apart), either pointer may be NULL; zeros while the
+ * history holds no picture.  kyhip_history_ms: the hipEvent span of the last temporal kernel, negative where there was none.
+ */
+typedef struct kyhip_history kyhip_history;
+typedef struct ky_temporal_params { float max_history, sigma_plane, min_weight; int32_t normal_squarings; } ky_temporal_params;
+void    kyhip_temporal_defaults(ky_temporal_params* out);
+int     kyhip_history_create(int device, int width, int height, kyhip_history** out);
+int     kyhip_history_destroy(kyhip_history* h);
+int     kyhip_history_reset(kyhip_history* h);
+int     kyhip_history_frames(const kyhip_history* h);
+int     kyhip_history_read(kyhip_history* h, float* colour_variance4, float* count, size_t row_stride_px);
+int     kyhip_history_ms(const kyhip_history* h, float* ms);
+int     kyhip_frame_denoise_temporal(kyhip_frame* f, kyhip_history* h, const ky_denoise_params* p, const ky_temporal_params* t, float* film_rgb,
+                                     size_t film_row_stride_px);
+
+/*
  * Slices: a frame's sample ranges rendered apart and merged, bit for bit (DESIGN.md section 3 "Slices").  A pixel's samples are keyed by their absolute index,
  * cut into chunks by a schedule of samples_per_pixel alone, and every chunk sum enters a 64-bit integer word scaled by 1 / total under the WHOLE frame's term
  * limit: frames of one (scene, params) that rendered disjoint sets of chunks hold words whose integer sum is the word of one frame that rendered them all, in

@@ -92,6 +92,10 @@ class DenoiseParams(C.Structure):   # ky_denoise_params
     _fields_ = [("levels", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_plane", C.c_float)]
 
 
+class TemporalParams(C.Structure):   # ky_temporal_params
+    _fields_ = [("max_history", C.c_float), ("sigma_plane", C.c_float), ("min_weight", C.c_float), ("normal_squarings", C.c_int32)]
+
+
 class PixelFilter(C.Structure):   # ky_pixel_filter
     _fields_ = [("kind", C.c_int32), ("radius", C.c_float), ("param", C.c_float), ("reserved", C.c_int32)]
 
@@ -202,6 +206,14 @@ KYHIP_SYMBOLS = {
     "kyhip_frame_albedo_grid": (C.c_int, [C.c_void_p]),
     "kyhip_frame_albedo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "kyhip_frame_albedo_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "kyhip_temporal_defaults": (None, [C.POINTER(TemporalParams)]),
+    "kyhip_history_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "kyhip_history_destroy": (C.c_int, [C.c_void_p]),
+    "kyhip_history_reset": (C.c_int, [C.c_void_p]),
+    "kyhip_history_frames": (C.c_int, [C.c_void_p]),
+    "kyhip_history_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "kyhip_history_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "kyhip_frame_denoise_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(TemporalParams), C.c_void_p, C.c_size_t]),
     "kyhip_slice_bounds": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "kyhip_frame_begin_slice": (C.c_int, [C.c_int, SP, PP, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "kyhip_frame_coverage": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
@@ -319,6 +331,9 @@ KYHOSTCHECK_SYMBOLS = {   # ky_amd/csrc/ky_hostcheck.cpp: present in the sanitiz
     "kyhostcheck_denoise_keyed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_double, C.c_void_p]),
     "kyhostcheck_denoise_albedo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_double,
                                              C.c_void_p]),
+    "kyhostcheck_temporal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                       C.POINTER(TemporalParams), C.c_double, C.POINTER(Camera), C.c_void_p, C.c_void_p]),
+    "kyhostcheck_temporal_refusal": (C.c_int, [PP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "kyhostcheck_slices": (C.c_int, [C.c_int, PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "kyhostcheck_filter": (C.c_int, []),

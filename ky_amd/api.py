@@ -276,6 +276,60 @@ def denoise_defaults():
     return q
 
 
+def temporal_defaults():
+    """kyhip_temporal_defaults (host only) as a ky_temporal_params (_abi.TemporalParams)."""
+    t = A.TemporalParams()
+    A.load_kyhip().kyhip_temporal_defaults(C.byref(t))
+    return t
+
+
+class History:
+    """What frames of ONE scene under a moving camera hand to each other (kyhip_history_*): `with History(w, h) as hist: ... f.denoise(history=hist)` for frame
+    after frame.  Per pixel the accumulated colour, variance and sample count, the guides and the camera of the frame that wrote them; on the device, independent
+    of any frame's lifetime, no part of a checkpoint.  The scene being the same but for the camera is the caller's contract.  reset(): it holds no picture
+    afterwards; frames: the temporal calls since; read(): ((H, W, 4) {r, g, b, v}, (H, W) counts); ms(): the last temporal kernel's span."""
+
+    def __init__(self, width, height, device=0):
+        self._lib = A.load_kyhip()
+        self._h = C.c_void_p()
+        self.width, self.height = int(width), int(height)
+        _check(self._lib.kyhip_history_create(int(device), self.width, self.height, C.byref(self._h)), self._lib)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.kyhip_history_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def reset(self):
+        _check(self._lib.kyhip_history_reset(self._h), self._lib)
+
+    @property
+    def frames(self):
+        n = self._lib.kyhip_history_frames(self._h)
+        if n < 0:
+            _check(n, self._lib)
+        return n
+
+    def read(self):
+        cv, m = np.zeros((self.height, self.width, 4), np.float32), np.zeros((self.height, self.width), np.float32)
+        _check(self._lib.kyhip_history_read(self._h, C.c_void_p(cv.ctypes.data), C.c_void_p(m.ctypes.data), self.width), self._lib)
+        return cv, m
+
+    def ms(self):
+        a = C.c_float(-1)
+        _check(self._lib.kyhip_history_ms(self._h, C.byref(a)), self._lib)
+        return a.value
+
+
 class Frame:
     """A frame rendered in passes (kyhip_frame_*): `with Frame(scene, params) as f: f.render(64); preview = f.resolve(normalise=True); ...`.
     params.samples_per_pixel is the frame's total; a complete frame's resolve() is render(scene, params), bit for bit.
@@ -505,20 +559,34 @@ class Frame:
         _check(self._lib.kyhip_frame_block_stats(self._f, C.byref(st)), self._lib)
         return st
 
-    def denoise(self, params=None, film=None, row_stride_px=None, origin_px=(0, 0)):
+    def denoise(self, params=None, film=None, row_stride_px=None, origin_px=(0, 0), history=None, temporal=None):
         """ADDS the denoised picture so far to `film` (a new zero film by default) and returns it (kyhip_frame_denoise): resolve(normalise=True) through an
         edge-avoiding a-trous filter guided by the frame's variance estimate and its first-hit geometry (guide_bounces: the geometry its specular chains end on).  params: a ky_denoise_params (_abi.DenoiseParams) or a dict
-        of its fields over denoise_defaults(); None: the defaults.  levels=0 is resolve(normalise=True)."""
+        of its fields over denoise_defaults(); None: the defaults.  levels=0 is resolve(normalise=True).
+        history=History(...): kyhip_frame_denoise_temporal -- before the levels every surface pixel is blended with what the history's frames of the same scene
+        saw of its point, and the history takes the result; temporal: a ky_temporal_params (_abi.TemporalParams) or a dict of its fields over
+        temporal_defaults().  levels=0 then delivers the accumulated picture unfiltered."""
         if isinstance(params, dict):
             q = denoise_defaults()
             for name, value in params.items():
                 setattr(q, name, value)
             params = q
+        if isinstance(temporal, dict):
+            t = temporal_defaults()
+            for name, value in temporal.items():
+                setattr(t, name, value)
+            temporal = t
+        if history is None and temporal is not None:
+            raise ValueError("temporal parameters without a history")
         if film is None:
             film = np.zeros((self.height, self.width, 3), np.float32)
         stride = film.shape[1] if row_stride_px is None else row_stride_px
         base = film.ctypes.data + (origin_px[1] * stride + origin_px[0]) * 12
-        _check(self._lib.kyhip_frame_denoise(self._f, None if params is None else C.byref(params), C.c_void_p(base), stride), self._lib)
+        if history is None:
+            _check(self._lib.kyhip_frame_denoise(self._f, None if params is None else C.byref(params), C.c_void_p(base), stride), self._lib)
+        else:
+            _check(self._lib.kyhip_frame_denoise_temporal(self._f, history._h, None if params is None else C.byref(params),
+                                                          None if temporal is None else C.byref(temporal), C.c_void_p(base), stride), self._lib)
         return film
 
     def guides(self):

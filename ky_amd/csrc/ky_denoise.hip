@@ -15,7 +15,9 @@
  *   denoise_albedo_kernel   once per frame with an albedo grid (kyhip_frame_set_albedo_grid), one thread per film pixel: grid x grid camera rays per pixel through
  *                           the frame's camera form, each walked like the chain guides' ray -> the mean colour of what they end on, {r, g, b, count};
  *   denoise_gather_albedo_kernel / denoise_add_albedo_kernel   the gather and the add of such a frame: a class-0 pixel is divided by its albedo before the
- *                           levels and multiplied by it behind them (demodulate_pixel / remodulate_pixel, ky_denoise.hpp); the level kernels are the same.
+ *                           levels and multiplied by it behind them (demodulate_pixel / remodulate_pixel, ky_denoise.hpp); the level kernels are the same;
+ *   denoise_temporal_kernel one thread per film pixel between the gather and the first level of kyhip_frame_denoise_temporal: temporal_pixel_t (ky_denoise.hpp) from the
+ *                           frame's buffers and a history's old side into its new side; at most four taps of three 16-byte loads.
  * No floating-point atomics and no order that depends on scheduling: two calls return identical bytes.  gfx950 only.
  */
 #include <hip/hip_runtime.h>
@@ -256,6 +258,22 @@ __global__ __launch_bounds__(KY_DN_BLOCK) void denoise_add_albedo_kernel(const P
     px[0] += fminf(fmaxf(c.x, 0.f), 1.f); px[1] += fminf(fmaxf(c.y, 0.f), 1.f); px[2] += fminf(fmaxf(c.z, 0.f), 1.f);
 }
 
+// Temporal reuse (kyhip_frame_denoise_temporal; DESIGN.md "Denoise", "Temporal"): one thread per film pixel between the gather and the first level.  It reads the
+// frame's three Px4 at the pixel (and its key when KEYED) and at most four taps of three Px4 from the history's old side -- bounds-checked inside temporal_pixel_t,
+// and not at all while the history holds no picture -- and writes the history's new side whole.  No LDS, no atomics, the taps in one order.
+template <bool KEYED>
+__global__ __launch_bounds__(KY_DN_BLOCK) void denoise_temporal_kernel(const Px4* __restrict__ cv, const Px4* __restrict__ ga, const Px4* __restrict__ gb,
+                                                                        const uint64_t* __restrict__ key, const Px4* __restrict__ hcv, const Px4* __restrict__ hga,
+                                                                        const Px4* __restrict__ hgb, Px4* __restrict__ ncv, Px4* __restrict__ nga, Px4* __restrict__ ngb,
+                                                                        TemporalConst k) {
+    const int i = blockIdx.x * KY_DN_BLOCK + threadIdx.x;
+    if (i >= k.width * k.height) return;
+    const TemporalPixel o = temporal_pixel_t<KEYED>(cv, ga, gb, key, hcv, hga, hgb, i % k.width, i / k.width, k);
+    ncv[i] = o.cv;
+    nga[i] = ga[i];
+    ngb[i] = o.gb;
+}
+
 namespace kydn {
 static dim3 film_grid(int width, int height) { return dim3((unsigned)((width * height + KY_DN_BLOCK - 1) / KY_DN_BLOCK)); }
 
@@ -338,6 +356,19 @@ int denoise_level_keyed_device(const void* cv_in, void* cv_out, const void* ga, 
     if (k.width <= 0 || k.height <= 0) return KY_OK;
     hipLaunchKernelGGL(denoise_level_keyed_kernel, film_grid(k.width, k.height), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, (const Px4*)cv_in, (Px4*)cv_out,
                        (const Px4*)ga, (const Px4*)gb, (const uint64_t*)key, step, k);
+    HIP_TRY(hipGetLastError());
+    return KY_OK;
+}
+
+int denoise_temporal_device(const void* cv, const void* ga, const void* gb, const void* key, const void* hcv, const void* hga, const void* hgb, void* ncv, void* nga,
+                            void* ngb, const TemporalConst& k, void* stream) {
+    if (k.width <= 0 || k.height <= 0) return KY_OK;
+    if (key)
+        hipLaunchKernelGGL(denoise_temporal_kernel<true>, film_grid(k.width, k.height), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, (const Px4*)cv, (const Px4*)ga,
+                           (const Px4*)gb, (const uint64_t*)key, (const Px4*)hcv, (const Px4*)hga, (const Px4*)hgb, (Px4*)ncv, (Px4*)nga, (Px4*)ngb, k);
+    else
+        hipLaunchKernelGGL(denoise_temporal_kernel<false>, film_grid(k.width, k.height), dim3(KY_DN_BLOCK), 0, (hipStream_t)stream, (const Px4*)cv, (const Px4*)ga,
+                           (const Px4*)gb, (const uint64_t*)nullptr, (const Px4*)hcv, (const Px4*)hga, (const Px4*)hgb, (Px4*)ncv, (Px4*)nga, (Px4*)ngb, k);
     HIP_TRY(hipGetLastError());
     return KY_OK;
 }

@@ -7,6 +7,7 @@
  * be restated, double division is -- and what one level hands to the next is stored as float32.  Plain C++: part of `make sanitize`.
  */
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #include "ky_noise.hpp"   // ky_shard.hpp, KY_NOFMA_*, noise_pixel_xy
@@ -175,6 +176,105 @@ constexpr uint64_t KY_DN_KEY_UNRESOLVED = (uint64_t)1 << 62;
 KY_HD inline uint64_t chain_digit(int surface, bool reflected) { return ((uint64_t)(surface + 1) << 1) | (reflected ? 0u : 1u); }
 KY_HD inline uint64_t chain_unresolved(uint64_t key) { return KY_DN_KEY_UNRESOLVED | (key & (((uint64_t)1 << KY_DN_KEY_DIGIT_BITS) - 1)); }
 
+// ---- temporal reuse (DESIGN.md "Denoise", "Temporal"; kyhip_frame_denoise_temporal) ----
+// A history (kyhip_history) holds, in film order, what an earlier frame of the SAME scene under another camera left: hcv {r, g, b, v} accumulated, hga {n, t} and
+// hgb {P, m} -- the class slot of guide B holds the accumulated sample count m (m > 0 says "class 0, key 0"; m = 0: nobody's tap, which is all a later frame asks).
+// A class-0 pixel p of the current frame (key 0 where the frame is keyed) projects its point P_p through the HISTORY's camera (o', f', r', u' as ky_camera stores
+// them), takes the up to four history pixels around the landing point as taps, and blends what they hold with its own mean, weighted by sample counts:
+//   d = P_p - o',  z = d . f'   (history only if z > 0)
+//   a = (d . r') / (r' . r'),  b = (d . u') / (u' . u'),  sx = W (0.5 + a / z) - 0.5,  sy = H (0.5 - b / z) - 0.5     (pixel (i, j)'s centre: sx = i, sy = j)
+//   i0 = floor(sx), fx = sx - i0, j0 = floor(sy), fy = sy - j0   (a landing point with no tap inside the film, -1 < sx < W and -1 < sy < H failing, takes none)
+//   tap q = (i0 + di, j0 + dj), dj outer, di inner, inside the film and m_q > 0:
+//     h  = (di ? fx : 1 - fx) (dj ? fy : 1 - fy)
+//     wn = max(0, n_p . n_q) squared normal_squarings times
+//     wp = 1 / (1 + xp^2)^2,  xp = n_p . (P_q - P_p) / max(sigma_plane t_p pix, 1e-300)          (the level's own plane and normal tests: the disocclusion test)
+//     w  = h wn wp
+//   sw = sum w; history is refused unless sw > 0 and sw >= min_weight
+//   c_h = sum w c_q / sw,  v_h = sum w^2 v_q / sw^2,  m_h = sum w m_q / sw
+//   M = min(m_h, max_history n_p),  alpha = n_p / (n_p + M)
+//   c = alpha c_p + (1 - alpha) c_h,  v = alpha^2 v_p + (1 - alpha)^2 v_h,  m = n_p + M
+// Without history the pixel keeps the gather's bits and m = n_p.  A pixel that is not class 0, or whose key is not 0, passes through with m = 0: it neither gives
+// nor takes history (a virtual image behind a mirror does not reproject by this formula).  n_p: the samples the frame holds (one count: no blocks here).
+struct TemporalConst {
+    int width, height;
+    int normal_squarings, has_history;   // has_history 0: the history holds no picture, nothing of its buffers is read
+    double n_p;                          // the samples per pixel the current frame holds
+    double max_history, sigma_plane, min_weight;
+    double pix;                          // the CURRENT camera's pixel width at unit distance (denoise_pixel_width)
+    ky_camera then;                      // the camera of the frame that wrote the history
+};
+struct TemporalPixel {
+    Px4 cv, gb;   // the history's new {r, g, b, v} and {P, m}
+};
+template <bool KEYED>
+KY_NOFMA_FN KY_HD inline TemporalPixel temporal_pixel_t(const Px4* __restrict__ cv, const Px4* __restrict__ ga, const Px4* __restrict__ gb, const uint64_t* __restrict__ key,
+                                                        const Px4* __restrict__ hcv, const Px4* __restrict__ hga, const Px4* __restrict__ hgb, int x, int y,
+                                                        const TemporalConst& k) {
+    KY_NOFMA_BODY
+    const size_t at = (size_t)y * (size_t)k.width + (size_t)x;
+    const Px4 cp = cv[at], bp = gb[at];
+    TemporalPixel o;
+    o.cv = cp;
+    o.gb = Px4{bp.x, bp.y, bp.z, 0.f};
+    if (!is_surface(bp)) return o;
+    if (KEYED && key[at] != 0) return o;
+    o.gb.w = (float)k.n_p;
+    if (!k.has_history) return o;
+    const Px4 ap = ga[at];
+    const double dx = (double)bp.x - (double)k.then.position[0], dy = (double)bp.y - (double)k.then.position[1], dz = (double)bp.z - (double)k.then.position[2];
+    const double fx_ = (double)k.then.front[0], fy_ = (double)k.then.front[1], fz_ = (double)k.then.front[2];
+    const double rx = (double)k.then.right[0], ry = (double)k.then.right[1], rz = (double)k.then.right[2];
+    const double ux = (double)k.then.up[0], uy = (double)k.then.up[1], uz = (double)k.then.up[2];
+    const double z = dx * fx_ + dy * fy_ + dz * fz_;
+    if (!(z > 0.0)) return o;
+    const double a = (dx * rx + dy * ry + dz * rz) / (rx * rx + ry * ry + rz * rz);
+    const double b = (dx * ux + dy * uy + dz * uz) / (ux * ux + uy * uy + uz * uz);
+    const double sx = (double)k.width * (0.5 + a / z) - 0.5;
+    const double sy = (double)k.height * (0.5 - b / z) - 0.5;
+    if (!(sx > -1.0 && sx < (double)k.width && sy > -1.0 && sy < (double)k.height)) return o;   // (also a NaN: no tap inside the film)
+    const double fi = floor(sx), fj = floor(sy);
+    const double fx = sx - fi, fy = sy - fj;
+    const int i0 = (int)fi, j0 = (int)fj;
+    const double plane_raw = k.sigma_plane * (double)ap.w * k.pix;
+    const double plane_den = plane_raw > 1e-300 ? plane_raw : 1e-300;
+    const double npx = (double)ap.x, npy = (double)ap.y, npz = (double)ap.z;
+    double sw = 0.0, sr = 0.0, sg = 0.0, sb = 0.0, sv = 0.0, sm = 0.0;
+    for (int dj = 0; dj <= 1; ++dj)
+        for (int di = 0; di <= 1; ++di) {
+            const int qx = i0 + di, qy = j0 + dj;
+            if (qx < 0 || qy < 0 || qx >= k.width || qy >= k.height) continue;
+            const size_t q = (size_t)qy * (size_t)k.width + (size_t)qx;
+            const Px4 bq = hgb[q];
+            if (!(bq.w > 0.f)) continue;
+            const Px4 aq = hga[q], cq = hcv[q];
+            const double h = (di ? fx : 1.0 - fx) * (dj ? fy : 1.0 - fy);
+            const double nd = npx * (double)aq.x + npy * (double)aq.y + npz * (double)aq.z;
+            double wn = nd > 0.0 ? nd : 0.0;
+            for (int s = 0; s < k.normal_squarings; ++s) wn = wn * wn;
+            const double ex = (double)bq.x - (double)bp.x, ey = (double)bq.y - (double)bp.y, ez = (double)bq.z - (double)bp.z;
+            const double xp = (npx * ex + npy * ey + npz * ez) / plane_den;
+            const double pa = 1.0 + xp * xp;
+            const double wp = 1.0 / (pa * pa);
+            const double w = h * wn * wp;
+            sw = sw + w;
+            sr = sr + w * (double)cq.x;
+            sg = sg + w * (double)cq.y;
+            sb = sb + w * (double)cq.z;
+            sv = sv + w * w * (double)cq.w;
+            sm = sm + w * (double)bq.w;
+        }
+    if (!(sw > 0.0 && sw >= k.min_weight)) return o;
+    const double m_h = sm / sw, m_cap = k.max_history * k.n_p;
+    const double M = m_h < m_cap ? m_h : m_cap;
+    const double alpha = k.n_p / (k.n_p + M), beta = 1.0 - alpha;
+    o.cv.x = (float)(alpha * (double)cp.x + beta * (sr / sw));
+    o.cv.y = (float)(alpha * (double)cp.y + beta * (sg / sw));
+    o.cv.z = (float)(alpha * (double)cp.z + beta * (sb / sw));
+    o.cv.w = (float)(alpha * alpha * (double)cp.w + beta * beta * (sv / (sw * sw)));
+    o.gb.w = (float)(k.n_p + M);
+    return o;
+}
+
 // ---- the kernels (ky_denoise.hip); every pointer is device memory, `stream` a hipStream_t ----
 constexpr int KY_DN_BLOCK = 256;
 // guides of the whole film, traced once per frame: ga = {n, t}, gb = {P, class 0 / 1 / 2}.  Uploads the scene, enqueues and WAITS (the scene cache's slot is held
@@ -204,4 +304,9 @@ int denoise_albedo_device(int device, const ky_scene* scene, int width, int heig
 int denoise_gather_albedo_device(const void* ws, const void* noise_state, const void* blocks, const ShardConst& sh, int width, int height, int total_spp, int n_done,
                                  int batches, const void* gb_traced, const void* albedo, void* cv, void* gb, void* stream);
 int denoise_add_albedo_device(const void* cv, const void* gb, const void* albedo, float* film, size_t stride_px, int width, int height, void* stream);
+// ---- temporal reuse (kyhip_frame_denoise_temporal) ----
+// temporal_pixel_t over the film: the frame's cv / ga / gb (key: NULL, or the chain keys of a frame with guide bounces) and the history's OLD side (hcv, hga, hgb;
+// not read when k.has_history is 0) -> the history's NEW side: ncv = the blended {r, g, b, v}, nga = the frame's {n, t}, ngb = {P, m}
+int denoise_temporal_device(const void* cv, const void* ga, const void* gb, const void* key, const void* hcv, const void* hga, const void* hgb, void* ncv, void* nga,
+                            void* ngb, const TemporalConst& k, void* stream);
 }  // namespace kydn

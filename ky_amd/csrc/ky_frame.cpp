@@ -82,6 +82,19 @@ struct kyhip_frame {
     TimedSpan merge;              // the last merge kernel (kyhip_frame_merge_ms)
 };
 
+// What frames of one scene under a moving camera hand to each other (kyhip_history_*; DESIGN.md "Denoise", "Temporal"): no part of a frame and of no checkpoint.
+// Film order, double-buffered: a temporal call reads side `side`, writes the other and swaps behind its wait.
+struct kyhip_history {
+    int device = 0, width = 0, height = 0;
+    int frames = 0;                    // temporal calls since create / reset; 0: the history holds no picture
+    int side = 0;
+    int albedo = -1;                   // whether its colours are albedo-demodulated (0 / 1); -1 while it holds no picture
+    ky_camera camera{};                // of the frame that wrote side `side`
+    DevBuf cv[2], ga[2], gb[2];        // width x height Px4 each: {r, g, b, v} accumulated; {n, t}; {P, m} (the accumulated sample count in the class slot)
+    std::vector<float> hcv, hgb;       // host copies (kyhip_history_read)
+    TimedSpan span;                    // the last temporal kernel (kyhip_history_ms)
+};
+
 static const void* block_state_or_null(const kyhip_frame* f) { return f->book.blocks.on ? f->blocks.state.p : nullptr; }
 
 // Waits for what was enqueued on `stream`, also after a failed enqueue, whose status `rcode` comes first; then the device's, as "<what> failed: <error><tail>"
@@ -694,6 +707,134 @@ int kyhip_frame_denoise(kyhip_frame* f, const ky_denoise_params* params, float* 
         if (d.albedo_grid > 0) return denoise_add_albedo_device(result, d.gb.p, d.albedo.p, dst, dst_stride, p->width, p->height, c->stream);
         return denoise_add_device(result, dst, dst_stride, p->width, p->height, c->stream);   // film order already
     });
+}
+
+// ---- temporal reuse (DESIGN.md "Denoise", "Temporal"; kyhip_temporal_defaults is host code: ky_pack.cpp) ----
+// Every refusal comes before any device work; the history is committed (side, camera, mode, count) only behind the wait for a call that was enqueued whole.
+
+int kyhip_history_create(int device, int width, int height, kyhip_history** out) {
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    *out = nullptr;
+    if (width < 1 || height < 1 || (long long)width * height > (1ll << 28)) return fail(KY_ERR_INVALID_VALUE, "a history of %d x %d pixels", width, height);
+    DeviceCtx* c;
+    KY_TRY(get_ctx(device, &c));
+    std::unique_ptr<kyhip_history> h(new kyhip_history);
+    h->device = device; h->width = width; h->height = height;
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(Px4);
+    for (int s = 0; s < 2; ++s)
+        for (DevBuf* b : {&h->cv[s], &h->ga[s], &h->gb[s]}) HIP_TRY(b->alloc(bytes));
+    KY_TRY(h->span.create());
+    *out = h.release();
+    return KY_OK;
+}
+
+int kyhip_history_destroy(kyhip_history* h) {
+    if (!h) return fail(KY_ERR_INVALID_VALUE, "history is NULL");
+    DeviceCtx* c;
+    if (get_ctx(h->device, &c) == KY_OK) (void)hipStreamSynchronize(c->stream);   // (the device is current for the buffers' release)
+    delete h;
+    return KY_OK;
+}
+
+int kyhip_history_reset(kyhip_history* h) {
+    if (!h) return fail(KY_ERR_INVALID_VALUE, "history is NULL");
+    h->frames = 0;
+    h->albedo = -1;
+    return KY_OK;
+}
+
+int kyhip_history_frames(const kyhip_history* h) {
+    if (!h) return fail(KY_ERR_INVALID_VALUE, "history is NULL");
+    return h->frames;
+}
+
+int kyhip_history_read(kyhip_history* h, float* colour_variance4, float* count, size_t stride_px) {
+    if (!h) return fail(KY_ERR_INVALID_VALUE, "history is NULL");
+    if (stride_px < (size_t)h->width) return fail(KY_ERR_INVALID_VALUE, "row_stride_px %zu: the history's rows are %d pixels", stride_px, h->width);
+    const size_t n = (size_t)h->width * (size_t)h->height * 4;
+    h->hcv.assign(n, 0.f);
+    h->hgb.assign(n, 0.f);
+    if (h->frames > 0) {
+        DeviceCtx* c;
+        KY_TRY(get_ctx(h->device, &c));
+        HIP_TRY(hipMemcpy(h->hcv.data(), h->cv[h->side].p, n * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h->hgb.data(), h->gb[h->side].p, n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    for (int y = 0; y < h->height; ++y) {
+        if (colour_variance4) std::memcpy(colour_variance4 + (size_t)y * stride_px * 4, h->hcv.data() + (size_t)y * h->width * 4, (size_t)h->width * 4 * sizeof(float));
+        if (count)
+            for (int x = 0; x < h->width; ++x) count[(size_t)y * stride_px + (size_t)x] = h->hgb[((size_t)y * h->width + (size_t)x) * 4 + 3];
+    }
+    return KY_OK;
+}
+
+int kyhip_history_ms(const kyhip_history* h, float* ms) {
+    if (!h) return fail(KY_ERR_INVALID_VALUE, "history is NULL");
+    if (ms) *ms = h->span.ms();
+    return KY_OK;
+}
+
+int kyhip_frame_denoise_temporal(kyhip_frame* f, kyhip_history* h, const ky_denoise_params* params, const ky_temporal_params* temporal, float* film_rgb, size_t stride_px) {
+    ky_denoise_params q;
+    kyhip_denoise_defaults(&q);
+    if (params) q = *params;
+    ky_temporal_params t;
+    kyhip_temporal_defaults(&t);
+    if (temporal) t = *temporal;
+    KY_TRY(denoise_params_check(&q));
+    KY_TRY(temporal_params_check(&t));
+    if (!f) return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+    if (!h) return fail(KY_ERR_INVALID_VALUE, "history is NULL");
+    DenoiseTrack& d = f->denoise;
+    KY_TRY(f->book.temporal_check(f->device, d.albedo_grid, h->device, h->width, h->height, h->frames > 0 ? h->albedo : -1));
+    const ky_render_params* p = &f->book.params;
+    if (!film_rgb || stride_px < (size_t)p->width) return fail(KY_ERR_INVALID_VALUE, "bad film arguments");
+    if (f->book.sh.n_pix == 0) return KY_OK;
+    DeviceCtx* c;
+    KY_TRY(get_ctx(f->device, &c));
+    int rcode = denoise_prepare(f, c, true);
+    if (rcode != KY_OK) return finish(c->stream, rcode, "denoise");   // (nothing of the filter is enqueued; its span stays invalid)
+    TemporalConst tk{};
+    tk.width = p->width; tk.height = p->height;
+    tk.normal_squarings = t.normal_squarings;
+    tk.has_history = h->frames > 0 ? 1 : 0;
+    tk.n_p = (double)f->book.held();
+    tk.max_history = (double)t.max_history; tk.sigma_plane = (double)t.sigma_plane; tk.min_weight = (double)t.min_weight;
+    tk.pix = denoise_pixel_width(f->scene.camera, p->width);
+    tk.then = h->camera;
+    const int from = h->side, to = h->side ^ 1;
+    h->span.begin(c->stream);
+    rcode = denoise_temporal_device(d.cv[0].p, d.ga.p, d.gb.p, d.guide_bounces > 0 ? d.key.p : nullptr, h->cv[from].p, h->ga[from].p, h->gb[from].p, h->cv[to].p, h->ga[to].p,
+                                    h->gb[to].p, tk, c->stream);
+    h->span.end(c->stream);
+    LevelConst k{};
+    k.width = p->width; k.height = p->height;
+    k.normal_squarings = q.normal_squarings;
+    k.sigma_l2 = (double)q.sigma_luminance * (double)q.sigma_luminance;
+    k.sigma_plane = (double)q.sigma_plane;
+    k.pix = tk.pix;
+    // the levels read the history's new side first and ping-pong between the frame's own buffers from then on: nothing filtered is fed back into the history
+    for (int l = 0; l < q.levels && rcode == KY_OK; ++l) {
+        const void* in = l == 0 ? h->cv[to].p : d.cv[l & 1].p;
+        rcode = d.guide_bounces > 0 ? denoise_level_keyed_device(in, d.cv[(l + 1) & 1].p, d.ga.p, d.gb.p, d.key.p, 1 << l, k, c->stream)
+                                    : denoise_level_device(in, d.cv[(l + 1) & 1].p, d.ga.p, d.gb.p, 1 << l, k, c->stream);
+    }
+    const void* result = q.levels == 0 ? h->cv[to].p : d.cv[q.levels & 1].p;
+    const bool enqueued = rcode == KY_OK;
+    rcode = deliver(f, c->stream, rcode, "denoise", &d.filter, film_rgb, stride_px, [&](float* dst, size_t dst_stride) {
+        if (d.albedo_grid > 0) return denoise_add_albedo_device(result, d.gb.p, d.albedo.p, dst, dst_stride, p->width, p->height, c->stream);
+        return denoise_add_device(result, dst, dst_stride, p->width, p->height, c->stream);
+    });
+    if (!enqueued || rcode != KY_OK) {   // the history keeps its old side: a failed call is not counted
+        h->span.valid = false;
+        return rcode;
+    }
+    h->span.valid = true;
+    h->side = to;
+    h->camera = f->scene.camera;
+    h->albedo = d.albedo_grid > 0 ? 1 : 0;
+    ++h->frames;
+    return KY_OK;
 }
 
 int kyhip_frame_guides(kyhip_frame* f, float* normal_t4, float* position_class4, size_t stride_px) {

@@ -452,6 +452,18 @@ int FrameBook::denoise_check(bool needs_variance) const {
     return KY_OK;
 }
 
+int FrameBook::temporal_check(int device, int albedo_grid, int hist_device, int hist_width, int hist_height, int hist_albedo) const {
+    KY_TRY(denoise_check(true));
+    if (blocks.on) return fail(KY_ERR_INVALID_VALUE, "the frame tracks blocks: a history holds one sample count per pixel, not per block");
+    if (hist_device != device) return fail(KY_ERR_INVALID_VALUE, "the history lives on device %d, the frame on device %d", hist_device, device);
+    if (hist_width != params.width || hist_height != params.height)
+        return fail(KY_ERR_INVALID_VALUE, "the history is %d x %d, the frame %d x %d", hist_width, hist_height, params.width, params.height);
+    if (hist_albedo >= 0 && hist_albedo != (albedo_grid > 0 ? 1 : 0))
+        return fail(KY_ERR_INVALID_VALUE, "the history holds %s colours, the frame's albedo grid is %d: reset the history or keep the mode",
+                    hist_albedo ? "albedo-demodulated" : "plain", albedo_grid);
+    return KY_OK;
+}
+
 int FrameBook::save_host(void* buf, size_t bytes) const {
     if (!buf || bytes < layout.total) return fail(KY_ERR_INVALID_VALUE, "frame state: a buffer of %zu bytes, the state has %zu", bytes, layout.total);
     CheckpointCounts n;

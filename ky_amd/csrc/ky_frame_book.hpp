@@ -82,6 +82,9 @@ struct FrameBook {
     int can_track_blocks() const;
     int resolve(int normalise, const float* film_rgb, size_t stride_px, ResolveStep* out) const;
     int denoise_check(bool needs_variance) const;
+    // kyhip_frame_denoise_temporal behind its NULL arguments and parameters: denoise_check(true), then a frame that tracks blocks, then a history of another
+    // device, size or albedo mode than this frame's (hist_albedo: -1 while the history holds no picture, else 0 / 1)
+    int temporal_check(int device, int albedo_grid, int hist_device, int hist_width, int hist_height, int hist_albedo) const;
     int save_host(void* buf, size_t bytes) const;          // refuses a short buffer, then writes the parts of the checkpoint the host holds
     int load_check(const void* buf, size_t bytes, CheckpointCounts* out) const;
     int filter_refusal(const void* buf, size_t bytes) const;   // a saved state that differs from this frame in its pixel filter: the refusal that names it

@@ -72,6 +72,7 @@ int threshold_check(float threshold);                                           
 int stop_rule_check(float threshold, float max_fraction_above, int min_batches);      // threshold_check, then the fraction in 0 .. 1, then min_batches >= 2
 int pass_samples_check(int min_samples_per_pass);                                      // >= 1
 int denoise_params_check(const ky_denoise_params* p);                                  // levels 0 .. 6, normal_squarings 0 .. 10, both sigmas > 0 (a NaN is not)
+int temporal_params_check(const ky_temporal_params* t);                                // max_history in (0, 1024], sigma_plane > 0, min_weight in [0, 1), normal_squarings 0 .. 10
 double denoise_pixel_width(const ky_camera& camera, int width);                        // the width of a pixel at unit distance: 2 |camera.right| / width
 
 // ---- scene packing (ky_pack.cpp) ----

@@ -554,6 +554,63 @@ int kyhostcheck_denoise_albedo(const float* cv, const float* ga, const float* gb
     return KY_OK;
 }
 
+// The temporal step's arithmetic (ky_denoise.hpp, temporal_pixel_t: what denoise_temporal_kernel does per pixel) over whole film-order buffers: the frame's cv, ga,
+// gb (width x height x 4 floats each; key: NULL, or width x height chain keys), the history's old side hcv, hga, hgb = {P, m} (all three NULL: a history that holds
+// no picture), n_p the samples the frame holds, `pix` the current camera's pixel width, `then` the history's camera.  Writes the history's new {r, g, b, v} to
+// out_cv and its new {P, m} to out_gb.  Returns temporal_params_check's status, or KY_ERR_INVALID_VALUE for arguments that are none.
+int kyhostcheck_temporal(const float* cv, const float* ga, const float* gb, const uint64_t* key, const float* hcv, const float* hga, const float* hgb, int width, int height,
+                         double n_p, const ky_temporal_params* t, double pix, const ky_camera* then, float* out_cv, float* out_gb) {
+    using namespace kydn;
+    const bool has = hcv && hga && hgb;
+    if (!cv || !ga || !gb || !t || !then || !out_cv || !out_gb || width < 1 || height < 1 || (!has && (hcv || hga || hgb))) return fail(KY_ERR_INVALID_VALUE, "bad arguments");
+    KY_TRY(temporal_params_check(t));
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<uint64_t> keys(key ? n : 0);
+    if (key) std::memcpy(keys.data(), key, n * sizeof(uint64_t));
+    std::vector<Px4> c(n), a(n), b(n), hc(has ? n : 0), ha(has ? n : 0), hb(has ? n : 0), oc(n), ob(n);   // (16-byte aligned copies: the caller's arrays need not be)
+    std::memcpy(c.data(), cv, n * sizeof(Px4));
+    std::memcpy(a.data(), ga, n * sizeof(Px4));
+    std::memcpy(b.data(), gb, n * sizeof(Px4));
+    if (has) {
+        std::memcpy(hc.data(), hcv, n * sizeof(Px4));
+        std::memcpy(ha.data(), hga, n * sizeof(Px4));
+        std::memcpy(hb.data(), hgb, n * sizeof(Px4));
+    }
+    TemporalConst k{};
+    k.width = width; k.height = height;
+    k.normal_squarings = t->normal_squarings;
+    k.has_history = has ? 1 : 0;
+    k.n_p = n_p;
+    k.max_history = (double)t->max_history; k.sigma_plane = (double)t->sigma_plane; k.min_weight = (double)t->min_weight;
+    k.pix = pix;
+    k.then = *then;
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const TemporalPixel o = key ? temporal_pixel_t<true>(c.data(), a.data(), b.data(), keys.data(), hc.data(), ha.data(), hb.data(), x, y, k)
+                                        : temporal_pixel_t<false>(c.data(), a.data(), b.data(), nullptr, hc.data(), ha.data(), hb.data(), x, y, k);
+            oc[(size_t)y * width + x] = o.cv;
+            ob[(size_t)y * width + x] = o.gb;
+        }
+    std::memcpy(out_cv, oc.data(), n * sizeof(Px4));
+    std::memcpy(out_gb, ob.data(), n * sizeof(Px4));
+    return KY_OK;
+}
+
+// What kyhip_frame_denoise_temporal refuses of a frame and a history (FrameBook::temporal_check), without a device: the book of a frame of p that tracks noise
+// (noise != 0) with `batches` noise batches and blocks (blocks != 0), on `device` with `albedo_grid`, against a history of hist_width x hist_height on hist_device
+// whose albedo mode is hist_albedo (-1: it holds no picture).  Returns the check's status.
+int kyhostcheck_temporal_refusal(const ky_render_params* p, int noise, int blocks, int batches, int device, int albedo_grid, int hist_device, int hist_width,
+                                 int hist_height, int hist_albedo) {
+    kyhip_frame* none;
+    KY_TRY(begin_check(nullptr, p, 0, p ? p->samples_per_pixel : 0, &none));
+    FrameBook book;
+    book.begin(p, 0x1234, 0, p->samples_per_pixel);
+    if (noise) KY_TRY(book_op(&book, 1, nullptr, 5, 0, 0, 0));
+    if (blocks) KY_TRY(book_op(&book, 1, nullptr, 6, 0, 0, 0));
+    book.noise.batches = batches;
+    return book.temporal_check(device, albedo_grid, hist_device, hist_width, hist_height, hist_albedo);
+}
+
 // The live rectangle (screen_bound, kyhip_scene_screen_bound) on degenerate inputs: a unit box of five matte rectangles (open towards -z) or one sphere, seen by a
 // camera that looks along +z.  Whatever the proof cannot cover must give the whole frame: the camera on the bound's face, inside the bound, a NaN vertex, no surfaces.
 // A sphere of radius zero is a bound that is a point: a rectangle of a few pixels.  Returns 0, or the number of the case that went wrong.
@@ -926,6 +983,29 @@ int kyhip_frame_set_albedo_grid(kyhip_frame*, int grid) {
 int kyhip_frame_albedo_grid(const kyhip_frame*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_albedo(kyhip_frame*, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
 int kyhip_frame_albedo_ms(const kyhip_frame*, float*) { return fail(KY_ERR_INVALID_VALUE, "frame is NULL"); }
+// (the temporal entries: both parameter sets first, as the real one checks them; a history needs a device; kyhip_temporal_defaults is host code, ky_pack.cpp)
+int kyhip_history_create(int, int width, int height, kyhip_history** out) {
+    if (!out) return fail(KY_ERR_INVALID_VALUE, "out is NULL");
+    *out = nullptr;
+    if (width < 1 || height < 1 || (long long)width * height > (1ll << 28)) return fail(KY_ERR_INVALID_VALUE, "a history of %d x %d pixels", width, height);
+    return no_gpu();
+}
+int kyhip_history_destroy(kyhip_history*) { return fail(KY_ERR_INVALID_VALUE, "history is NULL"); }
+int kyhip_history_reset(kyhip_history*) { return fail(KY_ERR_INVALID_VALUE, "history is NULL"); }
+int kyhip_history_frames(const kyhip_history*) { return fail(KY_ERR_INVALID_VALUE, "history is NULL"); }
+int kyhip_history_read(kyhip_history*, float*, float*, size_t) { return fail(KY_ERR_INVALID_VALUE, "history is NULL"); }
+int kyhip_history_ms(const kyhip_history*, float*) { return fail(KY_ERR_INVALID_VALUE, "history is NULL"); }
+int kyhip_frame_denoise_temporal(kyhip_frame*, kyhip_history*, const ky_denoise_params* p, const ky_temporal_params* t, float*, size_t) {
+    ky_denoise_params q;
+    kyhip_denoise_defaults(&q);
+    if (p) q = *p;
+    ky_temporal_params tt;
+    kyhip_temporal_defaults(&tt);
+    if (t) tt = *t;
+    KY_TRY(denoise_params_check(&q));
+    KY_TRY(temporal_params_check(&tt));
+    return fail(KY_ERR_INVALID_VALUE, "frame is NULL");
+}
 // (the filter entries refuse an invalid filter before they look for a device or a frame, like the real ones: filter_check is host code; a box filter is the unfiltered entry)
 int kyhip_render_filtered(int device, const ky_scene* scene, const ky_render_params* p, const ky_pixel_filter* filter, float* film, size_t stride) {
     if (filter) KY_TRY(filter_check(filter));

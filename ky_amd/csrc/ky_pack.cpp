@@ -202,6 +202,14 @@ int denoise_params_check(const ky_denoise_params* p) {
     if (!(p->sigma_plane > 0.f)) return fail(KY_ERR_INVALID_VALUE, "sigma_plane %g: a width is > 0", (double)p->sigma_plane);
     return KY_OK;
 }
+int temporal_params_check(const ky_temporal_params* t) {
+    if (!(t->max_history > 0.f && t->max_history <= 1024.f)) return fail(KY_ERR_INVALID_VALUE, "max_history %g: a multiple of the frame's samples in (0, 1024]", (double)t->max_history);   // (a NaN is refused)
+    if (!(t->sigma_plane > 0.f)) return fail(KY_ERR_INVALID_VALUE, "sigma_plane %g: a width is > 0", (double)t->sigma_plane);
+    if (!(t->min_weight >= 0.f && t->min_weight < 1.f)) return fail(KY_ERR_INVALID_VALUE, "min_weight %g: a share of the taps' weight in [0, 1)", (double)t->min_weight);
+    if (t->normal_squarings < 0 || t->normal_squarings > kydn::KY_DN_MAX_SQUARINGS)
+        return fail(KY_ERR_INVALID_VALUE, "normal_squarings %d: 0 .. %d", t->normal_squarings, kydn::KY_DN_MAX_SQUARINGS);
+    return KY_OK;
+}
 double denoise_pixel_width(const ky_camera& camera, int width) {
     const double x = (double)camera.right[0], y = (double)camera.right[1], z = (double)camera.right[2];
     return 2.0 * std::sqrt(x * x + y * y + z * z) / (double)width;
@@ -1597,6 +1605,13 @@ void kyhip_denoise_defaults(ky_denoise_params* out) {
     if (!out) return;
     out->levels = 5; out->normal_squarings = 7;
     out->sigma_luminance = 1.5f; out->sigma_plane = 0.25f;
+}
+
+// the temporal step's defaults, as tools/denoise_replay.py temporal settled them (profiles/denoise_temporal_replay.txt; DESIGN.md "Temporal")
+void kyhip_temporal_defaults(ky_temporal_params* out) {
+    if (!out) return;
+    out->max_history = 8.f; out->sigma_plane = 0.25f; out->min_weight = 0.05f;
+    out->normal_squarings = 7;
 }
 
 int64_t kyhip_shard_tile_count(const ky_render_params* p) {

@@ -835,6 +835,25 @@ enum class integrator_enum_t {
     simple_path_tracing_recursion, path_tracing_recursion, path_tracing_recursion_defered, path_tracing_iteration
 };
 
+// What frames of ONE scene under a moving camera hand to each other (kyhip_history_*, include/kyhip.h; no counterpart in the reference): the accumulated colour,
+// variance and sample count per pixel on the device, with the guides and the camera of the frame that wrote them.  integrator_t::render_denoised(..., history_t*)
+// reads and writes it.  The scene being the same but for the camera is the caller's contract.
+class history_t {
+public:
+    history_t(int width, int height, int device = 0) {
+        if (kyhip_history_create(device, width, height, &h_) != KY_OK) throw std::runtime_error(std::string("kyhip_history_create: ") + kyhip_last_error());
+    }
+    ~history_t() { if (h_) kyhip_history_destroy(h_); }
+    history_t(const history_t&) = delete;
+    history_t& operator=(const history_t&) = delete;
+    void reset() { kyhip_history_reset(h_); }
+    int frames() const { return kyhip_history_frames(h_); }
+    float ms() const { float v = -1.f; kyhip_history_ms(h_, &v); return v; }
+    kyhip_history* handle() const { return h_; }
+private:
+    kyhip_history* h_ = nullptr;
+};
+
 class integrator_t {
 public:
     virtual ~integrator_t() = default;
@@ -1026,6 +1045,13 @@ public:
     // (kyhip_frame_set_albedo_grid: the scene's textures stay sharp); 0: off.  Returns the samples done per pixel.
     int render_denoised(scene_t* scene, sampler_t* original_sampler, film_t* film, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params = nullptr,
                         int guide_bounces = 0, int albedo_grid = 0) {
+        return render_denoised(scene, original_sampler, film, min_samples_per_pass, stop_after_samples, params, guide_bounces, albedo_grid, nullptr);
+    }
+    // ... across frames: with a history the picture goes through kyhip_frame_denoise_temporal (temporal NULL: kyhip_temporal_defaults) -- every surface pixel is
+    // blended with what the history's earlier frames of the same scene saw of its point, and the history takes the result.  history NULL: the call above.  Use
+    // guide_bounces >= 1 where the scene has mirrors or glass: at 0 what they show reuses history like any surface and lags the camera.
+    int render_denoised(scene_t* scene, sampler_t* original_sampler, film_t* film, int min_samples_per_pass, int stop_after_samples, const ky_denoise_params* params,
+                        int guide_bounces, int albedo_grid, history_t* history, const ky_temporal_params* temporal = nullptr) {
         if (masked()) throw std::runtime_error("integrator_t::render_denoised: light classes are rendered by render() only");
         const ky_render_params p = params_for(original_sampler, film);
         kyhip_frame* frame = nullptr;
@@ -1041,6 +1067,9 @@ public:
                 if (kyhip_frame_render(frame, min_samples_per_pass, &done) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_render: ") + kyhip_last_error());
             if (passes < 2) {   // the frame was complete behind its first pass: one batch, no variance to guide a filter -- the complete frame as render() adds it
                 if (kyhip_frame_resolve(frame, 0, film->target_origin(), film->row_stride_px()) != KY_OK) throw std::runtime_error(std::string("kyhip_frame_resolve: ") + kyhip_last_error());
+            } else if (history) {
+                if (kyhip_frame_denoise_temporal(frame, history->handle(), params, temporal, film->target_origin(), film->row_stride_px()) != KY_OK)
+                    throw std::runtime_error(std::string("kyhip_frame_denoise_temporal: ") + kyhip_last_error());
             } else if (kyhip_frame_denoise(frame, params, film->target_origin(), film->row_stride_px()) != KY_OK) {
                 throw std::runtime_error(std::string("kyhip_frame_denoise: ") + kyhip_last_error());
             }

@@ -8,7 +8,10 @@ the gather and the add.  Next to a 64-sample pass's render kernel (kyhip_kernel_
 a warm-up.  Then, per guide bounce count 1 .. 4 (kyhip_frame_set_guide_bounces), a frame of its own: the chain trace and the keyed filter the same way.
   tools/denoise_rates.py albedo cornell|veach [spp]   (profiles/denoise_albedo_rates.txt; DESIGN.md "Denoise", "Albedo") the same two geometries under
 tests/texture_restatement.py's texture sets: the albedo trace (kyhip_frame_albedo_ms) at grids 1, 2, 4 and 8 -- once per frame, so the median over five frames
-each -- next to the guide trace and a 64-sample pass, and the default five-level filter's span with and without demodulation, medians of five calls."""
+each -- next to the guide trace and a 64-sample pass, and the default five-level filter's span with and without demodulation, medians of five calls.
+  tools/denoise_rates.py temporal cornell|veach [spp]   (profiles/denoise_temporal_rates.txt; DESIGN.md "Denoise", "Temporal") two frames of the geometry at guide
+bounces 0 and 1 that hand one history to each other: the temporal kernel's hipEvent span (kyhip_history_ms) next to one level's, measured in the same loop -- the
+level as the increment of the filter's span from 1 to 6 levels over five -- medians of five calls."""
 import ctypes as C
 import os
 import sys
@@ -17,7 +20,8 @@ import numpy as np
 from ky_amd import api, _abi as A
 
 ALBEDO = sys.argv[1:2] == ["albedo"]
-if ALBEDO:
+TEMPORAL = sys.argv[1:2] == ["temporal"]
+if ALBEDO or TEMPORAL:
     del sys.argv[1]
 what = sys.argv[1] if len(sys.argv) > 1 else "cornell"
 spp = int(sys.argv[2]) if len(sys.argv) > 2 else 512
@@ -69,8 +73,35 @@ def albedo_rates():
                       float(np.median(spans)), plain, " ".join("%.4f" % r for r in spans)), flush=True)
 
 
+def temporal_rates():
+    for bounces in (0, 1):
+        with api.History(W, H) as hist, api.Frame(scene, p, noise=True, guide_bounces=bounces) as f, api.Frame(scene, api.make_params(W, H, spp, seed=4321), noise=True,
+                                                                                                                 guide_bounces=bounces) as g:
+            for fr in (f, g):
+                fr.render(64)
+                fr.render(64)
+                fr.denoise(film=film.array, history=hist)   # warm-up; traces the guides; the second call reads what the first one wrote
+            rows = []
+            for _ in range(5):
+                spans = {}
+                for levels in (1, 6):
+                    for fr in (f, g):
+                        fr.denoise(dict(levels=levels), film=film.array, history=hist)
+                    spans[levels] = g.denoise_ms()[1]
+                rows.append((hist.ms(), (spans[6] - spans[1]) / 5, spans[6]))
+            t, level, six = (float(np.median([r[i] for r in rows])) for i in range(3))
+            took = float((hist.read()[1] > f.done).mean())
+            print("%s %d x %d, %d guide bounces: the temporal kernel %.4f ms = %.3f ns per pixel (five calls: %s); a %s level in the same loop %.4f ms (five: %s): "
+                  "temporal / level %.3f; the six-level span with the temporal kernel in it %.4f ms; %.1f %% of the pixels took history" % (
+                      what, W, H, bounces, t, t * 1e6 / (W * H), " ".join("%.4f" % r[0] for r in rows), "keyed" if bounces else "plain", level,
+                      " ".join("%.4f" % r[1] for r in rows), t / level, six, 100 * took), flush=True)
+
+
 if ALBEDO:
     albedo_rates()
+    sys.exit(0)
+if TEMPORAL:
+    temporal_rates()
     sys.exit(0)
 with api.Frame(scene, p, noise=True) as f:
     f.render(64)

@@ -15,9 +15,16 @@ at the default sigmas with today's filter and with albedo demodulation (tests/de
 rules (v / Y(a')^2, the one the library uses, and v Y(1 / a')^2).  The albedo is the oracle's camera and scene-intersect KATs at the sub-sample positions with the
 tiled material's colour.  RMSE over the whole film and over the pixels whose centre first hits a textured surface, at 48, 112, 224 and 500 samples.
 
+`temporal` (profiles/denoise_temporal_replay.txt; DESIGN.md "Denoise", "Temporal"): the Cornell box with both balls along a camera path
+(tests/denoise_temporal_restatement.py: PATH_FRAMES frames of PATH_SPP samples, one chunk per pass, frame k with seed + k, dolly, sideways move and pan), every
+frame's samples replayed on the oracle and fed through the NumPy restatements with specular-chain guides of one guide bounce: temporal + spatial against spatial
+alone against raw on the LAST frame, over a scan of the temporal parameters.  RMSE against the oracle at truth_spp samples of the last frame, over the whole film
+and over the non-floor pixels (the floor is Phong with exponent 90: its highlight is view-dependent, and history holds it where the earlier cameras saw it).
+
 usage: tools/denoise_replay.py [truth_spp]
        tools/denoise_replay.py chains [truth_spp]
-       tools/denoise_replay.py albedo [truth_spp]"""
+       tools/denoise_replay.py albedo [truth_spp]
+       tools/denoise_replay.py temporal [truth_spp]"""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,7 +42,8 @@ AT = (112, 224, 500)
 PAIRS = [(4.0, 1.0), (1.0, 1.0), (1.5, 1.0), (2.0, 1.0), (1.5, 0.25), (1.5, 0.1), (2.0, 0.25), (3.0, 0.25), (8.0, 1.0)]   # (4, 1): where the scan started; (1.5, 0.25): the defaults
 CHAINS = sys.argv[1:2] == ["chains"]
 ALBEDO = sys.argv[1:2] == ["albedo"]
-if CHAINS or ALBEDO:
+TEMPORAL = sys.argv[1:2] == ["temporal"]
+if CHAINS or ALBEDO or TEMPORAL:
     del sys.argv[1]
 TRUTH_SPP = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 
@@ -134,6 +142,71 @@ def replay_albedo():
         sum(table[(s, d, "film")][2][(4, "y2")] < table[(s, d, "film")][2][(1, "y2")] for s in seeds for d in at), n))
 
 
+def replay_temporal():
+    import denoise_albedo_restatement as DA
+    import denoise_chains_restatement as DC
+    import denoise_temporal_restatement as DT
+    from screen_cull_scenes import cornell_with_camera
+    n, spp, seeds = DT.PATH_FRAMES, DT.PATH_SPP, (DT.PATH_SEED, 101, 202)
+    debug = api.make_params(W, H, 1, max_path_depth=8, sampler=A.SAMPLER_DEBUG)
+    scan = [dict(DT.DEFAULTS)] + [dict(DT.DEFAULTS, max_history=m) for m in (1.0, 2.0, 4.0, 16.0)] + [dict(DT.DEFAULTS, min_weight=m) for m in (0.0, 0.25, 0.5)] + \
+           [dict(DT.DEFAULTS, sigma_plane=sp) for sp in (0.1, 1.0)] + [dict(DT.DEFAULTS, normal_squarings=q) for q in (3, 10)]
+    print("Cornell %d x %d with both balls, %d frames of %d spp (one chunk per pass, %d batches), frame k with seed + k, along the path dolly %g, sideways %g, pan %g; "
+          "guide bounces 1; truth: the oracle at %d spp of the last frame; D.DEFAULTS for the levels" % (
+              W, H, n, spp, len(api.pass_boundaries(spp)), DT.PATH_DOLLY, DT.PATH_SIDE, DT.PATH_PAN, TRUTH_SPP))
+    print("RMSE of clamp01(picture) of the LAST frame against the truth; s = spatial alone, t = temporal alone (levels 0), t+s = temporal + spatial.  Over the whole "
+          "film, over the pixels that do not first-hit the floor (plastic, Phong exponent 90), and over the pixels further than 2 pixels from a saturated one of the "
+          "truth (a channel >= 0.9: the lamp, its edge pixels, its mirror images)")
+    for tilt, name in ((0.0, "the lamp in view"), (DT.PATH_TILT, "tilted down by %g, the lamp out of view" % DT.PATH_TILT)):
+        scenes = [cornell_with_camera(A, api, W, H, lambda cam, s=k / (n - 1): DT.path_camera(A, cam, s, tilt)) for k in range(n)]
+        guides = []
+        for scene in scenes:
+            cls, key, ga, gb = DC.chains(lambda x, y: O.trace_li(scene, debug, x, y, 0), scene.scene, W, H, 1)
+            guides.append((ga, gb, key))
+        last = scenes[-1]
+        truth = O.render(last, api.make_params(W, H, TRUTH_SPP, seed=987654)).astype(np.float64)
+        c = last.scene
+        first_hit = np.asarray(O.kat_scene_intersect(last, D.centre_rays(O.kat_camera, c.camera, W, H)), np.float32)
+        surf = np.where(first_hit[:, 0] == 1, first_hit[:, 8], -1).astype(int).reshape(H, W)
+        floor = np.isin(surf, [s for s in range(c.surface_count) if c.materials[c.surfaces[s].material].kind == A.MATERIAL_PLASTIC])
+        bright = truth.max(axis=2) >= 0.9
+        near = np.zeros_like(bright)
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                ys, xs = np.clip(np.arange(H) + dy, 0, H - 1), np.clip(np.arange(W) + dx, 0, W - 1)
+                near |= bright[ys][:, xs]
+        where = (("film", np.ones((H, W), bool)), ("rest", ~floor), ("away", ~near))
+        print("\n== %s: %d of %d pixels first-hit the floor, %d carry a chain key, %d of the truth's are saturated and %d lie within 2 pixels of one" % (
+            name, int(floor.sum()), W * H, int((guides[-1][2] != 0).sum()), int(bright.sum()), int(near.sum())))
+        frames = {seed: [DA.replay(O, api, R, scene, W, H, spp, seed + k, (spp,))[spp] for k, scene in enumerate(scenes)] for seed in seeds}
+        print(" seed | max_history sigma_plane min_weight squarings |  film: raw        s        t      t+s  t+s / s | non-floor: s      t+s  t+s / s | away: s      t+s  t+s / s | took history")
+        ratios = {}
+        for t in scan:
+            for seed in seeds:
+                hist = DT.History()
+                for k, scene in enumerate(scenes):
+                    ga, gb, key = guides[k]
+                    out = hist.step(frames[seed][k], ga, gb, key, scene.scene.camera, W, spp, D.DEFAULTS, temporal_params=t)
+                cv = frames[seed][-1]
+                ga, gb, key = guides[-1]
+                spatial = DC.denoise(cv, ga, gb, key, D.pixel_width(c.camera, W), **D.DEFAULTS)
+                e = {w: [DA.rmse(f, truth, sel) for f in (cv, spatial, hist.read()[0], out)] for w, sel in where}
+                ratios.setdefault(tuple(sorted(t.items())), []).append([e[w][3] / e[w][1] for w, _ in where])
+                print("%5d | %11g %11g %10g %9d | %.5f  %.5f  %.5f  %.5f    %.3f |    %.5f  %.5f    %.3f | %.5f  %.5f   %.3f | %d of %d" % (
+                    seed, t["max_history"], t["sigma_plane"], t["min_weight"], t["normal_squarings"], e["film"][0], e["film"][1], e["film"][2], e["film"][3],
+                    e["film"][3] / e["film"][1], e["rest"][1], e["rest"][3], e["rest"][3] / e["rest"][1], e["away"][1], e["away"][3], e["away"][3] / e["away"][1],
+                    int(hist.took.sum()), W * H))
+        print()
+        for t, r in ratios.items():
+            r = np.array(r)
+            print("%s: t+s / s over the film %.3f .. %.3f (mean %.3f), non-floor %.3f .. %.3f (mean %.3f), away from saturated pixels %.3f .. %.3f (mean %.3f)" % (
+                " ".join("%s %g" % kv for kv in t), r[:, 0].min(), r[:, 0].max(), r[:, 0].mean(), r[:, 1].min(), r[:, 1].max(), r[:, 1].mean(),
+                r[:, 2].min(), r[:, 2].max(), r[:, 2].mean()))
+
+
+if TEMPORAL:
+    replay_temporal()
+    sys.exit(0)
 if CHAINS:
     replay_chains()
     sys.exit(0)
